@@ -2,6 +2,7 @@
 """Headline benchmark: MCTS simulations/sec (whole job) of the self-play search path.
 
     python bench.py [--gpus N] [--workload cartpole|tictactoe|connect4|atari84] [--steps K] [--warmup W]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,9 +23,14 @@ every `--bcast-every` steps all ranks take rank 0's flat weight buffer by one RC
 
 Launch: with N > 1 and no WORLD_SIZE in the environment this script starts its N ranks itself (fresh child
 processes, decided before anything touches the GPU) and relays rank 0's JSON line; under torch.distributed.run it
-joins the group it is given.  The timed region is K steps repeated until it lasts >= --min-seconds (a 20-step CartPole
-run would otherwise be a 5 ms sample): `steps` stays K, `timed_steps` says how many were timed, `ms_per_step` is
-per step.
+joins the group it is given.  The timed region is exactly the K steps that follow the W warm-up steps (`timed_steps` =
+`steps` = K).  A 20-step CartPole run is a 4 ms sample, taken before the clock has settled to what the chip sustains
+(it reads 10 % above a one-second region): K's default is per workload, sized for a timed region of a second or more.
+
+--dump-outputs DIR writes, after the timed region, what its last step handed its caller -- per env the root statistics
+of the search and the action sampled from them -- as DIR/<name>.npy (float32 / float64, envs of all ranks in global
+order; more than 64 MB -> a fixed seeded sample of the envs and their indices in env_index.npy).  Inputs, seeds and
+the number of steps before the dump depend on the arguments only, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).  Extra legs on rank 0:
   roofline      HIP-event pass of the same workload: per-kernel mean duration, algorithmic bytes per launch (SURVEY.md
@@ -79,16 +85,17 @@ REFERENCE_TIMING, REFERENCE_TIMING_HOST = _load_rho()
 # of two streams fill each other's gaps: TicTacToe 65536 envs 100 -> 138 M simulations/s with two groups, Connect4 8192
 # envs 4.94 -> 5.67 M, the 84x84 config 32768 envs 26.6 -> 27.9 M.
 WORKLOADS = {
-    "cartpole": dict(envs=4096, baseline_config=2, groups=2),
+    # steps: the default K, for a timed region of a second or more at the rates measured on one MI355X
+    "cartpole": dict(envs=4096, baseline_config=2, groups=2, steps=5000),
     # fused_step: expand_backup of a simulation and the descent of the next in one launch (MZ_FUSED_STEP, engine.py) --
     # measured on one box, three alternating pairs: 239.6 / 244.2 / 244.5 M without, 245.3 / 250.8 / 253.4 M with it;
     # config #5 the same either way, Connect4 6.82 M without against 6.71 M with it: on for TicTacToe only
-    "tictactoe": dict(envs=65536, baseline_config=3, groups=2, fused_step=True),
-    "connect4": dict(envs=8192, baseline_config=4, groups=2),
+    "tictactoe": dict(envs=65536, baseline_config=3, groups=2, fused_step=True, steps=200),
+    "connect4": dict(envs=8192, baseline_config=4, groups=2, steps=100),
     # (one group: a move is 42 ms of GPU work, the host's turn between moves is noise, and two half-size groups run
     #  every kernel at half its batch -- measured 38.9 M against 36.9 M simulations/s; TicTacToe needs its two groups
     #  to cover the host: 243 M against 160 M, and Connect4 gains 3 % from them)
-    "atari84": dict(envs=32768, baseline_config=5, groups=1),
+    "atari84": dict(envs=32768, baseline_config=5, groups=1, steps=100),
 }
 
 
@@ -99,12 +106,12 @@ def pkg(sub):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=0, help="timed steps (0 = the workload's default)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cartpole")
     ap.add_argument("--envs", type=int, default=0, help="envs (trees) per GPU (0 = the workload's default)")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="the K timed steps are repeated until the timed region lasts at least this long")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy")
     ap.add_argument("--bcast-every", type=int, default=50, help="weight broadcast period in steps (N>1)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--host-noise", action="store_true",
@@ -130,8 +137,12 @@ def parse_args(argv=None):
                     help="no GPU: run launch, rendezvous (gloo), weight broadcast, timing reduction and the JSON relay "
                          "with the search replaced by a sleep -- a test of the N>1 plumbing, never a measurement")
     args = ap.parse_args(argv)
+    if args.steps <= 0:
+        args.steps = WORKLOADS[args.workload]["steps"]
     if args.groups <= 0:
         args.groups = WORKLOADS[args.workload]["groups"]
+    if args.dump_outputs and args.rehearse_cpu:
+        ap.error("--dump-outputs needs the search; --rehearse-cpu runs none")
     if WORKLOADS[args.workload].get("fused_step"):
         os.environ.setdefault("MZ_FUSED_STEP", "on")     # (read by every engine this process creates)
     return args
@@ -329,7 +340,7 @@ class Workload:
         e = self.engine
         e.search(self.model, self.obs_sets[i % len(self.obs_sets)], self.legal, self.to_play, True,
                  num_legal=self.num_legal)
-        e.sample_actions(self.temperature)
+        self.last_actions = [e.sample_actions(self.temperature)]
 
     def one_step(self, i):
         if self.bcast and i % self.args.bcast_every == 0:
@@ -377,10 +388,11 @@ class Workload:
     def drain(self):
         if not self.pipe:
             return
+        self.last_actions = [None] * self.args.groups
         for g in range(self.args.groups):
             if self.started[g]:
                 self.pipe.finish(g)
-                self.pipe.engines[g].sample_actions(self.g_in[3])
+                self.last_actions[g] = self.pipe.engines[g].sample_actions(self.g_in[3])
                 self.started[g] = False
 
     # ---- fused CartPole, moves queued in batches (no host round trip inside a batch) --------------------------------
@@ -423,11 +435,29 @@ class Workload:
                 engine.moves_submit_next()
             t.append(time.perf_counter())
             self.pending_predraw = nxt if n + 1 == len(plan) else 0
+            self.last_batch = out
             if trace:
                 print(f"[bench] batch of {b}: enqueue {1e3 * (t[1] - t[0]):.2f} ms, predraw {1e3 * (t[2] - t[1]):.2f}, "
                       f"collect {1e3 * (t[3] - t[2]):.2f}, submit {1e3 * (t[4] - t[3]):.2f}; moves done min "
                       f"{int(out['moves_done'].min())}", file=sys.stderr, flush=True)
         return played
+
+    def last_outputs(self):
+        """What the last step handed its caller, name -> [E, ...]: the root statistics of every env's search (per child
+        slot: the i-th legal action) and the action sampled from them.  Valid until the next step."""
+        if self.batched:
+            out = self.last_batch
+            m = len(out["actions"]) - 1                      # the batch's last move
+            # an env that left the pre-drawn path earlier in the batch played no last move: its ring entries are
+            # undefined (engine.moves_collect) and read as moves_collect(copy=True) fills them
+            played = out["moves_done"] > m
+            arrays = {k: np.where(played[:, None] if out[k].ndim == 3 else played, out[k][m], -1 if k == "actions" else 0)
+                      for k in ("actions", "visits", "root_value_sum", "root_predicted", "max_depth")}
+            return dict(arrays, moves_done=out["moves_done"])
+        engines = self.pipe.engines if self.pipe else [self.engine]
+        arrays = {k: np.concatenate([e.stats[k] for e in engines]) for k in self.engine.stats}
+        actions, slots = (np.concatenate(x) for x in zip(*self.last_actions))
+        return dict(arrays, actions=actions, action_slots=slots)
 
     def close(self):
         if self.pipe:
@@ -435,7 +465,26 @@ class Workload:
         self.actor.close()
 
 
-def run_steps(wl, first, count, barrier, next_first=0):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """name -> [envs, ...] as directory/<name>.npy, float32 where the path computes float32 and float64 (exact for
+    every integer it returns) elsewhere; over DUMP_LIMIT_BYTES in all -> the same seeded sample of the envs each time."""
+    arrays = {k: np.asarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    envs = len(arrays["actions"])
+    assert all(len(a) == envs for a in arrays.values())
+    per_env = sum(a.nbytes for a in arrays.values()) // envs + 8     # (+ the env's index when sampled)
+    room = (DUMP_LIMIT_BYTES - 1024 * (len(arrays) + 1)) // per_env  # (1 KiB per file covers the .npy header)
+    if envs > room:
+        keep = np.sort(np.random.RandomState(0).choice(envs, room, replace=False))
+        arrays = dict({k: a[keep] for k, a in arrays.items()}, env_index=keep.astype(np.float64))
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
+def run_steps(wl, first, count, barrier):
     """`count` steps starting at step index `first`, bracketed by barrier + synchronize; returns (seconds, moves)."""
     if wl.batched:
         plan = wl.batch_sizes(first, count)
@@ -449,7 +498,7 @@ def run_steps(wl, first, count, barrier, next_first=0):
         # batch's draw produces rows nobody runs: it stands in for the first batch's, done before the timer started)
         if drawn_ahead:
             wl.engine.moves_submit_next()
-        played = wl.run_plan(plan, next_first or plan[0][1])
+        played = wl.run_plan(plan, plan[0][1])
         barrier()
         return time.perf_counter() - t0, played
     barrier()
@@ -507,7 +556,7 @@ def main(argv=None):
         return out
 
     K, W = args.steps, args.warmup
-    # ---- warm-up: W untimed steps, then an untimed probe of K steps that sizes the timed region ----------------------
+    # ---- warm-up: W untimed steps ------------------------------------------------------------------------------------
     if wl.batched:
         plan_all = wl.batch_sizes(0, max(W, 1) + K)
         wl.prepare(max(b for _, b in plan_all + wl.batch_sizes(0, args.moves_per_batch)))
@@ -519,21 +568,20 @@ def main(argv=None):
         for i in range(W):
             wl.one_step(i)
         wl.drain()
-    next_first = wl.batch_sizes(max(W, 1) + K, 1 << 30)[0][1] if wl.batched else 0
-    probe_s, _ = run_steps(wl, max(W, 1), K, barrier, next_first)
-    probe_s = reduce_max(probe_s)
-    repeats = max(1, int(math.ceil(args.min_seconds / max(probe_s, 1e-9))))
-    # ---- timed region: exactly repeats x K steps ---------------------------------------------------------------------
+    # ---- timed region: exactly K steps -------------------------------------------------------------------------------
     refreshes_before = wl.refreshes
-    elapsed, moves_played = run_steps(wl, max(W, 1) + K, repeats * K, barrier)
+    elapsed, moves_played = run_steps(wl, max(W, 1), K, barrier)
+    if args.dump_outputs:
+        shards = gather(wl.last_outputs())
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {k: np.concatenate([s[k] for s in shards]) for k in shards[0]})
     if wl.batched:
         wl.engine.moves_discard_next()
     per_rank = gather((elapsed, moves_played))
     elapsed = max(e for e, _ in per_rank)
     moves_played = sum(m for _, m in per_rank)
-    timed_steps = repeats * K
     # only searches that really ran count: in move batches an env whose tie-break words differ from the pre-drawn
-    # assumption sits out the rest of its batch, so moves_played <= world * E * timed_steps
+    # assumption sits out the rest of its batch, so moves_played <= world * E * K
     value = moves_played * S / elapsed
 
     # ---- the weight refresh by itself (not part of `value`; N > 1) ---------------------------------------------------
@@ -563,7 +611,7 @@ def main(argv=None):
     result = {
         "metric": "mcts_simulations_per_sec", "value": value, "unit": "simulations/s",
         "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": 1e3 * elapsed / timed_steps, "higher_is_better": True, "scaling": "weak",
+        "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": f"{wl.name}_{E}envs_x_{S}sims", "baseline_config": WORKLOADS[wl.name]["baseline_config"],
                    "envs_per_gpu": E, "simulations": S, "actions": A, "network": network,
@@ -576,9 +624,9 @@ def main(argv=None):
                    "exploration_noise": "drawn on the GPU (root_noise_kernel)" if engine._device_noise else
                                         "drawn on the host mirrors of the RNG streams",
                    "weight_broadcast_every_steps": args.bcast_every if world > 1 else None},
-        "timed_steps": timed_steps, "timed_seconds": elapsed, "repeats_of_steps": repeats,
+        "timed_steps": K, "timed_seconds": elapsed,
         "self_play_moves_per_sec": moves_played / elapsed,
-        "moves_played": moves_played, "moves_scheduled": world * E * timed_steps,
+        "moves_played": moves_played, "moves_scheduled": world * E * K,
     }
     if world > 1:
         backend = dist.get_backend()

@@ -310,10 +310,11 @@ PARITY_REPORT = {}
 
 
 def _write_parity_report():
-    """Worst deviations per config, for profiles/ (gpurun_out/ is merged back from the GPU box)."""
+    """Worst deviations per config, for profiles/ (tools/make_profiles.py picks the report up from the same place)."""
     import json
     import os
-    out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+    out_dir = os.environ.get("MZ_OUT_DIR") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                          "measure_out")
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "parity_report.json"), "w") as f:
         json.dump(PARITY_REPORT, f, indent=1, sort_keys=True)

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Copy / assemble the measurement summaries a GPU call left in gpurun_out/ (scratch) into profiles/ (tracked),
-named per round:   python tools/make_profiles.py [r02]"""
+"""Copy / assemble the measurement summaries the tools/*.sh recipes left in $MZ_OUT_DIR (default measure_out/, untracked)
+into profiles/ (tracked), named per round:   python tools/make_profiles.py [r02]"""
 import json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("MZ_OUT_DIR") or os.path.join(ROOT, "measure_out"), os.path.join(ROOT, "profiles")
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 
 def have(name):
@@ -48,7 +48,7 @@ for w in ("connect4", "tictactoe", "atari84"):
 if have("fused_sq_insts.json") and have("fused_sq_waits.json"):
     a = json.load(open(os.path.join(G, "fused_sq_insts.json")))
     b = json.load(open(os.path.join(G, "fused_sq_waits.json")))
-    out = {"command": "rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python3 bench.py --steps 20 --warmup 5 --min-seconds 0 "
+    out = {"command": "rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python3 bench.py --steps 20 --warmup 5 "
                       "--cpu-seconds 0 --profile-steps 0   (two passes: tools/profile_r02.sh fusedsq); tools/pmc_summary.py --sq 50",
            "note": "per wavefront (4 trees of 16 lanes) and simulation; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_* count quad-cycles (x4 in "
                    "cycles_per_simulation, shares are ratios of quad-cycles); one wavefront per SIMD at 4096 envs",
@@ -69,7 +69,7 @@ if have("fused_sq_insts.json") and have("fused_sq_waits.json"):
 
 # HBM-side traffic per launch (FETCH_SIZE / WRITE_SIZE passes) in the form bench.py's roofline leg reads
 if have("traffic_FETCH_SIZE.json") and have("traffic_WRITE_SIZE.json"):
-    out = {"command": "rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace -- python3 bench.py --steps 20 --warmup 5 --min-seconds 0 "
+    out = {"command": "rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace -- python3 bench.py --steps 20 --warmup 5 "
                       "--cpu-seconds 0 --profile-steps 0 (separate passes: tools/profile_r02.sh traffic)",
            "workload": "cartpole_fc_4096envs_x_50sims",
            "unit": "KB per launch (raw counter as rocprofv3 reports it; uncorrected, see DESIGN.md section 5)", "counters": {}}
