@@ -60,6 +60,45 @@ int mzenv_observe(mzenv *env, float *obs_out, int32_t *legal_out, int32_t *num_l
 int mzenv_advance(mzenv *env, const int32_t *actions, float *reward_out, uint8_t *done_out, float *obs_after_out,
                   float *obs_next_out, int32_t *legal_out, int32_t *num_legal_out, int32_t *to_play_out, void *stream);
 
+/* ---- evaluation games: a scripted opponent plays one side (reference self_play.py:189-221) -----------------------
+ * MZENV_OPPONENT_EXPERT  the plugin's expert_agent(): numpy.random.choice over the legal actions (always drawn), then
+ *                        the line scan of games/tictactoe.py / games/connect4.py (a winning completion returns at
+ *                        once, a block is kept while the scan goes on)
+ * MZENV_OPPONENT_RANDOM  numpy.random.choice over the legal actions
+ * In a reference worker the opponent draws from numpy's global generator, which is also the search's stream: mt_key
+ * (dev u32[E][624]) and mt_pos (dev i32[E]) are therefore the SEARCH ENGINE's per-env streams (mzmcts_rng_streams);
+ * the words an opponent consumed are reported per env so that the engine's host mirrors can step over them
+ * (mzmcts_rng_consumed).  A one-element legal set consumes no word.
+ *
+ * While the mode is on (kind != MZENV_OPPONENT_SELF), for an env whose side to move is not muzero_player
+ *   - mzenv_observe / mzenv_advance_opponent report num_legal = 0 (the engine's "this env sits the search out"; its
+ *     stream is left alone); the `legal` row stays filled;
+ *   - mzenv_step_opponent / mzenv_advance_opponent ignore the incoming action and play the opponent's move.
+ * An env on muzero_player's turn with action < 0 is left untouched as ever; on the opponent's turn "action < 0" no
+ * longer protects an env, so finished games are to be reset before the next step (mzenv_advance_opponent does it; after
+ * mzenv_step_opponent call mzenv_reset with the done mask).  An env whose board is full has no opponent move: it is left
+ * untouched (played_out -1, no word drawn).  A won but not full position that was not reset is played on.  mzenv_step / mzenv_advance refuse to run
+ * in opponent mode (nothing would report the opponent's moves).  One-player games have no opponent (error). */
+#define MZENV_OPPONENT_SELF 0
+#define MZENV_OPPONENT_EXPERT 1
+#define MZENV_OPPONENT_RANDOM 2
+int mzenv_set_opponent(mzenv *env, int32_t kind, int32_t muzero_player, uint32_t *mt_key, int32_t *mt_pos);
+
+/* mzenv_step / mzenv_advance with two more outputs per env (usable in either mode):
+ *   played_out dev i32[E]  the action actually played (the opponent's own on its turn; -1: env left untouched)
+ *   words_out  dev u32[E]  32-bit words the opponent's choice consumed from the env's stream (0 elsewhere) */
+int mzenv_step_opponent(mzenv *env, const int32_t *actions, float *reward_out, uint8_t *done_out, int32_t *played_out,
+                        uint32_t *words_out, void *stream);
+int mzenv_advance_opponent(mzenv *env, const int32_t *actions, float *reward_out, uint8_t *done_out, float *obs_after_out,
+                           float *obs_next_out, int32_t *legal_out, int32_t *num_legal_out, int32_t *to_play_out,
+                           int32_t *played_out, uint32_t *words_out, void *stream);
+
+/* Put every env of a board game into a given position: boards host i8[E][cells] (0 empty, +1 first player, -1 second;
+ * tic-tac-toe cell = 3 * row + column, connect four cell = 7 * row + column with row 0 at the bottom), players host
+ * i8[E] (+1 / -1 to move).  Blocking; cell and player values are checked, reachability is not (see above for what a
+ * step does with a finished position). */
+int mzenv_set_boards(mzenv *env, const int8_t *boards, const int8_t *players);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,9 @@
  *     observations[i, 0..n]  actions[i, 0..n] (index 0 = the reference's dummy action 0)  rewards[i, 0..n]
  *     to_play[i, 0..n]       child_visits[i, 0..n-1][A] (visit counts / num_simulations, by action)
  *     root_values[i, 0..n-1] (root value sum / num_simulations)
+ * Opponent plies of evaluation games (mzhist_moves.played) keep their slot in every array: root_values holds NaN
+ * there -- the reference's None -- and the child_visits row is zero; a reader that wants the reference's lists drops
+ * those child_visits rows (the reference appends none for such a ply).
  * Pure host code (memory movement over E x M small records), spread over the library's worker pool.
  */
 #ifndef MZHIST_H
@@ -49,6 +52,10 @@ typedef struct mzhist_moves {
     const int32_t *to_play_next;  /* [M][E] or NULL */
     int64_t legal_stride;         /* bytes from one move's legal sets to the next move's; 0 = the batch has one set */
     int64_t num_legal_stride;     /* (board games: mzmcts_moves_inputs hands out [M][E][A] / [M][E]) */
+    const int32_t *played;        /* [M][E] or NULL: the action the environment kernels actually played
+                                   * (mzenv_advance_opponent's played_out).  When given, a ply whose legal set is empty
+                                   * is an OPPONENT ply (reference self_play.py:497-512, store_search_statistics(None)):
+                                   * its action is played[m][e], its root value is NaN and its child_visits row is zero. */
 } mzhist_moves;
 
 /* File the batch; *n_finished = games that ended in it. */
@@ -67,6 +74,10 @@ int mzhist_finished(mzhist *hist, const int32_t **env_index, const int32_t **len
  * to_play i32[E][max_moves+1], child_visits f64[E][max_moves][A], root_values f64[E][max_moves], lengths i32[E]. */
 int mzhist_rows(mzhist *hist, float *observations, int32_t *actions, float *rewards, int32_t *to_play,
                 double *child_visits, double *root_values, int32_t *lengths, int32_t load);
+
+/* Plies filed since mzhist_create whose legal set was not empty, i.e. that were searched (evaluation games: the rest were
+ * an opponent's; self-play: every ply). */
+int64_t mzhist_searched_moves(const mzhist *hist);
 
 /* Moves filed so far in env e's running game (i32[E]). */
 const int32_t *mzhist_lengths(const mzhist *hist);

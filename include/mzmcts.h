@@ -116,6 +116,15 @@ int mzmcts_rng_set_state(mzmcts_engine *engine, int32_t env, const uint32_t *key
                          int32_t has_gauss, double cached_gaussian, void *stream);
 int mzmcts_rng_get_state(mzmcts_engine *engine, int32_t env, uint32_t *key, int32_t *pos,
                          int32_t *has_gauss, double *cached_gaussian, void *stream);
+/* The device copies of the per-env streams, for kernels of the caller that must draw from them as a reference worker's
+ * other users of numpy.random do (the scripted opponents of evaluation games: mzenv_set_opponent, include/mzenv.h):
+ * *mt_key_dev = dev u32[E][624], *mt_pos_dev = dev i32[E].  Such a kernel runs on the engine's stream between two
+ * searches, at a point where the device copy is not behind its host mirror (inside a device-input move batch, after
+ * its first move: mzmcts_moves_prepare_device), and the caller reports what it consumed:
+ * mzmcts_rng_consumed: words host u32[E] = 32-bit words the caller's kernels drew from each env's device copy since
+ * the last report; the host mirrors step over them before they are next used. */
+int mzmcts_rng_streams(mzmcts_engine *engine, uint32_t **mt_key_dev, int32_t **mt_pos_dev);
+int mzmcts_rng_consumed(mzmcts_engine *engine, const uint32_t *words);
 
 /* ---- one search = MCTS.run (self_play.py:261-362) -------------------------------------------
  * begin_search: host side of the root set-up (self_play.py:297-315).
@@ -335,6 +344,14 @@ int mzmcts_moves_end_lockstep(mzmcts_engine *engine, void *stream);
  * done_out) -- envs flagged there start a new game, their counter restarts at the next move of the batch.  One-shot:
  * consumed by the next mzmcts_moves_enqueue / mzmcts_moves_begin_lockstep. */
 int mzmcts_moves_temperature_threshold(mzmcts_engine *engine, int32_t threshold, const int32_t *game_moves, void *stream);
+/* Plies the caller's environment kernels play themselves inside a device-input batch (an opponent's: mzenv_set_opponent).
+ * Without this switch an env stops counting at its first unsearched move (moves_done[e] = moves up to the first action
+ * < 0).  Call right after mzmcts_moves_prepare_device with enabled != 0: for this batch an env whose recorded num_legal
+ * of a move is 0 sat that move out BY DESIGN -- it stays live and its later moves are collected (moves_done[e] counts
+ * the sat-out moves too; their action reads -1 and their visits / values are undefined: the caller knows the action its
+ * own kernel played), its pending mirror words are stepped over at the batch's first move like a searched env's, and
+ * the ply advances the env's move counter of the temperature-threshold rule. */
+int mzmcts_moves_sit_out(mzmcts_engine *engine, int32_t enabled);
 int mzmcts_moves_finished(mzmcts_engine *engine, const uint8_t *finished);
 const int32_t *mzmcts_moves_actions(mzmcts_engine *engine, int32_t move);
 int mzmcts_moves_collect(mzmcts_engine *engine, int32_t *moves_done, int32_t *actions, int32_t *visits,

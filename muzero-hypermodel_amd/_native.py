@@ -118,6 +118,9 @@ PROTOTYPES = {
     "mzmcts_moves_end_lockstep": (ctypes.c_int, [c_void, c_void]),
     "mzmcts_moves_temperature_threshold": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_void]),
     "mzmcts_moves_finished": (ctypes.c_int, [c_void, c_void]),
+    "mzmcts_moves_sit_out": (ctypes.c_int, [c_void, ctypes.c_int32]),
+    "mzmcts_rng_streams": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), ctypes.POINTER(c_void)]),
+    "mzmcts_rng_consumed": (ctypes.c_int, [c_void, c_u32_p]),
     "mzmcts_moves_actions": (c_void, [c_void, ctypes.c_int32]),
     "mzmcts_moves_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p, c_i32_p]),
     "mzmcts_moves_inputs_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p]),
@@ -163,6 +166,7 @@ PROTOTYPES = {
     "mzhist_file": (ctypes.c_int, [c_void, c_void, c_i32_p]),
     "mzhist_finished": (ctypes.c_int, [c_void] + [ctypes.POINTER(c_void)] * 8 + [c_i32_p]),
     "mzhist_lengths": (c_void, [c_void]),
+    "mzhist_searched_moves": (ctypes.c_int64, [c_void]),
     "mzhist_rows": (ctypes.c_int, [c_void] * 8 + [ctypes.c_int32]),
     "mzreplay_create": (ctypes.c_int, [c_void, ctypes.POINTER(c_void)]),
     "mzreplay_destroy": (None, [c_void]),
@@ -181,6 +185,10 @@ PROTOTYPES = {
     "mzenv_reset": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzenv_step": (ctypes.c_int, [c_void, c_void, c_void, c_void, c_void]),
     "mzenv_observe": (ctypes.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),
+    "mzenv_set_opponent": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.c_int32, c_void, c_void]),
+    "mzenv_step_opponent": (ctypes.c_int, [c_void] * 7),
+    "mzenv_advance_opponent": (ctypes.c_int, [c_void] * 12),
+    "mzenv_set_boards": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzmcts_rng_create": (c_void, [ctypes.c_uint32]),
     "mzmcts_rng_destroy": (None, [c_void]),
     "mzmcts_rng_reseed": (None, [c_void, ctypes.c_uint32]),
@@ -271,7 +279,7 @@ class MzHistMoves(ctypes.Structure):
                 ("visits_stride", ctypes.c_int64), ("root_value_sum", c_void), ("root_value_sum_stride", ctypes.c_int64),
                 ("legal", c_void), ("num_legal", c_void), ("rewards", c_void), ("done", c_void), ("obs_after", c_void),
                 ("obs_next", c_void), ("to_play_after", c_void), ("to_play_next", c_void),
-                ("legal_stride", ctypes.c_int64), ("num_legal_stride", ctypes.c_int64)]
+                ("legal_stride", ctypes.c_int64), ("num_legal_stride", ctypes.c_int64), ("played", c_void)]
 
 
 class HostRng:

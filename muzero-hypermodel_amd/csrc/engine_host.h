@@ -343,6 +343,7 @@ struct mzmcts_engine {
         uint8_t* d_game_moves = nullptr;             // i32[E]
         const uint8_t* finished = nullptr;
         bool lockstep_open = false;                  // between mzmcts_moves_begin_lockstep and mzmcts_moves_end_lockstep
+        bool sit_out = false;                        // mzmcts_moves_sit_out: empty legal sets are plies the caller plays
     } batch;
     int32_t *own_root_action = nullptr, *own_root_children = nullptr, *own_root_to_play = nullptr;   // (scratch of move_extras)
     bool skip_applied = false;   // the search in progress had its pending words stepped over already (lock-step batch moves)

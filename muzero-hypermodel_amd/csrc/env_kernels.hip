@@ -3,41 +3,16 @@
 // One thread per env: a move is a handful of byte operations per game, far below any roofline that
 // matters; what these kernels buy is that E games advance without E host-side Python calls per move.
 // Rules restate the reference's in-repo envs (games/tictactoe.py:242-305, games/connect4.py:219-304)
-// with the Game wrappers' reward scaling; CartPole restates the classic-control equations (unpinned).
+// with the Game wrappers' reward scaling; CartPole restates the classic-control equations (unpinned).  The board rules
+// and the scripted opponents of evaluation games live in board_rules.h (also compiled for the host by a CPU check).
 #include <hip/hip_runtime.h>
 
+#include "board_rules.h"
 #include "env_layout.h"
 #include "np_legacy_rng.h"
 
 namespace mz {
 
-
-// ---- tic-tac-toe ------------------------------------------------------------------------------------
-__device__ __forceinline__ bool ttt_winner(const int8_t* b, int p) {
-    const int t = 3 * p;
-    for (int i = 0; i < 3; ++i) {
-        if (b[3 * i] + b[3 * i + 1] + b[3 * i + 2] == t) return true;
-        if (b[i] + b[i + 3] + b[i + 6] == t) return true;
-    }
-    return (b[0] + b[4] + b[8] == t) || (b[2] + b[4] + b[6] == t);
-}
-
-// ---- connect four (row 0 = bottom) ---------------------------------------------------------------------
-__device__ __forceinline__ bool c4_winner(const int8_t* b, int p) {
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 7; ++c) {
-            if (b[r * 7 + c] != p) continue;
-            if (c + 3 < 7 && b[r * 7 + c + 1] == p && b[r * 7 + c + 2] == p && b[r * 7 + c + 3] == p) return true;
-            if (r + 3 < 6 && b[(r + 1) * 7 + c] == p && b[(r + 2) * 7 + c] == p && b[(r + 3) * 7 + c] == p) return true;
-            if (r + 3 < 6 && c + 3 < 7 && b[(r + 1) * 7 + c + 1] == p && b[(r + 2) * 7 + c + 2] == p &&
-                b[(r + 3) * 7 + c + 3] == p)
-                return true;
-            if (r - 3 >= 0 && c + 3 < 7 && b[(r - 1) * 7 + c + 1] == p && b[(r - 2) * 7 + c + 2] == p &&
-                b[(r - 3) * 7 + c + 3] == p)
-                return true;
-        }
-    return false;
-}
 
 __device__ __forceinline__ double mt_uniform(uint32_t* key, int32_t* pos) {
     const int32_t a = static_cast<int32_t>(mt_next(key, pos) >> 5);
@@ -60,10 +35,27 @@ __device__ __forceinline__ void env_reset_one(const EnvParams& p, int e) {
     }
 }
 
+// Opponent mode (mzenv_set_opponent): is the side to move in env e the scripted opponent's?
+__device__ __forceinline__ bool opponent_to_move(const EnvParams& p, int e) {
+    return p.opp_kind != kOpponentSelf && (p.player[e] == 1 ? 0 : 1) != p.opp_player;
+}
+
 // One move of env e; returns whether the game ended.  a < 0: the env is left alone this move (e.g. its search
-// was not run) -- nothing happened.
+// was not run) -- nothing happened.  On the opponent's turn the incoming action is ignored: the opponent chooses,
+// drawing from env e's stream (select_opponent_action, self_play.py:189-221).  played_out / words_out (null outside
+// opponent mode): the action actually played (-1: none) and the stream words the choice consumed.
 __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, float* __restrict__ reward_out,
-                                             uint8_t* __restrict__ done_out) {
+                                             uint8_t* __restrict__ done_out, int32_t* __restrict__ played_out = nullptr,
+                                             uint32_t* __restrict__ words_out = nullptr) {
+    uint32_t words = 0;
+    if (p.game != 0 && opponent_to_move(p, e)) {
+        int32_t pos = p.opp_pos[e];
+        a = opponent_action(p.game, p.opp_kind, p.board + static_cast<size_t>(e) * p.cells, p.player[e],
+                            p.opp_key + static_cast<size_t>(e) * kMtN, &pos, &words);
+        if (words) p.opp_pos[e] = pos;
+    }
+    if (played_out) played_out[e] = a < 0 ? -1 : a;
+    if (words_out) words_out[e] = words;
     if (a < 0) {
         reward_out[e] = 0.f;
         done_out[e] = 0;
@@ -139,15 +131,9 @@ __device__ __forceinline__ void env_observe_one(const EnvParams& p, int e, float
         o[p.cells + i] = b[i] == -1 ? 1.f : 0.f;
         o[2 * p.cells + i] = static_cast<float>(pl);
     }
-    int n = 0;
-    if (p.game == 1) {
-        for (int i = 0; i < 9; ++i)
-            if (b[i] == 0) l[n++] = i;
-    } else {
-        for (int c = 0; c < 7; ++c)
-            if (b[35 + c] == 0) l[n++] = c;
-    }
-    num_legal[e] = n;
+    const int n = (p.game == 1) ? ttt_legal(b, l) : c4_legal(b, l);
+    // opponent mode: an empty legal set is the engine's "this env sits the search out" (the row stays filled)
+    num_legal[e] = opponent_to_move(p, e) ? 0 : n;
     to_play[e] = pl == 1 ? 0 : 1;
 }
 
@@ -158,10 +144,11 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvParams p, const uint8
 }
 
 __global__ __launch_bounds__(256) void env_step_kernel(EnvParams p, const int32_t* __restrict__ actions,
-                                                       float* __restrict__ reward_out, uint8_t* __restrict__ done_out) {
+                                                       float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                       int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.E) return;
-    env_step_one(p, e, actions[e], reward_out, done_out);
+    env_step_one(p, e, actions[e], reward_out, done_out, played_out, words_out);
 }
 
 __global__ __launch_bounds__(256) void env_observe_kernel(EnvParams p, float* __restrict__ obs, int32_t* __restrict__ legal,
@@ -177,10 +164,11 @@ __global__ __launch_bounds__(256) void env_advance_kernel(EnvParams p, const int
                                                           float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
                                                           float* __restrict__ obs_after, float* __restrict__ obs_next,
                                                           int32_t* __restrict__ legal, int32_t* __restrict__ num_legal,
-                                                          int32_t* __restrict__ to_play) {
+                                                          int32_t* __restrict__ to_play, int32_t* __restrict__ played_out,
+                                                          uint32_t* __restrict__ words_out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.E) return;
-    const bool done = env_step_one(p, e, actions[e], reward_out, done_out);
+    const bool done = env_step_one(p, e, actions[e], reward_out, done_out, played_out, words_out);
     env_observe_one(p, e, obs_after, legal, num_legal, to_play);
     if (done) env_reset_one(p, e);
     env_observe_one(p, e, obs_next, legal, num_legal, to_play);
@@ -190,14 +178,16 @@ hipError_t launch_env_reset(const EnvParams& p, const uint8_t* mask, hipStream_t
     env_reset_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, mask);
     return hipGetLastError();
 }
-hipError_t launch_env_step(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, hipStream_t stream) {
-    env_step_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, reward, done);
+hipError_t launch_env_step(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, int32_t* played,
+                           uint32_t* words, hipStream_t stream) {
+    env_step_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, reward, done, played, words);
     return hipGetLastError();
 }
 hipError_t launch_env_advance(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, float* obs_after,
-                              float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play, hipStream_t stream) {
+                              float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play, int32_t* played,
+                              uint32_t* words, hipStream_t stream) {
     env_advance_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, reward, done, obs_after, obs_next, legal,
-                                                                          num_legal, to_play);
+                                                                          num_legal, to_play, played, words);
     return hipGetLastError();
 }
 hipError_t launch_env_observe(const EnvParams& p, float* obs, int32_t* legal, int32_t* num_legal, int32_t* to_play,

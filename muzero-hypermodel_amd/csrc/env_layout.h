@@ -12,6 +12,11 @@ struct EnvParams {
     int32_t* steps;    // [E]         cartpole
     uint32_t* mt_key;  // [E][624]    cartpole reset stream (numpy RandomState(seed))
     int32_t* mt_pos;   // [E]
+    // opponent mode of the board games (mzenv_set_opponent): kind (board_rules.h OpponentKind), the player MuZero
+    // plays, and the caller's per-env streams the opponent draws from (the search engine's: mzmcts_rng_streams)
+    int32_t opp_kind, opp_player;
+    uint32_t* opp_key;  // [E][624]
+    int32_t* opp_pos;   // [E]
 };
 
 }  // namespace mz

@@ -100,6 +100,10 @@ struct MoveInputsExtra {
     int32_t* own_to_play = nullptr;     // [E]
     int32_t* game_moves = nullptr;      // [E]
     const uint8_t* finished = nullptr;  // [E] the env kernels' `done` of the move before, or null
+    // mzmcts_moves_sit_out: an empty legal set is a ply the caller's environment kernels play themselves (an opponent's).
+    // The env stays in the batch: the mirror's pending words are stepped over for it too (the environment kernel draws
+    // from the stream next), and the ply counts as a move of its game.
+    bool sit_out = false;
 };
 
 // Group-uniform: true = this env must not be searched in this move (see MoveCtl).

@@ -609,11 +609,16 @@ __global__ __launch_bounds__(kThreads) void move_inputs_kernel(TreeParams p, con
     words_out[e] = 0u;
     double* row = p.noise_rows + static_cast<size_t>(e) * p.A;
     for (int i = 0; i < p.A; ++i) row[i] = 0.0;
-    if (n == 0 || (stall && stall[e]) || (move_limit && move_index >= move_limit[e])) return;
+    if ((n == 0 && !extra.sit_out) || (stall && stall[e]) || (move_limit && move_index >= move_limit[e])) return;
     uint32_t* key = p.mt_key + static_cast<size_t>(e) * kMtN;
     int32_t pos = p.mt_pos[e];
     const uint32_t skip = rng_skip ? rng_skip[e] : 0u;
     for (uint32_t i = 0; i < skip; ++i) (void)mt_next(key, &pos);
+    if (n == 0) {   // a ply the environment kernels play: no noise row; it is a move of the env's game all the same
+        p.mt_pos[e] = pos;
+        if (extra.game_moves) extra.game_moves[e] += 1;
+        return;
+    }
     if (draw_noise) {
         __shared__ uint32_t window[kThreads][kNoiseWindow + 1];
         const int ahead = (kMtN - pos < kNoiseWindow) ? kMtN - pos : kNoiseWindow;

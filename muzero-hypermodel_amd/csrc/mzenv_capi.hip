@@ -10,9 +10,11 @@
 
 namespace mz {
 hipError_t launch_env_reset(const EnvParams& p, const uint8_t* mask, hipStream_t stream);
-hipError_t launch_env_step(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, hipStream_t stream);
+hipError_t launch_env_step(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, int32_t* played,
+                           uint32_t* words, hipStream_t stream);
 hipError_t launch_env_advance(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, float* obs_after,
-                              float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play, hipStream_t stream);
+                              float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play, int32_t* played,
+                              uint32_t* words, hipStream_t stream);
 hipError_t launch_env_observe(const EnvParams& p, float* obs, int32_t* legal, int32_t* num_legal, int32_t* to_play,
                               hipStream_t stream);
 hipError_t launch_seed_streams(uint32_t* keys, int32_t* pos, const uint32_t* seeds, int E, hipStream_t stream);
@@ -127,9 +129,61 @@ int mzenv_reset(mzenv* env, const uint8_t* mask, void* stream) {
     return 0;
 }
 
+int mzenv_set_opponent(mzenv* env, int32_t kind, int32_t muzero_player, uint32_t* mt_key, int32_t* mt_pos) {
+    // (the arguments are judged before the handle: a wrong call reads the same with or without a device)
+    if (kind != MZENV_OPPONENT_SELF && kind != MZENV_OPPONENT_EXPERT && kind != MZENV_OPPONENT_RANDOM)
+        return env_fail(env, -1, "mzenv_set_opponent: unknown opponent kind (self, expert or random)");
+    if (kind != MZENV_OPPONENT_SELF && (!mt_key || !mt_pos))
+        return env_fail(env, -1, "mzenv_set_opponent: the opponent needs the per-env streams it draws from");
+    if (!env) return env_fail(nullptr, -1, "mzenv_set_opponent: null handle");
+    if (kind == MZENV_OPPONENT_SELF) {
+        env->p.opp_kind = MZENV_OPPONENT_SELF;
+        env->p.opp_player = 0;
+        env->p.opp_key = nullptr;
+        env->p.opp_pos = nullptr;
+        return 0;
+    }
+    if (env->players < 2) return env_fail(env, -1, "mzenv_set_opponent: a one-player game has no opponent");
+    if (muzero_player < 0 || muzero_player >= env->players)
+        return env_fail(env, -1, "mzenv_set_opponent: muzero_player is not a player of this game");
+    env->p.opp_kind = kind;
+    env->p.opp_player = muzero_player;
+    env->p.opp_key = mt_key;
+    env->p.opp_pos = mt_pos;
+    return 0;
+}
+
+int mzenv_set_boards(mzenv* env, const int8_t* boards, const int8_t* players) {
+    if (!env || !boards || !players) return env_fail(env, -1, "mzenv_set_boards: null argument");
+    if (env->players < 2) return env_fail(env, -1, "mzenv_set_boards: not a board game");
+    const size_t E = static_cast<size_t>(env->p.E), cells = static_cast<size_t>(env->p.cells);
+    for (size_t e = 0; e < E; ++e) {
+        if (players[e] != 1 && players[e] != -1) return env_fail(env, -1, "mzenv_set_boards: a player to move is +1 or -1");
+        for (size_t i = 0; i < cells; ++i)
+            if (boards[e * cells + i] < -1 || boards[e * cells + i] > 1)
+                return env_fail(env, -1, "mzenv_set_boards: a cell is 0, +1 or -1");
+    }
+    MZENV_HIP(env, hipSetDevice(env->device));
+    MZENV_HIP(env, hipDeviceSynchronize());
+    MZENV_HIP(env, hipMemcpy(env->p.board, boards, E * cells, hipMemcpyHostToDevice));
+    MZENV_HIP(env, hipMemcpy(env->p.player, players, E, hipMemcpyHostToDevice));
+    return 0;
+}
+
 int mzenv_step(mzenv* env, const int32_t* actions, float* reward_out, uint8_t* done_out, void* stream) {
     if (!env || !actions || !reward_out || !done_out) return env_fail(env, -1, "mzenv_step: null argument");
-    MZENV_HIP(env, mz::launch_env_step(env->p, actions, reward_out, done_out, static_cast<hipStream_t>(stream)));
+    if (env->p.opp_kind != MZENV_OPPONENT_SELF)
+        return env_fail(env, -1, "mzenv_step: opponent mode is on; mzenv_step_opponent reports the moves the opponent played");
+    MZENV_HIP(env, mz::launch_env_step(env->p, actions, reward_out, done_out, nullptr, nullptr, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mzenv_step_opponent(mzenv* env, const int32_t* actions, float* reward_out, uint8_t* done_out, int32_t* played_out,
+                        uint32_t* words_out, void* stream) {
+    if (!env || !actions || !reward_out || !done_out || !played_out || !words_out)
+        return env_fail(env, -1, "mzenv_step_opponent: null argument");
+    MZENV_HIP(env, mz::launch_env_step(env->p, actions, reward_out, done_out, played_out, words_out,
+                                       static_cast<hipStream_t>(stream)));
     return 0;
 }
 
@@ -147,9 +201,23 @@ int mzenv_advance(mzenv* env, const int32_t* actions, float* reward_out, uint8_t
     if (!env || !actions || !reward_out || !done_out || !obs_after_out || !obs_next_out || !legal_out || !num_legal_out ||
         !to_play_out)
         return env_fail(env, -1, "mzenv_advance: null argument");
+    if (env->p.opp_kind != MZENV_OPPONENT_SELF)
+        return env_fail(env, -1, "mzenv_advance: opponent mode is on; mzenv_advance_opponent reports the moves the opponent played");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     MZENV_HIP(env, mz::launch_env_advance(env->p, actions, reward_out, done_out, obs_after_out, obs_next_out, legal_out,
-                                          num_legal_out, to_play_out, stream));
+                                          num_legal_out, to_play_out, nullptr, nullptr, stream));
+    return 0;
+}
+
+int mzenv_advance_opponent(mzenv* env, const int32_t* actions, float* reward_out, uint8_t* done_out, float* obs_after_out,
+                           float* obs_next_out, int32_t* legal_out, int32_t* num_legal_out, int32_t* to_play_out,
+                           int32_t* played_out, uint32_t* words_out, void* stream_) {
+    if (!env || !actions || !reward_out || !done_out || !obs_after_out || !obs_next_out || !legal_out || !num_legal_out ||
+        !to_play_out || !played_out || !words_out)
+        return env_fail(env, -1, "mzenv_advance_opponent: null argument");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    MZENV_HIP(env, mz::launch_env_advance(env->p, actions, reward_out, done_out, obs_after_out, obs_next_out, legal_out,
+                                          num_legal_out, to_play_out, played_out, words_out, stream));
     return 0;
 }
 

@@ -2,6 +2,8 @@
 // library's worker pool.
 #include "engine_host.h"
 
+#include <limits>
+
 // ---- game-history filer (include/mzhist.h) ---------------------------------------------------------------------
 struct mzhist {
     int E = 0, L = 0, obs = 0, A = 0;
@@ -19,6 +21,7 @@ struct mzhist {
     std::vector<float> fin_observations, fin_rewards;
     std::vector<double> fin_child_visits, fin_root_values;
     int fin_n = 0, fin_row = 0;
+    int64_t searched = 0;              // plies filed with a non-empty legal set
 };
 
 extern "C" {
@@ -49,6 +52,8 @@ int mzhist_create(int32_t num_envs, int32_t max_moves, int32_t obs_floats, int32
 void mzhist_destroy(mzhist* h) { delete h; }
 
 const int32_t* mzhist_lengths(const mzhist* h) { return h ? h->length.data() : nullptr; }
+
+int64_t mzhist_searched_moves(const mzhist* h) { return h ? h->searched : 0; }
 
 int mzhist_begin(mzhist* h, const float* first_observations, const int32_t* first_to_play) {
     if (!h || !first_observations) return -1;
@@ -103,8 +108,10 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
     // pass 1: how many games end per env, and how long the longest of them is
     std::atomic<int> longest{0};
     std::atomic<bool> overflow{false}, bad_legal{false};
+    std::atomic<int64_t> searched{0};
     for_envs([&](int lo, int hi) {
         int local_longest = 0;
+        int64_t local_searched = 0;
         for (int e = lo; e < hi; ++e) {
             int len = h->length[e], count = 0;
             const int k = std::min(mv->moves_done[e], M);
@@ -118,6 +125,7 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
                     for (int i = 0; i < n_legal; ++i)
                         if (legal[i] < 0 || legal[i] >= A) bad_legal.store(true);
                 }
+                local_searched += n_legal > 0 ? 1 : 0;
                 ++len;
                 if (len > h->L) overflow.store(true);
                 if (mv->done[static_cast<size_t>(m) * E + e]) {
@@ -128,6 +136,7 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
             }
             h->fin_count[e] = count;
         }
+        searched.fetch_add(local_searched, std::memory_order_relaxed);
         int seen = longest.load();
         while (local_longest > seen && !longest.compare_exchange_weak(seen, local_longest)) {
         }
@@ -140,6 +149,7 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
         h->error = "mzhist_file: a game outgrew max_moves";
         return -1;
     }
+    h->searched += searched.load();
     h->fin_offset[0] = 0;
     for (int e = 0; e < E; ++e) h->fin_offset[e + 1] = h->fin_offset[e] + h->fin_count[e];
     const int n = h->fin_offset[E];
@@ -174,8 +184,13 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
                 double* cv = row_cv + static_cast<size_t>(len) * A;
                 for (int a = 0; a < A; ++a) cv[a] = 0.0;
                 for (int i = 0; i < n_legal; ++i) cv[legal[i]] = static_cast<double>(visits[i]) / S;
-                row_rv[len] = reinterpret_cast<const double*>(at(mv->root_value_sum, mv->root_value_sum_stride, m))[e] / S;
-                row_act[len + 1] = reinterpret_cast<const int32_t*>(at(mv->actions, mv->actions_stride, m))[e];
+                if (mv->played && n_legal == 0) {   // an opponent's ply: no search statistics (see mzhist_moves.played)
+                    row_rv[len] = std::numeric_limits<double>::quiet_NaN();
+                    row_act[len + 1] = mv->played[me];
+                } else {
+                    row_rv[len] = reinterpret_cast<const double*>(at(mv->root_value_sum, mv->root_value_sum_stride, m))[e] / S;
+                    row_act[len + 1] = reinterpret_cast<const int32_t*>(at(mv->actions, mv->actions_stride, m))[e];
+                }
                 row_rew[len + 1] = mv->rewards[me];
                 std::memcpy(row_obs + static_cast<size_t>(len + 1) * obs, mv->obs_after + me * obs, sizeof(float) * obs);
                 row_tp[len + 1] = mv->to_play_after ? mv->to_play_after[me] : 0;

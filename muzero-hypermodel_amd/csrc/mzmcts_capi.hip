@@ -247,6 +247,24 @@ int mzmcts_rng_set_state(mzmcts_engine* eng, int32_t env, const uint32_t* key, i
     return MZMCTS_OK;
 }
 
+int mzmcts_rng_streams(mzmcts_engine* eng, uint32_t** mt_key_dev, int32_t** mt_pos_dev) {
+    if (!eng || !mt_key_dev || !mt_pos_dev) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_rng_streams: null argument");
+    *mt_key_dev = eng->p.mt_key;
+    *mt_pos_dev = eng->p.mt_pos;
+    return MZMCTS_OK;
+}
+
+int mzmcts_rng_consumed(mzmcts_engine* eng, const uint32_t* words) {
+    if (!eng || !words) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_rng_consumed: null argument");
+    for (int e = 0; e < eng->p.E; ++e) {
+        if (words[e] && eng->lag[e])
+            return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_rng_consumed: the host mirror of an env was ahead of its device copy "
+                                                 "when the words were drawn (the draw read a stale stream)");
+        eng->behind[e] += words[e];
+    }
+    return MZMCTS_OK;
+}
+
 int mzmcts_rng_get_state(mzmcts_engine* eng, int32_t env, uint32_t* key, int32_t* pos, int32_t* has_gauss,
                          double* cached, void* stream_) {
     if (!eng || !key || !pos || env < 0 || env >= eng->p.E)

@@ -324,6 +324,7 @@ int mzmcts_moves_prepare_device(mzmcts_engine* eng, int32_t n_moves, const int32
     b.temperature_threshold = 0;                     // (mzmcts_moves_temperature_threshold sets it per batch)
     b.finished = nullptr;
     b.lockstep_open = false;
+    b.sit_out = false;                               // (mzmcts_moves_sit_out sets it per batch)
     b.dev_legal = legal_dev;
     b.dev_nlegal = num_legal_dev;
     b.dev_to_play = to_play_dev;
@@ -481,6 +482,15 @@ int mzmcts_moves_temperature_threshold(mzmcts_engine* eng, int32_t threshold, co
     return MZMCTS_OK;
 }
 
+int mzmcts_moves_sit_out(mzmcts_engine* eng, int32_t enabled) {
+    if (!eng) return MZMCTS_ERR_INVALID;
+    mzmcts_engine::MoveBatch& b = eng->batch;
+    if (!b.in_flight || !b.device_inputs || b.enqueued != 0)
+        return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_sit_out: call right after mzmcts_moves_prepare_device");
+    b.sit_out = enabled != 0;
+    return MZMCTS_OK;
+}
+
 int mzmcts_moves_finished(mzmcts_engine* eng, const uint8_t* finished_dev) {
     if (!eng) return MZMCTS_ERR_INVALID;
     mzmcts_engine::MoveBatch& b = eng->batch;
@@ -503,6 +513,7 @@ static mz::MoveInputsExtra move_extras(mzmcts_engine* eng, bool own_inputs) {
         x.game_moves = reinterpret_cast<int32_t*>(b.d_game_moves);
         x.finished = b.finished;
     }
+    x.sit_out = b.sit_out;
     return x;
 }
 
@@ -668,12 +679,17 @@ int mzmcts_moves_collect(mzmcts_engine* eng, int32_t* moves_done, int32_t* actio
         eng->for_each_env([&](int lo, int hi) {
             int64_t local = 0, local_depth = 0;
             for (int e = lo; e < hi; ++e) {
+                // (sit-out batches: a move recorded with an empty legal set was played by the caller's environment
+                // kernels -- the env stays live, its output block of that move holds nothing of the search)
+                auto sat_out = [&](int m) { return b.sit_out && reinterpret_cast<const int32_t*>(inputs(m, b.o2_nlegal))[e] == 0; };
                 int k = 0;
-                while (k < M && reinterpret_cast<const int32_t*>(block(k, b.o_actions))[e] >= 0) ++k;
+                while (k < M && (sat_out(k) || reinterpret_cast<const int32_t*>(block(k, b.o_actions))[e] >= 0)) ++k;
                 if (moves_done) moves_done[e] = k;
                 uint64_t words = 0;
+                int searched = 0;
                 for (int m = 0; m < M; ++m) {
-                    const bool live = m < k;
+                    const bool live = m < k && !sat_out(m);
+                    searched += live ? 1 : 0;
                     const size_t me = static_cast<size_t>(m) * E + e;
                     if (actions) actions[me] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_actions))[e] : -1;
                     if (visits)
@@ -690,9 +706,10 @@ int mzmcts_moves_collect(mzmcts_engine* eng, int32_t* moves_done, int32_t* actio
                     }
                 }
                 // (an env that searched nothing kept the pending words of its mirror: they were not stepped over)
-                if (k == 0) eng->lag[e] += reinterpret_cast<const uint32_t*>(c.h_in + b.o_skip)[e];
+                // (in a sit-out batch move 0 steps over them for every env)
+                if (k == 0 && !(b.sit_out && M > 0)) eng->lag[e] += reinterpret_cast<const uint32_t*>(c.h_in + b.o_skip)[e];
                 eng->behind[e] += words;             // (stepped over when the mirror is next asked for: mirror())
-                local += k;
+                local += searched;                   // (the profile counts simulations that ran: not the sat-out plies)
             }
             played_total.fetch_add(local, std::memory_order_relaxed);
             depth_total.fetch_add(local_depth, std::memory_order_relaxed);

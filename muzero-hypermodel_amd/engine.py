@@ -625,6 +625,25 @@ class BatchedMCTS:
         self._batch_keep.append(done_dev)
         self._check(self._lib.mzmcts_moves_finished(self._h, done_dev.data_ptr()))
 
+    def moves_sit_out(self, enabled=True):
+        """For the batch just prepared with moves_prepare_device: an empty legal set is a ply the caller's environment
+        kernels play themselves (an opponent's, games.device.DeviceEnvs.set_opponent) -- the env stays live in the
+        batch instead of ending its count at the unsearched move (include/mzmcts.h mzmcts_moves_sit_out)."""
+        self._check(self._lib.mzmcts_moves_sit_out(self._h, 1 if enabled else 0))
+
+    def rng_streams(self):
+        """Device addresses (mt_key u32 [E, 624], mt_pos i32 [E]) of the per-env streams, for kernels that must draw
+        from them as other users of numpy.random do in a reference worker; report what they drew with rng_consumed."""
+        key, pos = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.mzmcts_rng_streams(self._h, ctypes.byref(key), ctypes.byref(pos)))
+        return key.value, pos.value
+
+    def rng_consumed(self, words):
+        """`words` [E]: 32-bit words the caller's kernels drew from each env's device stream since the last report."""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        assert w.shape == (self.E,)
+        self._check(self._lib.mzmcts_rng_consumed(self._h, ptr(w, c_u32_p)))
+
     def moves_actions(self, move):
         """Device tensor (int32 [E]) holding move `move`'s sampled actions once its search has run."""
         addr = self._lib.mzmcts_moves_actions(self._h, int(move))

@@ -11,6 +11,7 @@ import torch
 from .. import _native
 
 GAME_IDS = {"cartpole": 0, "tictactoe": 1, "connect4": 2}
+OPPONENT_KINDS = {"self": 0, "expert": 1, "random": 2}      # include/mzenv.h MZENV_OPPONENT_*
 
 
 class DeviceEnvs:
@@ -44,6 +45,10 @@ class DeviceEnvs:
             self.reward = torch.zeros(self.E, dtype=torch.float32, device=self.device)
             self.done = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
             self._actions = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+            # opponent mode: the action actually played and the stream words the opponent's choice consumed (u32 bits)
+            self.played = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+            self.words = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+        self.opponent = ("self", 0)
         self.reset()
 
     def _stream(self):
@@ -64,15 +69,41 @@ class DeviceEnvs:
         except Exception:
             pass
 
+    def set_opponent(self, kind, muzero_player=0, engine=None):
+        """Evaluation games (reference self_play.py:189-221): `kind` "expert" or "random" plays every side but
+        `muzero_player`, drawing from `engine`'s per-env RNG streams (engine.BatchedMCTS: in a reference worker the
+        opponent and the search share numpy's global generator); "self" switches the mode off.  While it is on,
+        observe / advance report num_legal = 0 where the opponent is to move (the engine leaves such an env out of the
+        search), step / advance play the opponent's move there whatever action comes in, and both fill `played` (the
+        action actually played) and `words` (stream words consumed: hand their sums to engine.rng_consumed)."""
+        if kind not in OPPONENT_KINDS:
+            raise NotImplementedError('device envs play opponent "self", "expert" or "random" ("human": use SelfPlay)')
+        key = pos = None
+        if kind != "self":
+            if engine is None:
+                raise ValueError("set_opponent: the opponent draws from the search engine's streams; pass engine=")
+            key, pos = engine.rng_streams()
+        self._check(self._lib.mzenv_set_opponent(self._h, OPPONENT_KINDS[kind], int(muzero_player), key, pos))
+        self.opponent = ("self", 0) if kind == "self" else (kind, int(muzero_player))
+        self._opponent_engine = engine if kind != "self" else None    # (its streams must outlive the mode)
+
+    def set_boards(self, boards, players):
+        """Put the envs of a board game into given positions: boards int8 [E, cells] (0 / +1 / -1; connect four row 0
+        = bottom), players int8 [E] (+1 / -1 to move)."""
+        boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(self.E, -1)
+        players = np.ascontiguousarray(players, dtype=np.int8).reshape(self.E)
+        self._check(self._lib.mzenv_set_boards(self._h, boards.ctypes.data, players.ctypes.data))
+
     def reset(self, mask=None):
         """Game.reset() for the envs whose mask entry is non-zero (uint8 device tensor; None = all)."""
         self._keep = mask
         self._check(self._lib.mzenv_reset(self._h, None if mask is None else mask.data_ptr(), self._stream()))
 
-    def step(self, actions, reward=None, done=None):
+    def step(self, actions, reward=None, done=None, played=None, words=None):
         """Game.step per env; `actions`: int array / tensor [E] (negative = leave that env alone).
         Returns (reward, done) device tensors: the caller's `reward` (f32 [E]) / `done` (u8 [E]) when given,
-        otherwise this object's own buffers (valid until the next step)."""
+        otherwise this object's own buffers (valid until the next step).  In opponent mode (set_opponent) the played
+        actions and consumed stream words go to `played` / `words` (int32 [E]; default: this object's buffers)."""
         if torch.is_tensor(actions) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous():
             src = actions                                    # e.g. the search's own action buffer: no copy
         elif torch.is_tensor(actions):
@@ -81,14 +112,30 @@ class DeviceEnvs:
             src = self._actions.copy_(torch.from_numpy(np.ascontiguousarray(actions, dtype=np.int32)), non_blocking=True)
         reward = self.reward if reward is None else reward
         done = self.done if done is None else done
+        if self.opponent[0] != "self" or played is not None:
+            played = self.played if played is None else played
+            words = self.words if words is None else words
+            self._keep_step = (src, reward, done, played, words)
+            self._check(self._lib.mzenv_step_opponent(self._h, src.data_ptr(), reward.data_ptr(), done.data_ptr(),
+                                                      played.data_ptr(), words.data_ptr(), self._stream()))
+            return reward, done
         self._keep_step = (src, reward, done)
         self._check(self._lib.mzenv_step(self._h, src.data_ptr(), reward.data_ptr(), done.data_ptr(), self._stream()))
         return reward, done
 
-    def advance(self, actions, reward, done, obs_after, obs_next):
+    def advance(self, actions, reward, done, obs_after, obs_next, played=None, words=None):
         """One self-play move of every env in one call: step, observation after the move (terminal ones
         included), reset of the finished envs, observation the next search sees.  All arguments are resident
-        tensors (actions int32 [E]; outputs as in step / observe)."""
+        tensors (actions int32 [E]; outputs as in step / observe; played / words as in step)."""
+        if self.opponent[0] != "self" or played is not None:
+            played = self.played if played is None else played
+            words = self.words if words is None else words
+            self._keep_step = (actions, reward, done, obs_after, obs_next, played, words)
+            self._check(self._lib.mzenv_advance_opponent(self._h, actions.data_ptr(), reward.data_ptr(), done.data_ptr(),
+                                                         obs_after.data_ptr(), obs_next.data_ptr(), self.legal.data_ptr(),
+                                                         self.num_legal.data_ptr(), self.to_play.data_ptr(),
+                                                         played.data_ptr(), words.data_ptr(), self._stream()))
+            return obs_next
         self._keep_step = (actions, reward, done, obs_after, obs_next)
         self._check(self._lib.mzenv_advance(self._h, actions.data_ptr(), reward.data_ptr(), done.data_ptr(),
                                             obs_after.data_ptr(), obs_next.data_ptr(), self.legal.data_ptr(),

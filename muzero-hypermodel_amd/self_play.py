@@ -709,7 +709,9 @@ class PackedGames:
       rewards[i, 0..length]        reward_history      (index 0 = 0)
       to_play[i, 0..length]        to_play_history
       child_visits[i, 0..length-1] visit-count targets, root_values[i, 0..length-1]
-    Entries past a game's length are padding."""
+    Entries past a game's length are padding.  An opponent's ply of an evaluation game keeps its slot: its root value
+    is NaN (the reference's None: store_search_statistics(None, ...), self_play.py:497-512) and its child_visits row is
+    zero; `history(i)` turns the NaN into None and drops that row, as the reference appends none."""
 
     __slots__ = ("env_index", "length", "observations", "actions", "rewards", "to_play", "child_visits", "root_values")
 
@@ -728,8 +730,17 @@ class PackedGames:
         gh.action_history = self.actions[i, : n + 1].tolist()
         gh.reward_history = self.rewards[i, : n + 1].tolist()
         gh.to_play_history = self.to_play[i, : n + 1].tolist()
-        gh.child_visits = self.child_visits[i, :n].tolist()
-        gh.root_values = self.root_values[i, :n].tolist()
+        root_values = self.root_values[i, :n]
+        opponent_ply = numpy.isnan(root_values)
+        if opponent_ply.any():
+            if self.child_visits[i, :n][opponent_ply].any():
+                # (an opponent's ply has a zero row as well: this NaN came out of a search)
+                raise ValueError(f"game {i}: a searched ply has a NaN root value")
+            gh.child_visits = self.child_visits[i, :n][~opponent_ply].tolist()
+            gh.root_values = [None if o else v for v, o in zip(root_values.tolist(), opponent_ply.tolist())]
+        else:
+            gh.child_visits = self.child_visits[i, :n].tolist()
+            gh.root_values = root_values.tolist()
         return gh
 
 
@@ -791,16 +802,23 @@ class HistoryFiler:
             tp[...] = tp32
             lengths[...] = len32
 
+    def searched_moves(self):
+        """Plies filed so far that were searched (a non-empty legal set): all of them in self-play, MuZero's in
+        evaluation games."""
+        return int(self._lib.mzhist_searched_moves(self._h))
+
     def lengths(self):
         addr = self._lib.mzhist_lengths(self._h)
         return numpy.ctypeslib.as_array(self._ct.cast(addr, self._ct.POINTER(self._ct.c_int32)), shape=(self.E,))
 
     def file(self, out, legal, num_legal, num_simulations, rewards, done, obs_after, obs_next, to_play_after=None,
-             to_play_next=None):
+             to_play_next=None, played=None):
         """out: engine.moves_collect() result (copies or ring views); legal [E,A] / num_legal [E] for the whole batch or
         [M,E,A] / [M,E] per move (engine.moves_inputs); rewards f32 [M,E], done u8 [M,E],
         obs_after / obs_next f32 [M,E,...] host arrays; to_play_after / to_play_next [M,E] for two-player games.
-        Returns PackedGames of the games that ended, or None."""
+        played int32 [M,E] (evaluation games: the actions the environment kernels actually played): a ply whose legal
+        set is empty is then an opponent's -- its action comes from `played`, its root value is NaN, its child_visits
+        row zero (include/mzhist.h).  Returns PackedGames of the games that ended, or None."""
         ct = self._ct
         M = int(out["actions"].shape[0])
         def per_move_rows(a):
@@ -829,6 +847,10 @@ class HistoryFiler:
         if to_play_after is not None:
             keep += [numpy.ascontiguousarray(to_play_after, dtype=numpy.int32), numpy.ascontiguousarray(to_play_next, dtype=numpy.int32)]
             mv.to_play_after, mv.to_play_next = keep[7].ctypes.data, keep[8].ctypes.data
+        if played is not None:
+            keep.append(numpy.ascontiguousarray(played, dtype=numpy.int32))
+            assert keep[-1].shape == (M, self.E)
+            mv.played = keep[-1].ctypes.data
         n = ct.c_int32()
         if self._lib.mzhist_file(self._h, ct.byref(mv), ct.byref(n)) != 0:
             raise RuntimeError(self._lib.mzhist_last_error(self._h).decode())
@@ -914,23 +936,65 @@ class DeviceSelfPlay(ManyEnvLoop):
     def set_weights(self, weights):
         self.model.set_weights(weights)
 
-    def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None):
-        """One move in every env (the body of play_game's loop, self_play.py:129-182)."""
-        self.step_begin(on_game, on_games)
+    def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None, opponent=None,
+             muzero_player=None):
+        """One move in every env (the body of play_game's loop, self_play.py:129-182).  `opponent` / `muzero_player` as
+        in BatchedSelfPlay.step (default: what continuous_self_play's test mode set, else "self"): where it is not
+        MuZero's turn the environment kernels play the opponent's move, drawn on that env's stream, and the ply is filed
+        without search statistics.  Such a step is a one-move device-input batch (the opponent draws on the device copy
+        of the stream, which a host-sampled step leaves behind its mirror)."""
+        self.step_begin(on_game, on_games, opponent, muzero_player, temperature, temperature_threshold)
         self.step_end(temperature, temperature_threshold, on_game, on_games)
 
-    def _no_opponent(self):
-        if getattr(self, "_opponent", ("self", 0))[0] != "self":
-            raise NotImplementedError("device-resident envs play \"self\" in test mode; BatchedSelfPlay (host Game "
-                                      "plugins) plays expert / random opponents")
+    def _resolve_opponent(self, opponent, muzero_player):
+        if opponent is None:
+            opponent, muzero_player = getattr(self, "_opponent", ("self", 0))
+        elif muzero_player is None:
+            muzero_player = self.config.muzero_player
+        if opponent not in ("self", "expert", "random"):
+            raise NotImplementedError('many-env actors play opponent "self", "expert" or "random" ("human": use SelfPlay)')
+        return (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
 
-    def step_begin(self, on_game=None, on_games=None):
+    def _set_env_mode(self, mode):
+        """Switch the envs between self-play and an opponent; the positions stay, the legal counts the searches read are
+        observed again in the new mode."""
+        if self.envs.opponent == mode:
+            return
+        self.envs.set_opponent(mode[0], mode[1], self.engine)
+        obs, _, _, _ = self.envs.observe()
+        self._cur = dict(obs_dev=obs, on_device_only=True)
+
+    def _opponent_step_check(self, temperature):
+        """An opponent's plies exist in the device-input form of a move batch only: say what rules it out."""
+        cfg = self.config
+        if cfg.max_moves < self.envs.max_episode_steps:
+            raise NotImplementedError("a step against an opponent runs as a move batch, which ends games where the "
+                                      "environment does; max_moves is shorter")
+        if not 0.0 < float(cfg.root_dirichlet_alpha) <= 1.0:
+            raise NotImplementedError("a step against an opponent runs as a device-input move batch, whose exploration "
+                                      "noise is drawn on the GPU for 0 < root_dirichlet_alpha <= 1 only")
+        if not (temperature == 0 or temperature == float("inf") or _native.exact_inverse_temperature(temperature)):
+            raise NotImplementedError("a step against an opponent runs as a device-input move batch, whose actions are "
+                                      f"sampled on the GPU at temperature 0, inf or 1/k (k = 1..4) only; got {temperature}")
+
+    def step_begin(self, on_game=None, on_games=None, opponent=None, muzero_player=None, temperature=None,
+                   temperature_threshold=None):
         """First half of step(): queue the search of every env's current position on the engine's stream and return
         (the GPU works; `step_end` waits).  Two actors on streams of their own alternate their halves
-        (PipelinedDeviceSelfPlay): one's host work runs under the other's search."""
-        self._no_opponent()
+        (PipelinedDeviceSelfPlay): one's host work runs under the other's search.  Against an opponent the whole move
+        is queued here (search, action sampling, env step: a one-move batch), so the temperature is needed already."""
+        mode = self._resolve_opponent(opponent, muzero_player)
+        if mode[0] != "self":
+            if temperature is None:
+                raise ValueError("step_begin against an opponent samples the action on the device: pass temperature")
+            self._opponent_step_check(temperature)
+            self._device_batch_begin(1, temperature, on_game, on_games, temperature_threshold or 0, *mode)
+            self._device_batch_move(0)
+            self._step_is_batch = True
+            return
         self.flush(on_game, on_games)      # first: the unfiled batch holds views of the download ring
         self._drop_batch()
+        self._set_env_mode(mode)
         cur = self._current()
         if self.engine._fc_model is not None:
             self.engine.search_fused_begin(cur["obs_dev"].reshape(self.E, -1), cur["legal"], cur["to_play"], True,
@@ -941,6 +1005,11 @@ class DeviceSelfPlay(ManyEnvLoop):
 
     def step_end(self, temperature, temperature_threshold=None, on_game=None, on_games=None):
         """Second half of step(): wait for the search, sample the actions, step the envs, file the move."""
+        if getattr(self, "_step_is_batch", False):       # against an opponent: step_begin queued the whole move
+            self._step_is_batch = False
+            self._device_batch_end(on_game, on_games)
+            self.flush(on_game, on_games)
+            return
         cur = self._cur
         self.engine.readout()
         if temperature_threshold:
@@ -1007,15 +1076,19 @@ class DeviceSelfPlay(ManyEnvLoop):
             self._tp[idx, 0] = to_play_next[idx]
 
     # ---- whole batches of moves on the device (engine.moves_*, include/mzmcts.h) ---------------------------
-    def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None):
+    def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, opponent=None,
+                   muzero_player=None):
         """`n_moves` moves of every env with no host round trip in between: search (which samples the action),
         env step, terminal observation, reset of finished envs, next observation -- all queued on one stream.
         Fully-connected networks search in the fused whole-move kernel (games with a constant legal set: the exploration
         noise of the whole batch is drawn up front, and the next batch's while this one runs); residual networks search
         lock-step (engine.moves_enqueue_lockstep) with inputs, noise and action sampling on the device.
         `temperature_threshold` (default config.temperature_threshold) is play_game's rule, applied per env and move.
-        An env may come back with fewer than n_moves moves played (it plays the rest next time)."""
+        An env may come back with fewer than n_moves moves played (it plays the rest next time).
+        `opponent` / `muzero_player` as in step(): an opponent's plies are played by the environment kernels inside the
+        batch (always its device-input form; every env then plays all n_moves plies)."""
         E, eng, envs, cfg = self.E, self.engine, self.envs, self.config
+        mode = self._resolve_opponent(opponent, muzero_player)
         if cfg.max_moves < envs.max_episode_steps:
             raise NotImplementedError("play_moves ends games where the environment does; max_moves is shorter")
         # Everything but a fused search of a game with a constant legal set takes the device-input form of the batch:
@@ -1024,8 +1097,10 @@ class DeviceSelfPlay(ManyEnvLoop):
         # switch the kernels make from per-game move counters they keep on the device)
         if temperature_threshold is None:
             temperature_threshold = cfg.temperature_threshold
-        if not getattr(envs, "constant_legal_actions", False) or eng._fc_model is None or temperature_threshold:
-            return self._play_moves_device_inputs(n_moves, temperature, on_game, on_games, temperature_threshold)
+        if (not getattr(envs, "constant_legal_actions", False) or eng._fc_model is None or temperature_threshold
+                or mode[0] != "self"):
+            return self._play_moves_device_inputs(n_moves, temperature, on_game, on_games, temperature_threshold, *mode)
+        self._set_env_mode(mode)
         cur = self._current()
         params = (int(n_moves), float(temperature))
         if getattr(self, "_batch_ready", None) != params:
@@ -1052,30 +1127,36 @@ class DeviceSelfPlay(ManyEnvLoop):
         host = {k: pinned[k][:n_moves].numpy() for k in ("reward", "done", "obs_after", "obs_next")}
         eng.moves_submit_next()
         self._batch_ready = params
-        self._unfiled = (out, host, cur["legal"], cur["num_legal"], n_moves, None, None)
+        self._unfiled = (out, host, cur["legal"], cur["num_legal"], n_moves, None, None, None)
         self._cur = dict(cur, obs_dev=obs_in, obs=host["obs_next"][n_moves - 1])
         self.moves_played += int(out["moves_done"].sum())
         return out["moves_done"].copy()
 
-    def _play_moves_device_inputs(self, n_moves, temperature, on_game, on_games, temperature_threshold=None):
+    def _play_moves_device_inputs(self, n_moves, temperature, on_game, on_games, temperature_threshold=None,
+                                  opponent=None, muzero_player=None):
         """play_moves with the batch's inputs on the device: the searches read the legal sets and players to move from the
         environment kernels' device outputs and draw their exploration noise on the device (engine.moves_prepare_device),
         so a whole batch -- games ending and restarting inside it -- is queued without the host; afterwards every move
         is filed with the legal set it was searched with.  The search of a move is the fused whole-move kernel
         (fully-connected networks) or the lock-step loop with this actor's network (residual networks)."""
-        self._device_batch_begin(n_moves, temperature, on_game, on_games, temperature_threshold)
+        self._device_batch_begin(n_moves, temperature, on_game, on_games, temperature_threshold, opponent, muzero_player)
         for m in range(n_moves):
             self._device_batch_move(m)
         return self._device_batch_end(on_game, on_games)
 
     # (the three phases are separate so that PipelinedDeviceSelfPlay can interleave the batches of its groups move by move)
-    def _device_batch_begin(self, n_moves, temperature, on_game, on_games, temperature_threshold):
+    def _device_batch_begin(self, n_moves, temperature, on_game, on_games, temperature_threshold, opponent=None,
+                            muzero_player=None):
         eng, envs = self.engine, self.envs
+        mode = self._resolve_opponent(opponent, muzero_player)
         if getattr(self, "_batch_ready", None) or temperature_threshold:
             # a batch of the pre-drawn form is waiting to be filed / the threshold rule needs the games' current lengths
             self.flush(on_game, on_games)
         self._drop_batch()
+        self._set_env_mode(mode)
         eng.moves_prepare_device(n_moves, envs.legal, envs.num_legal, envs.to_play, temperature, True)
+        if mode[0] != "self":
+            eng.moves_sit_out(True)        # the opponent's plies: played by the environment kernels, filed from `played`
         if temperature_threshold:
             eng.moves_temperature_threshold(temperature_threshold, self._len)
         ring = self._move_ring(n_moves)
@@ -1086,7 +1167,8 @@ class DeviceSelfPlay(ManyEnvLoop):
         pinned = ring["pinned"][ring["flip"]]
         ring["flip"] ^= 1
         self._dev_batch = dict(n_moves=n_moves, ring=ring, obs_in=self._cur["obs_dev"], threshold=temperature_threshold,
-                               pinned=pinned)
+                               pinned=pinned, keys=("reward", "done", "obs_after", "obs_next")
+                               + (("played", "words") if mode[0] != "self" else ()))
 
     def _device_batch_move(self, m):
         b, eng, envs = self._dev_batch, self.engine, self.envs
@@ -1097,13 +1179,15 @@ class DeviceSelfPlay(ManyEnvLoop):
             eng.moves_enqueue(b["obs_in"].reshape(self.E, -1).contiguous())
         else:
             eng.moves_enqueue_lockstep(self.model, b["obs_in"])
+        opponent = "played" in b["keys"]
         b["obs_in"] = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
-                                   ring["obs_next"][m])
+                                   ring["obs_next"][m], played=ring["played"][m] if opponent else None,
+                                   words=ring["words"][m] if opponent else None)
         ran = torch.cuda.Event()
         ran.record(torch.cuda.current_stream(self.device))
         self._copy_stream.wait_event(ran)
         with torch.cuda.stream(self._copy_stream):
-            for k in ("reward", "done", "obs_after", "obs_next"):
+            for k in b["keys"]:
                 b["pinned"][k][m].copy_(ring[k][m], non_blocking=True)
 
     def _device_batch_end(self, on_game, on_games):
@@ -1118,12 +1202,17 @@ class DeviceSelfPlay(ManyEnvLoop):
         pinned = b["pinned"]
         last_to_play = envs.to_play.cpu().numpy()
         self._copy_stream.synchronize()                  # (the last move's downloads)
-        host = {k: pinned[k][:n_moves].numpy() for k in ("reward", "done", "obs_after", "obs_next")}
+        host = {k: pinned[k][:n_moves].numpy() for k in b["keys"]}
+        played = None
+        if "played" in host:
+            # the opponents drew on the device copies of the streams: the host mirrors step over those words
+            played = host["played"]
+            eng.rng_consumed(host["words"].view(numpy.uint32).sum(axis=0, dtype=numpy.uint64))
         two_players = len(self.config.players) > 1
         to_play = inputs["to_play"]
         to_play_after = (1 - to_play) if two_players else numpy.zeros_like(to_play)
         to_play_next = numpy.concatenate([to_play[1:], last_to_play[None]], axis=0)
-        self._unfiled = (out, host, inputs["legal"], inputs["num_legal"], n_moves, to_play_after, to_play_next)
+        self._unfiled = (out, host, inputs["legal"], inputs["num_legal"], n_moves, to_play_after, to_play_next, played)
         # the envs' current positions stay on the device: the next batch starts from the last move's observation (the
         # kernels' output, where it lies); a step() fetches what it needs first (_current)
         self._cur = dict(obs_dev=b["obs_in"], on_device_only=True)
@@ -1134,9 +1223,8 @@ class DeviceSelfPlay(ManyEnvLoop):
         """Can a pass of `moves_per_pass` moves run as one move batch on the device (play_moves)?"""
         if device_inputs is None:
             device_inputs = (not getattr(self.envs, "constant_legal_actions", False) or self.engine._fc_model is None
-                             or bool(temperature_threshold))
+                             or bool(temperature_threshold) or getattr(self, "_opponent", ("self", 0))[0] != "self")
         return (moves_per_pass is not None and self.config.max_moves >= self.envs.max_episode_steps
-                and getattr(self, "_opponent", ("self", 0))[0] == "self"
                 and (temperature == 0 or _native.exact_inverse_temperature(temperature))
                 # (a device-input batch draws its exploration noise on the GPU: the legacy gamma sampler for shapes <= 1)
                 and (not device_inputs or 0.0 < float(self.config.root_dirichlet_alpha) <= 1.0))
@@ -1158,11 +1246,12 @@ class DeviceSelfPlay(ManyEnvLoop):
         (HistoryFiler, include/mzhist.h): one pass over the batch on the library's worker pool."""
         if getattr(self, "_unfiled", None) is None:
             return
-        out, host, legal, num_legal, n_moves, to_play_after, to_play_next = self._unfiled
+        out, host, legal, num_legal, n_moves, to_play_after, to_play_next, played = self._unfiled
         self._unfiled = None
         filer = self._history_filer()
         batch = filer.file(out, legal, num_legal, self.config.num_simulations, host["reward"], host["done"],
-                           host["obs_after"], host["obs_next"], to_play_after=to_play_after, to_play_next=to_play_next)
+                           host["obs_after"], host["obs_next"], to_play_after=to_play_after, to_play_next=to_play_next,
+                           played=played)
         self._len[:] = filer.lengths()
         if batch is not None:
             self.games_finished += len(batch)
@@ -1171,6 +1260,12 @@ class DeviceSelfPlay(ManyEnvLoop):
             if on_game is not None:
                 for i, e in enumerate(batch.env_index):
                     on_game(int(e), batch.history(i))
+
+    @property
+    def searched_moves(self):
+        """Env-moves filed so far that ran a search (moves_played counts the opponent's plies too)."""
+        filer = getattr(self, "_filer", None)
+        return 0 if filer is None else filer.searched_moves()
 
     def _history_filer(self):
         """The native filer takes over the rows of the running games (and hands them back to step())."""
@@ -1195,9 +1290,13 @@ class DeviceSelfPlay(ManyEnvLoop):
             ring = dict(reward=torch.zeros((n_moves, self.E), dtype=torch.float32, device=dev),
                         done=torch.zeros((n_moves, self.E), dtype=torch.uint8, device=dev),
                         obs_after=torch.zeros((n_moves, self.E) + shape, dtype=torch.float32, device=dev),
-                        obs_next=torch.zeros((n_moves, self.E) + shape, dtype=torch.float32, device=dev))
+                        obs_next=torch.zeros((n_moves, self.E) + shape, dtype=torch.float32, device=dev),
+                        # evaluation games: the actions the environment kernels played, the stream words (u32 bits) the
+                        # opponents consumed
+                        played=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev),
+                        words=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev))
             ring["pinned"] = [{k: torch.zeros(ring[k].shape, dtype=ring[k].dtype).pin_memory()
-                               for k in ("reward", "done", "obs_after", "obs_next")} for _ in range(2)]
+                               for k in ("reward", "done", "obs_after", "obs_next", "played", "words")} for _ in range(2)]
             ring["flip"] = 0
             self._ring = ring
         return ring
@@ -1249,6 +1348,10 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
     def games_finished(self):
         return sum(a.games_finished for a in self.actors)
 
+    @property
+    def searched_moves(self):
+        return sum(a.searched_moves for a in self.actors)
+
     def set_weights(self, weights):
         self._no_batch_queued("set_weights")
         for a in self.actors:
@@ -1268,13 +1371,35 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             on_games(batch)
         return one, (None if on_games is None else many)
 
-    def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None, prefetch=True):
+    def _set_opponent(self, opponent, muzero_player):
+        """The groups play what this actor plays (`opponent` None: what continuous_self_play's test mode set)."""
+        if opponent is not None:
+            mode = (opponent, self.config.muzero_player if muzero_player is None else muzero_player)
+        else:
+            mode = getattr(self, "_opponent", ("self", 0))
+        for actor in self.actors:
+            actor._opponent = mode
+        return mode
+
+    def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None, prefetch=True, opponent=None,
+             muzero_player=None):
         """One move in every env of every group (each group's search was queued during the previous call).
         prefetch=False leaves no search queued behind (the next call then starts them): what a caller wants before it
-        changes the weights, so that no move is searched with the weights of the move before."""
+        changes the weights, so that no move is searched with the weights of the move before.
+        Against an opponent (`opponent` / `muzero_player` as in DeviceSelfPlay.step) the move is a one-move batch of every
+        group, queued on the groups' streams in turn; nothing is prefetched."""
         self._no_batch_queued("step")
+        mode = self._set_opponent(opponent, muzero_player)
+        if mode[0] != "self":
+            if any(self._started):
+                raise RuntimeError("step against an opponent: a search is queued ahead; call step(..., prefetch=False) first")
+            for actor in self.actors:
+                actor._opponent_step_check(temperature)
+            self.play_moves(1, temperature, on_game, on_games, temperature_threshold or 0, opponent=mode[0],
+                            muzero_player=mode[1])
+            self.flush(on_game, on_games)
+            return
         for g, actor in enumerate(self.actors):
-            actor._opponent = getattr(self, "_opponent", ("self", 0))
             if not self._started[g]:
                 with torch.cuda.stream(self.streams[g]):
                     actor.step_begin(*self._callbacks(g, on_game, on_games))
@@ -1288,7 +1413,8 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                     actor.step_begin(one, many)      # the next move's search runs while the other groups are served
                     self._started[g] = True
 
-    def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, prefetch=False):
+    def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, prefetch=False,
+                   opponent=None, muzero_player=None):
         """`n_moves` moves of every env of every group with no host round trip (DeviceSelfPlay.play_moves in its
         device-input form): each group's batch is queued on the group's own stream, move by move in turn, so the
         kernels of the groups fill each other's gaps (a tower workgroup's fill / epilogue / export phases leave the matrix
@@ -1298,8 +1424,10 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         anything is filed: collecting, filing and the callbacks of one group then run under the other group's kernels
         and the GPU never drains between calls -- the batch form of step()'s prefetch, with the same contract: the batch a
         call returns was queued by the call before (with that call's parameters and the weights of that time), and
-        the last call before the weights change passes prefetch=False."""
+        the last call before the weights change passes prefetch=False.
+        `opponent` / `muzero_player` as in DeviceSelfPlay.play_moves (a prefetched batch plays what its call asked for)."""
         cfg = self.config
+        self._set_opponent(opponent, muzero_player)
         if temperature_threshold is None:
             temperature_threshold = cfg.temperature_threshold
         queued = self.__dict__.setdefault("_batch_queued", [False] * self.groups)
@@ -1342,8 +1470,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         device-input form; nothing stays queued behind the pass: a weight pull follows), else move by move with the
         groups' halves alternating -- the last move of a pass queues nothing behind it either."""
         finished = []
-        for actor in self.actors:
-            actor._opponent = getattr(self, "_opponent", ("self", 0))
+        self._set_opponent(None, None)
         if self.actors[0]._batchable(temperature, temperature_threshold, moves_per_pass, device_inputs=True):
             collect = lambda e, gh: finished.append((e, gh))
             self.play_moves(moves_per_pass, temperature, on_game=collect, temperature_threshold=temperature_threshold or 0)
@@ -1361,3 +1488,122 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         torch.cuda.synchronize(self.device)      # (a queued search may still be running)
         for a in self.actors:
             a.close()
+
+
+def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_player=None, num_envs=64, seed=0,
+             device=None, moves_per_batch=8, groups=1, use_graph=True, warmup_batches=0):
+    """`MuZero.test` (reference muzero.py:346-396) on device-resident envs: `num_tests` games at temperature 0 and
+    temperature threshold 0 (play_game(0, 0, False, opponent, muzero_player)), `num_envs` of them at a time, env e on
+    the game and RNG stream of reference worker `seed + e`.
+
+    `opponent` "self", "expert" or "random", `muzero_player` the side MuZero plays; None means the config's value.
+    (The reference tests `if muzero_player`, which also sends an explicit 0 to the config; here only None does.)
+    One-player games have no opponent: they are played as "self".
+
+    The games counted are the first `num_tests` games STARTED, ordered by (ply of their env at which they began, env
+    index) -- not the first finished, which would over-represent short games.  Envs keep playing until those are over.
+
+    `warmup_batches` (for rate measurements): that many batches (or single moves, where batches do not apply) are
+    played on the same actor first -- its buffers, the captured hipGraph and the history filer exist afterwards --;
+    games that began during them are not counted and `seconds` / the move counts start after them.  With 0 the games
+    are those of a fresh actor (num_envs = 1: the consecutive games of one SelfPlay worker of that seed).
+
+    Returns a dict: `result` is MuZero.test's number (one player: mean total reward; otherwise the mean of the rewards
+    earned on muzero_player's moves), `muzero_reward` / `opponent_reward` the means per side (two players),
+    `mean_episode_length`, `wins` / `draws` / `losses` (by comparing the two sides' rewards; None for one player),
+    `games`, and the timed region's totals, counted games or not: `env_moves` (plies played by all envs),
+    `searched_moves` (those that ran a search, counted by the history filer), `simulations`, `seconds`."""
+    cfg = config
+    if opponent is None:
+        opponent = cfg.opponent
+    if muzero_player is None:
+        muzero_player = cfg.muzero_player
+    two_players = len(cfg.players) > 1
+    if not two_players or opponent is None:
+        opponent = "self"
+    num_tests, E = int(num_tests), int(num_envs)
+    if num_tests < 1:
+        raise ValueError("evaluate: num_tests must be positive")
+    if groups > 1:
+        actor = PipelinedDeviceSelfPlay(checkpoint, game_name, cfg, seed, E, groups=groups, device=device, use_graph=use_graph)
+        probe = actor.actors[0]
+    else:
+        actor = probe = DeviceSelfPlay(checkpoint, game_name, cfg, seed, E, device=device, use_graph=use_graph)
+    actor._opponent = (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
+    for a in getattr(actor, "actors", ()):
+        a._opponent = actor._opponent
+    clock = numpy.zeros(E, dtype=numpy.int64)          # plies of env e's finished games
+    plies = numpy.zeros(E, dtype=numpy.int64)          # plies env e has played
+    found = {k: [] for k in ("start", "env", "length", "mine", "theirs", "total")}
+
+    def on_games(batch):
+        n = len(batch)
+        env = numpy.array(batch.env_index, dtype=numpy.int64)
+        length = numpy.array(batch.length, dtype=numpy.int64)
+        W = batch.rewards.shape[1] - 1
+        # (a batch lists an env's games together, oldest first: each starts where the one before ended)
+        before = numpy.cumsum(length) - length
+        new_env = numpy.r_[True, env[1:] != env[:-1]]
+        found["start"].append(clock[env] + before - before[numpy.flatnonzero(new_env)][numpy.cumsum(new_env) - 1])
+        numpy.add.at(clock, env, length)
+        valid = numpy.arange(1, W + 1)[None, :] <= length[:, None]
+        rewards = numpy.where(valid, batch.rewards[:n, 1:], 0.0).astype(numpy.float64)
+        mine = (batch.to_play[:n, :W] == muzero_player) & valid      # reward i belongs to the player of move i - 1
+        found["env"].append(env)
+        found["length"].append(length)
+        found["mine"].append((rewards * mine).sum(axis=1))
+        found["theirs"].append((rewards * ~mine).sum(axis=1))
+        found["total"].append(rewards.sum(axis=1))
+
+    # the pipelined actor's batches always take the device-input form
+    batched = probe._batchable(0, 0, moves_per_batch, device_inputs=True if groups > 1 else None)
+
+    def play():
+        if batched:
+            plies[:] += actor.play_moves(moves_per_batch, 0, on_games=on_games, temperature_threshold=0)
+            actor.flush(on_games=on_games)
+        else:
+            actor.step(0, 0, on_games=on_games)
+            plies[:] += 1
+
+    for _ in range(int(warmup_batches)):
+        play()
+    first_ply = plies.copy()                           # games that began before it are not counted
+
+    def counted():
+        """Indices (into the concatenated records) of the first num_tests games started, once they are all over."""
+        if not found["start"]:
+            return None
+        start, env = numpy.concatenate(found["start"]), numpy.concatenate(found["env"])
+        e = int(numpy.lexsort((numpy.arange(E), clock))[0])       # the oldest game still running: every game that
+        running = (int(clock[e]), e)                              # starts from now on starts after it
+        eligible = start >= first_ply[env]
+        earlier = eligible & ((start < running[0]) | ((start == running[0]) & (env < running[1])))
+        if int(earlier.sum()) < num_tests:
+            return None
+        order = numpy.lexsort((env, start))
+        return order[eligible[order]][:num_tests]
+
+    torch.cuda.synchronize(probe.device)
+    began = time.perf_counter()
+    moves0, searched0 = actor.moves_played, actor.searched_moves
+    while True:
+        play()
+        pick = counted()
+        if pick is not None:
+            break
+    seconds = time.perf_counter() - began
+    env_moves, searched = actor.moves_played - moves0, actor.searched_moves - searched0
+    actor.close()
+    col = {k: numpy.concatenate(v)[pick] for k, v in found.items()}
+    out = dict(games=int(len(pick)), mean_episode_length=float(col["length"].mean()), env_moves=int(env_moves),
+               searched_moves=int(searched), simulations=int(searched) * int(cfg.num_simulations), seconds=seconds,
+               opponent=opponent, muzero_player=int(muzero_player), num_envs=E)
+    if two_players:
+        out.update(result=float(col["mine"].mean()), muzero_reward=float(col["mine"].mean()),
+                   opponent_reward=float(col["theirs"].mean()), wins=int((col["mine"] > col["theirs"]).sum()),
+                   draws=int((col["mine"] == col["theirs"]).sum()), losses=int((col["mine"] < col["theirs"]).sum()))
+    else:
+        out.update(result=float(col["total"].mean()), muzero_reward=float(col["total"].mean()), opponent_reward=0.0,
+                   wins=None, draws=None, losses=None)
+    return out

@@ -1,0 +1,73 @@
+"""Evaluation games on device-resident envs: MuZero against the expert / a random player / itself.
+
+    python tools/evaluate.py --game tictactoe --envs 65536 --tests 200000 [--opponent expert] [--muzero-player 0]
+                             [--fc 0] [--batch 8] [--groups 1] [--warmup-batches 3] [--compare-self]
+
+Prints one JSON line: self_play.evaluate's result (MuZero.test's number, rewards per side, win / draw / loss counts, mean
+episode length) with games per second, env-moves per second, simulations per second and the share of env-moves that
+sat a search out (searched plies are counted by the history filer, not estimated).  The warm-up batches run on the actor
+that is timed afterwards (buffers, hipGraph capture and filer are set up in them); a rate is worth quoting when
+`seconds` is at least one -- raise --tests otherwise.  --compare-self adds the same command line played as "self"
+(every ply searched) for the ratio.
+Weights are the seed-0 initialisation unless --weights points to a checkpoint (torch.save of {"weights": ...})."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+sp = importlib.import_module("muzero-hypermodel_amd.self_play")
+models = importlib.import_module("muzero-hypermodel_amd.models")
+
+
+def run(args, config, checkpoint, opponent, num_tests):
+    out = sp.evaluate(checkpoint, args.game, config, num_tests, opponent=opponent, muzero_player=args.muzero_player,
+                      num_envs=args.envs, seed=args.seed, moves_per_batch=args.batch, groups=args.groups,
+                      warmup_batches=args.warmup_batches)
+    s = out["seconds"]
+    out.update(games_per_s=out["games"] / s, env_moves_per_s=out["env_moves"] / s, simulations_per_s=out["simulations"] / s,
+               sat_out_share=1.0 - out["searched_moves"] / max(1, out["env_moves"]))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--game", default="tictactoe", choices=["tictactoe", "connect4", "cartpole"])
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--tests", type=int, default=20000, help="games to average (the first N started)")
+    ap.add_argument("--opponent", default=None, choices=["self", "expert", "random"], help="default: the config's")
+    ap.add_argument("--muzero-player", type=int, default=None, help="default: the config's")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=8, help="moves per host round trip")
+    ap.add_argument("--groups", type=int, default=1, help="> 1: env groups on HIP streams of their own")
+    ap.add_argument("--fc", type=int, default=0, help="N > 0: a fully-connected network of N units (fused whole-move search)")
+    ap.add_argument("--weights", default=None, help="checkpoint file; default: seed-0 initialisation")
+    ap.add_argument("--warmup-batches", type=int, default=3, help="untimed batches on the same actor first (code objects, "
+                    "rings, graph capture, filer); games that begin in them are not counted")
+    ap.add_argument("--compare-self", action="store_true")
+    args = ap.parse_args()
+    mod = importlib.import_module(f"muzero-hypermodel_amd.games.{args.game}")
+    config = mod.MuZeroConfig()
+    if args.fc:
+        config.network, config.encoding_size = "fullyconnected", args.fc
+        config.fc_representation_layers, config.fc_dynamics_layers = [], [args.fc]
+        config.fc_reward_layers = config.fc_value_layers = config.fc_policy_layers = [args.fc]
+    if args.weights:
+        checkpoint = torch.load(args.weights, map_location="cpu")
+    else:
+        torch.manual_seed(0)
+        checkpoint = {"weights": models.MuZeroNetwork(config).get_weights()}
+    opponent = args.opponent if args.opponent is not None else config.opponent
+    line = run(args, config, checkpoint, opponent, args.tests)
+    line.update(game=args.game, network=config.network)
+    if args.compare_self and opponent != "self":
+        line["self"] = run(args, config, checkpoint, "self", args.tests)
+        line["simulations_vs_self"] = line["simulations_per_s"] / line["self"]["simulations_per_s"]
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
