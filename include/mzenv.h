@@ -96,8 +96,29 @@ int mzenv_advance_opponent(mzenv *env, const int32_t *actions, float *reward_out
 /* Put every env of a board game into a given position: boards host i8[E][cells] (0 empty, +1 first player, -1 second;
  * tic-tac-toe cell = 3 * row + column, connect four cell = 7 * row + column with row 0 at the bottom), players host
  * i8[E] (+1 / -1 to move).  Blocking; cell and player values are checked, reachability is not (see above for what a
- * step does with a finished position). */
+ * step does with a finished position).  The ply counter of each env (below) becomes the number of stones on its board:
+ * a position handed in continues the game it came from. */
 int mzenv_set_boards(mzenv *env, const int8_t *boards, const int8_t *players);
+
+/* ---- move limit: games end at config.max_moves (reference self_play.py:129-131) ------------------------------------
+ * play_game() leaves its loop once len(action_history) exceeds max_moves, whatever the game's own rules say.  Every env
+ * counts the plies actually played in its current game -- in opponent mode the opponent's plies too, as
+ * len(action_history) does; an env left untouched (action < 0 on muzero_player's turn, a full board on the opponent's:
+ * played_out -1) does not count.  Game.reset() zeroes the counter, whether it comes from mzenv_reset (masked envs only)
+ * or from inside mzenv_advance / mzenv_advance_opponent.
+ *
+ * mzenv_set_max_moves: 0 (the value at create) = no limit: every call behaves as it does without this section.
+ *   max_moves > 0: the ply that brings an env's counter to max_moves (or beyond it, when the limit was lowered in
+ *   mid-game) reports done_out = 1 even if the game's own rules say it goes on, and mzenv_advance /
+ *   mzenv_advance_opponent reset that env like any finished one.  reward_out, obs_after_out, played_out and words_out
+ *   are what the ply produced; nothing else changes.  WITH A LIMIT SET, done MEANS "THE GAME IS OVER", NOT "THE POSITION
+ *   IS TERMINAL".  After mzenv_step / mzenv_step_opponent the caller resets the envs flagged done, as ever.
+ *   CartPole's own time limit (500 steps, gym's) is part of the game's rules and independent of this.
+ *   The limit travels with every launch: setting it is a host store -- no allocation, no synchronisation -- and is
+ *   legal between any two launches; launches already queued keep the limit they were queued with.  Negative: error.
+ * mzenv_game_moves: copies the counters to out_dev (dev i32[E]) on `stream`; asynchronous and allocation-free. */
+int mzenv_set_max_moves(mzenv *env, int32_t max_moves);
+int mzenv_game_moves(mzenv *env, int32_t *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

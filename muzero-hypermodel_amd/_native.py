@@ -189,6 +189,8 @@ PROTOTYPES = {
     "mzenv_step_opponent": (ctypes.c_int, [c_void] * 7),
     "mzenv_advance_opponent": (ctypes.c_int, [c_void] * 12),
     "mzenv_set_boards": (ctypes.c_int, [c_void, c_void, c_void]),
+    "mzenv_set_max_moves": (ctypes.c_int, [c_void, ctypes.c_int32]),
+    "mzenv_game_moves": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzmcts_rng_create": (c_void, [ctypes.c_uint32]),
     "mzmcts_rng_destroy": (None, [c_void]),
     "mzmcts_rng_reseed": (None, [c_void, ctypes.c_uint32]),

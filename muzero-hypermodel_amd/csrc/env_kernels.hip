@@ -27,12 +27,12 @@ __device__ __forceinline__ void env_reset_one(const EnvParams& p, int e) {
         int32_t pos = p.mt_pos[e];
         for (int i = 0; i < 4; ++i) p.state[4 * e + i] = -0.05 + (0.05 - -0.05) * mt_uniform(key, &pos);
         p.mt_pos[e] = pos;
-        p.steps[e] = 0;
     } else {
         int8_t* b = p.board + static_cast<size_t>(e) * p.cells;
         for (int i = 0; i < p.cells; ++i) b[i] = 0;
         p.player[e] = 1;
     }
+    p.steps[e] = 0;
 }
 
 // Opponent mode (mzenv_set_opponent): is the side to move in env e the scripted opponent's?
@@ -40,8 +40,9 @@ __device__ __forceinline__ bool opponent_to_move(const EnvParams& p, int e) {
     return p.opp_kind != kOpponentSelf && (p.player[e] == 1 ? 0 : 1) != p.opp_player;
 }
 
-// One move of env e; returns whether the game ended.  a < 0: the env is left alone this move (e.g. its search
-// was not run) -- nothing happened.  On the opponent's turn the incoming action is ignored: the opponent chooses,
+// One move of env e; returns whether the game ended: by its own rules, or (mzenv_set_max_moves) because this was the
+// last ply the move limit allows -- reward and position are the ply's own either way.  a < 0: the env is left alone
+// this move (e.g. its search was not run) -- nothing happened, no ply is counted.  On the opponent's turn the incoming action is ignored: the opponent chooses,
 // drawing from env e's stream (select_opponent_action, self_play.py:189-221).  played_out / words_out (null outside
 // opponent mode): the action actually played (-1: none) and the stream words the choice consumed.
 __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, float* __restrict__ reward_out,
@@ -63,6 +64,7 @@ __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, f
     }
     float reward = 0.f;
     bool done = false;
+    const int steps = ++p.steps[e];  // an opponent's ply counts like MuZero's (len(action_history), self_play.py:129-131)
     if (p.game == 0) {
         // classic-control cart-pole, Euler step (games/cartpole.py CartPolePhysics on the host)
         const double gravity = 9.8, mass_cart = 1.0, mass_pole = 0.1, half_length = 0.5, force_mag = 10.0, tau = 0.02;
@@ -80,7 +82,6 @@ __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, f
         s[1] = x_dot + tau * x_acc;
         s[2] = theta + tau * theta_dot;
         s[3] = theta_dot + tau * theta_acc;
-        const int steps = ++p.steps[e];
         const double theta_limit = 12 * 2 * 3.141592653589793 / 360;
         done = fabs(s[0]) > 2.4 || fabs(s[2]) > theta_limit || steps >= 500;
         reward = 1.0f;
@@ -106,6 +107,7 @@ __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, f
         done = won || full;
         p.player[e] = static_cast<int8_t>(-pl);
     }
+    done = done || (p.max_moves > 0 && steps >= p.max_moves);
     reward_out[e] = reward;
     done_out[e] = done ? 1 : 0;
     return done;

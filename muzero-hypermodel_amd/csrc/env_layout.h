@@ -9,7 +9,7 @@ struct EnvParams {
     int8_t* board;     // [E][cells]  tictactoe / connect4: 0 empty, +1 first player, -1 second player
     int8_t* player;    // [E]         +1 / -1: the player to move
     double* state;     // [E][4]      cartpole: x, x_dot, theta, theta_dot
-    int32_t* steps;    // [E]         cartpole
+    int32_t* steps;    // [E]         plies played in the env's current game (every game; cartpole's time limit reads it)
     uint32_t* mt_key;  // [E][624]    cartpole reset stream (numpy RandomState(seed))
     int32_t* mt_pos;   // [E]
     // opponent mode of the board games (mzenv_set_opponent): kind (board_rules.h OpponentKind), the player MuZero
@@ -17,6 +17,8 @@ struct EnvParams {
     int32_t opp_kind, opp_player;
     uint32_t* opp_key;  // [E][624]
     int32_t* opp_pos;   // [E]
+    // move limit (mzenv_set_max_moves): > 0 = the ply that brings steps[e] to it ends the game; 0 = the game's own rules only
+    int32_t max_moves;
 };
 
 }  // namespace mz

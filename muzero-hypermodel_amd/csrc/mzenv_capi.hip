@@ -76,6 +76,7 @@ int mzenv_create(int32_t game, int32_t num_envs, int32_t device, const uint32_t*
         mzenv_destroy(env);
         return code;
     };
+    if ((rc = env_alloc(env, &p.steps, num_envs))) return bail(rc);
     if (game == MZENV_CARTPOLE) {
         p.A = 2;
         p.cells = 0;
@@ -83,7 +84,6 @@ int mzenv_create(int32_t game, int32_t num_envs, int32_t device, const uint32_t*
         env->players = 1;
         env->shape[0] = 1, env->shape[1] = 1, env->shape[2] = 4;
         if ((rc = env_alloc(env, &p.state, static_cast<size_t>(num_envs) * 4))) return bail(rc);
-        if ((rc = env_alloc(env, &p.steps, num_envs))) return bail(rc);
         if ((rc = env_alloc(env, &p.mt_key, static_cast<size_t>(num_envs) * mz::kMtN))) return bail(rc);
         if ((rc = env_alloc(env, &p.mt_pos, num_envs))) return bail(rc);
         uint32_t* d_seeds = nullptr;
@@ -157,16 +157,35 @@ int mzenv_set_boards(mzenv* env, const int8_t* boards, const int8_t* players) {
     if (!env || !boards || !players) return env_fail(env, -1, "mzenv_set_boards: null argument");
     if (env->players < 2) return env_fail(env, -1, "mzenv_set_boards: not a board game");
     const size_t E = static_cast<size_t>(env->p.E), cells = static_cast<size_t>(env->p.cells);
+    std::vector<int32_t> stones(E, 0);  // the game a position came from has played one ply per stone
     for (size_t e = 0; e < E; ++e) {
         if (players[e] != 1 && players[e] != -1) return env_fail(env, -1, "mzenv_set_boards: a player to move is +1 or -1");
-        for (size_t i = 0; i < cells; ++i)
+        for (size_t i = 0; i < cells; ++i) {
             if (boards[e * cells + i] < -1 || boards[e * cells + i] > 1)
                 return env_fail(env, -1, "mzenv_set_boards: a cell is 0, +1 or -1");
+            stones[e] += boards[e * cells + i] != 0;
+        }
     }
     MZENV_HIP(env, hipSetDevice(env->device));
     MZENV_HIP(env, hipDeviceSynchronize());
     MZENV_HIP(env, hipMemcpy(env->p.board, boards, E * cells, hipMemcpyHostToDevice));
     MZENV_HIP(env, hipMemcpy(env->p.player, players, E, hipMemcpyHostToDevice));
+    MZENV_HIP(env, hipMemcpy(env->p.steps, stones.data(), E * sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int mzenv_set_max_moves(mzenv* env, int32_t max_moves) {
+    // (the argument is judged before the handle, as in mzenv_set_opponent)
+    if (max_moves < 0) return env_fail(env, -1, "mzenv_set_max_moves: the limit is a number of plies (0 = none)");
+    if (!env) return env_fail(nullptr, -1, "mzenv_set_max_moves: null handle");
+    env->p.max_moves = max_moves;  // (EnvParams travels by value with every launch: nothing on the device to update)
+    return 0;
+}
+
+int mzenv_game_moves(mzenv* env, int32_t* out_dev, void* stream) {
+    if (!env || !out_dev) return env_fail(env, -1, "mzenv_game_moves: null argument");
+    MZENV_HIP(env, hipMemcpyAsync(out_dev, env->p.steps, sizeof(int32_t) * env->p.E, hipMemcpyDeviceToDevice,
+                                  static_cast<hipStream_t>(stream)));
     return 0;
 }
 

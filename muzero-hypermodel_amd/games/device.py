@@ -49,6 +49,7 @@ class DeviceEnvs:
             self.played = torch.zeros(self.E, dtype=torch.int32, device=self.device)
             self.words = torch.zeros(self.E, dtype=torch.int32, device=self.device)
         self.opponent = ("self", 0)
+        self.max_moves = 0                                   # move limit (set_max_moves); 0 = the game's own rules only
         self.reset()
 
     def _stream(self):
@@ -89,10 +90,26 @@ class DeviceEnvs:
 
     def set_boards(self, boards, players):
         """Put the envs of a board game into given positions: boards int8 [E, cells] (0 / +1 / -1; connect four row 0
-        = bottom), players int8 [E] (+1 / -1 to move)."""
+        = bottom), players int8 [E] (+1 / -1 to move).  An env's ply count (game_moves) becomes its number of stones."""
         boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(self.E, -1)
         players = np.ascontiguousarray(players, dtype=np.int8).reshape(self.E)
         self._check(self._lib.mzenv_set_boards(self._h, boards.ctypes.data, players.ctypes.data))
+
+    def set_max_moves(self, max_moves):
+        """Games end at `max_moves` plies (config.max_moves, reference self_play.py:129-131): the ply that brings an
+        env's count to it -- the opponent's plies count too -- reports done = 1 whatever the game's own rules say, and
+        advance() resets the env like any finished one; reward and observations are the ply's own.  0 = no limit.  With
+        a limit set `done` means "the game is over", not "the position is terminal".  A host store: legal between any
+        two calls, in effect from the next step / advance on.  `max_episode_steps` stays the game's own length."""
+        self._check(self._lib.mzenv_set_max_moves(self._h, int(max_moves)))
+        self.max_moves = int(max_moves)
+
+    def game_moves(self):
+        """Plies played so far in each env's current game (int32 [E] device tensor, a copy): zeroed by a reset, set to
+        the number of stones by set_boards."""
+        out = torch.empty(self.E, dtype=torch.int32, device=self.device)
+        self._check(self._lib.mzenv_game_moves(self._h, out.data_ptr(), self._stream()))
+        return out
 
     def reset(self, mask=None):
         """Game.reset() for the envs whose mask entry is non-zero (uint8 device tensor; None = all)."""

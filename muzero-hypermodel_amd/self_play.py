@@ -956,8 +956,17 @@ class DeviceSelfPlay(ManyEnvLoop):
         return (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
 
     def _set_env_mode(self, mode):
-        """Switch the envs between self-play and an opponent; the positions stay, the legal counts the searches read are
-        observed again in the new mode."""
+        """Before anything is queued: the envs end games at config.max_moves where that is shorter than the game itself
+        (the environment kernels count the plies; read here because callers edit the config of a built actor), and
+        switch between self-play and an opponent; the positions stay, the legal counts the searches read are observed
+        again in the new mode."""
+        limit = int(self.config.max_moves)
+        if limit + 1 > self._rv.shape[1]:
+            raise ValueError(f"config.max_moves was raised to {limit} on a built actor whose history rows hold "
+                             f"{self._rv.shape[1] - 1} moves; build a new actor")
+        limit = limit if limit < self.envs.max_episode_steps else 0
+        if self.envs.max_moves != limit:
+            self.envs.set_max_moves(limit)
         if self.envs.opponent == mode:
             return
         self.envs.set_opponent(mode[0], mode[1], self.engine)
@@ -967,9 +976,6 @@ class DeviceSelfPlay(ManyEnvLoop):
     def _opponent_step_check(self, temperature):
         """An opponent's plies exist in the device-input form of a move batch only: say what rules it out."""
         cfg = self.config
-        if cfg.max_moves < self.envs.max_episode_steps:
-            raise NotImplementedError("a step against an opponent runs as a move batch, which ends games where the "
-                                      "environment does; max_moves is shorter")
         if not 0.0 < float(cfg.root_dirichlet_alpha) <= 1.0:
             raise NotImplementedError("a step against an opponent runs as a device-input move batch, whose exploration "
                                       "noise is drawn on the GPU for 0 < root_dirichlet_alpha <= 1 only")
@@ -1085,12 +1091,12 @@ class DeviceSelfPlay(ManyEnvLoop):
         lock-step (engine.moves_enqueue_lockstep) with inputs, noise and action sampling on the device.
         `temperature_threshold` (default config.temperature_threshold) is play_game's rule, applied per env and move.
         An env may come back with fewer than n_moves moves played (it plays the rest next time).
+        Games end where play_game ends them: by the game's rules or at config.max_moves plies, whichever comes first --
+        the environment kernels apply both (DeviceEnvs.set_max_moves), so a limit costs a batch nothing.
         `opponent` / `muzero_player` as in step(): an opponent's plies are played by the environment kernels inside the
         batch (always its device-input form; every env then plays all n_moves plies)."""
         E, eng, envs, cfg = self.E, self.engine, self.envs, self.config
         mode = self._resolve_opponent(opponent, muzero_player)
-        if cfg.max_moves < envs.max_episode_steps:
-            raise NotImplementedError("play_moves ends games where the environment does; max_moves is shorter")
         # Everything but a fused search of a game with a constant legal set takes the device-input form of the batch:
         # board games (legal sets change), residual networks (lock-step searches), and a temperature threshold
         # (play_game drops to temperature 0 once len(action_history) reaches it, self_play.py:152-158: a per-env, per-move
@@ -1224,7 +1230,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         if device_inputs is None:
             device_inputs = (not getattr(self.envs, "constant_legal_actions", False) or self.engine._fc_model is None
                              or bool(temperature_threshold) or getattr(self, "_opponent", ("self", 0))[0] != "self")
-        return (moves_per_pass is not None and self.config.max_moves >= self.envs.max_episode_steps
+        return (moves_per_pass is not None
                 and (temperature == 0 or _native.exact_inverse_temperature(temperature))
                 # (a device-input batch draws its exploration noise on the GPU: the legacy gamma sampler for shapes <= 1)
                 and (not device_inputs or 0.0 < float(self.config.root_dirichlet_alpha) <= 1.0))
@@ -1271,7 +1277,8 @@ class DeviceSelfPlay(ManyEnvLoop):
         """The native filer takes over the rows of the running games (and hands them back to step())."""
         filer = getattr(self, "_filer", None)
         if filer is None:
-            filer = self._filer = HistoryFiler(self.E, int(self.config.max_moves) + 1, self.envs.observation_shape, self.envs.A)
+            # (sized like the rows it takes over: config.max_moves of a built actor may have been lowered since)
+            filer = self._filer = HistoryFiler(self.E, self._rv.shape[1], self.envs.observation_shape, self.envs.A)
         if not getattr(self, "_filer_owns_rows", False):
             filer.load_rows(self._obs, self._act, self._rew, self._tp, self._cv, self._rv, self._len)
             self._filer_owns_rows = True
@@ -1436,8 +1443,6 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             actor = self.actors[g]
             if self._started[g]:                             # (a search queued by step(): finish that move first)
                 raise RuntimeError("play_moves: a step() is half done; call step(..., prefetch=False) before batches")
-            if cfg.max_moves < actor.envs.max_episode_steps:
-                raise NotImplementedError("play_moves ends games where the environment does; max_moves is shorter")
             one, many = self._callbacks(g, on_game, on_games)
             with torch.cuda.stream(self.streams[g]):
                 actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold)

@@ -1,7 +1,7 @@
 """Evaluation games on device-resident envs: MuZero against the expert / a random player / itself.
 
     python tools/evaluate.py --game tictactoe --envs 65536 --tests 200000 [--opponent expert] [--muzero-player 0]
-                             [--fc 0] [--batch 8] [--groups 1] [--warmup-batches 3] [--compare-self]
+                             [--fc 0] [--batch 8] [--groups 1] [--warmup-batches 3] [--compare-self] [--max-moves N]
 
 Prints one JSON line: self_play.evaluate's result (MuZero.test's number, rewards per side, win / draw / loss counts, mean
 episode length) with games per second, env-moves per second, simulations per second and the share of env-moves that
@@ -48,9 +48,13 @@ def main():
     ap.add_argument("--warmup-batches", type=int, default=3, help="untimed batches on the same actor first (code objects, "
                     "rings, graph capture, filer); games that begin in them are not counted")
     ap.add_argument("--compare-self", action="store_true")
+    ap.add_argument("--max-moves", type=int, default=None, help="end games after N plies (config.max_moves; default: the "
+                    "config's)")
     args = ap.parse_args()
     mod = importlib.import_module(f"muzero-hypermodel_amd.games.{args.game}")
     config = mod.MuZeroConfig()
+    if args.max_moves is not None:
+        config.max_moves = args.max_moves
     if args.fc:
         config.network, config.encoding_size = "fullyconnected", args.fc
         config.fc_representation_layers, config.fc_dynamics_layers = [], [args.fc]
@@ -62,7 +66,7 @@ def main():
         checkpoint = {"weights": models.MuZeroNetwork(config).get_weights()}
     opponent = args.opponent if args.opponent is not None else config.opponent
     line = run(args, config, checkpoint, opponent, args.tests)
-    line.update(game=args.game, network=config.network)
+    line.update(game=args.game, network=config.network, max_moves=config.max_moves)
     if args.compare_self and opponent != "self":
         line["self"] = run(args, config, checkpoint, "self", args.tests)
         line["simulations_vs_self"] = line["simulations_per_s"] / line["self"]["simulations_per_s"]

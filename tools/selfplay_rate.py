@@ -1,6 +1,6 @@
 """Whole self-play loop rate (search + env step + history filing), host-plugin envs vs device envs.
 
-    python tools/selfplay_rate.py [--game cartpole] [--envs 4096] [--moves 60]
+    python tools/selfplay_rate.py [--game cartpole] [--envs 4096] [--moves 60] [--max-moves N]
 
 Prints one JSON line per actor kind: moves/s, simulations/s, finished games.  This is the loop the
 reference runs in self_play.py:34-113 (continuous_self_play), without the replay buffer hand-off."""
@@ -32,9 +32,13 @@ def main():
                     "network = 'fullyconnected'), encoding and layers of N units -- board games through the fused whole-move search")
     ap.add_argument("--no-prefetch", action="store_true", help="device-pipelined-batch: every play_moves call drains the GPU "
                     "(what a loop does that pulls weights between calls)")
+    ap.add_argument("--max-moves", type=int, default=None, help="end games after N plies (config.max_moves; default: the "
+                    "config's): the device actors' batches apply it in the environment kernels")
     args = ap.parse_args()
     mod = importlib.import_module(f"muzero-hypermodel_amd.games.{args.game}")
     config = mod.MuZeroConfig()
+    if args.max_moves is not None:
+        config.max_moves = args.max_moves
     if args.fc:
         config.network, config.encoding_size = "fullyconnected", args.fc
         config.fc_representation_layers, config.fc_dynamics_layers = [], [args.fc]
@@ -94,7 +98,7 @@ def main():
             moves = args.moves * args.envs
         print(json.dumps({"actor": kind, "game": args.game, "envs": args.envs, "moves_per_s": moves / dt,
                           "simulations_per_s": moves * config.num_simulations / dt, "ms_per_move_step": 1e3 * dt * args.envs / moves,
-                          "games_finished": done[0], "weights": args.weights,
+                          "games_finished": done[0], "weights": args.weights, "max_moves": config.max_moves,
                           **({"moves_per_call": args.batch, "prefetch": not args.no_prefetch} if kind == "device-pipelined-batch" else {}),
                           **({"moves_per_call": args.batch} if kind == "device-batch" else {})}), flush=True)
         actor.close()
