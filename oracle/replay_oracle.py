@@ -11,8 +11,10 @@ uses float32):
     sample_* / get_batch    ReplayBuffer.get_batch and its samplers replay_buffer.py:67-195
     (reanalysed values)     Reanalyse.reanalyse's per-game step     replay_buffer.py:335-356, 226-231
 
-PINNED against fixtures G12 / G13 (tests/golden/g12_replay_*.npz, g13_reanalyse_cartpole.npz), recorded by running the reference's own
-ReplayBuffer on synthetic game histories (tests/golden/make_golden.py:g12_replay_targets).  Random draws go
+PINNED against fixtures G12 / G13 / G17 (tests/golden/g12_replay_*.npz, g13_reanalyse_cartpole.npz, g17_replay_edges_*.npz:
+sampled batches, reanalysed CartPole games, and every position of games that bootstrap with two players, pass 256 plies
+or fill max_moves), recorded by running the reference's own ReplayBuffer on synthetic game histories
+(tests/golden/make_golden.py:g12_replay_targets, g13_reanalyse, g17_replay_edges).  Random draws go
 through mz_oracle.Rng, the numpy legacy RandomState clone pinned by fixture G7.  Only tests/ may import this.
 """
 import numpy as np

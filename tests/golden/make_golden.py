@@ -779,6 +779,118 @@ def g13_reanalyse(ctx):
     save("g13_reanalyse_cartpole", **out)
 
 
+def g17_replay_edges(ctx):
+    """The replay path where G12 / G13 do not reach (replay_buffer.py:33-65, 222-295, self_play.py:514-548): two-player
+    games that bootstrap (td_steps below the game length, so the sign flip of compute_target_value runs), games longer
+    than 256 plies and of exactly max_moves plies, 1-ply games, stacked observations deeper than the position, and the
+    float32 branch (reanalysed_predicted_root_values) with two players.  EVERY position of every game is recorded, not
+    a sampled batch: priorities, compute_target_value with its result type, make_target, get_stacked_observations --
+    before and after half of the games received reanalysed values through update_game_history."""
+    import copy
+    import replay_buffer
+    self_play, cfgs = ctx["self_play"], ctx["configs"]
+    kinds = {int: 0, float: 1, numpy.float32: 2, numpy.float64: 3}
+    cases = (
+        ("tictactoe_td3", "tictactoe", dict(td_steps=3, num_unroll_steps=5, stacked_observations=3),
+         [9, 1, 4, 2], (8, 1, 10)),
+        ("connect4_td5", "connect4", dict(td_steps=5, num_unroll_steps=8, stacked_observations=0),
+         [42, 1, 41, 6], (6, 2, 25)),
+        ("cartpole_long", "cartpole", dict(td_steps=7, num_unroll_steps=10, stacked_observations=4, max_moves=500),
+         [500, 1, 256, 257, 8, 7], (6, 2, 80)),
+        ("cartpole_alpha1", "cartpole", dict(td_steps=7, num_unroll_steps=10, stacked_observations=4, max_moves=300,
+                                             PER_alpha=1.0),
+         [300, 1, 8, 7], (8, 2, 40)),
+    )
+    for case, (name, base, tweak, fixed, (n_seeded, lo, hi)) in enumerate(cases):
+        config = copy.deepcopy(cfgs[base])
+        for k, v in tweak.items():
+            setattr(config, k, v)
+        config.PER = True
+        rs = numpy.random.RandomState(1700 + case)
+        lengths = fixed + [int(v) for v in rs.randint(lo, hi, n_seeded)]
+        assert 1 in lengths and config.max_moves in lengths and max(lengths) == config.max_moves
+        games = [_synthetic_history(self_play, rs, config, n) for n in lengths]
+        for gh in games:      # observations on a 1/16 grid: as good for telling planes apart, and the files stay small
+            gh.observation_history = [numpy.round(o * 16) / numpy.float32(16) for o in gh.observation_history]
+            assert all(o.dtype == numpy.float32 for o in gh.observation_history)
+        rb = replay_buffer.ReplayBuffer({"num_played_games": 0, "num_played_steps": 0}, {}, config)
+        for gh in games:
+            rb.save_game(gh)
+        G, L, A, U1 = len(games), config.max_moves, len(config.action_space), config.num_unroll_steps + 1
+        has_reanalysed = numpy.arange(G) % 2 == 0
+        reanalysed = numpy.zeros((G, L), dtype="float32")
+        for g in numpy.flatnonzero(has_reanalysed):
+            reanalysed[g, : lengths[g]] = (rs.standard_normal(lengths[g]) * 3).astype("float32")
+
+        def all_positions(seed):
+            rec = dict(pairs=[], target=[], target_kind=[], value=[], value_kind=[], reward=[], policy=[], action=[],
+                       draws=[])
+            numpy.random.seed(seed)
+            for g, gh in enumerate(games):
+                n = lengths[g]
+                for pos in range(n):
+                    target = rb.compute_target_value(rb.buffer[g], pos)
+                    v, r, p, a = rb.make_target(rb.buffer[g], pos)
+                    rec["pairs"].append([g, pos])
+                    rec["target"].append(float(target))
+                    rec["target_kind"].append(kinds[type(target)])
+                    rec["value"].append([float(x) for x in v])
+                    rec["value_kind"].append([kinds[type(x)] for x in v])
+                    rec["reward"].append([float(x) for x in r])
+                    rec["policy"].append(p)
+                    rec["action"].append(a)
+                    rec["draws"].extend(a[u] for u in range(U1) if pos + u > n)
+            return rec
+
+        before = all_positions(1701)
+        for g in numpy.flatnonzero(has_reanalysed):
+            games[g].reanalysed_predicted_root_values = reanalysed[g, : lengths[g]].copy()
+            rb.update_game_history(int(g), games[g])
+        after = all_positions(1702)
+        assert before["reward"] == after["reward"] and before["policy"] == after["policy"]
+        stacked = [gh.get_stacked_observations(pos, config.stacked_observations)
+                   for g, gh in enumerate(games) for pos in range(lengths[g])]
+        out = dict(config_scalars(config))
+        out.update(td_steps=config.td_steps, num_unroll_steps=config.num_unroll_steps, PER=1, PER_alpha=config.PER_alpha,
+                   stacked_observations=config.stacked_observations, max_moves=config.max_moves,
+                   discount_is_int=int(isinstance(config.discount, int)),
+                   observation_shape=numpy.array(config.observation_shape), seed=config.seed,
+                   lengths=numpy.array(lengths, dtype="int32"), numpy_version=numpy.array(numpy.__version__))
+        obs = numpy.zeros((G, L + 1) + tuple(config.observation_shape), dtype="float32")
+        act = numpy.zeros((G, L + 1), dtype="int32")
+        rew = numpy.zeros((G, L + 1), dtype="float64")
+        tp = numpy.zeros((G, L + 1), dtype="int32")
+        cv = numpy.zeros((G, L, A), dtype="float64")
+        rv = numpy.zeros((G, L), dtype="float64")
+        pri = numpy.zeros((G, L), dtype="float32")
+        game_pri = numpy.zeros(G, dtype="float32")
+        for g, gh in enumerate(games):
+            n = lengths[g]
+            obs[g, : n + 1] = numpy.array(gh.observation_history)
+            act[g, : n + 1] = gh.action_history
+            rew[g, : n + 1] = gh.reward_history
+            tp[g, : n + 1] = gh.to_play_history
+            cv[g, :n] = gh.child_visits
+            rv[g, :n] = gh.root_values
+            pri[g, :n] = gh.priorities
+            game_pri[g] = gh.game_priority
+        out.update(observations=obs, actions=act, rewards=rew, to_play=tp, child_visits=cv, root_values=rv,
+                   priorities=pri, game_priority=game_pri, has_reanalysed=has_reanalysed, reanalysed=reanalysed,
+                   pairs=numpy.array(before["pairs"], dtype="int32"),
+                   stacked=numpy.array(stacked, dtype="float32"),
+                   reward_targets=numpy.array(before["reward"], dtype="float64"),
+                   policy_targets=numpy.array(before["policy"], dtype="float64"))
+        for tag, rec, seed in (("before", before, 1701), ("after", after, 1702)):
+            out.update({f"seed_{tag}": seed,
+                        f"target_value_{tag}": numpy.array(rec["target"], dtype="float64"),
+                        f"target_kind_{tag}": numpy.array(rec["target_kind"], dtype="int8"),
+                        f"value_targets_{tag}": numpy.array(rec["value"], dtype="float64"),
+                        f"value_kind_{tag}": numpy.array(rec["value_kind"], dtype="int8"),
+                        f"action_targets_{tag}": numpy.array(rec["action"], dtype="int64"),
+                        f"absorbing_draws_{tag}": numpy.array(rec["draws"], dtype="int64")})
+        save(f"g17_replay_edges_{name}", **out)
+
+
 def g14_trainer(ctx):
     """Trainer.update_lr / update_weights (trainer.py:124-298) for two steps on one ReplayBuffer batch, starting
     from the CartPole checkpoint: losses, new priorities and the weights after each step."""
@@ -992,7 +1104,8 @@ def make_configs():
 
 ALL = [g0_weights, g1_support_to_scalar, g2_fc_inference, g3_resnet_inference, g4_cartpole,
        g5_tictactoe, g5_connect4, g5_atari84, g5_degenerate, g6_play_game, g6_connect4_opponents, g7_rng, g8_select_action,
-       g9_stacked, g10_reference_speed, g11_envs, g12_replay_targets, g12_reference_speed, g13_reanalyse, g14_trainer, g15_self_play_loop, g16_trainer_resnet]
+       g9_stacked, g10_reference_speed, g11_envs, g12_replay_targets, g12_reference_speed, g13_reanalyse, g14_trainer, g15_self_play_loop, g16_trainer_resnet,
+       g17_replay_edges]
 
 
 def main():

@@ -309,3 +309,18 @@ def value_transform_bound(value, delta_x, eps=0.001):
     e_s = 2.0 * z * e_z + 0.5 * ulp(z * z)
     e_v = e_s + 0.5 * ulp(np.maximum(z * z - 1.0, 1e-30))
     return 1.01 * kappa * delta_x + 2.0 * e_v
+
+
+# ---- replay store ------------------------------------------------------------------------------
+def history_of(sp, fx, g):
+    """Game g of a replay fixture (G12 layout: arrays padded past `lengths[g]`) as a GameHistory with the field types
+    play_game leaves behind."""
+    n = int(fx["lengths"][g])
+    gh = sp.GameHistory()
+    gh.observation_history = [o for o in fx["observations"][g, : n + 1]]
+    gh.action_history = [int(a) for a in fx["actions"][g, : n + 1]]
+    gh.reward_history = [float(r) for r in fx["rewards"][g, : n + 1]]
+    gh.to_play_history = [int(t) for t in fx["to_play"][g, : n + 1]]
+    gh.child_visits = [[float(v) for v in row] for row in fx["child_visits"][g, :n]]
+    gh.root_values = [float(v) for v in fx["root_values"][g, :n]]
+    return gh

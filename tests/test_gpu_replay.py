@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity_helpers import load_golden
+from parity_helpers import history_of, load_golden
 from test_oracle_replay import NAMES, cfg_of, games_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,18 +25,6 @@ def config_of(fx, name):
     assert config.td_steps == int(fx["td_steps"]) and config.num_unroll_steps == int(fx["num_unroll_steps"])
     assert config.seed == int(fx["seed"]) and float(config.discount) == float(fx["cfg_discount"])
     return config
-
-
-def history_of(sp, fx, g):
-    n = int(fx["lengths"][g])
-    gh = sp.GameHistory()
-    gh.observation_history = [o for o in fx["observations"][g, : n + 1]]
-    gh.action_history = [int(a) for a in fx["actions"][g, : n + 1]]
-    gh.reward_history = [float(r) for r in fx["rewards"][g, : n + 1]]
-    gh.to_play_history = [int(t) for t in fx["to_play"][g, : n + 1]]
-    gh.child_visits = [[float(v) for v in row] for row in fx["child_visits"][g, :n]]
-    gh.root_values = [float(v) for v in fx["root_values"][g, :n]]
-    return gh
 
 
 @pytest.mark.parametrize("name", NAMES)
