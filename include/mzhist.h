@@ -69,12 +69,6 @@ int mzhist_finished(mzhist *hist, const int32_t **env_index, const int32_t **len
                     const int32_t **actions, const float **rewards, const int32_t **to_play,
                     const double **child_visits, const double **root_values, int32_t *row_moves);
 
-/* Exchange the rows of the RUNNING games with the caller (load != 0: take them over, load == 0: hand them back):
- * observations f32[E][max_moves+1][obs], actions i32[E][max_moves+1], rewards f32[E][max_moves+1],
- * to_play i32[E][max_moves+1], child_visits f64[E][max_moves][A], root_values f64[E][max_moves], lengths i32[E]. */
-int mzhist_rows(mzhist *hist, float *observations, int32_t *actions, float *rewards, int32_t *to_play,
-                double *child_visits, double *root_values, int32_t *lengths, int32_t load);
-
 /* Plies filed since mzhist_create whose legal set was not empty, i.e. that were searched (evaluation games: the rest were
  * an opponent's; self-play: every ply). */
 int64_t mzhist_searched_moves(const mzhist *hist);

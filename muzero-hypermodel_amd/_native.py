@@ -167,7 +167,6 @@ PROTOTYPES = {
     "mzhist_finished": (ctypes.c_int, [c_void] + [ctypes.POINTER(c_void)] * 8 + [c_i32_p]),
     "mzhist_lengths": (c_void, [c_void]),
     "mzhist_searched_moves": (ctypes.c_int64, [c_void]),
-    "mzhist_rows": (ctypes.c_int, [c_void] * 8 + [ctypes.c_int32]),
     "mzreplay_create": (ctypes.c_int, [c_void, ctypes.POINTER(c_void)]),
     "mzreplay_destroy": (None, [c_void]),
     "mzreplay_last_error": (ctypes.c_char_p, [c_void]),

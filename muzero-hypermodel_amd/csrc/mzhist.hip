@@ -69,25 +69,6 @@ int mzhist_begin(mzhist* h, const float* first_observations, const int32_t* firs
     return 0;
 }
 
-int mzhist_rows(mzhist* h, float* observations, int32_t* actions, float* rewards, int32_t* to_play, double* child_visits,
-                double* root_values, int32_t* lengths, int32_t load) {
-    if (!h || !observations || !actions || !rewards || !to_play || !child_visits || !root_values || !lengths) return -1;
-    auto move = [&](auto& mine, auto* theirs) {
-        if (load)
-            std::memcpy(mine.data(), theirs, sizeof(mine[0]) * mine.size());
-        else
-            std::memcpy(theirs, mine.data(), sizeof(mine[0]) * mine.size());
-    };
-    move(h->observations, observations);
-    move(h->actions, actions);
-    move(h->rewards, rewards);
-    move(h->to_play, to_play);
-    move(h->child_visits, child_visits);
-    move(h->root_values, root_values);
-    move(h->length, lengths);
-    return 0;
-}
-
 int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
     if (!h || !mv || !mv->moves_done || !mv->actions || !mv->visits || !mv->root_value_sum || !mv->legal || !mv->num_legal ||
         !mv->rewards || !mv->done || !mv->obs_after || !mv->obs_next) {

@@ -16,8 +16,10 @@ facade hands that global state to the engine's stream before a search and hands 
 (`numpy.random.get_state/set_state`), so a run interleaves with any other user of `numpy.random`
 (games, expert agents) exactly as the reference does.
 """
+import dataclasses
 import math
 import time
+import typing
 
 import numpy
 import torch
@@ -478,6 +480,47 @@ class ManyEnvLoop:
     collective calls.  Rank 0 alone talks to `shared_storage`; the loop condition travels as a 2-word broadcast and
     the weights as one broadcast of the flat buffer (weights.FlatWeights, RCCL over xGMI) when their version moved."""
 
+    # (opponent, muzero_player) the moves play when a call names none: class-level, because subclasses need not run a
+    # base constructor
+    _opponent = ("self", 0)
+
+    def _build_search(self, initial_checkpoint, config, seed, num_envs, device, use_graph):
+        """What a single-GPU actor starts from: the checkpoint's network on the device and a search engine of num_envs
+        trees, env e on the RNG stream of reference worker seed + e (fully-connected networks: the fused whole-move
+        kernel where the shape is in its range)."""
+        self.config = config
+        self.E = int(num_envs)
+        self.device = torch.device(device if device is not None else "cuda")
+        torch.manual_seed(seed)
+        self.model = models.MuZeroNetwork(config)
+        self.model.set_weights(initial_checkpoint["weights"])
+        self.model.to(self.device)
+        self.model.eval()
+        fused = config.network == "fullyconnected"
+        self.engine = BatchedMCTS(config, self.E, device=self.device, seeds=[seed + e for e in range(self.E)],
+                                  use_graph=use_graph, group_width=16 if fused and len(config.action_space) <= 16 else 0)
+        if fused:
+            try:
+                self.engine.configure_fused_fc(self.model)      # whole move in one HIP launch
+            except (NotImplementedError, RuntimeError):
+                pass
+
+    def set_opponent(self, opponent, muzero_player=None):
+        """From now on a step() / play_moves() that names no opponent plays `opponent` ("self", "expert" or "random")
+        with MuZero as `muzero_player` (None: the config's).  An opponent the actors cannot play is refused by the
+        first move, not here."""
+        self._opponent = (opponent, self.config.muzero_player if muzero_player is None else muzero_player)
+
+    def _resolve_opponent(self, opponent, muzero_player):
+        """The (opponent, muzero_player) one call plays: its own arguments, else what set_opponent stored."""
+        if opponent is None:
+            opponent, muzero_player = self._opponent
+        elif muzero_player is None:
+            muzero_player = self.config.muzero_player
+        if opponent not in ("self", "expert", "random"):
+            raise NotImplementedError('many-env actors play opponent "self", "expert" or "random" ("human": use SelfPlay)')
+        return (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
+
     def _loop_state(self):
         st = self.__dict__.get("_loop")
         if st is None:
@@ -533,9 +576,10 @@ class ManyEnvLoop:
             raise ValueError("several ranks: give moves_per_pass so that every rank makes the same collective calls")
         # test mode against an opponent (self_play.py:65-90: play_game(0, threshold, False, config.opponent,
         # config.muzero_player) for games with several players): the actors whose step() takes an opponent play it
-        self._opponent = ("self", 0)
         if test_mode and len(cfg.players) > 1:
-            self._opponent = (cfg.opponent, cfg.muzero_player)
+            self.set_opponent(cfg.opponent, cfg.muzero_player)
+        else:
+            self.set_opponent("self", 0)
         talker = not self._distributed() or torch.distributed.get_rank() == 0
         while True:
             step, stop = self._loop_control(shared_storage, cfg.training_steps)
@@ -589,24 +633,8 @@ class BatchedSelfPlay(ManyEnvLoop):
     """
 
     def __init__(self, initial_checkpoint, Game, config, seed, num_envs, device=None, use_graph=True):
-        self.config = config
-        self.E = int(num_envs)
-        self.games = [Game(seed + e) for e in range(self.E)]
-        self.device = torch.device(device if device is not None else "cuda")
-        torch.manual_seed(seed)
-        self.model = models.MuZeroNetwork(config)
-        self.model.set_weights(initial_checkpoint["weights"])
-        self.model.to(self.device)
-        self.model.eval()
-        fused = config.network == "fullyconnected"
-        self.engine = BatchedMCTS(config, self.E, device=self.device,
-                                  seeds=[seed + e for e in range(self.E)], use_graph=use_graph,
-                                  group_width=16 if fused and len(config.action_space) <= 16 else 0)
-        if fused:
-            try:
-                self.engine.configure_fused_fc(self.model)      # whole move in one HIP launch
-            except (NotImplementedError, RuntimeError):
-                pass
+        self.games = [Game(seed + e) for e in range(int(num_envs))]
+        self._build_search(initial_checkpoint, config, seed, num_envs, device, use_graph)
         self.histories = [None] * self.E
         self.observations = [None] * self.E
         self.moves_played = 0
@@ -629,15 +657,12 @@ class BatchedSelfPlay(ManyEnvLoop):
 
     def step(self, temperature, temperature_threshold=None, on_game=None, opponent=None, muzero_player=None):
         """One move in every env (the body of play_game's loop, self_play.py:129-182).  `opponent` / `muzero_player`
-        (default: what continuous_self_play's test mode set, else "self"): in an env where it is not MuZero's turn the
-        move comes from select_opponent_action (self_play.py:189-221) -- the plugin's expert_agent(), or
+        (default: what set_opponent stored, else "self"): in an env where it is not MuZero's turn the move comes from
+        select_opponent_action (self_play.py:189-221) -- the plugin's expert_agent(), or
         numpy.random.choice over the legal actions drawn on THAT env's stream -- and no search statistics are stored
         for it (root None: store_search_statistics appends only a None root value, self_play.py:497-512)."""
         cfg = self.config
-        if opponent is None:
-            opponent, muzero_player = getattr(self, "_opponent", ("self", 0))
-        if opponent not in ("self", "expert", "random"):
-            raise NotImplementedError('many-env actors play opponent "self", "expert" or "random" ("human": use SelfPlay)')
+        opponent, muzero_player = self._resolve_opponent(opponent, muzero_player)
         searching = [opponent == "self" or muzero_player == self.games[e].to_play() for e in range(self.E)]
         stacked = numpy.stack([
             self.histories[e].get_stacked_observations(-1, cfg.stacked_observations)
@@ -745,10 +770,10 @@ class PackedGames:
 
 
 class HistoryFiler:
-    """Host-side filing of whole move batches into per-env history rows in native code (include/mzhist.h):
-    what DeviceSelfPlay._file_move does one move at a time in numpy, for M moves at once on the library's
-    worker pool.  Finished games come back as PackedGames whose arrays are views of the library's buffers,
-    valid until the next `file` call."""
+    """Host-side filing of whole move batches into per-env history rows in native code (include/mzhist.h): the rows of
+    the running games live here and nowhere else; M moves are filed at once on the library's worker pool
+    (tests/test_history_filer.py holds the one-move-at-a-time numpy filing it must equal).  Finished games come back
+    as PackedGames whose arrays are views of the library's buffers, valid until the next `file` call."""
 
     def __init__(self, num_envs, max_moves, observation_shape, num_actions):
         import ctypes
@@ -780,34 +805,14 @@ class HistoryFiler:
         self._lib.mzhist_begin(self._h, self._native.ptr(obs, self._native.c_f32_p),
                                None if tp is None else self._native.ptr(tp, self._native.c_i32_p))
 
-    def load_rows(self, obs, act, rew, tp, cv, rv, lengths):
-        """Take over running games kept as numpy rows ([E, L+1, ...] / [E, L, ...] arrays, lengths [E])."""
-        self._rows(obs, act, rew, tp, cv, rv, lengths, 1)
-
-    def store_rows(self, obs, act, rew, tp, cv, rv, lengths):
-        """Hand the running games back into numpy rows of the same shapes."""
-        self._rows(obs, act, rew, tp, cv, rv, lengths, 0)
-
-    def _rows(self, obs, act, rew, tp, cv, rv, lengths, load):
-        n = self._native
-        assert obs.shape[1] == self.L + 1 and obs.dtype == numpy.float32 and act.dtype == numpy.int32
-        assert rew.dtype == numpy.float32 and cv.dtype == numpy.float64 and rv.dtype == numpy.float64
-        tp32 = numpy.ascontiguousarray(tp, dtype=numpy.int32)
-        len32 = numpy.ascontiguousarray(lengths, dtype=numpy.int32)
-        rc = self._lib.mzhist_rows(self._h, obs.ctypes.data, act.ctypes.data, rew.ctypes.data, tp32.ctypes.data,
-                                   cv.ctypes.data, rv.ctypes.data, len32.ctypes.data, load)
-        if rc != 0:
-            raise RuntimeError("mzhist_rows failed")
-        if not load:
-            tp[...] = tp32
-            lengths[...] = len32
-
     def searched_moves(self):
         """Plies filed so far that were searched (a non-empty legal set): all of them in self-play, MuZero's in
         evaluation games."""
         return int(self._lib.mzhist_searched_moves(self._h))
 
     def lengths(self):
+        """Moves filed so far in every env's running game: an int32 [E] view of the library's own counters, which
+        `file` and `begin` update in place (valid as long as this filer)."""
         addr = self._lib.mzhist_lengths(self._h)
         return numpy.ctypeslib.as_array(self._ct.cast(addr, self._ct.POINTER(self._ct.c_int32)), shape=(self.E,))
 
@@ -871,6 +876,36 @@ class HistoryFiler:
                            root_values=arr(ptrs[7], ct.c_double, (count, W)))
 
 
+ENV_OUTPUTS = ("reward", "done", "obs_after", "obs_next")    # what the environment kernels return for a move of a batch
+
+
+class UnfiledBatch(typing.NamedTuple):
+    """A collected move batch that DeviceSelfPlay.flush has yet to file: HistoryFiler.file's arguments, as views of the
+    engine's download ring and of the actor's pinned buffers (nothing is copied until the filer reads them)."""
+    out: dict                                               # engine.moves_collect(copy=False)
+    host: dict                                              # ENV_OUTPUTS -> [M, E, ...] host arrays
+    legal: numpy.ndarray                                    # [E, A] for the whole batch or [M, E, A] per move
+    num_legal: numpy.ndarray                                # [E] or [M, E]
+    to_play_after: typing.Optional[numpy.ndarray] = None    # [M, E]; None: player 0 throughout
+    to_play_next: typing.Optional[numpy.ndarray] = None
+    played: typing.Optional[numpy.ndarray] = None           # [M, E] evaluation games: what the environment kernels played
+
+
+@dataclasses.dataclass(slots=True)
+class DeviceBatch:
+    """A device-input move batch between DeviceSelfPlay._device_batch_begin and _device_batch_end."""
+    n_moves: int
+    ring: dict                   # the environment kernels' outputs on the device, [n_moves, E, ...] each
+    obs_in: torch.Tensor         # what the next move's search reads (the move before's next observation, where it lies)
+    threshold: int               # play_game's temperature threshold (0 / None: none)
+    pinned: dict                 # the host set the outputs are downloaded into, move by move
+    opponent: bool               # evaluation games: the kernels also return the played actions and the words drawn
+
+    @property
+    def keys(self):
+        return ENV_OUTPUTS + (("played", "words") if self.opponent else ())
+
+
 class DeviceSelfPlay(ManyEnvLoop):
     """Self-play with device-resident environments (games.device.DeviceEnvs): search, env step and
     observation all stay on the GPU; per move the host only draws the exploration noise, samples the
@@ -886,40 +921,24 @@ class DeviceSelfPlay(ManyEnvLoop):
     def __init__(self, initial_checkpoint, game_name, config, seed, num_envs, device=None, use_graph=True):
         from .games.device import DeviceEnvs
         assert config.stacked_observations == 0, "device envs do not stack past observations yet"
-        self.config = config
-        self.E = E = int(num_envs)
-        self.device = torch.device(device if device is not None else "cuda")
-        torch.manual_seed(seed)
-        self.model = models.MuZeroNetwork(config)
-        self.model.set_weights(initial_checkpoint["weights"])
-        self.model.to(self.device)
-        self.model.eval()
-        seeds = [seed + e for e in range(E)]
-        self.envs = DeviceEnvs(game_name, E, seeds=seeds, device=self.device)
+        self._build_search(initial_checkpoint, config, seed, num_envs, device, use_graph)
+        E = self.E
+        self.envs = DeviceEnvs(game_name, E, seeds=[seed + e for e in range(E)], device=self.device)
         assert self.envs.A == len(config.action_space) and self.envs.observation_shape == tuple(config.observation_shape)
-        fused = config.network == "fullyconnected"
-        self.engine = BatchedMCTS(config, E, device=self.device, seeds=seeds, use_graph=use_graph,
-                                  group_width=16 if fused and len(config.action_space) <= 16 else 0)
-        if fused:
-            try:
-                self.engine.configure_fused_fc(self.model)
-            except (NotImplementedError, RuntimeError):
-                pass
         self.moves_played = 0
         self.games_finished = 0
-        # packed history rows, one per env; every game starts at column 0 of its row
-        T, A = int(config.max_moves) + 1, self.envs.A
-        self._obs = numpy.zeros((E, T + 1) + self.envs.observation_shape, dtype=numpy.float32)
-        self._act = numpy.zeros((E, T + 1), dtype=numpy.int32)
-        self._rew = numpy.zeros((E, T + 1), dtype=numpy.float32)
-        self._tp = numpy.zeros((E, T + 1), dtype=numpy.int8)
-        self._cv = numpy.zeros((E, T, A), dtype=numpy.float64)
-        self._rv = numpy.zeros((E, T), dtype=numpy.float64)
-        self._len = numpy.zeros(E, dtype=numpy.int64)      # moves played in env e's current game
-        self._rows = numpy.arange(E)
         self._cur = self._observe_host()
-        self._obs[:, 0] = self._cur["obs"]
-        self._tp[:, 0] = self._cur["to_play"]
+        # the running games: one packed row per env in the native filer, long enough for a game of config.max_moves moves
+        self._filer = HistoryFiler(E, int(config.max_moves) + 1, self.envs.observation_shape, self.envs.A)
+        self._filer.begin(self._cur["obs"], self._cur["to_play"])
+        self._len = self._filer.lengths()       # moves played in env e's current game (the filer's own counters)
+        self._step_is_batch = False             # step_begin queued the whole move as a one-move batch (an opponent's turn)
+        self._batch_ready = None                # (n_moves, temperature) of the batch drawn and uploaded ahead (play_moves)
+        self._dev_batch = None                  # DeviceBatch being queued
+        self._unfiled = None                    # UnfiledBatch: collected, not filed yet
+        self._copy_stream = torch.cuda.Stream(device=self.device)    # downloads of a batch's env outputs
+        self._ring = None                       # env outputs of a batch on the device, sized by the first batch (_move_ring)
+        self._pinned, self._flip = None, 0      # their two alternating host sets (_next_pinned)
 
     def _observe_host(self):
         obs, legal, num_legal, to_play = self.envs.observe()
@@ -939,21 +958,12 @@ class DeviceSelfPlay(ManyEnvLoop):
     def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None, opponent=None,
              muzero_player=None):
         """One move in every env (the body of play_game's loop, self_play.py:129-182).  `opponent` / `muzero_player` as
-        in BatchedSelfPlay.step (default: what continuous_self_play's test mode set, else "self"): where it is not
-        MuZero's turn the environment kernels play the opponent's move, drawn on that env's stream, and the ply is filed
-        without search statistics.  Such a step is a one-move device-input batch (the opponent draws on the device copy
-        of the stream, which a host-sampled step leaves behind its mirror)."""
+        in BatchedSelfPlay.step (default: what set_opponent stored, else "self"): where it is not MuZero's turn the
+        environment kernels play the opponent's move, drawn on that env's stream, and the ply is filed without search
+        statistics.  Such a step is a one-move device-input batch (the opponent draws on the device copy of the stream,
+        which a host-sampled step leaves behind its mirror)."""
         self.step_begin(on_game, on_games, opponent, muzero_player, temperature, temperature_threshold)
         self.step_end(temperature, temperature_threshold, on_game, on_games)
-
-    def _resolve_opponent(self, opponent, muzero_player):
-        if opponent is None:
-            opponent, muzero_player = getattr(self, "_opponent", ("self", 0))
-        elif muzero_player is None:
-            muzero_player = self.config.muzero_player
-        if opponent not in ("self", "expert", "random"):
-            raise NotImplementedError('many-env actors play opponent "self", "expert" or "random" ("human": use SelfPlay)')
-        return (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
 
     def _set_env_mode(self, mode):
         """Before anything is queued: the envs end games at config.max_moves where that is shorter than the game itself
@@ -961,9 +971,9 @@ class DeviceSelfPlay(ManyEnvLoop):
         switch between self-play and an opponent; the positions stay, the legal counts the searches read are observed
         again in the new mode."""
         limit = int(self.config.max_moves)
-        if limit + 1 > self._rv.shape[1]:
+        if limit + 1 > self._filer.L:
             raise ValueError(f"config.max_moves was raised to {limit} on a built actor whose history rows hold "
-                             f"{self._rv.shape[1] - 1} moves; build a new actor")
+                             f"{self._filer.L - 1} moves; build a new actor")
         limit = limit if limit < self.envs.max_episode_steps else 0
         if self.envs.max_moves != limit:
             self.envs.set_max_moves(limit)
@@ -1011,7 +1021,7 @@ class DeviceSelfPlay(ManyEnvLoop):
 
     def step_end(self, temperature, temperature_threshold=None, on_game=None, on_games=None):
         """Second half of step(): wait for the search, sample the actions, step the envs, file the move."""
-        if getattr(self, "_step_is_batch", False):       # against an opponent: step_begin queued the whole move
+        if self._step_is_batch:                          # against an opponent: step_begin queued the whole move
             self._step_is_batch = False
             self._device_batch_end(on_game, on_games)
             self.flush(on_game, on_games)
@@ -1037,49 +1047,23 @@ class DeviceSelfPlay(ManyEnvLoop):
         # this move's; child visits by action and root values as store_search_statistics computes them (self_play.py:497-512)
         one = {"actions": actions.astype(numpy.int32)[None], "visits": stats["visits"][None],
                "root_value_sum": stats["root_value_sum"][None], "moves_done": numpy.ones(self.E, dtype=numpy.int32)}
-        batch = self._history_filer().file(one, cur["legal"], cur["num_legal"], self.config.num_simulations, reward[None],
-                                           over.astype(numpy.uint8)[None], after["obs"][None], nxt["obs"][None],
-                                           to_play_after=after["to_play"][None], to_play_next=nxt["to_play"][None])
-        self._len[:] = self._filer.lengths()
-        if batch is not None:
-            self.games_finished += len(batch)
-            if on_games is not None:
-                on_games(batch)
-            if on_game is not None:
-                for i, e in enumerate(batch.env_index):
-                    on_game(int(e), batch.history(i))
+        batch = self._filer.file(one, cur["legal"], cur["num_legal"], self.config.num_simulations, reward[None],
+                                 over.astype(numpy.uint8)[None], after["obs"][None], nxt["obs"][None],
+                                 to_play_after=after["to_play"][None], to_play_next=nxt["to_play"][None])
+        self._hand_out(batch, on_game, on_games)
         self._cur = nxt
         self.moves_played += self.E
 
-    def _file_move(self, played, actions, child_visits, root_values, reward, over, obs_after, to_play_after,
-                   obs_next, to_play_next, on_game, on_games):
-        """File one move of the envs in `played` into their history rows; hand finished games (`over`) out
-        and start their next game from obs_next (the reset observation)."""
-        rows = numpy.flatnonzero(played)
-        at = self._len[rows]
-        self._cv[rows, at] = child_visits[rows]
-        self._rv[rows, at] = root_values[rows]
-        self._act[rows, at + 1] = actions[rows]
-        self._rew[rows, at + 1] = reward[rows]
-        self._obs[rows, at + 1] = obs_after[rows]
-        self._tp[rows, at + 1] = to_play_after[rows]
-        self._len[rows] = at + 1
-        idx = numpy.flatnonzero(over & played)
-        if len(idx):
-            n = self._len[idx]
-            L = int(n.max())
-            batch = PackedGames(env_index=idx, length=n, observations=self._obs[idx, : L + 1],
-                                actions=self._act[idx, : L + 1], rewards=self._rew[idx, : L + 1],
-                                to_play=self._tp[idx, : L + 1], child_visits=self._cv[idx, :L], root_values=self._rv[idx, :L])
-            self.games_finished += len(idx)
-            if on_games is not None:
-                on_games(batch)
-            if on_game is not None:
-                for i, e in enumerate(idx):
-                    on_game(int(e), batch.history(i))
-            self._len[idx] = 0
-            self._obs[idx, 0] = obs_next[idx]
-            self._tp[idx, 0] = to_play_next[idx]
+    def _hand_out(self, batch, on_game, on_games):
+        """The games a filing finished (PackedGames or None) leave: counted, then as one batch, then one by one."""
+        if batch is None:
+            return
+        self.games_finished += len(batch)
+        if on_games is not None:
+            on_games(batch)
+        if on_game is not None:
+            for i, e in enumerate(batch.env_index):
+                on_game(int(e), batch.history(i))
 
     # ---- whole batches of moves on the device (engine.moves_*, include/mzmcts.h) ---------------------------
     def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, opponent=None,
@@ -1109,7 +1093,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         self._set_env_mode(mode)
         cur = self._current()
         params = (int(n_moves), float(temperature))
-        if getattr(self, "_batch_ready", None) != params:
+        if self._batch_ready != params:
             self.flush(on_game, on_games)                    # (the unfiled batch holds views of the download ring)
             self._drop_batch()
             eng.moves_prepare(n_moves, cur["legal"], cur["to_play"], temperature, True, num_legal=cur["num_legal"])
@@ -1125,15 +1109,14 @@ class DeviceSelfPlay(ManyEnvLoop):
         out = eng.moves_collect(copy=False)                  # views: filed (flush) before the next collect overwrites them
         # env outputs of the batch: one asynchronous copy each into pinned host buffers (alternating sets, so that
         # the batch waiting to be filed keeps its own), one wait
-        pinned = ring["pinned"][ring["flip"]]
-        ring["flip"] ^= 1
-        for k in ("reward", "done", "obs_after", "obs_next"):
+        pinned = self._next_pinned()
+        for k in ENV_OUTPUTS:
             pinned[k][:n_moves].copy_(ring[k][:n_moves], non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
-        host = {k: pinned[k][:n_moves].numpy() for k in ("reward", "done", "obs_after", "obs_next")}
+        host = {k: pinned[k][:n_moves].numpy() for k in ENV_OUTPUTS}
         eng.moves_submit_next()
         self._batch_ready = params
-        self._unfiled = (out, host, cur["legal"], cur["num_legal"], n_moves, None, None, None)
+        self._unfiled = UnfiledBatch(out=out, host=host, legal=cur["legal"], num_legal=cur["num_legal"])
         self._cur = dict(cur, obs_dev=obs_in, obs=host["obs_next"][n_moves - 1])
         self.moves_played += int(out["moves_done"].sum())
         return out["moves_done"].copy()
@@ -1155,7 +1138,7 @@ class DeviceSelfPlay(ManyEnvLoop):
                             muzero_player=None):
         eng, envs = self.engine, self.envs
         mode = self._resolve_opponent(opponent, muzero_player)
-        if getattr(self, "_batch_ready", None) or temperature_threshold:
+        if self._batch_ready or temperature_threshold:
             # a batch of the pre-drawn form is waiting to be filed / the threshold rule needs the games' current lengths
             self.flush(on_game, on_games)
         self._drop_batch()
@@ -1165,52 +1148,45 @@ class DeviceSelfPlay(ManyEnvLoop):
             eng.moves_sit_out(True)        # the opponent's plies: played by the environment kernels, filed from `played`
         if temperature_threshold:
             eng.moves_temperature_threshold(temperature_threshold, self._len)
-        ring = self._move_ring(n_moves)
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(device=self.device)
         # the env outputs of a move (reward, done, the observations the history rows need) go to pinned host memory on a
         # copy stream as soon as the move's env kernel has run: the downloads ride under the batch's remaining searches
-        pinned = ring["pinned"][ring["flip"]]
-        ring["flip"] ^= 1
-        self._dev_batch = dict(n_moves=n_moves, ring=ring, obs_in=self._cur["obs_dev"], threshold=temperature_threshold,
-                               pinned=pinned, keys=("reward", "done", "obs_after", "obs_next")
-                               + (("played", "words") if mode[0] != "self" else ()))
+        ring = self._move_ring(n_moves)
+        self._dev_batch = DeviceBatch(n_moves=n_moves, ring=ring, obs_in=self._cur["obs_dev"],
+                                      threshold=temperature_threshold, pinned=self._next_pinned(), opponent=mode[0] != "self")
 
     def _device_batch_move(self, m):
         b, eng, envs = self._dev_batch, self.engine, self.envs
-        ring = b["ring"]
-        if b["threshold"] and m > 0:
+        ring = b.ring
+        if b.threshold and m > 0:
             eng.moves_finished(ring["done"][m - 1])          # games that ended with the move before restart their count
         if eng._fc_model is not None:
-            eng.moves_enqueue(b["obs_in"].reshape(self.E, -1).contiguous())
+            eng.moves_enqueue(b.obs_in.reshape(self.E, -1).contiguous())
         else:
-            eng.moves_enqueue_lockstep(self.model, b["obs_in"])
-        opponent = "played" in b["keys"]
-        b["obs_in"] = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
-                                   ring["obs_next"][m], played=ring["played"][m] if opponent else None,
-                                   words=ring["words"][m] if opponent else None)
+            eng.moves_enqueue_lockstep(self.model, b.obs_in)
+        b.obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
+                                ring["obs_next"][m], played=ring["played"][m] if b.opponent else None,
+                                words=ring["words"][m] if b.opponent else None)
         ran = torch.cuda.Event()
         ran.record(torch.cuda.current_stream(self.device))
         self._copy_stream.wait_event(ran)
         with torch.cuda.stream(self._copy_stream):
-            for k in b["keys"]:
-                b["pinned"][k][m].copy_(ring[k][m], non_blocking=True)
+            for k in b.keys:
+                b.pinned[k][m].copy_(ring[k][m], non_blocking=True)
 
     def _device_batch_end(self, on_game, on_games):
         b, eng, envs = self._dev_batch, self.engine, self.envs
-        n_moves, ring = b["n_moves"], b["ring"]
+        n_moves = b.n_moves
         self._dev_batch = None
         self.flush(on_game, on_games)                        # the previous batch's games, while this one runs
         # (views of the engine's pinned rings, filled move by move while the batch ran: nothing is unpacked here; they
         # stay valid until the batch after the next one is prepared, and flush() files them before that)
         out = eng.moves_collect(copy=False)
         inputs = eng.moves_inputs(n_moves, copy=False)
-        pinned = b["pinned"]
         last_to_play = envs.to_play.cpu().numpy()
         self._copy_stream.synchronize()                  # (the last move's downloads)
-        host = {k: pinned[k][:n_moves].numpy() for k in b["keys"]}
+        host = {k: b.pinned[k][:n_moves].numpy() for k in b.keys}
         played = None
-        if "played" in host:
+        if b.opponent:
             # the opponents drew on the device copies of the streams: the host mirrors step over those words
             played = host["played"]
             eng.rng_consumed(host["words"].view(numpy.uint32).sum(axis=0, dtype=numpy.uint64))
@@ -1218,10 +1194,11 @@ class DeviceSelfPlay(ManyEnvLoop):
         to_play = inputs["to_play"]
         to_play_after = (1 - to_play) if two_players else numpy.zeros_like(to_play)
         to_play_next = numpy.concatenate([to_play[1:], last_to_play[None]], axis=0)
-        self._unfiled = (out, host, inputs["legal"], inputs["num_legal"], n_moves, to_play_after, to_play_next, played)
+        self._unfiled = UnfiledBatch(out=out, host=host, legal=inputs["legal"], num_legal=inputs["num_legal"],
+                                     to_play_after=to_play_after, to_play_next=to_play_next, played=played)
         # the envs' current positions stay on the device: the next batch starts from the last move's observation (the
         # kernels' output, where it lies); a step() fetches what it needs first (_current)
-        self._cur = dict(obs_dev=b["obs_in"], on_device_only=True)
+        self._cur = dict(obs_dev=b.obs_in, on_device_only=True)
         self.moves_played += int(out["moves_done"].sum())
         return out["moves_done"].copy()
 
@@ -1229,7 +1206,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         """Can a pass of `moves_per_pass` moves run as one move batch on the device (play_moves)?"""
         if device_inputs is None:
             device_inputs = (not getattr(self.envs, "constant_legal_actions", False) or self.engine._fc_model is None
-                             or bool(temperature_threshold) or getattr(self, "_opponent", ("self", 0))[0] != "self")
+                             or bool(temperature_threshold) or self._opponent[0] != "self")
         return (moves_per_pass is not None
                 and (temperature == 0 or _native.exact_inverse_temperature(temperature))
                 # (a device-input batch draws its exploration noise on the GPU: the legacy gamma sampler for shapes <= 1)
@@ -1250,48 +1227,27 @@ class DeviceSelfPlay(ManyEnvLoop):
         """File the moves of the last play_moves batch into the histories (play_moves does this for the
         batch before while the GPU runs the current one; call it once at the end).  Native code
         (HistoryFiler, include/mzhist.h): one pass over the batch on the library's worker pool."""
-        if getattr(self, "_unfiled", None) is None:
+        u, self._unfiled = self._unfiled, None
+        if u is None:
             return
-        out, host, legal, num_legal, n_moves, to_play_after, to_play_next, played = self._unfiled
-        self._unfiled = None
-        filer = self._history_filer()
-        batch = filer.file(out, legal, num_legal, self.config.num_simulations, host["reward"], host["done"],
-                           host["obs_after"], host["obs_next"], to_play_after=to_play_after, to_play_next=to_play_next,
-                           played=played)
-        self._len[:] = filer.lengths()
-        if batch is not None:
-            self.games_finished += len(batch)
-            if on_games is not None:
-                on_games(batch)
-            if on_game is not None:
-                for i, e in enumerate(batch.env_index):
-                    on_game(int(e), batch.history(i))
+        batch = self._filer.file(u.out, u.legal, u.num_legal, self.config.num_simulations, u.host["reward"], u.host["done"],
+                                 u.host["obs_after"], u.host["obs_next"], to_play_after=u.to_play_after,
+                                 to_play_next=u.to_play_next, played=u.played)
+        self._hand_out(batch, on_game, on_games)
 
     @property
     def searched_moves(self):
         """Env-moves filed so far that ran a search (moves_played counts the opponent's plies too)."""
-        filer = getattr(self, "_filer", None)
-        return 0 if filer is None else filer.searched_moves()
-
-    def _history_filer(self):
-        """The native filer takes over the rows of the running games (and hands them back to step())."""
-        filer = getattr(self, "_filer", None)
-        if filer is None:
-            # (sized like the rows it takes over: config.max_moves of a built actor may have been lowered since)
-            filer = self._filer = HistoryFiler(self.E, self._rv.shape[1], self.envs.observation_shape, self.envs.A)
-        if not getattr(self, "_filer_owns_rows", False):
-            filer.load_rows(self._obs, self._act, self._rew, self._tp, self._cv, self._rv, self._len)
-            self._filer_owns_rows = True
-        return filer
+        return self._filer.searched_moves()
 
     def _drop_batch(self):
         """Forget the batch that was drawn and uploaded ahead (its noise goes back into the RNG streams)."""
-        if getattr(self, "_batch_ready", None):
+        if self._batch_ready:
             self.engine.moves_collect()
             self._batch_ready = None
 
     def _move_ring(self, n_moves):
-        ring = getattr(self, "_ring", None)
+        ring = self._ring
         if ring is None or ring["reward"].shape[0] < n_moves:
             shape, dev = self.envs.observation_shape, self.device
             ring = dict(reward=torch.zeros((n_moves, self.E), dtype=torch.float32, device=dev),
@@ -1302,11 +1258,15 @@ class DeviceSelfPlay(ManyEnvLoop):
                         # opponents consumed
                         played=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev),
                         words=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev))
-            ring["pinned"] = [{k: torch.zeros(ring[k].shape, dtype=ring[k].dtype).pin_memory()
-                               for k in ("reward", "done", "obs_after", "obs_next", "played", "words")} for _ in range(2)]
-            ring["flip"] = 0
+            self._pinned = [{k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
             self._ring = ring
         return ring
+
+    def _next_pinned(self):
+        """The host set a batch's env outputs are downloaded into (after _move_ring): two alternate, so that the batch
+        waiting to be filed keeps its own."""
+        self._flip ^= 1
+        return self._pinned[self._flip]
 
     def close(self):
         self.envs.close()
@@ -1332,7 +1292,8 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             actor.engine.stream = stream
             self.actors.append(actor)
             self.streams.append(stream)
-        self._started = [False] * groups
+        self._started = [False] * groups         # group g's next search is queued (step)
+        self._batch_queued = [False] * groups    # group g's next move batch is queued (play_moves)
         self.device, self.model = self.actors[0].device, self.actors[0].model   # (what ManyEnvLoop's weight pull addresses)
 
     def _pull_weights(self, shared_storage, version):
@@ -1378,16 +1339,6 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             on_games(batch)
         return one, (None if on_games is None else many)
 
-    def _set_opponent(self, opponent, muzero_player):
-        """The groups play what this actor plays (`opponent` None: what continuous_self_play's test mode set)."""
-        if opponent is not None:
-            mode = (opponent, self.config.muzero_player if muzero_player is None else muzero_player)
-        else:
-            mode = getattr(self, "_opponent", ("self", 0))
-        for actor in self.actors:
-            actor._opponent = mode
-        return mode
-
     def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None, prefetch=True, opponent=None,
              muzero_player=None):
         """One move in every env of every group (each group's search was queued during the previous call).
@@ -1396,7 +1347,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         Against an opponent (`opponent` / `muzero_player` as in DeviceSelfPlay.step) the move is a one-move batch of every
         group, queued on the groups' streams in turn; nothing is prefetched."""
         self._no_batch_queued("step")
-        mode = self._set_opponent(opponent, muzero_player)
+        mode = self._resolve_opponent(opponent, muzero_player)
         if mode[0] != "self":
             if any(self._started):
                 raise RuntimeError("step against an opponent: a search is queued ahead; call step(..., prefetch=False) first")
@@ -1409,7 +1360,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         for g, actor in enumerate(self.actors):
             if not self._started[g]:
                 with torch.cuda.stream(self.streams[g]):
-                    actor.step_begin(*self._callbacks(g, on_game, on_games))
+                    actor.step_begin(*self._callbacks(g, on_game, on_games), *mode)
                 self._started[g] = True
         for g, actor in enumerate(self.actors):
             one, many = self._callbacks(g, on_game, on_games)
@@ -1417,7 +1368,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                 actor.step_end(temperature, temperature_threshold, one, many)
                 self._started[g] = False
                 if prefetch:
-                    actor.step_begin(one, many)      # the next move's search runs while the other groups are served
+                    actor.step_begin(one, many, *mode)   # the next move's search runs while the other groups are served
                     self._started[g] = True
 
     def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, prefetch=False,
@@ -1433,11 +1384,10 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         call returns was queued by the call before (with that call's parameters and the weights of that time), and
         the last call before the weights change passes prefetch=False.
         `opponent` / `muzero_player` as in DeviceSelfPlay.play_moves (a prefetched batch plays what its call asked for)."""
-        cfg = self.config
-        self._set_opponent(opponent, muzero_player)
+        mode = self._resolve_opponent(opponent, muzero_player)      # (the groups are told: they keep none of their own)
         if temperature_threshold is None:
-            temperature_threshold = cfg.temperature_threshold
-        queued = self.__dict__.setdefault("_batch_queued", [False] * self.groups)
+            temperature_threshold = self.config.temperature_threshold
+        queued = self._batch_queued
         fresh = [g for g in range(self.groups) if not queued[g]]
         for g in fresh:
             actor = self.actors[g]
@@ -1445,7 +1395,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                 raise RuntimeError("play_moves: a step() is half done; call step(..., prefetch=False) before batches")
             one, many = self._callbacks(g, on_game, on_games)
             with torch.cuda.stream(self.streams[g]):
-                actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold)
+                actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold, *mode)
         for m in range(n_moves):
             for g in fresh:
                 with torch.cuda.stream(self.streams[g]):
@@ -1459,7 +1409,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                 played.append(actor._device_batch_end(one, many))
                 queued[g] = False
                 if prefetch:
-                    actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold)
+                    actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold, *mode)
                     for m in range(n_moves):
                         actor._device_batch_move(m)
                     queued[g] = True
@@ -1467,7 +1417,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         return numpy.concatenate(played)
 
     def _no_batch_queued(self, what):
-        if any(self.__dict__.get("_batch_queued", ())):
+        if any(self._batch_queued):
             raise RuntimeError(f"{what}: a move batch is queued ahead; call play_moves(..., prefetch=False) first")
 
     def _play_pass(self, temperature, temperature_threshold, moves_per_pass):
@@ -1475,7 +1425,6 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         device-input form; nothing stays queued behind the pass: a weight pull follows), else move by move with the
         groups' halves alternating -- the last move of a pass queues nothing behind it either."""
         finished = []
-        self._set_opponent(None, None)
         if self.actors[0]._batchable(temperature, temperature_threshold, moves_per_pass, device_inputs=True):
             collect = lambda e, gh: finished.append((e, gh))
             self.play_moves(moves_per_pass, temperature, on_game=collect, temperature_threshold=temperature_threshold or 0)
@@ -1534,9 +1483,7 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
         probe = actor.actors[0]
     else:
         actor = probe = DeviceSelfPlay(checkpoint, game_name, cfg, seed, E, device=device, use_graph=use_graph)
-    actor._opponent = (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
-    for a in getattr(actor, "actors", ()):
-        a._opponent = actor._opponent
+    actor.set_opponent(opponent, muzero_player)
     clock = numpy.zeros(E, dtype=numpy.int64)          # plies of env e's finished games
     plies = numpy.zeros(E, dtype=numpy.int64)          # plies env e has played
     found = {k: [] for k in ("start", "env", "length", "mine", "theirs", "total")}

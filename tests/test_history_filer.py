@@ -1,15 +1,16 @@
-"""include/mzhist.h: native filing of move batches into game histories == the one-move-at-a-time numpy filing
-of DeviceSelfPlay._file_move (host code only: runs without a GPU)."""
+"""include/mzhist.h: native filing of move batches into game histories == filing them one move at a time in numpy
+(_Harness._file, the reference kept here; host code only: runs without a GPU)."""
 import importlib
 
 import numpy as np
 
 
 class _Harness:
-    """The filing half of DeviceSelfPlay, without envs or searches."""
+    """History rows of E running games in numpy, filed one move at a time: what the native filer must equal."""
 
     def __init__(self, sp, E, L, shape, A):
         self.E = E
+        self._packed = sp.PackedGames
         self._obs = np.zeros((E, L + 1) + shape, np.float32)
         self._act = np.zeros((E, L + 1), np.int32)
         self._rew = np.zeros((E, L + 1), np.float32)
@@ -18,7 +19,36 @@ class _Harness:
         self._rv = np.zeros((E, L))
         self._len = np.zeros(E, np.int64)
         self.games_finished = 0
-        self._file = sp.DeviceSelfPlay._file_move.__get__(self)
+
+    def _file(self, played, actions, child_visits, root_values, reward, over, obs_after, to_play_after, obs_next,
+              to_play_next, on_game, on_games):
+        """File one move of the envs in `played` into their history rows; hand finished games (`over`) out
+        and start their next game from obs_next (the reset observation)."""
+        rows = np.flatnonzero(played)
+        at = self._len[rows]
+        self._cv[rows, at] = child_visits[rows]
+        self._rv[rows, at] = root_values[rows]
+        self._act[rows, at + 1] = actions[rows]
+        self._rew[rows, at + 1] = reward[rows]
+        self._obs[rows, at + 1] = obs_after[rows]
+        self._tp[rows, at + 1] = to_play_after[rows]
+        self._len[rows] = at + 1
+        idx = np.flatnonzero(over & played)
+        if len(idx):
+            n = self._len[idx]
+            L = int(n.max())
+            batch = self._packed(env_index=idx, length=n, observations=self._obs[idx, : L + 1],
+                                 actions=self._act[idx, : L + 1], rewards=self._rew[idx, : L + 1],
+                                 to_play=self._tp[idx, : L + 1], child_visits=self._cv[idx, :L], root_values=self._rv[idx, :L])
+            self.games_finished += len(idx)
+            if on_games is not None:
+                on_games(batch)
+            if on_game is not None:
+                for i, e in enumerate(idx):
+                    on_game(int(e), batch.history(i))
+            self._len[idx] = 0
+            self._obs[idx, 0] = obs_next[idx]
+            self._tp[idx, 0] = to_play_next[idx]
 
 
 def test_native_filer_matches_numpy_filing(pkg):
