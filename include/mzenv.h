@@ -9,6 +9,13 @@
  *   MZENV_TICTACTOE  games/tictactoe.py:242-305 (rules), :132-145 (reward x20), observation planes
  *                    [own stones, opponent stones, player to move] as int-valued floats
  *   MZENV_CONNECT4   games/connect4.py:219-304 (rules), :132-143 (reward x10)
+ *   MZENV_GOMOKU     games/gomoku.py:219-289 (rules; is_finished :263-291), :236-249 (reward 1 for the ply that ends the game, a full-board
+ *                    draw included; no scaling).  11 x 11 board, cell = action = 11 * row + column, A = 121; a game
+ *                    ends when any stone of either colour starts five equal stones down-left, down, down-right or
+ *                    right (six in a row contains a five; a run does not wrap from column 10 into the next row), or
+ *                    when the board is full.  Scripted opponent: "random" only -- the reference defines no expert
+ *                    agent for Gomoku and mzenv_set_opponent refuses MZENV_OPPONENT_EXPERT there.  A wavefront per
+ *                    env, two cells per lane (csrc/env_kernels.hip); games 0-2 run one thread per env.
  *   MZENV_CARTPOLE   games/cartpole.py wraps gym's CartPole-v1; gym is not vendored by the reference, so
  *                    this restates the published classic-control equations (Euler, tau = 0.02) exactly as
  *                    muzero-hypermodel_amd/games/cartpole.py does on the host -- parity UNPINNED against gym
@@ -28,6 +35,7 @@ extern "C" {
 #define MZENV_CARTPOLE 0
 #define MZENV_TICTACTOE 1
 #define MZENV_CONNECT4 2
+#define MZENV_GOMOKU 3
 
 typedef struct mzenv mzenv;
 
@@ -63,7 +71,7 @@ int mzenv_advance(mzenv *env, const int32_t *actions, float *reward_out, uint8_t
 /* ---- evaluation games: a scripted opponent plays one side (reference self_play.py:189-221) -----------------------
  * MZENV_OPPONENT_EXPERT  the plugin's expert_agent(): numpy.random.choice over the legal actions (always drawn), then
  *                        the line scan of games/tictactoe.py / games/connect4.py (a winning completion returns at
- *                        once, a block is kept while the scan goes on)
+ *                        once, a block is kept while the scan goes on); not available for MZENV_GOMOKU (error)
  * MZENV_OPPONENT_RANDOM  numpy.random.choice over the legal actions
  * In a reference worker the opponent draws from numpy's global generator, which is also the search's stream: mt_key
  * (dev u32[E][624]) and mt_pos (dev i32[E]) are therefore the SEARCH ENGINE's per-env streams (mzmcts_rng_streams);
@@ -94,8 +102,8 @@ int mzenv_advance_opponent(mzenv *env, const int32_t *actions, float *reward_out
                            int32_t *played_out, uint32_t *words_out, void *stream);
 
 /* Put every env of a board game into a given position: boards host i8[E][cells] (0 empty, +1 first player, -1 second;
- * tic-tac-toe cell = 3 * row + column, connect four cell = 7 * row + column with row 0 at the bottom), players host
- * i8[E] (+1 / -1 to move).  Blocking; cell and player values are checked, reachability is not (see above for what a
+ * tic-tac-toe cell = 3 * row + column, connect four cell = 7 * row + column with row 0 at the bottom, gomoku cell =
+ * 11 * row + column), players host i8[E] (+1 / -1 to move).  Blocking; cell and player values are checked, reachability is not (see above for what a
  * step does with a finished position).  The ply counter of each env (below) becomes the number of stones on its board:
  * a position handed in continues the game it came from. */
 int mzenv_set_boards(mzenv *env, const int8_t *boards, const int8_t *players);

@@ -4,10 +4,12 @@
 //
 // Boards are int8[cells], 0 empty, +1 first player, -1 second player; tic-tac-toe cell = 3 * row + column,
 // connect four cell = 7 * row + column with row 0 at the bottom.  The rules restate this package's host plugins
-// (games/tictactoe.py, games/connect4.py), which fixture G11 pins to the reference move by move.
+// (games/tictactoe.py, games/connect4.py), which fixture G11 pins to the reference move by move.  Gomoku's rules
+// (11 x 11, cell = 11 * row + column; fixture G18) live in gomoku_rules.h; its scripted opponent is below.
 #pragma once
 #include <cstdint>
 
+#include "gomoku_rules.h"
 #include "np_legacy_rng.h"
 
 namespace mz {
@@ -155,6 +157,16 @@ MZ_HD inline int opponent_action(int game, int kind, const int8_t* b, int player
     if (n == 0) return -1;
     if (kind == kOpponentRandom) return random_legal_action(legal, n, key, pos, words);
     return (game == 1) ? ttt_expert(b, player, legal, n, key, pos, words) : c4_expert(b, player, legal, n, key, pos, words);
+}
+
+// The scripted opponent's move on a Gomoku board, drawn from the stream key/pos.  The reference's Gomoku has no
+// expert_agent (AbstractGame.expert_agent raises), so there is one kind: numpy.random.choice over the legal cells, up
+// to 121 of them (one legal cell draws no word).  A full board has no move: -1, nothing drawn.
+MZ_HD inline int gmk_opponent_action(const int8_t* b, uint32_t* key, int32_t* pos, uint32_t* words) {
+    int32_t legal[kGmkCells];
+    const int n = gmk_legal(b, legal);
+    if (n == 0) return -1;
+    return random_legal_action(legal, n, key, pos, words);
 }
 
 }  // namespace mz

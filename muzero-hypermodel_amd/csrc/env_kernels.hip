@@ -2,6 +2,7 @@
 //
 // One thread per env: a move is a handful of byte operations per game, far below any roofline that
 // matters; what these kernels buy is that E games advance without E host-side Python calls per move.
+// Gomoku's 121 cells do not fit that shape: its kernels (further down) give an env a wavefront and a lane two cells.
 // Rules restate the reference's in-repo envs (games/tictactoe.py:242-305, games/connect4.py:219-304)
 // with the Game wrappers' reward scaling; CartPole restates the classic-control equations (unpinned).  The board rules
 // and the scripted opponents of evaluation games live in board_rules.h (also compiled for the host by a CPU check).
@@ -176,24 +177,299 @@ __global__ __launch_bounds__(256) void env_advance_kernel(EnvParams p, const int
     env_observe_one(p, e, obs_next, legal, num_legal, to_play);
 }
 
+// ---- Gomoku: a wavefront owns an env, a lane owns cells -------------------------------------------------------------
+// An 11 x 11 board does not fit the one-thread-per-env shape above: 363 strided float stores per observation and lane
+// (every store instruction of a wavefront touching 64 different cache lines) and a serial 121 x 4 x 5 line scan.  Here
+// the 64 lanes of a wavefront share ONE env: lane l holds cells l and 64 + l (the second for l < 57) in registers,
+// four envs make a 256-thread workgroup.
+//   line scan     the board is staged once in LDS with its zero border (gomoku_rules.h: 15 x 15 bytes), every lane
+//                 runs gmk_five_from on its own cells, the verdict is an __any over the wavefront
+//   legal list    __ballot of "my cell is empty" per 64-cell half; a lane's slot is the popcount of the mask bits
+//                 below it (plus the first half's count): ascending cell order without a serial loop
+//   observations  lane l writes floats l and 64 + l of each 121-float plane: consecutive lanes, consecutive addresses
+//   opponent      lane 0 draws the slot from env e's Mersenne stream (the stream is serial); the slot reaches the other
+//                 lanes by a register broadcast, and the lane holding that slot's cell names the action by a ballot
+// Everything an env shares (player, ply counter, outputs per env) is read by all lanes and written by lane 0.
+constexpr int kGmkEnvsPerBlock = 4;
+enum GmkOp : int { kGmkReset = 0, kGmkStep = 1, kGmkObserve = 2, kGmkAdvance = 3 };
+
+struct GmkCells {
+    int b0, b1;  // this lane's cells l and 64 + l (b1 = a stone of nobody's colour, 2, for the lanes that have none)
+};
+
+__device__ __forceinline__ uint64_t gmk_lanes_below(int lane) { return (1ull << lane) - 1ull; }
+
+// observation planes [board == 1, board == -1, player to move] of one env, coalesced
+__device__ __forceinline__ void gmk_write_obs(float* __restrict__ o, int lane, GmkCells c, int player) {
+    const bool second = lane + 64 < kGmkCells;
+    const float turn = static_cast<float>(player);
+    o[lane] = c.b0 == 1 ? 1.f : 0.f;
+    if (second) o[64 + lane] = c.b1 == 1 ? 1.f : 0.f;
+    o[kGmkCells + lane] = c.b0 == -1 ? 1.f : 0.f;
+    if (second) o[kGmkCells + 64 + lane] = c.b1 == -1 ? 1.f : 0.f;
+    o[2 * kGmkCells + lane] = turn;
+    if (second) o[2 * kGmkCells + 64 + lane] = turn;
+}
+
+// legal list by ordered compaction; returns the number of empty cells.  slot0 / slot1: where this lane's cells stand
+// in the list (meaningful for its empty cells only).
+__device__ __forceinline__ int gmk_legal_slots(int lane, GmkCells c, int* slot0, int* slot1) {
+    const uint64_t m0 = __ballot(c.b0 == 0), m1 = __ballot(c.b1 == 0);
+    const int n0 = __popcll(m0);
+    *slot0 = __popcll(m0 & gmk_lanes_below(lane));
+    *slot1 = n0 + __popcll(m1 & gmk_lanes_below(lane));
+    return n0 + __popcll(m1);
+}
+
+__device__ __forceinline__ void gmk_write_observation(const EnvParams& p, int e, int lane, GmkCells c, int player,
+                                                      float* __restrict__ obs, int32_t* __restrict__ legal,
+                                                      int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play) {
+    gmk_write_obs(obs + static_cast<size_t>(e) * (3 * kGmkCells), lane, c, player);
+    int slot0, slot1;
+    const int n = gmk_legal_slots(lane, c, &slot0, &slot1);
+    int32_t* l = legal + static_cast<size_t>(e) * kGmkCells;
+    if (c.b0 == 0) l[slot0] = lane;
+    if (c.b1 == 0) l[slot1] = 64 + lane;
+    if (lane == 0) {
+        // opponent mode: an empty legal set is the engine's "this env sits the search out" (the row stays filled)
+        const bool opponent = p.opp_kind != kOpponentSelf && (player == 1 ? 0 : 1) != p.opp_player;
+        num_legal[e] = opponent ? 0 : n;
+        to_play[e] = player == 1 ? 0 : 1;
+    }
+}
+
+template <int OP>
+__global__ __launch_bounds__(64 * kGmkEnvsPerBlock) void gomoku_env_kernel(
+    EnvParams p, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
+    uint8_t* __restrict__ done_out, float* __restrict__ obs_after, float* __restrict__ obs_next,
+    int32_t* __restrict__ legal, int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play,
+    int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
+    __shared__ __attribute__((aligned(16))) int8_t padded_all[kGmkEnvsPerBlock][256];  // 225 bytes used per env
+    const int lane = threadIdx.x & 63, group = threadIdx.x >> 6;
+    const int e = blockIdx.x * kGmkEnvsPerBlock + group;
+    const bool live = e < p.E;  // (a wavefront without an env stays for the workgroup barrier and touches no memory)
+    int8_t* padded = padded_all[group];
+    const bool second = lane + 64 < kGmkCells;
+    int8_t* board = p.board + static_cast<size_t>(live ? e : 0) * kGmkCells;
+
+    if (OP == kGmkReset) {
+        if (!live || (mask && !mask[e])) return;
+        board[lane] = 0;
+        if (second) board[64 + lane] = 0;
+        if (lane == 0) {
+            p.player[e] = 1;
+            p.steps[e] = 0;
+        }
+        return;
+    }
+
+    GmkCells c{2, 2};
+    int player = 1;
+    if (live) {
+        c.b0 = board[lane];
+        if (second) c.b1 = board[64 + lane];
+        player = p.player[e];
+    }
+    if (OP == kGmkObserve) {
+        if (live) gmk_write_observation(p, e, lane, c, player, obs_after, legal, num_legal, to_play);
+        return;
+    }
+
+    // ---- Game.step ----
+    int a = live ? actions[e] : -1;
+    uint32_t words = 0;
+    if (live && p.opp_kind != kOpponentSelf && (player == 1 ? 0 : 1) != p.opp_player) {
+        // the opponent's turn: the incoming action is ignored, numpy.random.choice(legal) decides (random_legal_action's
+        // bounded draw; the list it indexes is never written out: entry k is the empty cell whose slot is k)
+        int slot0, slot1;
+        const int n = gmk_legal_slots(lane, c, &slot0, &slot1);
+        int k = -1;
+        if (lane == 0 && n > 0) {
+            int32_t pos = p.opp_pos[e];
+            k = static_cast<int>(mt_below(p.opp_key + static_cast<size_t>(e) * kMtN, &pos, static_cast<uint32_t>(n), &words));
+            if (words) p.opp_pos[e] = pos;
+        }
+        k = __shfl(k, 0);  // (`words` stays lane 0's: lane 0 reports it)
+        // the k-th empty cell: at most one lane holds it, in one of its two cells
+        const uint64_t hit0 = __ballot(c.b0 == 0 && slot0 == k), hit1 = __ballot(c.b1 == 0 && slot1 == k);
+        a = hit0 ? __ffsll(static_cast<unsigned long long>(hit0)) - 1
+                 : (hit1 ? 64 + __ffsll(static_cast<unsigned long long>(hit1)) - 1 : -1);  // a full board has no move
+    }
+    if (live && lane == 0) {
+        if (played_out) played_out[e] = a < 0 ? -1 : a;
+        if (words_out) words_out[e] = words;
+    }
+    bool done = false;
+    float reward = 0.f;
+    const bool moved = live && a >= 0;
+    if (moved) {
+        // (an action that names no cell owns no lane: no stone is placed and no store leaves the board)
+        if (a == lane) {
+            c.b0 = player;
+            board[lane] = static_cast<int8_t>(player);
+        }
+        if (second && a == 64 + lane) {
+            c.b1 = player;
+            board[64 + lane] = static_cast<int8_t>(player);
+        }
+        // stage the board with its zero border: 256 bytes cleared, then the cells at their padded places
+        reinterpret_cast<int32_t*>(padded)[lane] = 0;
+    }
+    __syncthreads();
+    if (moved) {
+        padded[gmk_padded_index(lane)] = static_cast<int8_t>(c.b0);
+        if (second) padded[gmk_padded_index(64 + lane)] = static_cast<int8_t>(c.b1);
+    }
+    __syncthreads();
+    if (moved) {
+        const bool five = gmk_five_from(padded, gmk_padded_index(lane)) ||
+                          (second && gmk_five_from(padded, gmk_padded_index(64 + lane)));
+        const bool empty = c.b0 == 0 || c.b1 == 0;
+        done = __any(five) || !__any(empty);
+        reward = done ? 1.f : 0.f;  // the ply that finishes the game, a full-board draw included (no scaling in Game.step)
+        const int steps = p.steps[e] + 1;  // an opponent's ply counts like MuZero's (len(action_history))
+        done = done || (p.max_moves > 0 && steps >= p.max_moves);
+        player = -player;
+        if (lane == 0) {
+            p.steps[e] = steps;
+            p.player[e] = static_cast<int8_t>(player);
+        }
+    }
+    if (live && lane == 0) {
+        reward_out[e] = reward;
+        done_out[e] = done ? 1 : 0;
+    }
+    if (OP == kGmkStep || !live) return;
+
+    // ---- observation after the move, Game.reset() of a finished env, observation the next search sees ----
+    gmk_write_observation(p, e, lane, c, player, obs_after, legal, num_legal, to_play);
+    if (done) {
+        c.b0 = 0;
+        c.b1 = second ? 0 : 2;
+        player = 1;
+        board[lane] = 0;
+        if (second) board[64 + lane] = 0;
+        if (lane == 0) {
+            p.player[e] = 1;
+            p.steps[e] = 0;
+        }
+    }
+    gmk_write_observation(p, e, lane, c, player, obs_next, legal, num_legal, to_play);
+}
+
+// The same rules with one thread per env, as games 1 and 2 run: kept for measurement and as a cross-check of the
+// wavefront form (EnvParams::gomoku_serial, set at mzenv_create from the environment; never the default).
+__device__ __forceinline__ void gmk_serial_observe(const EnvParams& p, int e, float* __restrict__ obs,
+                                                   int32_t* __restrict__ legal, int32_t* __restrict__ num_legal,
+                                                   int32_t* __restrict__ to_play) {
+    float* o = obs + static_cast<size_t>(e) * (3 * kGmkCells);
+    const int8_t* b = p.board + static_cast<size_t>(e) * kGmkCells;
+    const int pl = p.player[e];
+    for (int i = 0; i < kGmkCells; ++i) {
+        o[i] = b[i] == 1 ? 1.f : 0.f;
+        o[kGmkCells + i] = b[i] == -1 ? 1.f : 0.f;
+        o[2 * kGmkCells + i] = static_cast<float>(pl);
+    }
+    const int n = gmk_legal(b, legal + static_cast<size_t>(e) * kGmkCells);
+    num_legal[e] = opponent_to_move(p, e) ? 0 : n;
+    to_play[e] = pl == 1 ? 0 : 1;
+}
+
+__device__ __forceinline__ void gmk_serial_reset(const EnvParams& p, int e) {
+    int8_t* b = p.board + static_cast<size_t>(e) * kGmkCells;
+    for (int i = 0; i < kGmkCells; ++i) b[i] = 0;
+    p.player[e] = 1;
+    p.steps[e] = 0;
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void gomoku_env_serial_kernel(
+    EnvParams p, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
+    uint8_t* __restrict__ done_out, float* __restrict__ obs_after, float* __restrict__ obs_next,
+    int32_t* __restrict__ legal, int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play,
+    int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.E) return;
+    if (OP == kGmkReset) {
+        if (!mask || mask[e]) gmk_serial_reset(p, e);
+        return;
+    }
+    if (OP == kGmkObserve) {
+        gmk_serial_observe(p, e, obs_after, legal, num_legal, to_play);
+        return;
+    }
+    int8_t* b = p.board + static_cast<size_t>(e) * kGmkCells;
+    int a = actions[e];
+    uint32_t words = 0;
+    if (opponent_to_move(p, e)) {
+        int32_t pos = p.opp_pos[e];
+        a = gmk_opponent_action(b, p.opp_key + static_cast<size_t>(e) * kMtN, &pos, &words);
+        if (words) p.opp_pos[e] = pos;
+    }
+    if (played_out) played_out[e] = a < 0 ? -1 : a;
+    if (words_out) words_out[e] = words;
+    bool done = false;
+    float reward = 0.f;
+    if (a >= 0) {
+        const int pl = p.player[e];
+        if (a < kGmkCells) b[a] = static_cast<int8_t>(pl);
+        done = gmk_finished(b);
+        reward = done ? 1.f : 0.f;
+        const int steps = ++p.steps[e];
+        done = done || (p.max_moves > 0 && steps >= p.max_moves);
+        p.player[e] = static_cast<int8_t>(-pl);
+    }
+    reward_out[e] = reward;
+    done_out[e] = done ? 1 : 0;
+    if (OP == kGmkStep) return;
+    gmk_serial_observe(p, e, obs_after, legal, num_legal, to_play);
+    if (done) gmk_serial_reset(p, e);
+    gmk_serial_observe(p, e, obs_next, legal, num_legal, to_play);
+}
+
+template <int OP>
+hipError_t launch_gomoku(const EnvParams& p, const uint8_t* mask, const int32_t* actions, float* reward, uint8_t* done,
+                         float* obs_after, float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play,
+                         int32_t* played, uint32_t* words, hipStream_t stream) {
+    if (p.gomoku_serial)
+        gomoku_env_serial_kernel<OP><<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(
+            p, mask, actions, reward, done, obs_after, obs_next, legal, num_legal, to_play, played, words);
+    else
+        gomoku_env_kernel<OP><<<dim3((p.E + kGmkEnvsPerBlock - 1) / kGmkEnvsPerBlock), dim3(64 * kGmkEnvsPerBlock), 0, stream>>>(
+            p, mask, actions, reward, done, obs_after, obs_next, legal, num_legal, to_play, played, words);
+    return hipGetLastError();
+}
+
 hipError_t launch_env_reset(const EnvParams& p, const uint8_t* mask, hipStream_t stream) {
+    if (p.game == 3)
+        return launch_gomoku<kGmkReset>(p, mask, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr, stream);
     env_reset_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, mask);
     return hipGetLastError();
 }
 hipError_t launch_env_step(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, int32_t* played,
                            uint32_t* words, hipStream_t stream) {
+    if (p.game == 3)
+        return launch_gomoku<kGmkStep>(p, nullptr, actions, reward, done, nullptr, nullptr, nullptr, nullptr, nullptr, played,
+                                       words, stream);
     env_step_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, reward, done, played, words);
     return hipGetLastError();
 }
 hipError_t launch_env_advance(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, float* obs_after,
                               float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play, int32_t* played,
                               uint32_t* words, hipStream_t stream) {
+    if (p.game == 3)
+        return launch_gomoku<kGmkAdvance>(p, nullptr, actions, reward, done, obs_after, obs_next, legal, num_legal, to_play,
+                                          played, words, stream);
     env_advance_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, reward, done, obs_after, obs_next, legal,
                                                                           num_legal, to_play, played, words);
     return hipGetLastError();
 }
 hipError_t launch_env_observe(const EnvParams& p, float* obs, int32_t* legal, int32_t* num_legal, int32_t* to_play,
                               hipStream_t stream) {
+    if (p.game == 3)
+        return launch_gomoku<kGmkObserve>(p, nullptr, nullptr, nullptr, nullptr, obs, nullptr, legal, num_legal, to_play, nullptr,
+                                          nullptr, stream);
     env_observe_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, obs, legal, num_legal, to_play);
     return hipGetLastError();
 }

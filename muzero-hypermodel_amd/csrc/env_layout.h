@@ -6,7 +6,7 @@ namespace mz {
 
 struct EnvParams {
     int32_t game, E, A, cells, obs_floats;
-    int8_t* board;     // [E][cells]  tictactoe / connect4: 0 empty, +1 first player, -1 second player
+    int8_t* board;     // [E][cells]  tictactoe / connect4 / gomoku: 0 empty, +1 first player, -1 second player
     int8_t* player;    // [E]         +1 / -1: the player to move
     double* state;     // [E][4]      cartpole: x, x_dot, theta, theta_dot
     int32_t* steps;    // [E]         plies played in the env's current game (every game; cartpole's time limit reads it)
@@ -19,6 +19,9 @@ struct EnvParams {
     int32_t* opp_pos;   // [E]
     // move limit (mzenv_set_max_moves): > 0 = the ply that brings steps[e] to it ends the game; 0 = the game's own rules only
     int32_t max_moves;
+    // Gomoku only: non-zero runs the one-thread-per-env form of its kernels instead of the wavefront-per-env form (a
+    // measurement and cross-check switch, read from the environment at mzenv_create; never the default)
+    int32_t gomoku_serial;
 };
 
 }  // namespace mz

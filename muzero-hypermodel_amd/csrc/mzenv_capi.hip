@@ -1,6 +1,7 @@
 // mzenv_capi.hip -- host side of the device-resident environments (include/mzenv.h).
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -58,7 +59,7 @@ extern "C" {
 const char* mzenv_last_error(const mzenv* env) { return env ? env->error.c_str() : g_env_error.c_str(); }
 
 int mzenv_create(int32_t game, int32_t num_envs, int32_t device, const uint32_t* seeds, mzenv** out) {
-    if (!out || !seeds || num_envs <= 0 || game < 0 || game > 2) return env_fail(nullptr, -1, "mzenv_create: bad argument");
+    if (!out || !seeds || num_envs <= 0 || game < 0 || game > MZENV_GOMOKU) return env_fail(nullptr, -1, "mzenv_create: bad argument");
     *out = nullptr;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
@@ -93,12 +94,18 @@ int mzenv_create(int32_t game, int32_t num_envs, int32_t device, const uint32_t*
         if (err == hipSuccess) err = hipDeviceSynchronize();
         if (err != hipSuccess) return bail(env_fail(env, -2, std::string("seeding: ") + hipGetErrorString(err)));
     } else {
-        const bool ttt = game == MZENV_TICTACTOE;
-        p.A = ttt ? 9 : 7;
-        p.cells = ttt ? 9 : 42;
+        const int rows = game == MZENV_TICTACTOE ? 3 : (game == MZENV_CONNECT4 ? 6 : 11);
+        const int cols = game == MZENV_TICTACTOE ? 3 : (game == MZENV_CONNECT4 ? 7 : 11);
+        p.cells = rows * cols;
+        p.A = game == MZENV_CONNECT4 ? cols : p.cells;
         p.obs_floats = 3 * p.cells;
         env->players = 2;
-        env->shape[0] = 3, env->shape[1] = ttt ? 3 : 6, env->shape[2] = ttt ? 3 : 7;
+        env->shape[0] = 3, env->shape[1] = rows, env->shape[2] = cols;
+        if (game == MZENV_GOMOKU) {
+            // measurement / cross-check switch: the one-thread-per-env form of the Gomoku kernels (env_kernels.hip)
+            const char* serial = std::getenv("MZENV_GOMOKU_SERIAL");
+            p.gomoku_serial = (serial && serial[0] && serial[0] != '0') ? 1 : 0;
+        }
         if ((rc = env_alloc(env, &p.board, static_cast<size_t>(num_envs) * p.cells))) return bail(rc);
         if ((rc = env_alloc(env, &p.player, num_envs))) return bail(rc);
     }
@@ -146,6 +153,9 @@ int mzenv_set_opponent(mzenv* env, int32_t kind, int32_t muzero_player, uint32_t
     if (env->players < 2) return env_fail(env, -1, "mzenv_set_opponent: a one-player game has no opponent");
     if (muzero_player < 0 || muzero_player >= env->players)
         return env_fail(env, -1, "mzenv_set_opponent: muzero_player is not a player of this game");
+    if (env->p.game == MZENV_GOMOKU && kind == MZENV_OPPONENT_EXPERT)
+        return env_fail(env, -1, "mzenv_set_opponent: gomoku has no expert agent (the reference's games/gomoku.py defines none); "
+                                 "its scripted opponent is \"random\"");
     env->p.opp_kind = kind;
     env->p.opp_player = muzero_player;
     env->p.opp_key = mt_key;

@@ -10,7 +10,8 @@ import torch
 
 from .. import _native
 
-GAME_IDS = {"cartpole": 0, "tictactoe": 1, "connect4": 2}
+GAME_IDS = {"cartpole": 0, "tictactoe": 1, "connect4": 2, "gomoku": 3}
+MAX_EPISODE_STEPS = {"cartpole": 500, "tictactoe": 9, "connect4": 42, "gomoku": 121}   # the games' own lengths
 OPPONENT_KINDS = {"self": 0, "expert": 1, "random": 2}      # include/mzenv.h MZENV_OPPONENT_*
 
 
@@ -36,7 +37,7 @@ class DeviceEnvs:
         self._lib.mzenv_shape(self._h, ctypes.byref(a), ctypes.byref(p), shape)
         self.A, self.players, self.observation_shape = a.value, p.value, tuple(shape)
         self.constant_legal_actions = game == "cartpole"     # every action legal in every state
-        self.max_episode_steps = {"cartpole": 500, "tictactoe": 9, "connect4": 42}[game]
+        self.max_episode_steps = MAX_EPISODE_STEPS[game]
         with torch.cuda.device(self.device):
             self.obs = torch.zeros((self.E, *self.observation_shape), dtype=torch.float32, device=self.device)
             self.legal = torch.zeros((self.E, self.A), dtype=torch.int32, device=self.device)
@@ -79,6 +80,9 @@ class DeviceEnvs:
         action actually played) and `words` (stream words consumed: hand their sums to engine.rng_consumed)."""
         if kind not in OPPONENT_KINDS:
             raise NotImplementedError('device envs play opponent "self", "expert" or "random" ("human": use SelfPlay)')
+        if kind == "expert" and self.game == "gomoku":
+            # (AbstractGame.expert_agent raises the same for a host Game: the reference's games/gomoku.py defines none)
+            raise NotImplementedError('gomoku has no expert agent; its scripted opponent is "random"')
         key = pos = None
         if kind != "self":
             if engine is None:
@@ -90,7 +94,7 @@ class DeviceEnvs:
 
     def set_boards(self, boards, players):
         """Put the envs of a board game into given positions: boards int8 [E, cells] (0 / +1 / -1; connect four row 0
-        = bottom), players int8 [E] (+1 / -1 to move).  An env's ply count (game_moves) becomes its number of stones."""
+        = bottom; gomoku cell = 11 * row + column), players int8 [E] (+1 / -1 to move).  An env's ply count (game_moves) becomes its number of stones."""
         boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(self.E, -1)
         players = np.ascontiguousarray(players, dtype=np.int8).reshape(self.E)
         self._check(self._lib.mzenv_set_boards(self._h, boards.ctypes.data, players.ctypes.data))

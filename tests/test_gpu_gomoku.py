@@ -1,0 +1,525 @@
+"""Gomoku on the device: the wavefront-per-env environment kernels (csrc/env_kernels.hip) against fixture G18 (recorded
+from the reference's games/gomoku.py) and the host plugin; 121-action searches against the reference's traces; the
+self-play, evaluation and replay layers on an 11 x 11 game.  Networks are small (1 block x 8 or 16 channels) and take
+the PyTorch-ROCm path of models.py: there is no 11 x 11 tower kernel."""
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from gomoku_cases import CELLS, TRACE_FILES, edge_boards, fixture_boards, full_board_without_five
+from parity_helpers import load_golden, run_injected_on_engine, run_injected_on_oracle, synthetic_model
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+
+
+def gomoku():
+    return importlib.import_module("muzero-hypermodel_amd.games.gomoku")
+
+
+@pytest.fixture(scope="module")
+def dev(pkg):
+    importlib.import_module("muzero-hypermodel_amd.build").build_native()
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    return importlib.import_module("muzero-hypermodel_amd.games.device")
+
+
+@pytest.fixture(scope="module")
+def sp(pkg):
+    return importlib.import_module("muzero-hypermodel_amd.self_play")
+
+
+@pytest.fixture(scope="module")
+def models_mod(pkg):
+    return importlib.import_module("muzero-hypermodel_amd.models")
+
+
+@pytest.fixture(scope="module")
+def eng(pkg):
+    return importlib.import_module("muzero-hypermodel_amd.engine")
+
+
+def small_config(channels=8, simulations=12, max_moves=None, threshold=None):
+    config = gomoku().MuZeroConfig()
+    config.blocks, config.channels, config.num_simulations = 1, channels, simulations
+    config.temperature_threshold = threshold
+    if max_moves is not None:
+        config.max_moves = max_moves
+    return config
+
+
+# ---- the environment kernels ------------------------------------------------------------------------------------------
+def replay_g18(dev):
+    """Env g plays fixture game g, all games in lock step (a finished game's env is left alone: action -1); returns the
+    number of positions compared."""
+    fx = load_golden("g18_gomoku_env")
+    game, step = fx["game"].astype(int), fx["step"].astype(int)
+    G = int(game.max()) + 1
+    row_of = {(int(g), int(t)): r for r, (g, t) in enumerate(zip(game, step))}
+    length = [int(n) for n in fx["length"]]
+    envs = dev.DeviceEnvs("gomoku", G, seeds=list(range(G)))
+    assert (envs.A, envs.players, envs.observation_shape, envs.max_episode_steps) == (121, 2, (3, 11, 11), 121)
+    compared = 0
+    for t in range(max(length) + 1):
+        obs, legal, nl, tp = (x.cpu().numpy() for x in envs.observe())
+        moves = envs.game_moves().cpu().numpy()
+        actions = np.full(G, -1, np.int32)
+        for g in range(G):
+            if t > length[g]:
+                continue
+            r = row_of[(g, t)]
+            assert np.array_equal(obs[g], fx["obs"][r]), (g, t)
+            n = int(fx["n_legal"][r])
+            assert nl[g] == n and legal[g][:n].tolist() == fx["legal"][r][:n].tolist(), (g, t)
+            assert tp[g] == fx["to_play"][r] and moves[g] == t, (g, t)
+            compared += 1
+            if t < length[g]:
+                actions[g] = int(fx["action"][row_of[(g, t + 1)]])
+        if (actions < 0).all():
+            break
+        reward, done = envs.step(actions)
+        reward, done = reward.cpu().numpy(), done.cpu().numpy().astype(bool)
+        for g in range(G):
+            if actions[g] >= 0:
+                r = row_of[(g, t + 1)]
+                assert reward[g] == fx["reward"][r] and done[g] == bool(fx["done"][r]), (g, t)
+            else:
+                assert reward[g] == 0 and not done[g]
+    envs.close()
+    assert compared == len(fx["game"])
+    return compared
+
+
+def test_device_envs_replay_reference_playouts_g18(dev):
+    """The HIP env kernels replay the reference's recorded Gomoku games: observation, legal list (ordered compaction by
+    ballots), to_play, ply counter, reward and done of every recorded position, bit-identical -- fives in the four
+    directions and on the edges, the six, the full-board draw (ply 121, reward 1), the runs that only wrap."""
+    assert replay_g18(dev) > 1200
+
+
+def random_plies(dev, E, plies, limit_at, limit, seed):
+    """E device envs against E host Games over random plies (some envs sit a ply out with action -1), a move limit set
+    half way through; `advance` must equal step + observe + reset + observe on a twin."""
+    mod = gomoku()
+    envs = dev.DeviceEnvs("gomoku", E, seeds=list(range(E)))
+    twin = dev.DeviceEnvs("gomoku", E, seeds=list(range(E)))
+    host = [mod.Game(e) for e in range(E)]
+    host_obs = [np.asarray(g.reset(), dtype=np.float32) for g in host]
+    host_moves = np.zeros(E, int)
+    rs = np.random.RandomState(seed)
+    reward, done = torch.zeros(E, device="cuda"), torch.zeros(E, dtype=torch.uint8, device="cuda")
+    obs_after, obs_next = torch.zeros((E, 3, 11, 11), device="cuda"), torch.zeros((E, 3, 11, 11), device="cuda")
+    finished = cut = 0
+    max_moves = 0
+    for ply in range(plies):
+        if ply == limit_at:
+            max_moves = limit
+            envs.set_max_moves(limit)
+            twin.set_max_moves(limit)
+        actions = np.array([rs.choice(g.legal_actions()) for g in host], dtype=np.int32)
+        actions[rs.rand(E) < 0.1] = -1
+        before = [o.copy() for o in host_obs]
+        want_after = []
+        want_reward, want_done = np.zeros(E, np.float32), np.zeros(E, bool)
+        for e, g in enumerate(host):
+            if actions[e] < 0:
+                want_after.append(before[e])
+                continue
+            o, r, d = g.step(int(actions[e]))
+            host_moves[e] += 1
+            over = bool(d) or (max_moves > 0 and host_moves[e] >= max_moves)
+            cut += over and not d
+            want_reward[e], want_done[e] = r, over
+            want_after.append(np.asarray(o, dtype=np.float32))
+            host_obs[e] = want_after[-1]
+            if over:
+                finished += 1
+                host_obs[e] = np.asarray(g.reset(), dtype=np.float32)
+                host_moves[e] = 0
+        act = torch.from_numpy(actions).cuda()
+        envs.advance(act, reward, done, obs_after, obs_next)
+        # the twin takes the four steps one by one
+        r2, d2 = twin.step(actions)
+        after2 = twin.observe()[0].clone()
+        twin.reset(d2)
+        next2, legal2, nl2, tp2 = twin.observe()
+        assert torch.equal(reward, r2) and torch.equal(done, d2) and torch.equal(obs_after, after2) and torch.equal(obs_next, next2)
+        assert torch.equal(envs.num_legal, nl2) and torch.equal(envs.to_play, tp2) and torch.equal(envs.game_moves(), twin.game_moves())
+        nl = nl2.cpu().numpy()
+        legal, legal_twin = envs.legal.cpu().numpy(), legal2.cpu().numpy()
+        assert np.array_equal(reward.cpu().numpy(), want_reward) and np.array_equal(done.cpu().numpy().astype(bool), want_done), ply
+        assert np.array_equal(obs_after.cpu().numpy(), np.stack(want_after)), ply            # untouched envs included
+        assert np.array_equal(obs_next.cpu().numpy(), np.stack(host_obs)), ply
+        assert np.array_equal(envs.game_moves().cpu().numpy(), host_moves), ply
+        tp = envs.to_play.cpu().numpy()
+        for e, g in enumerate(host):
+            assert legal[e][: nl[e]].tolist() == legal_twin[e][: nl[e]].tolist() == g.legal_actions() and tp[e] == g.to_play(), (ply, e)
+    envs.close()
+    twin.close()
+    return finished, cut
+
+
+def test_device_envs_match_host_plugins_over_random_plies(dev):
+    """96 envs x 150 random plies: games end by fives and restart inside `advance`; from ply 75 on a move limit of 30
+    (set_max_moves) ends the others -- games already past it on their next ply; envs handed action -1 stay untouched."""
+    finished, cut = random_plies(dev, 96, 150, 75, 30, seed=5)
+    assert finished >= 96 and cut >= 48
+
+
+def edge_positions():
+    cases = edge_boards()
+    boards = np.stack([c[1] for c in cases])
+    return cases, boards, np.array([c[2] for c in cases], dtype=np.int8), np.array([c[3] for c in cases], dtype=np.int32)
+
+
+def test_set_boards_edge_positions_one_ply(dev):
+    """The hand-made edge boards (runs that wrap around a row end, fours on the edges, a six, a five of the side NOT to
+    move, the last cell of a draw) handed in by set_boards, then one ply through step and through advance: done, reward
+    and observation are the host plugin's (whose verdicts the CPU suite holds to the hand-stated ones)."""
+    mod = gomoku()
+    cases, boards, players, actions = edge_positions()
+    E = len(cases)
+    envs = dev.DeviceEnvs("gomoku", E)
+    for form in ("step", "advance"):
+        envs.set_boards(boards, players)
+        assert envs.game_moves().cpu().numpy().tolist() == [int((b != 0).sum()) for b in boards]
+        want_obs, want_done = [], []
+        for name, board, player, action, finished in cases:
+            host = mod.Gomoku()
+            host.board, host.player = board.reshape(11, 11).astype("int32"), int(player)
+            o, r, d = host.step(int(action))
+            assert d is finished
+            want_obs.append(np.asarray(o, dtype=np.float32))
+            want_done.append(d)
+        if form == "step":
+            reward, done = envs.step(actions)
+            obs = envs.observe()[0]
+        else:
+            reward, done = torch.zeros(E, device="cuda"), torch.zeros(E, dtype=torch.uint8, device="cuda")
+            obs, nxt = torch.zeros((E, 3, 11, 11), device="cuda"), torch.zeros((E, 3, 11, 11), device="cuda")
+            envs.advance(torch.from_numpy(actions).cuda(), reward, done, obs, nxt)
+            fresh = np.zeros((3, 11, 11), np.float32)
+            fresh[2] = 1
+            for e, d in enumerate(want_done):                  # finished envs were reset, the others go on
+                assert np.array_equal(nxt[e].cpu().numpy(), fresh if d else want_obs[e]), cases[e][0]
+        assert done.cpu().numpy().astype(bool).tolist() == want_done, form
+        assert reward.cpu().numpy().tolist() == [1.0 if d else 0.0 for d in want_done], form
+        assert np.array_equal(obs.cpu().numpy(), np.stack(want_obs)), form
+    envs.close()
+
+
+def test_random_opponent_in_every_g18_position(dev, eng):
+    """Every non-terminal position of G18 set up on a device env whose stream is seeded like numpy: one opponent-mode
+    step plays numpy.random.choice(legal)'s move, reports the words numpy consumed, and the engine's mirror, told of
+    them, stands where numpy's generator stands.  On MuZero's own turn action -1 leaves an env alone; "expert" is
+    refused; a full board has no opponent move."""
+    fx = load_golden("g18_gomoku_env")
+    boards, players = fixture_boards(fx)
+    keep = np.flatnonzero(~fx["done"].astype(bool))
+    boards, players = boards[keep], players[keep]
+    E = len(keep)
+    seeds = [5000 + 3 * int(r) for r in keep]
+    config = small_config()
+    engine = eng.BatchedMCTS(config, E, device="cuda", seeds=seeds)
+    envs = dev.DeviceEnvs("gomoku", E, seeds=seeds)
+    tp = np.where(players == 1, 0, 1)
+    want, want_words, want_state = [], [], []
+    for e in range(E):
+        np.random.seed(seeds[e])
+        want.append(int(np.random.choice(np.flatnonzero(boards[e] == 0))))
+        want_state.append(np.random.get_state())
+        want_words.append(want_state[-1][2] % 624)
+    with pytest.raises(NotImplementedError, match="no expert agent"):
+        envs.set_opponent("expert", 0, engine)
+    key, pos = engine.rng_streams()
+    assert envs._lib.mzenv_set_opponent(envs._h, 1, 0, key, pos) == -1
+    assert b"gomoku has no expert agent" in envs._lib.mzenv_last_error(envs._h)
+    played = np.full(E, -1)
+    words = np.zeros(E, np.uint32)
+    for mzp in (0, 1):
+        envs.set_boards(boards, players)
+        envs.set_opponent("random", mzp, engine)
+        obs, legal, num_legal, to_play = envs.observe()
+        mine = tp == mzp
+        assert ((num_legal.cpu().numpy() == 0) == ~mine).all() and np.array_equal(to_play.cpu().numpy(), tp)
+        legal = legal.cpu().numpy()                             # the row stays filled on the opponent's turn
+        assert all(legal[e][: int((boards[e] == 0).sum())].tolist() == np.flatnonzero(boards[e] == 0).tolist() for e in range(0, E, 7))
+        reward, done = envs.step(np.full(E, -1, np.int32))
+        torch.cuda.synchronize()
+        sel = tp != mzp
+        got = envs.played.cpu().numpy()
+        assert (got[~sel] == -1).all() and (envs.words.cpu().numpy()[~sel] == 0).all()
+        played[sel] = got[sel]
+        words[sel] = envs.words.cpu().numpy().view(np.uint32)[sel]
+        after = envs.observe()[0].cpu().numpy()
+        now = (after[:, 0] - after[:, 1]).reshape(E, CELLS).astype(np.int8)
+        assert np.array_equal(now[~sel], boards[~sel])         # MuZero's turn with action -1: untouched
+        expect = boards.copy()
+        expect[np.flatnonzero(sel), got[sel]] = players[sel]
+        assert np.array_equal(now[sel], expect[sel])
+    assert played.tolist() == want
+    assert words.tolist() == want_words and (words[(boards == 0).sum(axis=1) > 1] >= 1).all()
+    engine.rng_consumed(words)
+    for e in range(E):
+        state, ref = engine.get_rng_state(e), want_state[e]
+        assert state[2] == ref[2] and np.array_equal(state[1], ref[1]), e
+    # a single empty cell is played without a word; a full board is left alone
+    last = full_board_without_five()
+    last[CELLS - 1] = 0
+    tail = np.tile(last, (E, 1))
+    tail[1::2] = full_board_without_five()
+    envs.set_boards(tail, np.full(E, -1, np.int8))
+    envs.set_opponent("random", 0, engine)
+    reward, done = envs.step(np.full(E, 3, np.int32))
+    torch.cuda.synchronize()
+    assert (envs.played.cpu().numpy()[0::2] == CELLS - 1).all() and (envs.played.cpu().numpy()[1::2] == -1).all()
+    assert (envs.words.cpu().numpy() == 0).all()
+    assert (done.cpu().numpy()[0::2] == 1).all() and (reward.cpu().numpy()[0::2] == 1).all()
+    assert not done.cpu().numpy()[1::2].any() and not reward.cpu().numpy()[1::2].any()
+    envs.close()
+    engine.close()
+
+
+def test_one_thread_per_env_form_agrees_with_the_wavefront_form():
+    """MZENV_GOMOKU_SERIAL=1 (read at mzenv_create) runs the same rules one thread per env, the shape games 0-2 use; a
+    fresh process replays G18 and the random plies with it -- the measurement in DESIGN.md 7.7 compares like with like."""
+    code = ("import sys; sys.path[:0] = [%r, %r]\n"
+            "import importlib, test_gpu_gomoku as t\n"
+            "dev = importlib.import_module('muzero-hypermodel_amd.games.device')\n"
+            "print('replayed', t.replay_g18(dev), 'finished', t.random_plies(dev, 64, 80, 40, 30, seed=9))\n") % (
+                ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, MZENV_GOMOKU_SERIAL="1")
+    proc = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0 and "replayed" in proc.stdout, proc.stdout + proc.stderr
+
+
+# ---- 121-action searches ----------------------------------------------------------------------------------------------
+def trace_groups():
+    return [(f"{simulations} simulations", load_golden(name)) for simulations, name in TRACE_FILES]
+
+
+def test_engine_replays_gomoku_traces_bit_exact_in_injected_mode(eng, oracle):
+    """The tree kernels' chunked A > 64 path on real Gomoku positions (masked roots from 121 down to 3 legal cells, both
+    players; 12 searches of 30 simulations, one of the config's 400): bit for bit the C oracle's and the reference's
+    recorded noise, paths, tie-list sizes, visits, value sums, targets and sampled actions."""
+    for where, fx in trace_groups():
+        idx = list(range(len(fx["seed"])))
+        S = int(fx["cfg_S"])
+        temps = fx["temperature"].tolist()
+        got = run_injected_on_engine(eng, None, fx, idx, temperature=temps)
+        want = run_injected_on_oracle(oracle, fx, idx=idx, temperature=temps)
+        for key in ("noise", "visits", "child_value_sum", "child_prior", "child_reward", "root_value_sum", "root_visits",
+                    "max_tree_depth", "min_max", "sim_depth", "sim_actions", "sim_ties", "child_visits_target",
+                    "root_value_target", "action"):
+            assert np.array_equal(got[key], want[key]), (where, key)
+        for key in ("noise", "visits", "child_value_sum", "child_prior", "child_reward", "root_value_sum", "max_tree_depth",
+                    "sim_depth", "child_visits_target", "root_value_target"):
+            assert np.array_equal(got[key], fx[key]), (where, key)
+        assert np.array_equal(got["sim_actions"], fx["sim_actions"][:, :, :S]) and np.array_equal(got["sim_ties"], fx["sim_ties"][:, :, :S])
+        assert np.array_equal(got["action"], fx["action_T"]), where
+        assert np.array_equal(want["rng_words_run"], fx["rng_words_run"])
+
+
+# traces whose native search leaves the reference's path because an fp32-rounding-sized difference of the network outputs
+# (MIOpen convolutions against torch's CPU ones) flips a UCB near-tie; everything else must match simulation for simulation.
+# The 400-simulation search builds chains up to 63 plies deep with these synthetic weights; the logit deviation grows along
+# a chain of recurrent inferences (9e-7 per evaluation, 8e-4 at the deepest leaves of the 30-simulation traces), and
+# on MI355X it flips a near-tie at simulation 71 of 400.  Its root logits, noise, and visit totals are still held.
+GOMOKU_EXPECTED_DIVERGENT = {"30 simulations": (), "400 simulations": (0,)}
+
+
+def test_native_gomoku_search_vs_reference(eng, models_mod):
+    """Native mode at 11 x 11 (the towers and heads take models.py's PyTorch-ROCm path): root logits within 1e-5, paths
+    the reference's, decoded values and value targets within the bounds derived from the measured logit deviation
+    (test_gpu_parity.native_vs_fixture), the 400-simulation search included."""
+    from test_gpu_parity import RESNET_TOL, native_vs_fixture
+    for where, fx in trace_groups():
+        config = small_config(channels=16, simulations=int(fx["cfg_S"]))
+        model, _ = synthetic_model(models_mod, config, "cuda")
+        idx = list(range(len(fx["seed"])))
+        native_vs_fixture(eng, model, config, fx, idx, GOMOKU_EXPECTED_DIVERGENT[where], logit_tol=RESNET_TOL["logit_tol"])
+
+
+# ---- self-play --------------------------------------------------------------------------------------------------------
+def host_games(sp, weights, config, seed, E, n_moves, temperature, threshold, opponent="self", mzp=0):
+    finished = [[] for _ in range(E)]
+    actor = sp.BatchedSelfPlay({"weights": weights}, gomoku().Game, config, seed, E, use_graph=False)
+    for _ in range(n_moves):
+        actor.step(temperature, threshold, on_game=lambda e, gh: finished[e].append(gh), opponent=opponent, muzero_player=mzp)
+    actor.close()
+    return finished
+
+
+def assert_same_games(got, want, where):
+    from test_gpu_parity import RESNET_TOL
+    assert [len(g) for g in got] == [len(g) for g in want], where
+    for e, (mine, theirs) in enumerate(zip(got, want)):
+        for a, b in zip(mine, theirs):
+            assert a.action_history == b.action_history, (where, e)
+            assert a.reward_history == b.reward_history and a.to_play_history == b.to_play_history, (where, e)
+            assert [v is None for v in a.root_values] == [v is None for v in b.root_values], (where, e)
+            assert np.array(a.child_visits, dtype=float).shape[1:] == (CELLS,), (where, e)
+            assert np.array_equal(np.array(a.child_visits, dtype=float), np.array(b.child_visits, dtype=float)), (where, e)
+            np.testing.assert_allclose([v for v in a.root_values if v is not None], [v for v in b.root_values if v is not None],
+                                       rtol=0, atol=RESNET_TOL["value_tol"])
+            assert np.array_equal(np.array(a.observation_history), np.array(b.observation_history, dtype=np.float32)), (where, e)
+
+
+SIZES = [1, 5, 9, 3, 8]          # 26 plies: with max_moves = 20 every env files a game inside a batch
+
+
+@pytest.mark.parametrize("threshold", [None, 6])
+def test_device_self_play_equals_host_self_play(sp, models_mod, threshold):
+    """DeviceSelfPlay("gomoku") files, env by env, the games BatchedSelfPlay files on host Game plugins with the same
+    small network and seeds: move by move and as play_moves batches (legal sets and players from the env kernels'
+    device outputs, noise drawn on the device: alpha 0.3 over up to 121 legal cells), with the captured hipGraph and
+    without, max_moves = 20 ending the games (set_max_moves), with and without a temperature threshold; and
+    PipelinedDeviceSelfPlay with two groups."""
+    E = 16
+    config = small_config(channels=16, simulations=10, max_moves=20, threshold=threshold)
+    _, weights = synthetic_model(models_mod, config, "cpu")
+    want = host_games(sp, weights, config, 30, E, sum(SIZES), 1.0, threshold)
+    assert sum(len(g) for g in want) >= E and all(len(gh.action_history) <= 21 for g in want for gh in g)
+    for use_graph in (True, False):
+        got = [[] for _ in range(E)]
+        actor = sp.DeviceSelfPlay({"weights": weights}, "gomoku", config, 30, E, use_graph=use_graph)
+        for m in SIZES:
+            played = actor.play_moves(m, 1.0, on_game=lambda e, gh: got[e].append(gh), temperature_threshold=threshold)
+            assert (played == m).all()
+        actor.flush(on_game=lambda e, gh: got[e].append(gh))
+        assert (actor.engine._graph is not None) == use_graph and actor.envs.max_moves == 20
+        actor.close()
+        assert_same_games(got, want, f"batches graph={use_graph} threshold={threshold}")
+    got = [[] for _ in range(E)]
+    actor = sp.DeviceSelfPlay({"weights": weights}, "gomoku", config, 30, E)
+    for _ in range(sum(SIZES)):
+        actor.step(1.0, threshold, on_game=lambda e, gh: got[e].append(gh))
+    actor.close()
+    assert_same_games(got, want, f"steps threshold={threshold}")
+    if threshold is None:
+        got = [[] for _ in range(E)]
+        actor = sp.PipelinedDeviceSelfPlay({"weights": weights}, "gomoku", config, 30, E, groups=2)
+        for m in SIZES:
+            actor.play_moves(m, 1.0, on_game=lambda e, gh: got[e].append(gh), temperature_threshold=threshold)
+        actor.flush(on_game=lambda e, gh: got[e].append(gh))
+        actor.close()
+        assert_same_games(got, want, "pipelined batches")
+    else:
+        late = [(gh, m) for g in want for gh in g for m in range(len(gh.child_visits)) if m + 1 >= threshold]
+        assert late and all(gh.action_history[m + 1] == int(np.argmax(gh.child_visits[m])) for gh, m in late)
+
+
+@pytest.mark.parametrize("mzp", [0, 1])
+def test_evaluation_games_against_the_random_opponent(sp, models_mod, mzp):
+    """Test mode on an 11 x 11 board with MuZero as either player: the device actor (batches and single moves) files the
+    games the host actor files -- the opponent's plies are the ones numpy.random.choice draws from the same per-env
+    streams --, every game's plies alternate, every ply lands on an empty cell, searched plies carry a 121-wide visit
+    row and the opponent's none; evaluate()'s counts add up; "expert" raises as AbstractGame.expert_agent does."""
+    E = 16
+    config = small_config(channels=16, simulations=10, max_moves=14)
+    _, weights = synthetic_model(models_mod, config, "cpu")
+    want = host_games(sp, weights, config, 40, E, 22, 0, None, opponent="random", mzp=mzp)
+    assert sum(len(g) for g in want) >= E
+    got = [[] for _ in range(E)]
+    actor = sp.DeviceSelfPlay({"weights": weights}, "gomoku", config, 40, E)
+    for m in (1, 4, 9, 8):
+        played = actor.play_moves(m, 0, on_game=lambda e, gh: got[e].append(gh), temperature_threshold=0, opponent="random",
+                                  muzero_player=mzp)
+        assert (played == m).all()
+    actor.flush(on_game=lambda e, gh: got[e].append(gh))
+    assert 0 < actor.searched_moves < actor.moves_played
+    actor.close()
+    assert_same_games(got, want, f"random opponent, MuZero plays {mzp}: batches")
+    got = [[] for _ in range(E)]
+    actor = sp.DeviceSelfPlay({"weights": weights}, "gomoku", config, 40, E)
+    for _ in range(22):
+        actor.step(0, None, on_game=lambda e, gh: got[e].append(gh), opponent="random", muzero_player=mzp)
+    assert_same_games(got, want, f"random opponent, MuZero plays {mzp}: steps")
+    with pytest.raises(NotImplementedError, match="no expert agent"):
+        actor.step(0, None, opponent="expert", muzero_player=mzp)
+    actor.close()
+    for gh in (gh for g in got for gh in g):
+        n = len(gh.action_history) - 1
+        assert gh.to_play_history == [i % 2 for i in range(n + 1)]
+        assert len(set(gh.action_history[1:])) == n and all(0 <= a < CELLS for a in gh.action_history[1:])
+        assert [v is None for v in gh.root_values] == [i % 2 != mzp for i in range(n)]
+        assert len(gh.child_visits) == sum(i % 2 == mzp for i in range(n))
+        searched = [i for i in range(n) if i % 2 == mzp]
+        for row, i in zip(gh.child_visits, searched):
+            assert len(row) == CELLS and abs(sum(row) - 1) < 1e-9
+            assert all(row[a] == 0 for a in gh.action_history[1:i + 1])         # no visits on occupied cells
+    out = sp.evaluate({"weights": weights}, "gomoku", config, 24, opponent="random", muzero_player=mzp, num_envs=E, seed=40)
+    assert out["games"] == 24 and out["wins"] + out["draws"] + out["losses"] == 24
+    assert (out["opponent"], out["muzero_player"]) == ("random", mzp)
+    assert out["mean_episode_length"] <= 14 and 0 < out["searched_moves"] < out["env_moves"]
+    assert out["simulations"] == out["searched_moves"] * 10
+
+
+@pytest.mark.parametrize("td_steps", [121, 5])
+def test_filed_gomoku_games_become_the_replay_oracles_batch(sp, models_mod, oracle, td_steps):
+    """Games DeviceSelfPlay filed (121-wide child_visits rows, two players) through ReplayBuffer.save_games and
+    get_batch with Gomoku's own unroll (121) and td_steps (121: no target bootstraps inside a 20-ply game), and with
+    td_steps = 5 (targets bootstrap from root values, signed by the side to move): every position's targets and the
+    sampled batch are oracle/replay_oracle.py's on the same arrays."""
+    import test_gpu_replay_edges as edges
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import types
+    mods = types.SimpleNamespace(rb=importlib.import_module("muzero-hypermodel_amd.replay_buffer"), sp=sp, models=models_mod,
+                                 ro=importlib.import_module("replay_oracle"))
+    ro, E = mods.ro, 16
+    config = small_config(channels=16, simulations=10, max_moves=20)
+    assert (config.num_unroll_steps, config.td_steps) == (121, 121)
+    config.td_steps = td_steps
+    config.PER, config.batch_size, config.replay_buffer_size = True, 32, 256
+    _, weights = synthetic_model(models_mod, config, "cpu")
+    rb = edges.new_store(mods, config)
+    filed = []
+
+    def on_games(batch):
+        filed.append({k: np.array(getattr(batch, k)) for k in edges.FIELDS + ("length",)})
+        rb.save_games(batch)
+
+    actor = sp.DeviceSelfPlay({"weights": weights}, "gomoku", config, 30, E)
+    for m in SIZES:
+        actor.play_moves(m, 1.0, on_games=on_games, temperature_threshold=0)
+    actor.flush(on_games=on_games)
+    actor.close()
+    games, lengths = [], []
+    for batch in filed:
+        for i, n in enumerate(batch["length"]):
+            n = int(n)
+            games.append(ro.Game(batch["observations"][i, : n + 1], batch["actions"][i, : n + 1], batch["rewards"][i, : n + 1],
+                                 batch["to_play"][i, : n + 1], batch["child_visits"][i, :n], batch["root_values"][i, :n]))
+            assert batch["child_visits"].shape[2] == CELLS and np.allclose(batch["child_visits"][i, :n].sum(axis=1), 1)
+            lengths.append(n)
+    G = len(games)
+    assert G >= E and rb.num_played_games == G and max(lengths) == 20
+    edges.assert_priorities(rb, ro, config, games, range(G), "gomoku")
+    rs = np.random.RandomState(3)
+    pairs = edges.all_pairs(range(G), lengths)[::7]
+    absorbing = edges.absorbing_for(rs, pairs, lengths, config.num_unroll_steps + 1, CELLS)
+    edges.assert_targets(edges.device_targets(rb, pairs, absorbing, sizes=(1, 33)), edges.oracle_batch(ro, config, games, pairs, absorbing), "gomoku")
+    for g, game in enumerate(games):
+        rb.buffer[g]["priorities"], rb.buffer[g]["game_priority"] = game.priorities.copy(), game.game_priority
+    cfg = dict(batch_size=config.batch_size, PER=True, td_steps=config.td_steps, discount=config.discount,
+               num_unroll_steps=config.num_unroll_steps, action_space=list(config.action_space),
+               stacked_observations=config.stacked_observations)
+    want = ro.get_batch(games, cfg, oracle.Rng(config.seed))
+    index_batch, (obs, act, val, rew, pol, weight, scale) = rb.get_batch()
+    assert np.array_equal(np.array(index_batch), np.array(want["index"])) and np.array_equal(weight, want["weight"])
+    assert tuple(pol.shape) == (32, 122, CELLS) and tuple(obs.shape) == (32, 3, 11, 11)
+    pol_sums = pol.cpu().numpy().sum(axis=2)
+    assert np.allclose(pol_sums, 1)                             # searched rows and the uniform rows past the end alike
+    got = dict(observation=obs, action=act, value=val, reward=rew, policy=pol, gradient_scale=scale)
+    dtypes = dict(observation=np.float32, action=np.int64)
+    edges.assert_targets({k: t.cpu().numpy() for k, t in got.items()},
+                         {k: np.array([[float(x) for x in row] for row in want[k]] if k == "value" else want[k],
+                                      dtype=dtypes.get(k, np.float64)) for k in got}, "gomoku get_batch")
+    if td_steps < 20:
+        assert (val.cpu().numpy()[:, 0] != 0).any()              # bootstrapped targets (the oracle's signs, compared above)
+    rb.close()

@@ -60,7 +60,7 @@ class Replay:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--game", choices=["connect4", "tictactoe", "cartpole"], default="connect4")
+    ap.add_argument("--game", choices=["connect4", "tictactoe", "gomoku", "cartpole"], default="connect4")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--passes", type=int, default=10)
     ap.add_argument("--moves-per-pass", type=int, default=4)

@@ -1,9 +1,15 @@
 """Whole self-play loop rate (search + env step + history filing), host-plugin envs vs device envs.
 
     python tools/selfplay_rate.py [--game cartpole] [--envs 4096] [--moves 60] [--max-moves N]
+    python tools/selfplay_rate.py --game gomoku --kinds search,device-batch [--simulations S --channels C --blocks B]
 
-Prints one JSON line per actor kind: moves/s, simulations/s, finished games.  This is the loop the
-reference runs in self_play.py:34-113 (continuous_self_play), without the replay buffer hand-off."""
+Prints one JSON line per actor kind: moves/s, simulations/s, finished games, the engine's device bytes.  This is the
+loop the reference runs in self_play.py:34-113 (continuous_self_play), without the replay buffer hand-off.  Kind
+"search" times the search alone (fixed start positions, no env step, no filing) for comparison with the whole loop.
+
+Gomoku at the reference's config (400 simulations, 6 blocks x 128 channels, 11 x 11) is heavy: a tree holds 401 hidden
+states of 62 KB, about 26 MB per env, so its default is 256 envs (~7 GB); the towers run as PyTorch-ROCm convolutions
+(there is no 11 x 11 tower kernel)."""
 import argparse
 import importlib
 import json
@@ -18,10 +24,47 @@ sp = importlib.import_module("muzero-hypermodel_amd.self_play")
 models = importlib.import_module("muzero-hypermodel_amd.models")
 
 
+def engine_bytes(actor):
+    """Device bytes of the actor's search engine(s): trees, hidden-state pool, per-move buffers."""
+    actors = getattr(actor, "actors", [actor])
+    return int(sum(a.engine.device_bytes() for a in actors))
+
+
+def search_only(args, config, weights):
+    """The search alone: every env searches its start position `--moves` times (no env step, no history filing)."""
+    engine_mod = importlib.import_module("muzero-hypermodel_amd.engine")
+    device_mod = importlib.import_module("muzero-hypermodel_amd.games.device")
+    model = models.MuZeroNetwork(config)
+    model.set_weights(weights)
+    model.to("cuda").eval()
+    envs = device_mod.DeviceEnvs(args.game, args.envs)
+    obs, legal, num_legal, to_play = envs.observe()
+    torch.cuda.synchronize()
+    n = num_legal.cpu().tolist()
+    legal_lists = [row[:k] for row, k in zip(legal.cpu().tolist(), n)]
+    to_play = to_play.cpu().tolist()
+    engine = engine_mod.BatchedMCTS(config, args.envs, device="cuda", use_graph=True)
+    with torch.no_grad():
+        for _ in range(2):
+            engine.search(model, obs, legal_lists, to_play, True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.moves):
+            engine.search(model, obs, legal_lists, to_play, True)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    moves = args.moves * args.envs
+    print(json.dumps({"actor": "search", "game": args.game, "envs": args.envs, "moves_per_s": moves / dt,
+                      "simulations_per_s": moves * config.num_simulations / dt, "ms_per_move_step": 1e3 * dt / args.moves,
+                      "num_simulations": config.num_simulations, "engine_device_bytes": engine.device_bytes()}), flush=True)
+    engine.close()
+    envs.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="cartpole")
-    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--envs", type=int, default=None, help="default 4096; gomoku 256 (a tree is ~26 MB at its config)")
     ap.add_argument("--moves", type=int, default=60)
     ap.add_argument("--kinds", default="host,device")
     ap.add_argument("--batch", type=int, default=20, help="moves per host round trip of the device-batch actor")
@@ -34,9 +77,17 @@ def main():
                     "(what a loop does that pulls weights between calls)")
     ap.add_argument("--max-moves", type=int, default=None, help="end games after N plies (config.max_moves; default: the "
                     "config's): the device actors' batches apply it in the environment kernels")
+    ap.add_argument("--simulations", type=int, default=None, help="config.num_simulations (default: the config's)")
+    ap.add_argument("--channels", type=int, default=None, help="config.channels of a residual network (default: the config's)")
+    ap.add_argument("--blocks", type=int, default=None, help="config.blocks of a residual network (default: the config's)")
     args = ap.parse_args()
+    if args.envs is None:
+        args.envs = 256 if args.game == "gomoku" else 4096
     mod = importlib.import_module(f"muzero-hypermodel_amd.games.{args.game}")
     config = mod.MuZeroConfig()
+    for name, value in (("num_simulations", args.simulations), ("channels", args.channels), ("blocks", args.blocks)):
+        if value is not None:
+            setattr(config, name, value)
     if args.max_moves is not None:
         config.max_moves = args.max_moves
     if args.fc:
@@ -52,6 +103,9 @@ def main():
         fixture = numpy.load(os.path.join(root, "tests", "golden", "cartpole_weights.npz"))
         weights = {k: torch.from_numpy(fixture[k]) for k in fixture.files}
     for kind in args.kinds.split(","):
+        if kind == "search":
+            search_only(args, config, weights)
+            continue
         if kind == "host":
             actor = sp.BatchedSelfPlay({"weights": weights}, mod.Game, config, 0, args.envs)
         elif kind in ("device-pipelined", "device-pipelined-batch"):
@@ -99,6 +153,7 @@ def main():
         print(json.dumps({"actor": kind, "game": args.game, "envs": args.envs, "moves_per_s": moves / dt,
                           "simulations_per_s": moves * config.num_simulations / dt, "ms_per_move_step": 1e3 * dt * args.envs / moves,
                           "games_finished": done[0], "weights": args.weights, "max_moves": config.max_moves,
+                          "num_simulations": config.num_simulations, "engine_device_bytes": engine_bytes(actor),
                           **({"moves_per_call": args.batch, "prefetch": not args.no_prefetch} if kind == "device-pipelined-batch" else {}),
                           **({"moves_per_call": args.batch} if kind == "device-batch" else {})}), flush=True)
         actor.close()
