@@ -289,7 +289,8 @@ int32_t mzmcts_fused_variant(mzmcts_engine *engine);
  * the caller plays the missing moves in the next batch.  Played moves are bit-identical to the one-at-a-time
  * path.  Legal action sets are those of a game whose action set does not change between moves (the Dirichlet
  * dimension must be known in advance); temperature per env must be 0, +inf (one move per batch) or 1/k with
- * k = 1..4, the values for which visit_count ** (1 / T) is exact integer arithmetic.
+ * k = 1..4, the values for which visit_count ** (1 / T) is exact integer arithmetic -- or, after
+ * mzmcts_set_device_temperatures(engine, 1), any temperature that call's comment admits (two words, like 1/k).
  *   prepare   blocking host work (noise rows of the whole batch) + asynchronous uploads
  *   predraw_next / submit_next
  *             the same in two halves, so that the host draws batch b+1 WHILE batch b runs: predraw_next (any
@@ -315,7 +316,7 @@ int mzmcts_moves_discard_next(mzmcts_engine *engine);
  * them as they are when it runs.  The exploration noise is drawn on the device (numpy.random.dirichlet on each tree's own
  * stream, 0 < root_dirichlet_alpha <= 1), because the length of a move's noise row -- its legal count -- is not known
  * to the host before the moves before it have been played; nothing is pre-drawn, nothing can stall.  temperature: host
- * f64[E] (0, inf or 1/k).  Then mzmcts_moves_enqueue per move and mzmcts_moves_collect as for a host-input batch (the
+ * f64[E] (0, inf or 1/k; any samplable value after mzmcts_set_device_temperatures).  Then mzmcts_moves_enqueue per move and mzmcts_moves_collect as for a host-input batch (the
  * mirrors of the RNG streams step over every word the batch consumed); mzmcts_moves_inputs afterwards returns what each
  * move was searched with: num_legal i32[M][E], legal i32[M][E][A] (child slot -> action), to_play i32[M][E] (any NULL). */
 int mzmcts_moves_prepare_device(mzmcts_engine *engine, int32_t n_moves, const int32_t *legal_actions,
@@ -554,6 +555,26 @@ int mzmcts_get_noise(mzmcts_engine *engine, double *noise_out);
 int mzmcts_device_libm(const double *x, const double *y, int64_t n, double *log_out, double *pow_out);
 int mzmcts_device_dirichlet(const uint32_t *seeds, int32_t n_streams, double alpha, int32_t k, int32_t draws,
                             double *out, uint32_t *words_out);
+
+/* ---- action sampling at any temperature on the device (SelfPlay.select_action, self_play.py:223-246) ----
+ * Which temperatures a move batch (mzmcts_moves_prepare / _predraw_next / _prepare_device) takes: 0 (default) = 0, +inf
+ * and 1/k, k = 1..4, with num_simulations ** k < 9e15, sampled by the whole-move kernels in integer arithmetic; anything
+ * else is refused (such a config plays through mzmcts_sample_actions, one host round trip per move).  1 = additionally
+ * every finite T > 0 for which num_actions * num_simulations ** (1 / T) is finite: visit_count ** (1 / T) is glibc's pow
+ * on the device (csrc/glibc_libm.h), the sums, the divisions and numpy.random.choice(p=...) in the reference's order
+ * (csrc/select_action.h), computed by a small kernel queued behind each search of a batch that holds such a temperature
+ * (the whole-move kernels are the same either way).  The sampled actions, the two words consumed and the streams
+ * afterwards are those of the host path to the last bit; such an env stays in a multi-move batch.  NaN, negative and
+ * overflowing temperatures (the reference fails inside numpy.random.choice on them) return MZMCTS_ERR_INVALID with a
+ * message that says so.  Takes effect with the next batch prepared. */
+int mzmcts_set_device_temperatures(mzmcts_engine *engine, int32_t enabled);
+/* Blocking self-check, host arrays in and out: stream s = numpy.random.seed(seeds[s]) followed by `draws` x
+ * select_action on the visit row visits[s] (i32[n_streams][n], by child slot) at temperature[s] (f64[n_streams]: 0,
+ * +inf or finite and positive with n * sum(visits[s]) ** (1 / T) finite and a visit in the row), all on the GPU, with
+ * the sampler the move batches use.  slots_out i32[n_streams][draws] = chosen child slots, words_out[s] = 32-bit words
+ * consumed.  Bad arguments return MZMCTS_ERR_INVALID before the device is touched. */
+int mzmcts_device_select_action(const uint32_t *seeds, int32_t n_streams, const int32_t *visits, int32_t n,
+                                const double *temperature, int32_t draws, int32_t *slots_out, uint32_t *words_out);
 
 /* ---- stand-alone host RNG stream (numpy legacy RandomState clone) ----------------------------
  * The same generator the engine uses per env, exposed for host logic that has no engine

@@ -205,6 +205,9 @@ PROTOTYPES = {
     "mzmcts_device_libm": (ctypes.c_int, [c_f64_p, c_f64_p, ctypes.c_int64, c_f64_p, c_f64_p]),
     "mzmcts_device_dirichlet": (ctypes.c_int, [c_u32_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
                                                c_f64_p, c_u32_p]),
+    "mzmcts_set_device_temperatures": (ctypes.c_int, [c_void, ctypes.c_int32]),
+    "mzmcts_device_select_action": (ctypes.c_int, [c_u32_p, ctypes.c_int32, c_i32_p, ctypes.c_int32, c_f64_p, ctypes.c_int32,
+                                                   c_i32_p, c_u32_p]),
     "mzmcts_rng_export": (None, [c_void, c_u32_p, c_i32_p, c_i32_p, c_f64_p]),
     "mzmcts_rng_import": (None, [c_void, c_u32_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double]),
     "mzmcts_rng_select_action": (ctypes.c_int32, [c_void, c_i32_p, ctypes.c_int32, ctypes.c_double]),
@@ -356,9 +359,27 @@ class MzTowerLayer(ctypes.Structure):
                 ("gate", ctypes.c_void_p)]
 
 
+def device_select_action(seeds, visits, temperature, draws=1):
+    """mzmcts_device_select_action: stream s = numpy.random.seed(seeds[s]), then `draws` x SelfPlay.select_action on
+    visits[s] ([N, n] by child slot) at temperature[s], all on the GPU with the move batches' sampler.
+    Returns (slots int32 [N, draws], words uint32 [N])."""
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    visits = np.ascontiguousarray(visits, dtype=np.int32)
+    n_streams, n = visits.shape
+    temps = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=np.float64), (n_streams,)))
+    assert seeds.shape == (n_streams,)
+    slots = np.zeros((n_streams, int(draws)), dtype=np.int32)
+    words = np.zeros(n_streams, dtype=np.uint32)
+    rc = load().mzmcts_device_select_action(ptr(seeds, c_u32_p), n_streams, ptr(visits, c_i32_p), n, ptr(temps, c_f64_p),
+                                            int(draws), ptr(slots, c_i32_p), ptr(words, c_u32_p))
+    if rc != 0:
+        raise RuntimeError(f"mzmcts_device_select_action failed ({rc})")
+    return slots, words
+
+
 def exact_inverse_temperature(temperature):
     """k when 1 / temperature is an integer k in 1..4 (the temperatures the device sampler handles exactly:
-    csrc/kernel_common.h exact_inverse_temperature), else 0."""
+    csrc/np_legacy_rng.h exact_inverse_temperature), else 0."""
     if temperature in (0, float("inf")) or temperature != temperature:
         return 0
     inv = 1.0 / float(temperature)

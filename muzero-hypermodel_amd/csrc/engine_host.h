@@ -2,7 +2,7 @@
 // implement the C ABI:
 //     mzmcts_capi.hip    create / destroy, the lock-step search steps, readout, the fused whole-move launch, profiling
 //     mzmcts_moves.hip   batches of moves without host round trips: RNG mirror bookkeeping, speculation and rewind
-//     mzmcts_rng.hip     stand-alone numpy-compatible host streams
+//     mzmcts_rng.hip     stand-alone numpy-compatible host streams; device self-checks; select_action_general_kernel
 //     mzhist.hip         game-history filer (include/mzhist.h)
 // The launchers of the kernels (mcts_kernels.hip, fused_narrow.hip) are declared here; the helpers are inline so that
 // every translation unit shares one worker pool and one error string.
@@ -58,6 +58,9 @@ hipError_t launch_move_inputs(const TreeParams& p, const uint32_t* rng_skip, con
                               int move_index, bool draw_noise, int32_t* nlegal_out, int32_t* to_play_out, uint32_t* words_out,
                               int32_t* legal_out, const MoveInputsExtra& extra, hipStream_t stream);
 hipError_t launch_lockstep_move_finish(const TreeParams& p, const MoveCtl& ctl, hipStream_t stream);
+// (mzmcts_rng.hip) actions the move's own sampler left at -2, sampled with temperature[e] from ctl.visits (select_action.h)
+hipError_t launch_select_action_general(const TreeParams& p, const MoveCtl& ctl, const double* temperature,
+                                        hipStream_t stream);
 hipError_t launch_gather_dynamics_input(const TreeParams& p, const int64_t* action, float* out, int plane, int action_space,
                                         hipStream_t stream);
 hipError_t launch_expand_roots(const TreeParams& p, const float* value_logits, const float* reward_logits,
@@ -267,6 +270,7 @@ struct mzmcts_engine {
     bool profiling = false;
     bool device_noise = false;       // mzmcts_set_device_noise: exploration noise drawn by root_noise_kernel
     bool noise_on_device = false;    // ... and it was, for the search in progress (readout fetches rows + word counts)
+    bool device_temperatures = false;  // mzmcts_set_device_temperatures: move batches take any samplable temperature
     uint32_t* h_noise_words = nullptr;
     int select_queue_trees = 0;      // mzmcts_set_select_queue: 0 = one descent per lane group
     std::vector<EventPair> events;
@@ -307,6 +311,11 @@ struct mzmcts_engine {
         std::vector<uint64_t> twist_words;           // [E] word count at the first such regeneration
         std::vector<uint32_t> twist_keys;            // [E][624] the block just before it
         std::vector<double> temperature;             // [E]
+        // some env's temperature needs pow (select_action.h general_temperature): every move of the batch is followed by
+        // select_action_general_kernel, which reads the temperatures from h_general_t's device copy (h_in's are what the
+        // whole-move kernels are told: see kernel_temperature, mzmcts_moves.hip)
+        bool general = false;
+        double* h_general_t = nullptr;               // pinned [E], allocated with the first such batch
         std::vector<uint32_t> tail_ties, tail_sample;  // [E] words assumed for the last move of the batch underneath
         std::vector<uint8_t> deferred;               // [E] speculative set: rows not drawn yet (unknown word counts)
     };
@@ -329,6 +338,7 @@ struct mzmcts_engine {
         hipStream_t copy_stream = nullptr;
         hipEvent_t move_done = nullptr;
         uint8_t* d_stall = nullptr;
+        double* d_general_t = nullptr;               // [E] ChainSet::h_general_t of the batch in flight
         hipEvent_t done = nullptr;
         // batches whose inputs live on the device (mzmcts_moves_prepare_device): the legal sets / players to move the
         // caller's kernels rewrite between the moves, and per move what the search was run with (for the host afterwards)

@@ -119,19 +119,12 @@ __device__ __forceinline__ bool move_stalled(const TreeParams& p, const MoveCtl&
     return stalled;
 }
 
-// Temperatures whose visit_count ** (1 / T) is exact integer arithmetic everywhere: 1 / T an integer k in 1..4
-// (the reference's schedules use 1, 0.5, 0.25: cartpole.py:118-128).  Returns k, or 0.
-__host__ __device__ inline int exact_inverse_temperature(double temperature) {
-    const double inv = 1.0 / temperature;
-    const int k = static_cast<int>(inv);
-    return (inv == static_cast<double>(k) && k >= 1 && k <= 4) ? k : 0;
-}
-
 // SelfPlay.select_action (self_play.py:223-246) on the device copy of the stream, for the temperatures
 // whose arithmetic is exact everywhere: 0 (arg-max), +inf (choice without p) and 1/k (visits ** k by
 // multiplication -- libm's pow returns the same exactly representable integers --, normalise, cumulative
-// sum, one legacy double, right-bisect: RandomState.choice(p=...)).
-// Returns the chosen child slot, or -2 for a temperature the host must handle (pow()).
+// sum, one legacy double, right-bisect: RandomState.choice(p=...)).  exact_inverse_temperature: np_legacy_rng.h.
+// Returns the chosen child slot, or -2 for any other temperature: the host samples it (mzmcts_sample_actions), or, in a
+// move batch, select_action_general_kernel right behind the search (select_action.h, mzmcts_rng.hip).
 template <typename VisitOf>
 __device__ __forceinline__ int device_select_action(VisitOf visit_of, int n, double temperature, uint32_t* key,
                                                     int32_t* pos, uint32_t* words) {

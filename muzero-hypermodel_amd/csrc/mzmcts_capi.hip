@@ -1005,6 +1005,12 @@ int mzmcts_set_device_noise(mzmcts_engine* eng, int32_t enabled) {
     return MZMCTS_OK;
 }
 
+int mzmcts_set_device_temperatures(mzmcts_engine* eng, int32_t enabled) {
+    if (!eng) return MZMCTS_ERR_INVALID;
+    eng->device_temperatures = enabled != 0;
+    return MZMCTS_OK;
+}
+
 int mzmcts_get_noise(mzmcts_engine* eng, double* noise_out) {
     if (!eng || !noise_out) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_get_noise: null argument");
     if (eng->noise_on_device && !eng->have_readout)

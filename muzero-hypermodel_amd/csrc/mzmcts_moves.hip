@@ -2,6 +2,7 @@
 // mzmcts_moves_*): the host mirror of every env's numpy stream, the speculative draw of a batch's exploration noise,
 // the rewind of a mirror whose env left the pre-drawn path, and the collection of a batch's results.
 #include "engine_host.h"
+#include "select_action.h"
 
 extern "C" {
 
@@ -104,6 +105,38 @@ static int ensure_batch_capacity(mzmcts_engine* eng, int n_moves) {
     return 0;
 }
 
+// mzmcts_set_device_temperatures(1): why a temperature is refused all the same (select_action.h temperature_samplable)
+static std::string unsamplable_temperature(const mzmcts_engine* eng, const char* who, double t) {
+    char value[32];
+    std::snprintf(value, sizeof(value), "%g", t);
+    return std::string(who) + ": temperature " + value + " cannot be sampled: it must be 0, +inf, or finite and positive with " +
+           "num_actions * num_simulations ** (1 / T) finite (" + std::to_string(eng->p.A) + " * " + std::to_string(eng->p.S) +
+           " ** (1 / T) here; numpy.random.choice would be handed NaN probabilities)";
+}
+
+// What the whole-move kernels are told env e's temperature is: T itself, except for 1 / k whose powers leave the integers
+// a double holds exactly.  Their sampler would take its multiplication path for it; any T that is not 0, inf or 1 / k
+// makes it answer -2 instead, which hands the env to select_action_general_kernel (that one reads the true T).
+static double kernel_temperature(const mzmcts_engine* eng, double t) {
+    constexpr double kNotExact = 3.0;
+    return (eng->device_temperatures && mz::general_temperature(t, eng->p.S) && mz::exact_inverse_temperature(t)) ? kNotExact : t;
+}
+
+// Does set c hold a temperature that needs pow?  Then its true temperatures are staged for select_action_general_kernel.
+static int stage_general_temperatures(mzmcts_engine* eng, ChainSet& c) {
+    mzmcts_engine::MoveBatch& b = eng->batch;
+    const size_t E = static_cast<size_t>(eng->p.E);
+    c.general = false;
+    if (!eng->device_temperatures) return 0;
+    for (size_t e = 0; e < E && !c.general; ++e) c.general = mz::general_temperature(c.temperature[e], eng->p.S);
+    if (!c.general) return 0;
+    int rc;
+    if (!b.d_general_t && (rc = dev_alloc(eng, &b.d_general_t, E))) return rc;
+    if (!c.h_general_t && (rc = pinned_alloc(eng, &c.h_general_t, E))) return rc;
+    std::memcpy(c.h_general_t, c.temperature.data(), sizeof(double) * E);
+    return 0;
+}
+
 static int check_move_inputs(mzmcts_engine* eng, int32_t n_moves, const int32_t* legal, const int32_t* num_legal,
                              const int32_t* to_play, const double* temperature, const char* who) {
     if (!eng || !legal || !num_legal || !to_play || !temperature) return fail(eng, MZMCTS_ERR_INVALID, std::string(who) + ": null argument");
@@ -120,7 +153,9 @@ static int check_move_inputs(mzmcts_engine* eng, int32_t n_moves, const int32_t*
                 return fail(eng, MZMCTS_ERR_LEGAL_RANGE, "Legal actions should be a subset of the action space.");
         }
         const double t = temperature[e];
-        if (!(t == 0.0 || std::isinf(t) || (mz::exact_inverse_temperature(t) && std::pow(eng->p.S, 1.0 / t) < 9.0e15)))
+        if (eng->device_temperatures) {
+            if (!mz::temperature_samplable(t, A, eng->p.S)) return fail(eng, MZMCTS_ERR_INVALID, unsamplable_temperature(eng, who, t));
+        } else if (!(t == 0.0 || std::isinf(t) || (mz::exact_inverse_temperature(t) && std::pow(eng->p.S, 1.0 / t) < 9.0e15)))
             return fail(eng, MZMCTS_ERR_INVALID, std::string(who) + ": the device samples actions at temperature 0, inf or 1/k, "
                                                                     "k = 1..4, only (visit_count ** (1 / T) needs the host's pow)");
     }
@@ -151,7 +186,7 @@ static bool draw_env_rows(mzmcts_engine* eng, ChainSet& c, int e, bool tail, con
     const double t = c.temperature[e];
     const int assumed = assumed_sample_words(t);
     const uint32_t tie_words = assumed_tie_words(n);
-    h_temp[e] = t;
+    h_temp[e] = kernel_temperature(eng, t);
     h_limit[e] = (n == 0) ? 0 : (assumed < 0 ? 1 : n_moves);
     h_expect[e] = tie_words;
     c.env_twisted[e] = 0;
@@ -224,6 +259,7 @@ static int upload_set(mzmcts_engine* eng, ChainSet& c, hipStream_t stream) {
     std::memcpy(eng->h_to_play, c.to_play.data(), sizeof(int32_t) * E);
     MZ_HIP(eng, hipMemcpyAsync(eng->d_upload, eng->h_upload, eng->upload_bytes_no_noise, hipMemcpyHostToDevice, stream));
     MZ_HIP(eng, hipMemcpyAsync(b.d_in, c.h_in, b.in_bytes, hipMemcpyHostToDevice, stream));
+    if (c.general) MZ_HIP(eng, hipMemcpyAsync(b.d_general_t, c.h_general_t, sizeof(double) * static_cast<size_t>(E), hipMemcpyHostToDevice, stream));
     MZ_HIP(eng, hipMemsetAsync(b.d_stall, 0, static_cast<size_t>(E), stream));
     b.enqueued = 0;
     b.in_flight = true;
@@ -244,6 +280,7 @@ int mzmcts_moves_prepare(mzmcts_engine* eng, int32_t n_moves, const int32_t* leg
     ChainSet& c = b.set[b.cur];
     b.device_inputs = false;
     fill_set(eng, c, n_moves, legal, num_legal, to_play, add_noise, temperature);
+    if ((rc = stage_general_temperatures(eng, c))) return rc;
     eng->for_each_env([&](int lo, int hi) {
         for (int e = lo; e < hi; ++e) draw_env_rows(eng, c, e, false, nullptr);
     });
@@ -286,7 +323,10 @@ int mzmcts_moves_prepare_device(mzmcts_engine* eng, int32_t n_moves, const int32
     const int E = eng->p.E;
     for (int e = 0; e < E; ++e) {
         const double t = temperature[e];
-        if (!(t == 0.0 || std::isinf(t) || (mz::exact_inverse_temperature(t) && std::pow(eng->p.S, 1.0 / t) < 9.0e15)))
+        if (eng->device_temperatures) {
+            if (!mz::temperature_samplable(t, eng->p.A, eng->p.S))
+                return fail(eng, MZMCTS_ERR_INVALID, unsamplable_temperature(eng, "mzmcts_moves_prepare_device", t));
+        } else if (!(t == 0.0 || std::isinf(t) || (mz::exact_inverse_temperature(t) && std::pow(eng->p.S, 1.0 / t) < 9.0e15)))
             return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_prepare_device: the device samples actions at temperature 0, "
                                                  "inf or 1/k, k = 1..4, only");
     }
@@ -305,6 +345,7 @@ int mzmcts_moves_prepare_device(mzmcts_engine* eng, int32_t n_moves, const int32
     c.n_moves = n_moves;
     c.add_noise = add_noise != 0;
     std::memcpy(c.temperature.data(), temperature, sizeof(double) * E);
+    if ((rc = stage_general_temperatures(eng, c))) return rc;
     // control block: words the mirrors consumed since the device copies last moved (move 0 steps over them), the
     // temperatures, a move limit of the whole batch; no noise rows, no assumed tie-break counts
     uint32_t* skip = reinterpret_cast<uint32_t*>(c.h_in + b.o_skip);
@@ -315,8 +356,9 @@ int mzmcts_moves_prepare_device(mzmcts_engine* eng, int32_t n_moves, const int32
         reinterpret_cast<int32_t*>(c.h_in + b.o_limit)[e] = n_moves;
         reinterpret_cast<uint32_t*>(c.h_in + b.o_expect)[e] = 0u;
     }
-    std::memcpy(c.h_in + b.o_temp, temperature, sizeof(double) * E);
+    for (int e = 0; e < E; ++e) reinterpret_cast<double*>(c.h_in + b.o_temp)[e] = kernel_temperature(eng, temperature[e]);
     MZ_HIP(eng, hipMemcpyAsync(b.d_in + b.o_skip, c.h_in + b.o_skip, b.in_bytes - b.o_skip, hipMemcpyHostToDevice, stream));
+    if (c.general) MZ_HIP(eng, hipMemcpyAsync(b.d_general_t, c.h_general_t, sizeof(double) * static_cast<size_t>(E), hipMemcpyHostToDevice, stream));
     MZ_HIP(eng, hipMemsetAsync(b.d_stall, 0, static_cast<size_t>(E), stream));
     b.enqueued = 0;
     b.in_flight = true;
@@ -364,6 +406,7 @@ int mzmcts_moves_predraw_next(mzmcts_engine* eng, int32_t n_moves, const int32_t
     ChainSet& under = b.set[b.cur];
     ChainSet& c = b.set[b.cur ^ 1];
     fill_set(eng, c, n_moves, legal, num_legal, to_play, add_noise, temperature);
+    if ((rc = stage_general_temperatures(eng, c))) return rc;
     eng->for_each_env([&](int lo, int hi) {
         for (int e = lo; e < hi; ++e) draw_env_rows(eng, c, e, true, &under);
     });
@@ -458,6 +501,10 @@ int mzmcts_moves_enqueue(mzmcts_engine* eng, const float* observations, void* st
         ctl.temperature_threshold = b.temperature_threshold;
     }
     int rc = mzhost_launch_fused_move(eng, observations, ctl, true, stream);
+    if (!rc && c.general) {   // the envs whose temperature needs pow: sampled right behind the search (select_action.h)
+        const hipError_t err = mz::launch_select_action_general(eng->p, ctl, b.d_general_t, stream);
+        if (err != hipSuccess) rc = hip_fail(eng, err, "select_action_general_kernel");
+    }
     eng->p.root_action = const_cast<int32_t*>(host_legal);
     eng->p.root_children = const_cast<int32_t*>(host_nlegal);
     eng->p.root_to_play = const_cast<int32_t*>(host_to_play);
@@ -584,6 +631,10 @@ int mzmcts_moves_end_lockstep(mzmcts_engine* eng, void* stream_) {
     }
     hipError_t err = mz::launch_lockstep_move_finish(eng->p, ctl, stream);
     if (err != hipSuccess) return hip_fail(eng, err, "lockstep_move_finish_kernel");
+    if (b.set[b.cur].general) {
+        err = mz::launch_select_action_general(eng->p, ctl, b.d_general_t, stream);
+        if (err != hipSuccess) return hip_fail(eng, err, "select_action_general_kernel");
+    }
     // the move's blocks go to the host now, under the batch's remaining searches (collect then finds them there)
     if (b.downloaded == m) {
         MZ_HIP(eng, hipEventRecord(b.move_done, stream));

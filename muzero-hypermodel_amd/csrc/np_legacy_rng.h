@@ -12,7 +12,9 @@
 //     mirror of the stream that is kept in step with the device copy by word counts;
 //   * the Dirichlet draw for shape <= 1 (every reference config: root_dirichlet_alpha 0.1 ... 0.3) ALSO runs on the
 //     device (DeviceStream below, on glibc's log / pow restated in glibc_libm.h), so that a batch of moves needs
-//     no pre-drawn noise from the host.
+//     no pre-drawn noise from the host;
+//   * select_action at the temperatures that need pow ALSO runs on the device, on the same restated pow, behind the
+//     searches of a move batch (select_action.h; mzmcts_set_device_temperatures).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -96,6 +98,14 @@ MZ_HD inline uint32_t mt_below(uint32_t* key, int32_t* pos, uint32_t n, uint32_t
         ++*words;
     } while (v > top);
     return v;
+}
+
+// Temperatures whose visit_count ** (1 / T) is exact integer arithmetic everywhere: 1 / T an integer k in 1..4
+// (the reference's schedules use 1, 0.5, 0.25: cartpole.py:118-128).  Returns k, or 0.
+MZ_HD inline int exact_inverse_temperature(double temperature) {
+    const double inv = 1.0 / temperature;
+    const int k = static_cast<int>(inv);
+    return (inv == static_cast<double>(k) && k >= 1 && k <= 4) ? k : 0;
 }
 
 // ---- the legacy distributions of the exploration noise over caller-provided MT19937 storage ------------

@@ -79,6 +79,7 @@ class BatchedMCTS:
         mode = os.environ.get("MZ_FUSED_STEP", "auto")
         self.fused_step = mode == "on" or (mode != "off" and self.E >= 16384)
         self._device_noise = False
+        self._device_temperatures = False
 
         with torch.cuda.device(self.device):
             self.pool = torch.empty((self.S + 1, self.E, self.H), dtype=torch.float32, device=self.device)
@@ -528,7 +529,8 @@ class BatchedMCTS:
 
     def moves_prepare(self, n_moves, legal_actions, to_play, temperature, add_exploration_noise=True, num_legal=None):
         """Draw the exploration noise of the next `n_moves` moves and upload it; the legal action sets must stay
-        the same over the batch, temperature (scalar or [E]) must be 0, 1 or inf."""
+        the same over the batch; temperature (scalar or [E]) must be 0, inf (one move per batch) or 1 / k, k = 1..4 --
+        after set_device_temperatures() any finite T > 0 whose powers do not overflow."""
         t = self._move_inputs(legal_actions, to_play, temperature, num_legal)
         self._check(self._lib.mzmcts_moves_prepare(self._h, int(n_moves), self._p_legal, self._p_nlegal, self._p_to_play,
                                                    1 if add_exploration_noise else 0, ptr(t, c_f64_p), self._stream()))
@@ -752,6 +754,15 @@ class BatchedMCTS:
         then holds a search's rows after its readout()."""
         self._check(self._lib.mzmcts_set_device_noise(self._h, 1 if enabled else 0))
         self._device_noise = bool(enabled)
+
+    def set_device_temperatures(self, enabled=True):
+        """Let the move batches (moves_prepare / moves_predraw_next / moves_prepare_device) sample at any finite T > 0 for
+        which num_actions * num_simulations ** (1 / T) is finite, not only at 0, inf and 1 / k: visit_count ** (1 / T) by
+        glibc's pow on the GPU, in a small kernel behind each search of a batch that holds such a temperature.  Same
+        actions, same streams as sample_actions() on the host, to the last bit.  Off by default: such a temperature is
+        then refused, as are NaN, negative and overflowing ones either way."""
+        self._check(self._lib.mzmcts_set_device_temperatures(self._h, 1 if enabled else 0))
+        self._device_temperatures = bool(enabled)
 
     def sample_actions(self, temperature):
         """SelfPlay.select_action per env on its own RNG stream; returns (actions, slots)."""

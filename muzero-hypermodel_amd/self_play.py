@@ -955,6 +955,20 @@ class DeviceSelfPlay(ManyEnvLoop):
     def set_weights(self, weights):
         self.model.set_weights(weights)
 
+    def set_device_temperatures(self, enabled=True):
+        """Move batches at any softmax temperature (engine.set_device_temperatures): play_moves, a step against an
+        opponent, continuous_self_play(moves_per_pass=K) and evaluate() then run a config whose temperature is not 0,
+        inf or 1 / k as batches too, the actions sampled on the GPU -- the games step() plays, bit for bit.  Off by
+        default: such a config plays through step(), one host round trip per move."""
+        self.engine.set_device_temperatures(enabled)
+
+    def _device_samples(self, temperature):
+        """Can a move batch sample at `temperature` (engine.moves_prepare* would accept it)?"""
+        if temperature == 0 or _native.exact_inverse_temperature(temperature):
+            return True
+        # (1 / k whose powers leave the exact integers is refused by the engine unless the switch is on; not asked here)
+        return bool(self.engine._device_temperatures) and 0.0 < float(temperature) < float("inf")
+
     def step(self, temperature, temperature_threshold=None, on_game=None, on_games=None, opponent=None,
              muzero_player=None):
         """One move in every env (the body of play_game's loop, self_play.py:129-182).  `opponent` / `muzero_player` as
@@ -989,7 +1003,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         if not 0.0 < float(cfg.root_dirichlet_alpha) <= 1.0:
             raise NotImplementedError("a step against an opponent runs as a device-input move batch, whose exploration "
                                       "noise is drawn on the GPU for 0 < root_dirichlet_alpha <= 1 only")
-        if not (temperature == 0 or temperature == float("inf") or _native.exact_inverse_temperature(temperature)):
+        if not (temperature == float("inf") or self._device_samples(temperature)):
             raise NotImplementedError("a step against an opponent runs as a device-input move batch, whose actions are "
                                       f"sampled on the GPU at temperature 0, inf or 1/k (k = 1..4) only; got {temperature}")
 
@@ -1208,7 +1222,7 @@ class DeviceSelfPlay(ManyEnvLoop):
             device_inputs = (not getattr(self.envs, "constant_legal_actions", False) or self.engine._fc_model is None
                              or bool(temperature_threshold) or self._opponent[0] != "self")
         return (moves_per_pass is not None
-                and (temperature == 0 or _native.exact_inverse_temperature(temperature))
+                and self._device_samples(temperature)
                 # (a device-input batch draws its exploration noise on the GPU: the legacy gamma sampler for shapes <= 1)
                 and (not device_inputs or 0.0 < float(self.config.root_dirichlet_alpha) <= 1.0))
 
@@ -1307,6 +1321,11 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             stream.wait_stream(current)
             with torch.cuda.stream(stream):
                 actor.model.set_weights(state)
+
+    def set_device_temperatures(self, enabled=True):
+        """DeviceSelfPlay.set_device_temperatures for every group's engine."""
+        for a in self.actors:
+            a.set_device_temperatures(enabled)
 
     @property
     def moves_played(self):
@@ -1445,7 +1464,8 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
 
 
 def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_player=None, num_envs=64, seed=0,
-             device=None, moves_per_batch=8, groups=1, use_graph=True, warmup_batches=0):
+             device=None, moves_per_batch=8, groups=1, use_graph=True, warmup_batches=0, temperature=0,
+             device_temperatures=False):
     """`MuZero.test` (reference muzero.py:346-396) on device-resident envs: `num_tests` games at temperature 0 and
     temperature threshold 0 (play_game(0, 0, False, opponent, muzero_player)), `num_envs` of them at a time, env e on
     the game and RNG stream of reference worker `seed + e`.
@@ -1461,6 +1481,10 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
     played on the same actor first -- its buffers, the captured hipGraph and the history filer exist afterwards --;
     games that began during them are not counted and `seconds` / the move counts start after them.  With 0 the games
     are those of a fresh actor (num_envs = 1: the consecutive games of one SelfPlay worker of that seed).
+
+    `temperature` (MuZero.test plays at 0) samples MuZero's moves instead of taking the most visited one;
+    `device_temperatures` switches set_device_temperatures on, so that a temperature other than 0, inf and 1 / k runs as
+    batches (against an opponent it cannot run at all without it).
 
     Returns a dict: `result` is MuZero.test's number (one player: mean total reward; otherwise the mean of the rewards
     earned on muzero_player's moves), `muzero_reward` / `opponent_reward` the means per side (two players),
@@ -1484,6 +1508,8 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
     else:
         actor = probe = DeviceSelfPlay(checkpoint, game_name, cfg, seed, E, device=device, use_graph=use_graph)
     actor.set_opponent(opponent, muzero_player)
+    if device_temperatures:
+        actor.set_device_temperatures(True)
     clock = numpy.zeros(E, dtype=numpy.int64)          # plies of env e's finished games
     plies = numpy.zeros(E, dtype=numpy.int64)          # plies env e has played
     found = {k: [] for k in ("start", "env", "length", "mine", "theirs", "total")}
@@ -1508,14 +1534,14 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
         found["total"].append(rewards.sum(axis=1))
 
     # the pipelined actor's batches always take the device-input form
-    batched = probe._batchable(0, 0, moves_per_batch, device_inputs=True if groups > 1 else None)
+    batched = probe._batchable(temperature, 0, moves_per_batch, device_inputs=True if groups > 1 else None)
 
     def play():
         if batched:
-            plies[:] += actor.play_moves(moves_per_batch, 0, on_games=on_games, temperature_threshold=0)
+            plies[:] += actor.play_moves(moves_per_batch, temperature, on_games=on_games, temperature_threshold=0)
             actor.flush(on_games=on_games)
         else:
-            actor.step(0, 0, on_games=on_games)
+            actor.step(temperature, 0, on_games=on_games)
             plies[:] += 1
 
     for _ in range(int(warmup_batches)):

@@ -2,6 +2,7 @@
 
     python tools/evaluate.py --game tictactoe --envs 65536 --tests 200000 [--opponent expert] [--muzero-player 0]
                              [--fc 0] [--batch 8] [--groups 1] [--warmup-batches 3] [--compare-self] [--max-moves N]
+                             [--temperature 0.35 --device-temperatures]
 
 Prints one JSON line: self_play.evaluate's result (MuZero.test's number, rewards per side, win / draw / loss counts, mean
 episode length) with games per second, env-moves per second, simulations per second and the share of env-moves that
@@ -26,7 +27,8 @@ models = importlib.import_module("muzero-hypermodel_amd.models")
 def run(args, config, checkpoint, opponent, num_tests):
     out = sp.evaluate(checkpoint, args.game, config, num_tests, opponent=opponent, muzero_player=args.muzero_player,
                       num_envs=args.envs, seed=args.seed, moves_per_batch=args.batch, groups=args.groups,
-                      warmup_batches=args.warmup_batches)
+                      warmup_batches=args.warmup_batches, temperature=args.temperature,
+                      device_temperatures=args.device_temperatures)
     s = out["seconds"]
     out.update(games_per_s=out["games"] / s, env_moves_per_s=out["env_moves"] / s, simulations_per_s=out["simulations"] / s,
                sat_out_share=1.0 - out["searched_moves"] / max(1, out["env_moves"]))
@@ -48,6 +50,9 @@ def main():
     ap.add_argument("--warmup-batches", type=int, default=3, help="untimed batches on the same actor first (code objects, "
                     "rings, graph capture, filer); games that begin in them are not counted")
     ap.add_argument("--compare-self", action="store_true")
+    ap.add_argument("--temperature", type=float, default=0.0, help="softmax temperature of MuZero's moves (MuZero.test: 0)")
+    ap.add_argument("--device-temperatures", action="store_true", help="a temperature other than 0, inf and 1 / k, k = 1..4, "
+                    "sampled on the GPU: batches (and plies against an opponent at all) instead of one move per round trip")
     ap.add_argument("--max-moves", type=int, default=None, help="end games after N plies (config.max_moves; default: the "
                     "config's)")
     args = ap.parse_args()

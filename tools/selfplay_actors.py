@@ -66,6 +66,11 @@ def main():
     ap.add_argument("--moves-per-pass", type=int, default=4)
     ap.add_argument("--groups", type=int, default=1,
                     help="board games: engine groups per actor on streams of their own (PipelinedDeviceSelfPlay: pays from tens of thousands of envs per GPU on); 1 = one engine")
+    ap.add_argument("--temperature", type=float, default=None,
+                    help="softmax temperature of every pass (default: the config's visit_softmax_temperature_fn)")
+    ap.add_argument("--device-temperatures", action="store_true",
+                    help="passes at a temperature other than 0 and 1 / k, k = 1..4, run as move batches too: sampled on the GPU "
+                         "(set_device_temperatures); without it they go move by move")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         bench = importlib.import_module("bench")
@@ -82,6 +87,8 @@ def main():
     device = torch.device("cuda", local_rank)
     config = pkg(f"games.{args.game}").MuZeroConfig()
     config.training_steps, config.ratio, config.self_play_delay = args.passes, None, 0
+    if args.temperature is not None:
+        config.visit_softmax_temperature_fn = lambda trained_steps: args.temperature
     if args.game == "cartpole":
         from parity_helpers import load_golden
         w = load_golden("cartpole_weights")
@@ -97,6 +104,9 @@ def main():
                                            groups=args.groups, device=device)
     else:
         actor = sp.DeviceSelfPlay({"weights": weights}, args.game, config, config.seed + rank * args.envs, args.envs, device=device)
+
+    if args.device_temperatures:
+        actor.set_device_temperatures(True)
 
     play_pass = actor._play_pass
 

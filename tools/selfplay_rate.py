@@ -2,6 +2,7 @@
 
     python tools/selfplay_rate.py [--game cartpole] [--envs 4096] [--moves 60] [--max-moves N]
     python tools/selfplay_rate.py --game gomoku --kinds search,device-batch [--simulations S --channels C --blocks B]
+    python tools/selfplay_rate.py --kinds device-batch --temperature 0.35 --device-temperatures
 
 Prints one JSON line per actor kind: moves/s, simulations/s, finished games, the engine's device bytes.  This is the
 loop the reference runs in self_play.py:34-113 (continuous_self_play), without the replay buffer hand-off.  Kind
@@ -80,6 +81,9 @@ def main():
     ap.add_argument("--simulations", type=int, default=None, help="config.num_simulations (default: the config's)")
     ap.add_argument("--channels", type=int, default=None, help="config.channels of a residual network (default: the config's)")
     ap.add_argument("--blocks", type=int, default=None, help="config.blocks of a residual network (default: the config's)")
+    ap.add_argument("--temperature", type=float, default=1.0, help="softmax temperature of the action sampling")
+    ap.add_argument("--device-temperatures", action="store_true", help="device actors: batches sample at any temperature on "
+                    "the GPU (set_device_temperatures); without it the batch kinds take 0 and 1 / k, k = 1..4, only")
     args = ap.parse_args()
     if args.envs is None:
         args.envs = 256 if args.game == "gomoku" else 4096
@@ -114,6 +118,8 @@ def main():
             actor = sp.DeviceSelfPlay({"weights": weights}, args.game, config, 0, args.envs)
             if kind == "device-batch" and actor.engine._fc_model is not None:
                 actor.engine.set_fused_options("auto", publish_tree=False)
+        if args.device_temperatures and kind != "host":
+            actor.set_device_temperatures(True)
         done = [0]
 
         def on_game(e, gh):
@@ -126,7 +132,7 @@ def main():
         if kind in ("device-batch", "device-pipelined-batch"):
             # searches, env steps and resets queued back to back, `--batch` moves per host round trip
             for _ in range(3):                       # buffers, the native history filer, the pre-drawn next batch
-                actor.play_moves(args.batch, 1.0, **cb)
+                actor.play_moves(args.batch, args.temperature, **cb)
             torch.cuda.synchronize()
             done[0] = 0
             t0 = time.perf_counter()
@@ -135,18 +141,18 @@ def main():
             for i in range(calls):
                 # (two groups: each group's next batch is queued before its last one is filed; the last call drains)
                 ahead = dict(prefetch=i + 1 < calls and not args.no_prefetch) if kind == "device-pipelined-batch" else {}
-                moves += int(actor.play_moves(args.batch, 1.0, **cb, **ahead).sum())
+                moves += int(actor.play_moves(args.batch, args.temperature, **cb, **ahead).sum())
             actor.flush(**cb)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
         else:
             for _ in range(5):
-                actor.step(1.0, None, **cb)
+                actor.step(args.temperature, None, **cb)
             torch.cuda.synchronize()
             done[0] = 0
             t0 = time.perf_counter()
             for _ in range(args.moves):
-                actor.step(1.0, None, **cb)
+                actor.step(args.temperature, None, **cb)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             moves = args.moves * args.envs
@@ -154,6 +160,7 @@ def main():
                           "simulations_per_s": moves * config.num_simulations / dt, "ms_per_move_step": 1e3 * dt * args.envs / moves,
                           "games_finished": done[0], "weights": args.weights, "max_moves": config.max_moves,
                           "num_simulations": config.num_simulations, "engine_device_bytes": engine_bytes(actor),
+                          "temperature": args.temperature, "device_temperatures": bool(args.device_temperatures and kind != "host"),
                           **({"moves_per_call": args.batch, "prefetch": not args.no_prefetch} if kind == "device-pipelined-batch" else {}),
                           **({"moves_per_call": args.batch} if kind == "device-batch" else {})}), flush=True)
         actor.close()
