@@ -15,9 +15,17 @@
  *                           GameHistory.get_stacked_observations for a batch of (game, position) pairs
  *                           (replay_buffer.py:222-295, self_play.py:514-548)
  *
- * Which games and positions go into a batch, and the random actions of absorbing states, are the
- * caller's draws (the reference takes them from numpy's legacy RandomState in a fixed order:
- * replay_buffer.py:67-195); this library only evaluates them.  fp64 sums run in the reference's order with
+ * Which games and positions go into a batch, and the random actions of absorbing states, are draws from numpy's
+ * legacy RandomState in a fixed order (replay_buffer.py:67-195).  By default they are the caller's and this library
+ * only evaluates them (mzreplay_make_batch).  After mzreplay_sampler_enable the store also holds the priorities and
+ * a numpy stream of its own on the device, and
+ *
+ *   mzreplay_sample_batch         draws a batch's games, positions, absorbing actions and importance weights there,
+ *                                 draw for draw and bit for bit the reference's (csrc/replay_sampler.h)
+ *   mzreplay_make_batch_device    builds the targets from those device-resident indices, in the trainer's dtypes
+ *   mzreplay_update_priorities    ReplayBuffer.update_priorities (replay_buffer.py:197-220) from device tensors
+ *
+ * so that a training step needs no host round trip.  fp64 sums run in the reference's order with
  * `discount ** i` taken from a table the caller fills with its own libm (Python floats), so values and
  * policies are bit-identical to the reference's; priorities go through the device's pow() and agree to
  * float32 rounding.
@@ -76,6 +84,44 @@ int mzreplay_game_observations(mzreplay *store, int32_t slot, int32_t length, fl
  * bootstrap from them, accumulating in float32 as the reference does once the values are a numpy float32 array
  * (NumPy >= 2 promotion; recorded in fixture G13).  mzreplay_add_games into the slot forgets them.  Asynchronous. */
 int mzreplay_set_reanalysed(mzreplay *store, int32_t slot, const float *values, int32_t length, void *stream);
+
+/* ---- sampling on the device ----------------------------------------------------------------------------------------
+ * Switch the sampler on (once per store; calling it again only reseeds): the store then owns, on the device,
+ * priorities f32[capacity][max_moves], game_priority f32[capacity], the game id of every slot and an MT19937 stream
+ * seeded as numpy.random.seed(seed).  From here on mzreplay_add_games also leaves the initial priorities it computes in
+ * those arrays and numbers the games it stores next_game_id, next_game_id + 1, ...  Blocking. */
+int mzreplay_sampler_enable(mzreplay *store, uint32_t seed, int64_t next_game_id);
+/* The stream as RandomState.get_state() gives it: key u32[624] (host) and the position 0..624.  Blocking. */
+int mzreplay_sampler_get_rng(mzreplay *store, uint32_t *key, int32_t *pos);
+int mzreplay_sampler_set_rng(mzreplay *store, const uint32_t *key, int32_t pos);
+/* Priorities of the game in `slot` given by the caller (a GameHistory that carries its own, a restored buffer):
+ * host f32[length]; the game priority becomes their numpy.max, the slot's game id `game_id`.  Blocking. */
+int mzreplay_set_priorities(mzreplay *store, int32_t slot, int64_t game_id, const float *priorities, int32_t length,
+                            void *stream);
+/* Read a slot back (host outputs, each may be NULL): priorities f32[max_moves], game priority, game id (-1: empty).
+ * Blocking. */
+int mzreplay_get_priorities(mzreplay *store, int32_t slot, float *priorities, float *game_priority, int64_t *game_id,
+                            void *stream);
+/* ReplayBuffer.get_batch's draws for `batch` samples (1..4096) over the n_games stored games whose ids start at
+ * oldest_game_id (slot = id % capacity); total_samples = the sum of their lengths; per != 0: prioritised replay.
+ * Device outputs: game_ids i64[B], slots i32[B], positions i32[B], absorbing_actions i32[B][U+1] (the action index
+ * drawn for every unrolled step past the end of the game, 0 elsewhere), weights f32[B] (per != 0 only; may be NULL
+ * otherwise).  The stream advances by exactly the words the reference would consume.  Asynchronous on `stream`. */
+int mzreplay_sample_batch(mzreplay *store, int32_t batch, int64_t oldest_game_id, int32_t n_games, int64_t total_samples,
+                          int32_t per, int64_t *game_ids, int32_t *slots, int32_t *positions, int32_t *absorbing_actions,
+                          float *weights, void *stream);
+/* mzreplay_make_batch with slots / positions / absorbing_actions in device memory, writing the trainer's dtypes:
+ * observations f32, actions i64, values / rewards / policies / gradient_scale f32 (the fp64 results of
+ * mzreplay_make_batch rounded to nearest at the store).  Needs no sampler.  Asynchronous. */
+int mzreplay_make_batch_device(mzreplay *store, int32_t batch, const int32_t *slots, const int32_t *positions,
+                               const int32_t *absorbing_actions, float *observations, int64_t *actions, float *values,
+                               float *rewards, float *policies, float *gradient_scale, void *stream);
+/* ReplayBuffer.update_priorities: device inputs game_ids i64[B], positions i32[B], priorities f32[B][U+1].  Samples are
+ * applied in batch order (where two samples of one game overlap, the later one's values stay), rows end at the game's
+ * end, a sample whose game id no longer sits in its slot is skipped, and game_priority = max(priorities) of every
+ * touched game.  Asynchronous. */
+int mzreplay_update_priorities(mzreplay *store, int32_t batch, const int64_t *game_ids, const int32_t *positions,
+                               const float *priorities, void *stream);
 
 /* Bytes of device memory the store occupies. */
 int64_t mzreplay_device_bytes(const mzreplay *store);

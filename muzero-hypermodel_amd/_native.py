@@ -177,6 +177,16 @@ PROTOTYPES = {
     "mzreplay_game_observations": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.c_int32, c_void, c_void]),
     "mzreplay_set_reanalysed": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, ctypes.c_int32, c_void]),
     "mzreplay_device_bytes": (ctypes.c_int64, [c_void]),
+    "mzreplay_sampler_enable": (ctypes.c_int, [c_void, ctypes.c_uint32, ctypes.c_int64]),
+    "mzreplay_sampler_get_rng": (ctypes.c_int, [c_void, c_u32_p, c_i32_p]),
+    "mzreplay_sampler_set_rng": (ctypes.c_int, [c_void, c_u32_p, ctypes.c_int32]),
+    "mzreplay_set_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.c_int64, c_f32_p, ctypes.c_int32, c_void]),
+    "mzreplay_get_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_f32_p, c_f32_p, c_i64_p, c_void]),
+    "mzreplay_sample_batch": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                             ctypes.c_int32, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "mzreplay_make_batch_device": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, c_void, c_void, c_void, c_void,
+                                                  c_void, c_void, c_void, c_void]),
+    "mzreplay_update_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, c_void, c_void]),
     "mzenv_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_u32_p, ctypes.POINTER(c_void)]),
     "mzenv_destroy": (None, [c_void]),
     "mzenv_last_error": (ctypes.c_char_p, [c_void]),

@@ -8,6 +8,16 @@
 //                       reward sum in the reference's order, |root - target| ** alpha, block max
 //   make_batch_kernel   one workgroup per sample: threads 0..U evaluate the U+1 unroll targets, all threads
 //                       copy the policy rows and the (stacked) observation planes
+// The sampler (mzreplay_sampler_enable; arithmetic in replay_sampler.h) keeps priorities f32 [G][L], game_priority
+// f32 [G], game_id i64 [G] and numpy's MT19937 stream on the device and draws a batch in four launches:
+//   sample_games_kernel      one workgroup: game probabilities (numpy's pairwise float32 sum, leaves in parallel), their
+//                            fp64 running sum (ONE lane: the order of the additions is the contract), B game draws
+//   position_tables_kernel   one wavefront per sample: the game's float32 sum and fp64 running sum (one lane each)
+//   sample_walk_kernel       one wavefront walks the samples in batch order: position uniform, number of absorbing
+//                            steps (from the table's last U entries, staged in LDS), their rejection draws 64 words
+//                            at a time by ballot; the MT19937 twist runs across the lanes
+//   sample_finish_kernel     positions by bisection, importance weights, batch maximum, all samples in parallel
+// and update_priorities in two (writes with the reference's later-sample-wins order, then the game maxima).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,6 +26,7 @@
 #include <vector>
 
 #include "../../include/mzreplay.h"
+#include "replay_sampler.h"
 
 namespace {
 
@@ -127,14 +138,17 @@ __global__ __launch_bounds__(128) void game_observations_kernel(StoreParams p, i
     stacked_observation(p, slot, pos, obs_out + static_cast<size_t>(pos) * (p.C + p.stacked * (p.C + 1)) * p.H * p.W);
 }
 
+// T = double: the reference's dtypes; T = float: the trainer's (the fp64 results rounded to nearest at the store)
+template <typename T>
 __global__ __launch_bounds__(128) void make_batch_kernel(StoreParams p, const int32_t* __restrict__ slots,
                                                          const int32_t* __restrict__ positions,
                                                          const int32_t* __restrict__ absorbing,  // [B][U+1]
                                                          float* __restrict__ obs_out, int64_t* __restrict__ actions_out,
-                                                         double* __restrict__ values_out, double* __restrict__ rewards_out,
-                                                         double* __restrict__ policies_out, double* __restrict__ scale_out) {
+                                                         T* __restrict__ values_out, T* __restrict__ rewards_out,
+                                                         T* __restrict__ policies_out, T* __restrict__ scale_out) {
     const int b = blockIdx.x;
     const int slot = slots[b], pos = positions[b];
+    if (slot < 0 || slot >= p.G || pos < 0 || pos > p.L) return;   // indices that come from the device are checked here
     const int n = p.length[slot];
     const int U1 = p.unroll + 1;
     const double* rewards = p.rewards + static_cast<size_t>(slot) * (p.L + 1);
@@ -155,11 +169,11 @@ __global__ __launch_bounds__(128) void make_batch_kernel(StoreParams p, const in
         } else {
             action = absorbing[o];  // numpy.random.choice(action_space), drawn by the caller in the reference's order
         }
-        values_out[o] = value;
-        rewards_out[o] = reward;
+        values_out[o] = static_cast<T>(value);
+        rewards_out[o] = static_cast<T>(reward);
         actions_out[o] = action;
         const int remaining = n + 1 - pos;  // len(action_history) - game_pos
-        scale_out[o] = static_cast<double>(p.unroll < remaining ? p.unroll : remaining);
+        scale_out[o] = static_cast<T>(p.unroll < remaining ? p.unroll : remaining);
     }
     // ---- policies: child_visits[cur], or the uniform policy at and past the end of the game
     const double uniform = 1 / static_cast<double>(p.A);
@@ -167,9 +181,388 @@ __global__ __launch_bounds__(128) void make_batch_kernel(StoreParams p, const in
         const int u = t / p.A, a = t - u * p.A;
         const int cur = pos + u;
         policies_out[static_cast<size_t>(b) * U1 * p.A + t] =
-            cur < n ? p.child_visits[(static_cast<size_t>(slot) * p.L + cur) * p.A + a] : uniform;
+            static_cast<T>(cur < n ? p.child_visits[(static_cast<size_t>(slot) * p.L + cur) * p.A + a] : uniform);
     }
     stacked_observation(p, slot, pos, obs_out + static_cast<size_t>(b) * (p.C + p.stacked * (p.C + 1)) * p.H * p.W);
+}
+
+
+// ---- the sampler (replay_sampler.h) ---------------------------------------------------------------------------------
+struct SamplerParams {
+    float* priorities;       // [G][L]
+    float* game_priority;    // [G]
+    int64_t* game_id;        // [G], -1 while the slot is empty
+    uint32_t* mt_key;        // [624] numpy's stream as RandomState.get_state() gives it
+    int32_t* mt_pos;         // [1]
+    float* probs;            // [G] scratch where the game tables do not fit LDS
+    double* cdf;             // [G]
+    int32_t lds_games;       // 1: probabilities and their running sum live in LDS
+    // one batch
+    int32_t* game_len;       // [Bcap]
+    float* game_prob;        // [Bcap]
+    double* u_game;          // [Bcap]
+    double* u_pos;           // [Bcap]
+    float* totals;           // [Bcap]
+    double* tables;          // [Bcap][L] normalised running sums of the sampled games' position probabilities
+};
+
+constexpr int kMaxLeaves = 512;        // pairwise leaves summed in parallel (covers 32 768 games; beyond: one lane)
+constexpr int kSampleThreads = 256;
+
+// the next block of 624 words, across the workgroup's (or the wavefront's) lanes: three ranges that each read only
+// what the previous one wrote, then the last word.  `sync` separates them.
+template <typename Sync>
+__device__ __forceinline__ void twist_parallel(uint32_t* key, uint32_t* fresh, int lane, int lanes, Sync sync) {
+    for (int k = lane; k < mz::kMtN - mz::kMtM; k += lanes) fresh[k] = mz::mt_mix(key[k], key[k + 1], key[k + mz::kMtM]);
+    sync();
+    for (int k = mz::kMtN - mz::kMtM + lane; k < 2 * (mz::kMtN - mz::kMtM); k += lanes)
+        fresh[k] = mz::mt_mix(key[k], key[k + 1], fresh[k + mz::kMtM - mz::kMtN]);
+    sync();
+    for (int k = 2 * (mz::kMtN - mz::kMtM) + lane; k < mz::kMtN - 1; k += lanes)
+        fresh[k] = mz::mt_mix(key[k], key[k + 1], fresh[k + mz::kMtM - mz::kMtN]);
+    sync();
+    if (lane == 0) fresh[mz::kMtN - 1] = mz::mt_mix(key[mz::kMtN - 1], fresh[0], fresh[mz::kMtM - 1]);
+    sync();
+    for (int k = lane; k < mz::kMtN; k += lanes) key[k] = fresh[k];
+    sync();
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_games_kernel(StoreParams p, SamplerParams s, int batch,
+                                                                      int64_t oldest_id, int n_games, int per,
+                                                                      int64_t* __restrict__ game_ids,
+                                                                      int32_t* __restrict__ slots) {
+    extern __shared__ double lds_dyn[];
+    __shared__ uint32_t key[mz::kMtN], fresh[mz::kMtN];
+    __shared__ int32_t leaf_off[kMaxLeaves], leaf_len[kMaxLeaves];
+    __shared__ float leaf_sum[kMaxLeaves];
+    __shared__ float total_s;
+    __shared__ int32_t leaves_s, pos_s, done_s, have_hi_s;
+    __shared__ uint32_t hi_s;
+    const int t = threadIdx.x;
+    double* cdf = s.lds_games ? lds_dyn : s.cdf;
+    float* probs = s.lds_games ? reinterpret_cast<float*>(lds_dyn + p.G) : s.probs;
+    auto sync = [] { __syncthreads(); };
+    for (int k = t; k < mz::kMtN; k += kSampleThreads) key[k] = s.mt_key[k];
+    if (t == 0) {
+        pos_s = s.mt_pos[0];
+        done_s = 0;
+        have_hi_s = 0;
+    }
+    if (per) {
+        // game_probs in ring order, oldest to newest
+        for (int i = t; i < n_games; i += kSampleThreads)
+            probs[i] = s.game_priority[static_cast<int>((oldest_id + i) % p.G)];
+        __syncthreads();
+        if (t == 0) {
+            int count = 0;
+            mz::replay::numpy_sum_walk(n_games, [&](int off, int len) {
+                if (count < kMaxLeaves) {
+                    leaf_off[count] = off;
+                    leaf_len[count] = len;
+                }
+                ++count;
+                return 0.f;
+            });
+            leaves_s = count;
+        }
+        __syncthreads();
+        const int leaves = leaves_s;
+        auto at = [&](int i) { return probs[i]; };
+        if (leaves <= kMaxLeaves) {
+            for (int k = t; k < leaves; k += kSampleThreads) leaf_sum[k] = mz::replay::pairwise_leaf(at, leaf_off[k], leaf_len[k]);
+            __syncthreads();
+            if (t == 0) {
+                int k = 0;
+                total_s = mz::replay::numpy_sum_walk(n_games, [&](int, int) { return leaf_sum[k++]; });
+            }
+        } else if (t == 0) {
+            total_s = mz::replay::numpy_sum_f32(at, n_games);
+        }
+        __syncthreads();
+        const float total = total_s;
+        for (int i = t; i < n_games; i += kSampleThreads) {
+            const float q = probs[i] / total;
+            probs[i] = q;
+            cdf[i] = static_cast<double>(q);
+        }
+        __syncthreads();
+        if (t == 0) {   // cumsum: one chain of fp64 additions, left to right
+            double run = 0.0;
+            for (int i = 0; i < n_games; ++i) {
+                run += cdf[i];
+                cdf[i] = run;
+            }
+        }
+        __syncthreads();
+        const double last = cdf[n_games - 1];
+        __syncthreads();
+        for (int i = t; i < n_games; i += kSampleThreads) cdf[i] = cdf[i] / last;
+    }
+    __syncthreads();
+    // B game draws: lane 0 consumes the words, every lane helps with the twist
+    const uint32_t top = static_cast<uint32_t>(n_games) - 1u;
+    const uint32_t mask = mz::mask_for(top);
+    if (!per && top == 0u) {
+        for (int b = t; b < batch; b += kSampleThreads) s.game_len[b] = 0;   // (index 0; filled in below)
+        if (t == 0) done_s = batch;
+        __syncthreads();
+    }
+    while (done_s < batch) {
+        if (pos_s >= mz::kMtN) {
+            twist_parallel(key, fresh, t, kSampleThreads, sync);
+            if (t == 0) pos_s = 0;
+        }
+        __syncthreads();
+        if (t == 0) {
+            int pos = pos_s, b = done_s;
+            while (pos < mz::kMtN && b < batch) {
+                const uint32_t w = mz::mt_temper(key[pos++]);
+                if (per) {
+                    if (!have_hi_s) {
+                        hi_s = w;
+                        have_hi_s = 1;
+                    } else {
+                        s.u_game[b++] = mz::replay::uniform_from_words(hi_s, w);
+                        have_hi_s = 0;
+                    }
+                } else if ((w & mask) <= top) {
+                    s.game_len[b++] = static_cast<int32_t>(w & mask);   // the drawn index, replaced by the length below
+                }
+            }
+            pos_s = pos;
+            done_s = b;
+        }
+        __syncthreads();
+    }
+    for (int b = t; b < batch; b += kSampleThreads) {
+        int g;
+        if (per) {
+            g = mz::replay::bisect_right([&](int i) { return cdf[i]; }, n_games, s.u_game[b]);
+            if (g >= n_games) g = n_games - 1;
+            s.game_prob[b] = probs[g];
+        } else {
+            g = s.game_len[b];
+        }
+        const int64_t id = oldest_id + g;
+        const int slot = static_cast<int>(id % p.G);
+        game_ids[b] = id;
+        slots[b] = slot;
+        s.game_len[b] = p.length[slot];
+    }
+    __syncthreads();
+    for (int k = t; k < mz::kMtN; k += kSampleThreads) s.mt_key[k] = key[k];
+    if (t == 0) s.mt_pos[0] = pos_s;
+}
+
+// one wavefront per sample: position_probs = priorities / sum(priorities) and choice()'s table for it
+__global__ __launch_bounds__(64) void position_tables_kernel(StoreParams p, SamplerParams s, int lds_rows,
+                                                             const int32_t* __restrict__ slots) {
+    extern __shared__ double lds_dyn[];
+    __shared__ float total_s;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int slot = slots[b];
+    const int n = s.game_len[b];
+    const float* pri = s.priorities + static_cast<size_t>(slot) * p.L;
+    double* row = s.tables + static_cast<size_t>(b) * p.L;
+    double* work = lds_rows ? lds_dyn : row;
+    for (int i = t; i < n; i += 64) work[i] = static_cast<double>(pri[i]);   // (exact both ways)
+    __syncthreads();
+    if (t == 0) total_s = mz::replay::python_sum_f32([&](int i) { return static_cast<float>(work[i]); }, n);
+    __syncthreads();
+    const float total = total_s;
+    for (int i = t; i < n; i += 64) work[i] = static_cast<double>(static_cast<float>(work[i]) / total);
+    __syncthreads();
+    if (t == 0) {
+        double run = 0.0;
+        for (int i = 0; i < n; ++i) {
+            run += work[i];
+            work[i] = run;
+        }
+        s.totals[b] = total;
+    }
+    __syncthreads();
+    const double last = work[n - 1];
+    __syncthreads();
+    for (int i = t; i < n; i += 64) row[i] = work[i] / last;
+}
+
+// One wavefront, every lane in step: the part of a batch whose word positions depend on the draws before them.
+__global__ __launch_bounds__(64) void sample_walk_kernel(StoreParams p, SamplerParams s, int batch, int per, int tail,
+                                                         int lds_tails, int32_t* __restrict__ positions,
+                                                         int32_t* __restrict__ absorbing) {
+    extern __shared__ double lds_dyn[];   // [batch] lengths as i32 behind [batch][tail] table ends
+    __shared__ uint32_t key[mz::kMtN], fresh[mz::kMtN];
+    const int lane = threadIdx.x;
+    const int U = p.unroll, U1 = p.unroll + 1;
+    double* tails = lds_dyn;
+    int32_t* len_s = reinterpret_cast<int32_t*>(lds_dyn + (lds_tails ? static_cast<size_t>(batch) * tail : 0));
+    auto sync = [] { __syncthreads(); };
+    for (int k = lane; k < mz::kMtN; k += 64) key[k] = s.mt_key[k];
+    for (int b = lane; b < batch; b += 64) len_s[b] = s.game_len[b];
+    __syncthreads();
+    // entry j of sample b's tail is table entry max(0, n - U) + j: the positions from which unrolling passes the end
+    auto tail_entry = [&](int b, int j) {
+        const int n = len_s[b];
+        const int i = (n - U > 0 ? n - U : 0) + j;
+        return i < n ? s.tables[static_cast<size_t>(b) * p.L + i] : INFINITY;
+    };
+    if (per && lds_tails)
+        for (int idx = lane; idx < batch * tail; idx += 64) tails[idx] = tail_entry(idx / tail, idx % tail);
+    __syncthreads();
+    int wp = s.mt_pos[0];
+    const uint32_t top_a = static_cast<uint32_t>(p.A) - 1u;
+    const uint32_t mask_a = mz::mask_for(top_a);
+    auto word = [&]() {   // the next word, for every lane
+        if (wp >= mz::kMtN) {
+            twist_parallel(key, fresh, lane, 64, sync);
+            wp = 0;
+        }
+        return mz::mt_temper(key[wp++]);
+    };
+    for (int b = 0; b < batch; ++b) {
+        const int n = len_s[b];
+        int c;   // unrolled steps past the end of the game
+        if (per) {
+            const uint32_t w0 = word(), w1 = word();
+            const double u = mz::replay::uniform_from_words(w0, w1);
+            if (lane == 0) s.u_pos[b] = u;
+            int beyond = 0;   // table entries <= u among the last min(U, n): the position is that far into the tail
+            for (int j0 = 0; j0 < tail; j0 += 64) {
+                const int j = j0 + lane;
+                const bool le = j < tail && (lds_tails ? tails[static_cast<size_t>(b) * tail + j] : tail_entry(b, j)) <= u;
+                beyond += __popcll(__ballot(le));
+            }
+            c = beyond + (U - n > 0 ? U - n : 0);
+        } else {
+            const uint32_t top = static_cast<uint32_t>(n) - 1u;
+            const uint32_t mask = mz::mask_for(top);
+            uint32_t v = 0u;
+            if (top != 0u) do { v = word() & mask; } while (v > top);
+            if (lane == 0) positions[b] = static_cast<int32_t>(v);
+            c = mz::replay::absorbing_steps(static_cast<int>(v), n, U);
+        }
+        if (c > U1) c = U1;
+        int u_next = U1 - c;
+        if (top_a == 0u) c = 0;   // one action: choice() consumes nothing and answers 0 (the rows are zeroed)
+        while (c > 0) {           // masked rejection, up to 64 words per round
+            if (wp >= mz::kMtN) {
+                twist_parallel(key, fresh, lane, 64, sync);
+                wp = 0;
+            }
+            const int avail = mz::kMtN - wp < 64 ? mz::kMtN - wp : 64;
+            const uint32_t v = lane < avail ? (mz::mt_temper(key[wp + lane]) & mask_a) : 0u;
+            const bool ok = lane < avail && v <= top_a;
+            unsigned long long accepted = __ballot(ok);
+            const int k = __popcll(accepted);
+            const int rank = __popcll(accepted & ((1ull << lane) - 1ull));
+            int consumed = avail;
+            if (k >= c) {         // the c-th accepted word ends the sample
+                unsigned long long m = accepted;
+                for (int r = 1; r < c; ++r) m &= m - 1ull;
+                consumed = __ffsll(static_cast<long long>(m));
+            }
+            if (ok && rank < c) absorbing[static_cast<size_t>(b) * U1 + u_next + rank] = static_cast<int32_t>(v);
+            const int took = k < c ? k : c;
+            u_next += took;
+            c -= took;
+            wp += consumed;
+        }
+    }
+    __syncthreads();
+    for (int k = lane; k < mz::kMtN; k += 64) s.mt_key[k] = key[k];
+    if (lane == 0) s.mt_pos[0] = wp;
+}
+
+// positions, importance weights and their maximum: nothing here depends on the stream
+__global__ __launch_bounds__(kSampleThreads) void sample_finish_kernel(StoreParams p, SamplerParams s, int batch,
+                                                                       int64_t total_samples,
+                                                                       const int32_t* __restrict__ slots,
+                                                                       int32_t* __restrict__ positions,
+                                                                       float* __restrict__ weights) {
+    __shared__ float block_max[kSampleThreads];
+    const int t = threadIdx.x;
+    float best = -INFINITY;
+    for (int b = t; b < batch; b += kSampleThreads) {
+        const int n = s.game_len[b];
+        const double* row = s.tables + static_cast<size_t>(b) * p.L;
+        int pos = mz::replay::bisect_right([&](int i) { return row[i]; }, n, s.u_pos[b]);
+        if (pos >= n) pos = n - 1;
+        positions[b] = pos;
+        const float pos_prob = s.priorities[static_cast<size_t>(slots[b]) * p.L + pos] / s.totals[b];
+        const float w = mz::replay::importance_weight(total_samples, s.game_prob[b], pos_prob);
+        weights[b] = w;
+        best = w > best ? w : best;
+    }
+    block_max[t] = best;
+    __syncthreads();
+    for (int half = kSampleThreads / 2; half > 0; half >>= 1) {
+        if (t < half) block_max[t] = block_max[t + half] > block_max[t] ? block_max[t + half] : block_max[t];
+        __syncthreads();
+    }
+    const float top = block_max[0];
+    for (int b = t; b < batch; b += kSampleThreads) weights[b] = weights[b] / top;
+}
+
+// update_priorities, first half: one workgroup per sample writes its row, except where a later sample of the same game
+// covers the position (the reference applies the samples in batch order)
+__global__ __launch_bounds__(128) void update_priorities_kernel(StoreParams p, SamplerParams s, int batch,
+                                                                const int64_t* __restrict__ game_ids,
+                                                                const int32_t* __restrict__ positions,
+                                                                const float* __restrict__ fresh) {
+    extern __shared__ double lds_dyn[];   // [batch] game ids, [batch] positions
+    int64_t* ids = reinterpret_cast<int64_t*>(lds_dyn);
+    int32_t* pos = reinterpret_cast<int32_t*>(ids + batch);
+    const int b = blockIdx.x, U1 = p.unroll + 1;
+    for (int i = threadIdx.x; i < batch; i += blockDim.x) {
+        ids[i] = game_ids[i];
+        pos[i] = positions[i];
+    }
+    __syncthreads();
+    const int64_t id = ids[b];
+    if (id < 0 || pos[b] < 0) return;
+    const int slot = static_cast<int>(id % p.G);
+    if (s.game_id[slot] != id) return;   // the game was removed since its selection
+    const int n = p.length[slot];
+    for (int k = threadIdx.x; k < U1 && pos[b] + k < n; k += blockDim.x)
+        if (mz::replay::update_survives(b, k, batch, U1, [&](int i) { return ids[i]; }, [&](int i) { return pos[i]; }, n))
+            s.priorities[static_cast<size_t>(slot) * p.L + pos[b] + k] = fresh[static_cast<size_t>(b) * U1 + k];
+}
+
+// second half: game_priority = numpy.max(priorities) of every touched game (samples of one game write the same value)
+__global__ __launch_bounds__(64) void game_priority_kernel(StoreParams p, SamplerParams s,
+                                                           const int64_t* __restrict__ game_ids) {
+    __shared__ float lane_max[64];
+    const int64_t id = game_ids[blockIdx.x];
+    if (id < 0) return;
+    const int slot = static_cast<int>(id % p.G);
+    if (s.game_id[slot] != id) return;
+    const int n = p.length[slot];
+    const float* pri = s.priorities + static_cast<size_t>(slot) * p.L;
+    float best = pri[0];
+    for (int i = threadIdx.x; i < n; i += 64) best = mz::replay::numpy_max2(best, pri[i]);
+    lane_max[threadIdx.x] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 64; ++i) best = mz::replay::numpy_max2(best, lane_max[i]);
+        s.game_priority[slot] = best;
+    }
+}
+
+// mzreplay_add_games with the sampler on: the new games' priorities, game priorities and ids into the sampler's arrays
+__global__ __launch_bounds__(256) void adopt_games_kernel(StoreParams p, SamplerParams s, int n_new, int64_t first_id,
+                                                          const int32_t* __restrict__ slots,
+                                                          const float* __restrict__ priorities,
+                                                          const float* __restrict__ game_priority) {
+    const int g = blockIdx.x;
+    const int slot = slots[g];
+    for (int later = g + 1; later < n_new; ++later)
+        if (slots[later] == slot) return;   // overwritten within this call
+    for (int i = threadIdx.x; i < p.L; i += blockDim.x)
+        s.priorities[static_cast<size_t>(slot) * p.L + i] = priorities[static_cast<size_t>(g) * p.L + i];
+    if (threadIdx.x == 0) {
+        s.game_priority[slot] = game_priority[g];
+        s.game_id[slot] = first_id + g;
+    }
 }
 
 }  // namespace
@@ -186,6 +579,10 @@ struct mzreplay {
     float* d_priorities = nullptr;
     float* d_game_priority = nullptr;
     size_t staging_games = 0, staging_batch = 0;
+    bool sampler_on = false;
+    SamplerParams sp{};
+    int64_t next_game_id = 0;        // id of the next game mzreplay_add_games stores (sampler on)
+    size_t sampler_batch = 0;        // samples the per-batch scratch holds
 };
 
 namespace {
@@ -320,6 +717,12 @@ int mzreplay_add_games(mzreplay* s, int32_t n, const int32_t* slots, const int32
     RP_HIP(s, hipMemcpyAsync(s->d_slots, slots, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream));
     priorities_kernel<<<dim3(n), dim3(256), 0, stream>>>(s->p, s->d_slots, s->d_priorities, s->d_game_priority);
     RP_HIP(s, hipGetLastError());
+    if (s->sampler_on) {
+        adopt_games_kernel<<<dim3(n), dim3(256), 0, stream>>>(s->p, s->sp, n, s->next_game_id, s->d_slots, s->d_priorities,
+                                                             s->d_game_priority);
+        RP_HIP(s, hipGetLastError());
+        s->next_game_id += n;
+    }
     if (priorities)
         RP_HIP(s, hipMemcpyAsync(priorities, s->d_priorities, sizeof(float) * n * L, hipMemcpyDeviceToHost, stream));
     if (game_priority)
@@ -370,8 +773,177 @@ int mzreplay_make_batch(mzreplay* s, int32_t batch, const int32_t* slots, const 
     RP_HIP(s, hipMemcpyAsync(s->d_positions, positions, sizeof(int32_t) * batch, hipMemcpyHostToDevice, stream));
     RP_HIP(s, hipMemcpyAsync(d_slots, slots, sizeof(int32_t) * batch, hipMemcpyHostToDevice, stream));
     RP_HIP(s, hipMemcpyAsync(s->d_absorbing, absorbing_actions, sizeof(int32_t) * batch * U1, hipMemcpyHostToDevice, stream));
-    make_batch_kernel<<<dim3(batch), dim3(128), 0, stream>>>(s->p, d_slots, s->d_positions, s->d_absorbing, observations,
+    make_batch_kernel<double><<<dim3(batch), dim3(128), 0, stream>>>(s->p, d_slots, s->d_positions, s->d_absorbing, observations,
                                                             actions, values, rewards, policies, gradient_scale);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+// ---- the sampler's entries ---------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kLdsBudget = 144 * 1024;   // of the 160 KB of a CU, beside the kernels' static arrays (11 KB)
+
+int sampler_ready(mzreplay* s, const char* who) {
+    if (!s) return fail(s, std::string(who) + ": null store");
+    if (!s->sampler_on) return fail(s, std::string(who) + ": call mzreplay_sampler_enable first");
+    return 0;
+}
+
+int grow_batch_scratch(mzreplay* s, size_t batch) {
+    if (batch <= s->sampler_batch) return 0;
+    SamplerParams& sp = s->sp;
+    if (dev_alloc(s, &sp.game_len, batch) || dev_alloc(s, &sp.game_prob, batch) || dev_alloc(s, &sp.u_game, batch) ||
+        dev_alloc(s, &sp.u_pos, batch) || dev_alloc(s, &sp.totals, batch) ||
+        dev_alloc(s, &sp.tables, batch * static_cast<size_t>(s->p.L)))
+        return -1;
+    s->sampler_batch = batch;
+    return 0;
+}
+}  // namespace
+
+int mzreplay_sampler_enable(mzreplay* s, uint32_t seed, int64_t next_game_id) {
+    if (!s) return fail(s, "mzreplay_sampler_enable: null store");
+    if (next_game_id < 0) return fail(s, "mzreplay_sampler_enable: negative game id");
+    if (!s->sampler_on) {
+        SamplerParams& sp = s->sp;
+        const size_t G = s->p.G, L = s->p.L;
+        if (dev_alloc(s, &sp.priorities, G * L) || dev_alloc(s, &sp.game_priority, G) || dev_alloc(s, &sp.game_id, G) ||
+            dev_alloc(s, &sp.mt_key, static_cast<size_t>(mz::kMtN)) || dev_alloc(s, &sp.mt_pos, 1) ||
+            dev_alloc(s, &sp.probs, G) || dev_alloc(s, &sp.cdf, G))
+            return -1;
+        RP_HIP(s, hipMemset(sp.game_id, 0xff, sizeof(int64_t) * G));   // -1: empty slots
+        sp.lds_games = G * (sizeof(double) + sizeof(float)) <= kLdsBudget ? 1 : 0;
+        RP_HIP(s, hipFuncSetAttribute(reinterpret_cast<const void*>(sample_games_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        RP_HIP(s, hipFuncSetAttribute(reinterpret_cast<const void*>(position_tables_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        RP_HIP(s, hipFuncSetAttribute(reinterpret_cast<const void*>(sample_walk_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBudget)));
+        s->sampler_on = true;
+    }
+    s->next_game_id = next_game_id;
+    uint32_t key[mz::kMtN];
+    int32_t pos;
+    mz::mt_seed(key, &pos, seed);   // numpy.random.seed(seed)
+    return mzreplay_sampler_set_rng(s, key, pos);
+}
+
+int mzreplay_sampler_set_rng(mzreplay* s, const uint32_t* key, int32_t pos) {
+    if (sampler_ready(s, "mzreplay_sampler_set_rng")) return -1;
+    if (!key || pos < 0 || pos > mz::kMtN) return fail(s, "mzreplay_sampler_set_rng: bad state");
+    RP_HIP(s, hipDeviceSynchronize());
+    RP_HIP(s, hipMemcpy(s->sp.mt_key, key, sizeof(uint32_t) * mz::kMtN, hipMemcpyHostToDevice));
+    RP_HIP(s, hipMemcpy(s->sp.mt_pos, &pos, sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int mzreplay_sampler_get_rng(mzreplay* s, uint32_t* key, int32_t* pos) {
+    if (sampler_ready(s, "mzreplay_sampler_get_rng")) return -1;
+    if (!key || !pos) return fail(s, "mzreplay_sampler_get_rng: null argument");
+    RP_HIP(s, hipDeviceSynchronize());
+    RP_HIP(s, hipMemcpy(key, s->sp.mt_key, sizeof(uint32_t) * mz::kMtN, hipMemcpyDeviceToHost));
+    RP_HIP(s, hipMemcpy(pos, s->sp.mt_pos, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mzreplay_set_priorities(mzreplay* s, int32_t slot, int64_t game_id, const float* priorities, int32_t length,
+                            void* stream_) {
+    if (sampler_ready(s, "mzreplay_set_priorities")) return -1;
+    if (!priorities || slot < 0 || slot >= s->p.G || length < 1 || length > s->p.L || game_id < 0)
+        return fail(s, "mzreplay_set_priorities: bad argument");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    std::vector<float> row(static_cast<size_t>(s->p.L), 0.f);
+    float top = priorities[0];
+    for (int i = 0; i < length; ++i) {
+        row[i] = priorities[i];
+        top = mz::replay::numpy_max2(top, priorities[i]);
+    }
+    RP_HIP(s, hipMemcpyAsync(s->sp.priorities + static_cast<size_t>(slot) * s->p.L, row.data(), sizeof(float) * s->p.L,
+                             hipMemcpyHostToDevice, stream));
+    RP_HIP(s, hipMemcpyAsync(s->sp.game_priority + slot, &top, sizeof(float), hipMemcpyHostToDevice, stream));
+    RP_HIP(s, hipMemcpyAsync(s->sp.game_id + slot, &game_id, sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int mzreplay_get_priorities(mzreplay* s, int32_t slot, float* priorities, float* game_priority, int64_t* game_id,
+                            void* stream_) {
+    if (sampler_ready(s, "mzreplay_get_priorities")) return -1;
+    if (slot < 0 || slot >= s->p.G) return fail(s, "mzreplay_get_priorities: bad slot");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (priorities)
+        RP_HIP(s, hipMemcpyAsync(priorities, s->sp.priorities + static_cast<size_t>(slot) * s->p.L, sizeof(float) * s->p.L,
+                                 hipMemcpyDeviceToHost, stream));
+    if (game_priority)
+        RP_HIP(s, hipMemcpyAsync(game_priority, s->sp.game_priority + slot, sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (game_id) RP_HIP(s, hipMemcpyAsync(game_id, s->sp.game_id + slot, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int mzreplay_sample_batch(mzreplay* s, int32_t batch, int64_t oldest_game_id, int32_t n_games, int64_t total_samples,
+                          int32_t per, int64_t* game_ids, int32_t* slots, int32_t* positions, int32_t* absorbing_actions,
+                          float* weights, void* stream_) {
+    if (sampler_ready(s, "mzreplay_sample_batch")) return -1;
+    if (!game_ids || !slots || !positions || !absorbing_actions || (per && !weights))
+        return fail(s, "mzreplay_sample_batch: null argument");
+    const StoreParams& p = s->p;
+    if (batch <= 0 || batch > 4096) return fail(s, "mzreplay_sample_batch: batch must be 1..4096");
+    if (n_games < 1 || n_games > p.G || oldest_game_id < 0 || total_samples < 1)
+        return fail(s, "mzreplay_sample_batch: no stored games, or more than the capacity");
+    if (grow_batch_scratch(s, static_cast<size_t>(batch))) return -1;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const SamplerParams& sp = s->sp;
+    const size_t U1 = static_cast<size_t>(p.unroll) + 1;
+    RP_HIP(s, hipMemsetAsync(absorbing_actions, 0, sizeof(int32_t) * batch * U1, stream));
+    const size_t games_lds = sp.lds_games ? static_cast<size_t>(p.G) * (sizeof(double) + sizeof(float)) : 0;
+    sample_games_kernel<<<dim3(1), dim3(kSampleThreads), games_lds, stream>>>(p, sp, batch, oldest_game_id, n_games,
+                                                                             per ? 1 : 0, game_ids, slots);
+    RP_HIP(s, hipGetLastError());
+    const int tail = p.unroll < p.L ? p.unroll : p.L;
+    int lds_tails = 0;
+    if (per) {
+        const int lds_rows = sizeof(double) * static_cast<size_t>(p.L) <= kLdsBudget ? 1 : 0;
+        position_tables_kernel<<<dim3(batch), dim3(64), lds_rows ? sizeof(double) * p.L : 0, stream>>>(p, sp, lds_rows, slots);
+        RP_HIP(s, hipGetLastError());
+        lds_tails = sizeof(double) * static_cast<size_t>(batch) * tail + sizeof(int32_t) * batch <= kLdsBudget ? 1 : 0;
+    }
+    const size_t walk_lds = (lds_tails ? sizeof(double) * static_cast<size_t>(batch) * tail : 0) + sizeof(int32_t) * batch;
+    sample_walk_kernel<<<dim3(1), dim3(64), walk_lds, stream>>>(p, sp, batch, per ? 1 : 0, tail, lds_tails, positions,
+                                                               absorbing_actions);
+    RP_HIP(s, hipGetLastError());
+    if (per) {
+        sample_finish_kernel<<<dim3(1), dim3(kSampleThreads), 0, stream>>>(p, sp, batch, total_samples, slots, positions,
+                                                                          weights);
+        RP_HIP(s, hipGetLastError());
+    }
+    return 0;
+}
+
+int mzreplay_make_batch_device(mzreplay* s, int32_t batch, const int32_t* slots, const int32_t* positions,
+                               const int32_t* absorbing_actions, float* observations, int64_t* actions, float* values,
+                               float* rewards, float* policies, float* gradient_scale, void* stream_) {
+    if (!s || !slots || !positions || !absorbing_actions || !observations || !actions || !values || !rewards || !policies ||
+        !gradient_scale)
+        return fail(s, "mzreplay_make_batch_device: null argument");
+    if (batch <= 0) return 0;
+    make_batch_kernel<float><<<dim3(batch), dim3(128), 0, static_cast<hipStream_t>(stream_)>>>(
+        s->p, slots, positions, absorbing_actions, observations, actions, values, rewards, policies, gradient_scale);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+int mzreplay_update_priorities(mzreplay* s, int32_t batch, const int64_t* game_ids, const int32_t* positions,
+                               const float* priorities, void* stream_) {
+    if (sampler_ready(s, "mzreplay_update_priorities")) return -1;
+    if (!game_ids || !positions || !priorities) return fail(s, "mzreplay_update_priorities: null argument");
+    if (batch <= 0) return 0;
+    if (batch > 4096) return fail(s, "mzreplay_update_priorities: batch must be 1..4096");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    update_priorities_kernel<<<dim3(batch), dim3(128), (sizeof(int64_t) + sizeof(int32_t)) * batch, stream>>>(
+        s->p, s->sp, batch, game_ids, positions, priorities);
+    RP_HIP(s, hipGetLastError());
+    game_priority_kernel<<<dim3(batch), dim3(64), 0, stream>>>(s->p, s->sp, game_ids);
     RP_HIP(s, hipGetLastError());
     return 0;
 }

@@ -7,6 +7,11 @@ absorbing states, drawn in the reference's order from a numpy-compatible legacy 
 config.seed (the reference seeds numpy's global stream in the buffer's own process, replay_buffer.py:31).
 Sampling reads the priorities, which are mirrored on the host (a few floats per game).
 
+With `device_sampling=True` the sampling moves to the device as well (include/mzreplay.h mzreplay_sample_batch,
+csrc/replay_sampler.h): priorities, game priorities and a numpy stream of its own live in the store, `get_batch` queues
+the sampler and the target kernels and returns without waiting, and `update_priorities` takes the trainer's device
+tensor -- draw for draw what the host path returns.
+
 Not carried over: Ray (`.remote`), `get_buffer()`'s live GameHistory objects are only kept when games
 arrive as GameHistory (save_game), and `update_game_history` (Reanalyse).
 """
@@ -26,8 +31,50 @@ class MzReplayConfig(ctypes.Structure):
                [("per_alpha", ctypes.c_double), ("discount_powers", ctypes.c_void_p)]
 
 
+class DeviceIndexBatch:
+    """index_batch of a device-sampled batch: game_ids i64[B], positions i32[B] (and the slots the targets were read
+    from) as CUDA tensors.  `tolist()` gives the reference's list of [game_id, game_pos] pairs, waiting for the device."""
+
+    def __init__(self, game_ids, slots, positions):
+        self.game_ids, self.slots, self.positions = game_ids, slots, positions
+
+    def __len__(self):
+        return int(self.game_ids.shape[0])
+
+    def tolist(self):
+        return [list(pair) for pair in zip(self.game_ids.tolist(), self.positions.tolist())]
+
+
+class _DeviceEntry(dict):
+    """A buffer entry whose priorities live in the store: "priorities" / "game_priority" are downloaded when asked for,
+    assigning "priorities" uploads them (the game priority follows as their maximum)."""
+
+    def __init__(self, owner, game_id, **fields):
+        super().__init__(**fields)
+        self._owner, self._game_id = owner, game_id
+
+    def __getitem__(self, key):
+        if key == "priorities":
+            return self._owner.download_priorities(self._game_id)[0]
+        if key == "game_priority":
+            return self._owner.download_priorities(self._game_id)[1]
+        return super().__getitem__(key)
+
+    def __setitem__(self, key, value):
+        if key == "priorities":
+            self._owner.load_priorities(self._game_id, value)
+        elif key == "game_priority":
+            raise KeyError("the game priority of a device-sampled buffer is the maximum of the priorities it holds")
+        else:
+            super().__setitem__(key, value)
+
+
 class ReplayBuffer:
-    def __init__(self, initial_checkpoint, initial_buffer, config, device=None):
+    def __init__(self, initial_checkpoint, initial_buffer, config, device=None, device_sampling=False):
+        """device_sampling=True: get_batch / update_priorities run on the device (see the module docstring).  Batch
+        sampling then has a stream of its own, seeded with config.seed; sample_game / sample_position (Reanalyse and
+        other host callers) keep drawing from the host generator -- as in the reference, where Reanalyse is another
+        process with its own numpy stream."""
         if not torch.cuda.is_available():
             raise RuntimeError("the device replay store needs a HIP device (there is no CPU fallback)")
         self.config = config
@@ -53,6 +100,11 @@ class ReplayBuffer:
             raise RuntimeError(self._lib.mzreplay_last_error(None).decode())
         self._h = handle
         self.rng = _native.HostRng(config.seed)           # numpy.random.seed(self.config.seed)
+        self.device_sampling = bool(device_sampling)
+        if self.device_sampling:
+            if list(config.action_space) != list(range(self.A)):
+                raise NotImplementedError("device sampling draws absorbing actions as indices: action_space must be range(A)")
+            self._check(self._lib.mzreplay_sampler_enable(self._h, int(config.seed) & 0xFFFFFFFF, int(self.num_played_games)))
         self.buffer = {}                                  # game_id -> dict(length, priorities, game_priority[, history])
         for game_history in (initial_buffer or {}).values():
             self.save_game(game_history)
@@ -127,7 +179,13 @@ class ReplayBuffer:
         for g in range(n_games):
             n = int(lengths[g])
             entry = dict(length=n, history=histories[g])
-            if self.config.PER:
+            if self.device_sampling:
+                entry = _DeviceEntry(self, self.num_played_games, length=n, history=histories[g])
+                given = getattr(histories[g], "priorities", None) if histories[g] is not None else None
+                if self.config.PER and given is not None:
+                    self.buffer[self.num_played_games] = entry
+                    self.load_priorities(self.num_played_games, given)
+            elif self.config.PER:
                 given = getattr(histories[g], "priorities", None) if histories[g] is not None else None
                 entry["priorities"] = numpy.copy(given) if given is not None else pri[g, :n].copy()
                 entry["game_priority"] = numpy.max(entry["priorities"]) if given is not None else game_pri[g]
@@ -181,8 +239,82 @@ class ReplayBuffer:
             position_index = self.rng.choice(entry["length"])
         return position_index, position_prob
 
+    # ---- the sampler's state (device_sampling=True) ---------------------------------------------------
+    def load_priorities(self, game_id, priorities):
+        """Priorities of a stored game given by the caller (float32 [length]); its game priority becomes their maximum."""
+        pri = numpy.ascontiguousarray(priorities, dtype=numpy.float32)
+        assert len(pri) == dict.__getitem__(self.buffer[game_id], "length")
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_set_priorities(self._h, self._slot(game_id), int(game_id), ptr(pri, c_f32_p),
+                                                          len(pri), self._stream()))
+
+    def download_priorities(self, game_id):
+        """(priorities float32 [length], game priority) of a stored game, read from the device (waits for it)."""
+        row = numpy.zeros(self.L, dtype=numpy.float32)
+        game_priority, stored_id = ctypes.c_float(), ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_get_priorities(self._h, self._slot(game_id), ptr(row, c_f32_p),
+                                                          ctypes.byref(game_priority), ctypes.byref(stored_id), self._stream()))
+        assert stored_id.value == game_id, "the slot holds another game"
+        return row[: dict.__getitem__(self.buffer[game_id], "length")].copy(), numpy.float32(game_priority.value)
+
+    def sampler_state(self):
+        """The batch sampler's stream as numpy.random.get_state() gives it."""
+        key = numpy.zeros(624, dtype=numpy.uint32)
+        pos = ctypes.c_int32()
+        self._check(self._lib.mzreplay_sampler_get_rng(self._h, ptr(key, _native.c_u32_p), ctypes.byref(pos)))
+        return ("MT19937", key, pos.value, 0, 0.0)
+
+    def set_sampler_state(self, state):
+        key = numpy.ascontiguousarray(state[1], dtype=numpy.uint32)
+        self._check(self._lib.mzreplay_sampler_set_rng(self._h, ptr(key, _native.c_u32_p), int(state[2])))
+
+    def _get_batch_device(self, out=None):
+        B, dev = int(self.config.batch_size), self.device
+        stacked = int(self.config.stacked_observations)
+        game_ids = torch.empty(B, dtype=torch.int64, device=dev)
+        slots = torch.empty(B, dtype=torch.int32, device=dev)
+        positions = torch.empty(B, dtype=torch.int32, device=dev)
+        absorbing = torch.empty((B, self.U1), dtype=torch.int32, device=dev)
+        if out is None:
+            out = dict(observations=torch.empty((B, self.C + stacked * (self.C + 1), self.H, self.W), dtype=torch.float32, device=dev),
+                       actions=torch.empty((B, self.U1), dtype=torch.int64, device=dev),
+                       values=torch.empty((B, self.U1), dtype=torch.float32, device=dev),
+                       rewards=torch.empty((B, self.U1), dtype=torch.float32, device=dev),
+                       policies=torch.empty((B, self.U1, self.A), dtype=torch.float32, device=dev),
+                       weights=torch.empty(B, dtype=torch.float32, device=dev) if self.config.PER else None,
+                       gradient_scales=torch.empty((B, self.U1), dtype=torch.float32, device=dev))
+        for key, dtype, count in (("observations", torch.float32, B * (self.C + stacked * (self.C + 1)) * self.H * self.W),
+                                  ("actions", torch.int64, B * self.U1), ("values", torch.float32, B * self.U1),
+                                  ("rewards", torch.float32, B * self.U1), ("policies", torch.float32, B * self.U1 * self.A),
+                                  ("gradient_scales", torch.float32, B * self.U1)) + \
+                ((("weights", torch.float32, B),) if self.config.PER else ()):
+            t = out[key]
+            if not (t.is_cuda and t.dtype == dtype and t.numel() == count and t.is_contiguous()):
+                raise ValueError(f"get_batch(out=...): {key} must be a contiguous {dtype} CUDA tensor of {count} elements")
+        weights = out["weights"] if self.config.PER else None
+        with torch.cuda.device(dev):
+            self._check(self._lib.mzreplay_sample_batch(
+                self._h, B, self.num_played_games - len(self.buffer), len(self.buffer), int(self.total_samples),
+                1 if self.config.PER else 0, game_ids.data_ptr(), slots.data_ptr(), positions.data_ptr(),
+                absorbing.data_ptr(), weights.data_ptr() if weights is not None else None, self._stream()))
+            self._check(self._lib.mzreplay_make_batch_device(
+                self._h, B, slots.data_ptr(), positions.data_ptr(), absorbing.data_ptr(), out["observations"].data_ptr(),
+                out["actions"].data_ptr(), out["values"].data_ptr(), out["rewards"].data_ptr(), out["policies"].data_ptr(),
+                out["gradient_scales"].data_ptr(), self._stream()))
+        return DeviceIndexBatch(game_ids, slots, positions), (out["observations"], out["actions"], out["values"], out["rewards"],
+                                                             out["policies"], weights, out["gradient_scales"])
+
     # ---- get_batch (replay_buffer.py:67-133) -----------------------------------------------------------
-    def get_batch(self):
+    def get_batch(self, out=None):
+        """(index_batch, batch).  Host sampling: the reference's list of pairs and fp64 device targets.  Device sampling:
+        a DeviceIndexBatch and float32 / int64 CUDA tensors, queued on the current stream without waiting; `out` (a dict
+        with the trainer's keys: observations, actions, values, rewards, policies, weights, gradient_scales) receives
+        them in place."""
+        if self.device_sampling:
+            return self._get_batch_device(out)
+        if out is not None:
+            raise ValueError("get_batch(out=...) needs device_sampling=True")
         B = self.config.batch_size
         index_batch, weight_batch = [], [] if self.config.PER else None
         slots = numpy.zeros(B, dtype=numpy.int32)
@@ -251,6 +383,19 @@ class ReplayBuffer:
 
     # ---- priorities (replay_buffer.py:197-220) ---------------------------------------------------------
     def update_priorities(self, priorities, index_info):
+        if self.device_sampling:
+            dev = self.device
+            if not isinstance(index_info, DeviceIndexBatch):
+                pairs = numpy.asarray(index_info, dtype=numpy.int64).reshape(-1, 2)
+                index_info = DeviceIndexBatch(torch.from_numpy(pairs[:, 0].copy()).to(dev), None,
+                                              torch.from_numpy(pairs[:, 1].astype(numpy.int32)).to(dev))
+            pri = torch.as_tensor(priorities, dtype=torch.float32, device=dev).contiguous()
+            assert pri.shape == (len(index_info), self.U1), "priorities: [batch, num_unroll_steps + 1]"
+            with torch.cuda.device(dev):
+                self._check(self._lib.mzreplay_update_priorities(self._h, len(index_info), index_info.game_ids.data_ptr(),
+                                                                 index_info.positions.data_ptr(), pri.data_ptr(),
+                                                                 self._stream()))
+            return
         for i in range(len(index_info)):
             game_id, game_pos = index_info[i]
             if next(iter(self.buffer)) <= game_id:

@@ -141,11 +141,16 @@ class Trainer:
             time.sleep(0.1)
         done = 0
         while self.training_step < self.config.training_steps and not shared_storage.get_info("terminate"):
-            index_batch, batch = replay_buffer.get_batch()
-            self.update_lr()
-            priorities, total_loss, value_loss, reward_loss, policy_loss = self.update_weights(batch)
-            if self.config.PER:
-                replay_buffer.update_priorities(priorities, index_batch)
+            if getattr(replay_buffer, "device_sampling", False):
+                # one host synchronisation per step here (the losses are published after every step, as in the
+                # reference); callers that want none between checkpoints call train_steps(replay_buffer, n) themselves
+                total_loss, value_loss, reward_loss, policy_loss = self.train_steps(replay_buffer, 1)
+            else:
+                index_batch, batch = replay_buffer.get_batch()
+                self.update_lr()
+                priorities, total_loss, value_loss, reward_loss, policy_loss = self.update_weights(batch)
+                if self.config.PER:
+                    replay_buffer.update_priorities(priorities, index_batch)
             if self.training_step % self.config.checkpoint_interval == 0:
                 shared_storage.set_info({"weights": copy.deepcopy(self.model.get_weights()),
                                          "optimizer_state": self.optimizer_state()})
@@ -163,6 +168,52 @@ class Trainer:
                 while (self.training_step / max(1, shared_storage.get_info("num_played_steps")) > self.config.ratio
                        and self.training_step < self.config.training_steps and not shared_storage.get_info("terminate")):
                     time.sleep(0.5)
+
+    def train_steps(self, replay_buffer, n):
+        """`n` training steps on a device-sampling replay buffer (ReplayBuffer(device_sampling=True)): get_batch ->
+        update_lr -> step -> update_priorities, queued back to back on the current stream with no synchronisation in
+        between; in graph mode the batch is written straight into the capture's static buffers.  Returns the last step's
+        (total, value, reward, policy) losses, read back with one synchronisation at the end."""
+        if not getattr(replay_buffer, "device_sampling", False):
+            raise ValueError("train_steps needs a ReplayBuffer(device_sampling=True)")
+        device = next(self.model.parameters()).device
+        if device.type != "cuda":
+            raise NotImplementedError("train_steps queues HIP work: the model must be on the GPU")
+        report = None
+        for _ in range(int(n)):
+            if self._graph_mode and self._graph is not None:
+                index_batch, _batch = replay_buffer.get_batch(out=self._static)
+                b = None
+            else:
+                index_batch, (obs, act, val, rew, pol, weights, scales) = replay_buffer.get_batch()
+                b = {"observations": obs, "actions": act.unsqueeze(-1), "values": val, "rewards": rew, "policies": pol,
+                     "weights": weights if self.config.PER else None, "gradient_scales": scales}
+            self.update_lr()
+            if self._graph_mode:
+                if self._graph is None:
+                    self._capture(b)
+                    for key, value in b.items():
+                        if value is not None:
+                            self._static[key].copy_(value)
+                self._graph.replay()
+                report, priorities = self._graph_out
+            else:
+                steps = self._unroll(b["observations"], b["actions"])
+                sample_loss, head_sums, priorities = _UnrollLoss.apply(
+                    torch.stack([s[0] for s in steps]), torch.stack([s[1] for s in steps]),
+                    torch.stack([s[2] for s in steps]), b, self.config.support_size, self.config.value_loss_weight,
+                    self.config.PER_alpha)
+                loss = sample_loss.mean()
+                self.optimizer.zero_grad()
+                loss.backward()
+                self.optimizer.step()
+                report = torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)])
+            self.training_step += 1
+            if self.config.PER:
+                replay_buffer.update_priorities(priorities, index_batch)
+        if report is None:
+            return None
+        return tuple(report.tolist())
 
     # ---- one training step (trainer.py:124-268) ---------------------------------------------------------
     def _batch_on_device(self, batch):
@@ -260,34 +311,7 @@ class Trainer:
         stream capture requires), captures it on static copies of the batch, and every call copies its batch in,
         replays, and reads loss / head sums / priorities out of the capture's output tensors."""
         if self._graph is None:
-            self._static = {k: (v.clone() if v is not None else None) for k, v in b.items()}
-            side = torch.cuda.Stream(device=b["values"].device)
-            side.wait_stream(torch.cuda.current_stream(b["values"].device))
-            state = (copy.deepcopy(self.model.state_dict()), copy.deepcopy(self.optimizer.state_dict()))
-            with torch.cuda.stream(side):
-                for _ in range(3):                       # warm-up steps, undone below
-                    self.optimizer.zero_grad(set_to_none=True)
-                    self._loss_native(self._static)[0].mean().backward()
-                    self.optimizer.step()
-            torch.cuda.current_stream(b["values"].device).wait_stream(side)
-            self.model.load_state_dict(state[0])
-            # the optimizer's moments and step counters must exist BEFORE the capture (created inside it they would be
-            # re-initialised by every replay): keep the tensors the warm-up made, put the saved values back in place
-            live = self.optimizer.state_dict()["state"]
-            for index, entry in live.items():
-                saved = state[1]["state"].get(index)
-                for name, value in entry.items():
-                    if torch.is_tensor(value):
-                        value.copy_(saved[name]) if saved is not None else value.zero_()
-            self.optimizer.zero_grad(set_to_none=True)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                sample_loss, head_sums, priorities = self._loss_native(self._static)
-                loss = sample_loss.mean()
-                loss.backward()
-                self.optimizer.step()
-                self._graph_out = (torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)]), priorities)
-            # (the capture itself does not execute the step)
+            self._capture(b)
         for key, value in b.items():
             if value is not None:
                 self._static[key].copy_(value)
@@ -295,6 +319,37 @@ class Trainer:
         self.training_step += 1
         report = self._graph_out[0].tolist()
         return (self._graph_out[1].cpu().numpy(), report[0], report[1], report[2], report[3])
+
+    def _capture(self, b):
+        """Warm the step up on a side stream and capture it on static copies of the batch `b` (not executed)."""
+        self._static = {k: (v.clone() if v is not None else None) for k, v in b.items()}
+        side = torch.cuda.Stream(device=b["values"].device)
+        side.wait_stream(torch.cuda.current_stream(b["values"].device))
+        state = (copy.deepcopy(self.model.state_dict()), copy.deepcopy(self.optimizer.state_dict()))
+        with torch.cuda.stream(side):
+            for _ in range(3):                       # warm-up steps, undone below
+                self.optimizer.zero_grad(set_to_none=True)
+                self._loss_native(self._static)[0].mean().backward()
+                self.optimizer.step()
+        torch.cuda.current_stream(b["values"].device).wait_stream(side)
+        self.model.load_state_dict(state[0])
+        # the optimizer's moments and step counters must exist BEFORE the capture (created inside it they would be
+        # re-initialised by every replay): keep the tensors the warm-up made, put the saved values back in place
+        live = self.optimizer.state_dict()["state"]
+        for index, entry in live.items():
+            saved = state[1]["state"].get(index)
+            for name, value in entry.items():
+                if torch.is_tensor(value):
+                    value.copy_(saved[name]) if saved is not None else value.zero_()
+        self.optimizer.zero_grad(set_to_none=True)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            sample_loss, head_sums, priorities = self._loss_native(self._static)
+            loss = sample_loss.mean()
+            loss.backward()
+            self.optimizer.step()
+            self._graph_out = (torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)]), priorities)
+        # (the capture itself does not execute the step)
 
     def update_lr(self):
         lr = self.config.lr_init * self.config.lr_decay_rate ** (self.training_step / self.config.lr_decay_steps)

@@ -4,7 +4,10 @@ device replay store -> Trainer -> weights published back into the actor's flat b
 weights.  Not a benchmark: it shows that the pieces learn together (the reference's README curve reaches
 ~420 reward after ~2000 training steps with one worker).
 
-    python tools/train_cartpole.py [--envs 64] [--iterations 30] [--moves 8] [--train-steps 100]
+    python tools/train_cartpole.py [--envs 64] [--iterations 30] [--moves 8] [--train-steps 100] [--device-sampling]
+
+--device-sampling: replay batches are drawn on the device and an iteration's training steps are queued without a host
+round trip (Trainer.train_steps); the log is the host-sampling run's, line for line, except the seconds.
 """
 import argparse
 import importlib
@@ -28,6 +31,8 @@ def main():
     ap.add_argument("--train-steps", type=int, default=100, help="training steps per iteration")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eager-trainer", action="store_true", help="launch the training step op by op instead of as one hipGraph replay")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="sample replay batches on the device; an iteration's training steps run as Trainer.train_steps")
     args = ap.parse_args()
     sp = importlib.import_module("muzero-hypermodel_amd.self_play")
     rb_mod = importlib.import_module("muzero-hypermodel_amd.replay_buffer")
@@ -40,7 +45,8 @@ def main():
     weights = models.MuZeroNetwork(config).get_weights()
     actor = sp.DeviceSelfPlay({"weights": weights}, "cartpole", config, args.seed, args.envs)
     actor.engine.set_fused_options("auto", publish_tree=False)
-    replay = rb_mod.ReplayBuffer({"num_played_games": 0, "num_played_steps": 0}, {}, config)
+    replay = rb_mod.ReplayBuffer({"num_played_games": 0, "num_played_steps": 0}, {}, config,
+                                 device_sampling=args.device_sampling)
     trainer = tr_mod.Trainer({"weights": weights, "training_step": 0, "optimizer_state": None}, config, device="cuda",
                                 graph=not args.eager_trainer)   # the step as one hipGraph replay
     flat = actor.engine._fc_flat                     # the buffer the actor's network (and the fused kernel) alias
@@ -56,7 +62,10 @@ def main():
         temperature = config.visit_softmax_temperature_fn(trainer.training_step)
         actor.play_moves(args.moves, temperature, on_games=on_games)
         losses = None
-        if replay.num_played_games > 0:
+        if replay.num_played_games > 0 and args.device_sampling:
+            losses = list(trainer.train_steps(replay, args.train_steps))
+            trainer.publish(flat)
+        elif replay.num_played_games > 0:
             for _ in range(args.train_steps):
                 index_batch, batch = replay.get_batch()
                 trainer.update_lr()
