@@ -576,6 +576,48 @@ int mzmcts_set_device_temperatures(mzmcts_engine *engine, int32_t enabled);
 int mzmcts_device_select_action(const uint32_t *seeds, int32_t n_streams, const int32_t *visits, int32_t n,
                                 const double *temperature, int32_t draws, int32_t *slots_out, uint32_t *words_out);
 
+/* ---- the narrow kernels' cut-down arithmetic against the plain forms (csrc/device_checks.hip) ----------
+ * csrc/narrow_device.h replaces library calls by the instruction sequences their operands need and states that the
+ * results keep the library's bits.  Blocking self-check: the GPU evaluates the short form and the plain form side by side
+ * on `count` operands -- operand i is built from the pattern first + i -- and reduces on the device:
+ *   *mismatches_out   operands on which the check's statement fails;
+ *   first_bad_out[8]  patterns of such operands ([0] the smallest, [1..7] others; 0 beyond *mismatches_out);
+ *   *worst_out        the largest distance to a float64 evaluation met (unit per check, below).
+ * which                 pattern                          statement, distance
+ *   _EXP                float32 bits                     exp_nonpositive(x) has expf(x)'s bits (defined for x <= 0; NaNs are
+ *                                                        skipped); distance to float64 exp in float32 ulps
+ *   _RECIPROCAL         float32 bits                     reciprocal_of_sum(d) has (1.0f / d)'s bits (defined for 1 <= d <= 32);
+ *                                                        distance to the float64 quotient in float32 ulps (<= 0.5: correctly
+ *                                                        rounded)
+ *   _INVERSE_TRANSFORM  float32 bits                     inverse_value_transform_narrow(x, inverse_transform_reciprocal()) has
+ *                                                        inverse_value_transform(x)'s bits (defined for |x| <= 16); absolute
+ *                                                        distance to the float64 formula divided by sqrt(|value| + 1)
+ *   _QUOTIENT           case index < 32768 * 2 * 803 * 4 quotient_with(n, d, refined_reciprocal(d)) has (n / d)'s bits: d = 1 +
+ *                                                        index % 32768, n = +-m 2^e, e = -401 .. 401, m all zeros / all ones /
+ *                                                        seeded; distance between the two forms in float64 ulps
+ *   _NORMALIZED         seeded case index < 2^40         normalized_value / normalized_pair, short form, have the bits of
+ *                                                        (v - min) / (max - min); min = r + 0.997 q from float32 r, q (or 1.0),
+ *                                                        ranges from one ulp to 1e3, v at / next to / between the bounds
+ *   _QUOTIENT_GUARDED   case index < 32768 * 2 * 2048 * 4  the same quotients with n over EVERY exponent field (subnormals,
+ *                                                        infinities, NaNs; -0.0 excepted, which no caller produces): counts
+ *                                                        the cases where the forms differ and leaves_plain_range(n) does
+ *                                                        not say so
+ *   _PLAIN_RANGE        float64 bits                     counts (and lists) the doubles on which leaves_plain_range fires; the
+ *                                                        caller holds the rule
+ * count <= MZMCTS_NUMERICS_MAX_COUNT per call (a caller walks a domain in a loop, so no launch is long).  Null pointers,
+ * an unknown `which`, count == 0 or over the cap, and patterns outside the check's index space return
+ * MZMCTS_ERR_INVALID before the device is touched. */
+#define MZMCTS_NUMERICS_EXP 1
+#define MZMCTS_NUMERICS_RECIPROCAL 2
+#define MZMCTS_NUMERICS_INVERSE_TRANSFORM 3
+#define MZMCTS_NUMERICS_QUOTIENT 4
+#define MZMCTS_NUMERICS_NORMALIZED 5
+#define MZMCTS_NUMERICS_QUOTIENT_GUARDED 6
+#define MZMCTS_NUMERICS_PLAIN_RANGE 7
+#define MZMCTS_NUMERICS_MAX_COUNT (1ull << 28)
+int mzmcts_device_numerics(int32_t which, uint64_t first, uint64_t count, uint64_t *mismatches_out,
+                           uint64_t *first_bad_out, double *worst_out);
+
 /* ---- stand-alone host RNG stream (numpy legacy RandomState clone) ----------------------------
  * The same generator the engine uses per env, exposed for host logic that has no engine
  * (SelfPlay.select_opponent_action's numpy.random.choice, self_play.py:217) and for CPU tests. */

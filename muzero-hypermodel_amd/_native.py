@@ -13,6 +13,7 @@ from .build import LIB_PATH
 c_i32_p = ctypes.POINTER(ctypes.c_int32)
 c_i64_p = ctypes.POINTER(ctypes.c_int64)
 c_u32_p = ctypes.POINTER(ctypes.c_uint32)
+c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_f64_p = ctypes.POINTER(ctypes.c_double)
 c_f32_p = ctypes.POINTER(ctypes.c_float)
 c_void = ctypes.c_void_p
@@ -218,6 +219,7 @@ PROTOTYPES = {
     "mzmcts_set_device_temperatures": (ctypes.c_int, [c_void, ctypes.c_int32]),
     "mzmcts_device_select_action": (ctypes.c_int, [c_u32_p, ctypes.c_int32, c_i32_p, ctypes.c_int32, c_f64_p, ctypes.c_int32,
                                                    c_i32_p, c_u32_p]),
+    "mzmcts_device_numerics": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, c_u64_p, c_u64_p, c_f64_p]),
     "mzmcts_rng_export": (None, [c_void, c_u32_p, c_i32_p, c_i32_p, c_f64_p]),
     "mzmcts_rng_import": (None, [c_void, c_u32_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double]),
     "mzmcts_rng_select_action": (ctypes.c_int32, [c_void, c_i32_p, ctypes.c_int32, ctypes.c_double]),
@@ -385,6 +387,32 @@ def device_select_action(seeds, visits, temperature, draws=1):
     if rc != 0:
         raise RuntimeError(f"mzmcts_device_select_action failed ({rc})")
     return slots, words
+
+
+NUMERICS = {"exp": 1, "reciprocal": 2, "inverse_transform": 3, "quotient": 4, "normalized": 5, "quotient_guarded": 6,
+            "plain_range": 7}
+NUMERICS_MAX_COUNT = 1 << 28
+
+
+def device_numerics(which, first, count):
+    """mzmcts_device_numerics over the patterns first .. first + count - 1 of check `which` (a NUMERICS key), walked in
+    calls of at most NUMERICS_MAX_COUNT.  Returns (mismatches, offending patterns (up to 8 per call), worst distance);
+    stops at the first call that does not return MZMCTS_OK."""
+    lib, code = load(), NUMERICS[which]
+    mismatches, bad, worst = 0, [], 0.0
+    n_bad, w = ctypes.c_uint64(), ctypes.c_double()
+    patterns = (ctypes.c_uint64 * 8)()
+    done = 0
+    while done < count:
+        step = min(NUMERICS_MAX_COUNT, count - done)
+        rc = lib.mzmcts_device_numerics(code, first + done, step, ctypes.byref(n_bad), patterns, ctypes.byref(w))
+        if rc != 0:
+            raise RuntimeError(f"mzmcts_device_numerics({which}, {first + done}, {step}) failed ({rc})")
+        mismatches += n_bad.value
+        bad += [int(p) for p in patterns[:min(8, n_bad.value)]]
+        worst = max(worst, w.value)
+        done += step
+    return mismatches, bad, worst
 
 
 def exact_inverse_temperature(temperature):

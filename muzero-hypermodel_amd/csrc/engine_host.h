@@ -38,6 +38,7 @@ int default_group_width(int A);
 hipError_t launch_fc_inference(const TreeParams& p, const FcNet& net, const float* weights, bool initial, const float* in,
                                const int64_t* action, float* value_logits, float* reward_logits, float* policy_logits,
                                float* hidden_out, hipStream_t stream);
+size_t fc_inference_lds_bytes(const TreeParams& p, const FcNet& net);
 bool plan_fused_layout(const TreeParams& p, const FcNet& net, bool want_hidden_in_lds, size_t lds_limit,
                        FusedLayout* out);
 bool narrow_supported(const TreeParams& p, const FcNet& net);

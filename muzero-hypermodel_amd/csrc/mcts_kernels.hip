@@ -1142,22 +1142,31 @@ static int host_table_entries(const FcNet& net, int G) {
            host_list_entries(net.rec_post, net.n_rec_post, G);
 }
 
+// Dynamic LDS of fc_inference_kernel: every weight (rows padded to four floats), one activation scratch per tree of the
+// workgroup and the neuron tables.  The C entries refuse a network whose figure exceeds a workgroup's LDS.
+size_t fc_inference_lds_bytes(const TreeParams& p, const FcNet& net) {
+    const int G = p.A > 64 ? 64 : p.group;   // (dispatch_group's choice)
+    return sizeof(float) * (static_cast<size_t>((net.n_weights_lds + 3) & ~3) +
+                            static_cast<size_t>(net.scratch_floats) * (kThreads / G)) +
+           sizeof(NeuronDesc) * static_cast<size_t>(host_table_entries(net, G));
+}
+
 hipError_t launch_fc_inference(const TreeParams& p, const FcNet& net, const float* weights, bool initial, const float* in,
                                const int64_t* action, float* value_logits, float* reward_logits, float* policy_logits,
                                float* hidden_out, hipStream_t stream) {
     const int grid = tree_grid(p);
+    const size_t lds = fc_inference_lds_bytes(p, net);
+    hipError_t attr_err = hipSuccess;
     dispatch_group(p, [&](auto g, auto) {
         constexpr int G = decltype(g)::value;
-        const size_t lds = sizeof(float) * (static_cast<size_t>((net.n_weights_lds + 3) & ~3) +
-                                            static_cast<size_t>(net.scratch_floats) * (kThreads / G)) +
-                           sizeof(NeuronDesc) * static_cast<size_t>(host_table_entries(net, G));
-        if (initial)
-            fc_inference_kernel<G, true><<<dim3(grid), dim3(kThreads), lds, stream>>>(
-                net, weights, p.E, in, action, value_logits, reward_logits, policy_logits, hidden_out);
-        else
-            fc_inference_kernel<G, false><<<dim3(grid), dim3(kThreads), lds, stream>>>(
-                net, weights, p.E, in, action, value_logits, reward_logits, policy_logits, hidden_out);
+        auto kernel = initial ? fc_inference_kernel<G, true> : fc_inference_kernel<G, false>;
+        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds));
+        if (attr_err != hipSuccess) return;
+        kernel<<<dim3(grid), dim3(kThreads), lds, stream>>>(net, weights, p.E, in, action, value_logits, reward_logits,
+                                                            policy_logits, hidden_out);
     });
+    if (attr_err != hipSuccess) return attr_err;
     return hipGetLastError();
 }
 

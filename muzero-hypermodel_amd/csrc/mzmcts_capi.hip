@@ -897,6 +897,9 @@ int mzmcts_fc_initial_inference(mzmcts_engine* eng, const float* observations, f
     if (!eng || !observations || !value_logits || !reward_logits || !policy_logits || !hidden_out)
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_fc_initial_inference: null argument");
     if (!eng->fc_ready) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_fc_initial_inference: call mzmcts_fc_configure first");
+    if (!mzhost_use_narrow(eng) && mz::fc_inference_lds_bytes(eng->p, eng->fc) > kLdsPerWorkgroup)
+        return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_fc_initial_inference: the network's weights and activations do not fit "
+                                             "a workgroup's 160 KB of LDS");
     if (mzhost_use_narrow(eng))
         MZ_HIP(eng, mz::launch_fc_inference_narrow(eng->p, eng->fc, eng->fc_weights, true, observations, nullptr,
                                                    value_logits, reward_logits, policy_logits, hidden_out,
@@ -912,6 +915,9 @@ int mzmcts_fc_recurrent_inference(mzmcts_engine* eng, const float* hidden, const
     if (!eng || !hidden || !action || !value_logits || !reward_logits || !policy_logits || !hidden_out)
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_fc_recurrent_inference: null argument");
     if (!eng->fc_ready) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_fc_recurrent_inference: call mzmcts_fc_configure first");
+    if (!mzhost_use_narrow(eng) && mz::fc_inference_lds_bytes(eng->p, eng->fc) > kLdsPerWorkgroup)
+        return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_fc_recurrent_inference: the network's weights and activations do not fit "
+                                             "a workgroup's 160 KB of LDS");
     if (mzhost_use_narrow(eng))
         MZ_HIP(eng, mz::launch_fc_inference_narrow(eng->p, eng->fc, eng->fc_weights, false, hidden, action, value_logits,
                                                    reward_logits, policy_logits, hidden_out,

@@ -486,7 +486,11 @@ struct LdsTreeV {
 // same for every level of a descent, so y is computed once per simulation and a level pays the last three
 // operations.  The backups watch every value that can become v, min or max (`exotic`): while all of them are zero
 // or within 2^-400 .. 2^400, n and d are zero or within 2^-453 .. 2^401 and n <= d, where scale and fixup are the
-// identity (n == 0 gives 0 either way) -- the same bits as the division.  Otherwise the division itself runs.
+// identity (n == +0.0 gives +0.0 either way) -- the same bits as the division.  Otherwise the division itself runs.
+// One operand is outside the claim: n == -0.0, where the short form answers +0.0 (r = fma(-d, -0.0, -0.0) is +0.0) and the
+// division -0.0.  No caller produces it: value sums start at +0.0 and a sum rounded to nearest is -0.0 only when both terms
+// are; v - min is +0.0 when the two are equal; only while max <= min (x = v) can a -0.0 value term arrive, and there the
+// two zeros score alike.  tests/test_gpu_device_numerics.py sweeps the claim (and finds exactly this operand).
 struct Normalizer {
     double minimum, range, y;
     bool fast;
@@ -544,7 +548,8 @@ __device__ __forceinline__ void normalized_pair(const Normalizer& n, double v0, 
 
 // numerator / denominator with the denominator's reciprocal prepared ahead (refined_reciprocal): the last three
 // operations of the IEEE division sequence -- the same bits while the numerator is zero or within 2^-400 .. 2^400 and
-// the denominator a small positive integer (see Normalizer); the caller checks the numerator (leaves_plain_range)
+// the denominator a small positive integer (see Normalizer; not for a numerator of -0.0, which no caller has); the
+// caller checks the numerator (leaves_plain_range)
 __device__ __forceinline__ double refined_reciprocal(double d) {
     const double y0 = __builtin_amdgcn_rcp(d);
     const double e0 = __builtin_fma(-d, y0, 1.0);
@@ -558,10 +563,12 @@ __device__ __forceinline__ double quotient_with(double n, double d, double y) {
     return __builtin_fma(r, y, q0);
 }
 
-// true when a value handed to the min-max statistics leaves the range normalized_value's short form is exact for
+// true when a value handed to the min-max statistics leaves the range normalized_value's short form is exact for.
+// The rule, exactly: plain = zero (either sign) or 2^-400 <= |seen| < 2^400 (1 + 2^-20) -- the test reads the high word
+// only, so the upper end is the binade's first 2^-20th, not 2^400 itself; infinities and NaNs are not plain.
 __device__ __forceinline__ bool leaves_plain_range(double seen) {
     const uint32_t hi = static_cast<uint32_t>(__double2hiint(seen)) & 0x7fffffffu;
-    return (hi - 0x26F00000u) > 0x32000000u && seen != 0.0;  // exponent outside 1023 - 400 .. 1023 + 400
+    return (hi - 0x26F00000u) > 0x32000000u && seen != 0.0;  // high word outside 1023 - 400 .. 1023 + 400, mantissa 0
 }
 
 // The `while node.expanded()` loop (self_play.py:321-335) with select_child / ucb_score

@@ -259,6 +259,108 @@ def synthetic_model(models_mod, config, device="cpu", seed=0):
     return model, weights
 
 
+# ---- a fully-connected network in float64, and what float32 kernels may differ from it by ---------------------------
+def fc_reference_model(model, dtype=None):
+    """A copy of a models.MuZeroFullyConnectedNetwork on the CPU in `dtype` (float64 unless told otherwise): the module's
+    own forward, nothing else, is the reference the FC kernels are compared with."""
+    import copy
+    import torch
+    ref = copy.deepcopy(model).cpu().to(dtype if dtype is not None else torch.float64)
+    ref._zero_reward_cache = None
+    ref.eval()
+    return ref
+
+
+def fc_reference_inference(ref, observations=None, hidden=None, action=None):
+    """(value logits, reward logits, policy logits, hidden state) as numpy arrays from `ref` (fc_reference_model):
+    initial_inference(observations) or recurrent_inference(hidden, action)."""
+    import torch
+    dtype = next(ref.parameters()).dtype
+    with torch.no_grad():
+        if observations is not None:
+            out = ref.initial_inference(torch.as_tensor(np.asarray(observations)).to(dtype))
+        else:
+            act = torch.as_tensor(np.asarray(action)).long().reshape(-1, 1)
+            out = ref.recurrent_inference(torch.as_tensor(np.asarray(hidden)).to(dtype), act)
+    return tuple(t.to(dtype).numpy().copy() for t in out)      # (the constant reward row of initial_inference is float32)
+
+
+F32_UNIT = 2.0 ** -24        # unit roundoff of float32
+
+
+def _mlp_rounding_bound(seq, x, e):
+    """Forward `seq` (Linear / ELU stack of a float64 model) on x and carry a bound e on the distance between a float32
+    evaluation's activations and these.  A neuron is a sum of m products and a bias in some order (the narrow kernel: two
+    FMA chains and one addition; the generic one: FMA chains per lane and a butterfly): every term passes through at most
+    m + 1 roundings, so its error is at most gamma(m + 2) (|W| |x| + |b|) on top of |W| e, and nothing when no product is
+    non-zero (adding exact zeros to the bias rounds nothing).  ELU is 1-Lipschitz; its exponential and the subtraction of 1
+    stay within 2^-23 of the exact value on the negative side."""
+    import torch
+    linears = [m for m in seq if isinstance(m, torch.nn.Linear)]
+    for i, lin in enumerate(linears):
+        w, b = lin.weight, lin.bias
+        y = x @ w.T + b
+        magnitude = (x.abs() + e) @ w.abs().T + b.abs()
+        products = (x != 0).to(x.dtype) @ (w != 0).to(x.dtype).T
+        k = products + 2.0
+        rounding = torch.where(products > 0, k * F32_UNIT / (1.0 - k * F32_UNIT) * magnitude, torch.zeros_like(magnitude))
+        e = e @ w.abs().T + rounding
+        if i + 1 < len(linears):
+            x = torch.nn.functional.elu(y)
+            e = e + 2.0 ** -23
+        else:
+            x = y
+    return x, e
+
+
+def _rescale_rounding_bound(raw, e):
+    """models._unit_rescale with the bound carried along: minimum and maximum move by at most max(e); the span takes one
+    rounding, the 1e-5 constant is float32's and its addition rounds once more; the quotient (raw - min) / span then
+    differs by (e_numerator + quotient * e_span) / (span - e_span) and one rounding.  An input error grows by 1 / span."""
+    import torch
+    low, high = raw.amin(dim=1, keepdim=True), raw.amax(dim=1, keepdim=True)
+    worst = e.amax(dim=1, keepdim=True)
+    span = high - low
+    undecided = ((span - 1e-5).abs() <= 2.0 * worst + 2.0 * F32_UNIT * 1e-5)
+    assert not bool(undecided.any()), "a span within rounding of the 1e-5 threshold: the two evaluations may take different branches"
+    span = torch.where(span < 1e-5, span + 1e-5, span)
+    e_span = 2.0 * worst + 4.0 * F32_UNIT * span
+    numerator = raw - low
+    e_numerator = e + worst + F32_UNIT * numerator
+    quotient = numerator / span
+    return quotient, (e_numerator + quotient * e_span) / (span - e_span) + F32_UNIT * quotient
+
+
+def fc_rounding_bounds(ref, observations=None, hidden=None, action=None, hidden_error=None):
+    """Per-element bounds on |float32 kernel - float64 reference| for (value logits, reward logits, policy logits, hidden
+    state) of one inference of `ref` (a float64 fc_reference_model), from the arithmetic alone: inputs and weights are
+    float32 numbers, so the first layer starts without error (`hidden_error`: a bound on the hidden input's own distance,
+    for chained inferences); see _mlp_rounding_bound / _rescale_rounding_bound.  The reward bound of an initial inference
+    is zero (the logits are constants)."""
+    import torch
+    with torch.no_grad():
+        if observations is not None:
+            x = torch.as_tensor(np.asarray(observations)).double().reshape(len(observations), -1)
+            raw, e = _mlp_rounding_bound(ref.representation_network.module, x, torch.zeros_like(x))
+            e_reward = None
+        else:
+            h = torch.as_tensor(np.asarray(hidden)).double()
+            act = torch.as_tensor(np.asarray(action)).long().reshape(-1, 1)
+            one_hot = (act == torch.arange(ref.action_space_size)).double()
+            x = torch.cat((h, one_hot), dim=1)
+            e_in = torch.zeros_like(x)
+            if hidden_error is not None:
+                e_in[:, :h.shape[1]] = torch.as_tensor(np.asarray(hidden_error)).double()
+            raw, e = _mlp_rounding_bound(ref.dynamics_encoded_state_network.module, x, e_in)
+            _, e_reward = _mlp_rounding_bound(ref.dynamics_reward_network.module, raw, e)
+        state, e_state = _rescale_rounding_bound(raw, e)
+        _, e_policy = _mlp_rounding_bound(ref.prediction_policy_network.module, state, e_state)
+        _, e_value = _mlp_rounding_bound(ref.prediction_value_network.module, state, e_state)
+        if e_reward is None:
+            e_reward = torch.zeros_like(e_value)
+    return tuple(t.numpy() for t in (e_value, e_reward, e_policy, e_state))
+
+
 # ---- the value transform seen as an error amplifier (reference models.py:641-662) ----------------------
 def categorical_mean(logits, support_size):
     """x = sum(softmax(logits) * [-s .. s]) in float64 (the quantity the inverse transform is applied to)."""

@@ -350,6 +350,8 @@ def test_fused_other_fc_shapes(eng, models_mod, oracle, name, group):
     a, b = runs["lockstep_fc"], runs["fused"]
     for key in a[0]:
         assert np.array_equal(a[0][key], b[0][key]), key              # same device code, LDS vs HBM: bit-identical
+    # (where that device code meets an independent reference -- the network in float64, at every admitted shape edge:
+    #  tests/test_gpu_fc_shapes.py; its cut-down arithmetic over whole operand domains: tests/test_gpu_device_numerics.py)
     assert np.array_equal(a[1], b[1]) and np.array_equal(a[3], b[3])
     for key in a[2]:
         assert np.array_equal(a[2][key], b[2][key]), key

@@ -144,3 +144,33 @@ def test_host_rng_replay_sampling_helpers_match_numpy(native):
         idx, prob = native.HostRng(seed).choice_priorities(priorities)
         want_idx = np.random.RandomState(seed).choice(len(probs), p=probs)
         assert idx == want_idx and prob == probs[want_idx]
+
+
+def test_device_numerics_refuses_bad_arguments_without_a_device(native):
+    """mzmcts_device_numerics checks its arguments before anything touches the GPU: null result pointers, an unknown check,
+    an empty or over-long run (the cap keeps every launch short) and patterns outside the check's index space come back
+    as MZMCTS_ERR_INVALID; the Python wrapper turns that into an exception."""
+    import ctypes
+    lib = native.load()
+    n_bad, worst, patterns = ctypes.c_uint64(), ctypes.c_double(), (ctypes.c_uint64 * 8)()
+
+    def call(which=native.NUMERICS["exp"], first=0x80000000, count=16, n=ctypes.byref(n_bad), p=patterns, w=ctypes.byref(worst)):
+        return lib.mzmcts_device_numerics(which, first, count, n, p, w)
+
+    cap = native.NUMERICS_MAX_COUNT
+    assert cap == 1 << 28
+    for bad in (dict(n=None), dict(p=None), dict(w=None), dict(which=0), dict(which=8), dict(which=-1), dict(count=0),
+                dict(count=cap + 1), dict(first=1 << 32), dict(first=(1 << 32) - 8, count=9),
+                dict(which=native.NUMERICS["reciprocal"], first=1 << 32),
+                dict(which=native.NUMERICS["inverse_transform"], first=(1 << 32) - 1, count=2),
+                dict(which=native.NUMERICS["quotient"], first=32768 * 2 * 803 * 4, count=1),
+                dict(which=native.NUMERICS["quotient_guarded"], first=32768 * 2 * 2048 * 4 - 1, count=2),
+                dict(which=native.NUMERICS["normalized"], first=1 << 40, count=1),
+                dict(which=native.NUMERICS["plain_range"], first=(1 << 64) - 4, count=5)):
+        assert call(**bad) == native.ERR_INVALID, bad
+    with pytest.raises(KeyError):
+        native.device_numerics("cosine", 0, 1)
+    if not torch.cuda.is_available():               # a good call gets as far as the device and says so
+        assert call() == native.ERR_HIP
+        with pytest.raises(RuntimeError, match="mzmcts_device_numerics"):
+            native.device_numerics("exp", 0, 1)
