@@ -370,6 +370,12 @@ int mzmcts_moves_ring(mzmcts_engine *engine, void **host_base, int64_t *move_str
  * so both calls return the ring of the batch prepared last, and views of a collected batch stay valid while the NEXT
  * batch runs and is collected -- until the mzmcts_moves_prepare_device after that. */
 int mzmcts_moves_inputs_ring(mzmcts_engine *engine, void **host_base, int64_t *move_stride, int64_t *offsets);
+/* The DEVICE rings those two are downloaded from (one of each kind; a batch's blocks stay until the next batch's
+ * searches overwrite them): same strides, same offsets, device base pointers.  For consumers that read a batch where
+ * it lies, queued on the batch's stream behind its last kernel (include/mzreplay.h mzreplay_filer_file). */
+int mzmcts_moves_device_ring(mzmcts_engine *engine, void **device_base, int64_t *move_stride, int64_t *offsets,
+                             int32_t *capacity_moves);
+int mzmcts_moves_inputs_device_ring(mzmcts_engine *engine, void **device_base, int64_t *move_stride, int64_t *offsets);
 
 /* ---- residual-network epilogue (no engine: any device tensor of the current device) ---------
  * What follows every convolution of the reference's residual networks in eval() -- BatchNorm2d with its

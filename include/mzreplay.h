@@ -25,7 +25,11 @@
  *   mzreplay_make_batch_device    builds the targets from those device-resident indices, in the trainer's dtypes
  *   mzreplay_update_priorities    ReplayBuffer.update_priorities (replay_buffer.py:197-220) from device tensors
  *
- * so that a training step needs no host round trip.  fp64 sums run in the reference's order with
+ *   mzreplay_filer_*              finished self-play games appended straight from the search engine's and the
+ *                                 environment kernels' device rings (csrc/replay_filer.h); mzreplay_read_games reads
+ *                                 stored games back
+ *
+ * so that neither a training step nor a self-play batch needs a host round trip through the store.  fp64 sums run in the reference's order with
  * `discount ** i` taken from a table the caller fills with its own libm (Python floats), so values and
  * policies are bit-identical to the reference's; priorities go through the device's pow() and agree to
  * float32 rounding.
@@ -122,6 +126,87 @@ int mzreplay_make_batch_device(mzreplay *store, int32_t batch, const int32_t *sl
  * touched game.  Asynchronous. */
 int mzreplay_update_priorities(mzreplay *store, int32_t batch, const int64_t *game_ids, const int32_t *positions,
                                const float *priorities, void *stream);
+
+/* Read stored games back (host outputs in mzreplay_add_games' input layout, each may be NULL): lengths i32[n],
+ * observations f32[n][max_moves+1][C*H*W], actions i32[n][max_moves+1], rewards f64[n][max_moves+1], to_play
+ * i32[n][max_moves+1], child_visits f64[n][max_moves][A], root_values f64[n][max_moves]; entries past a game's length are
+ * zero.  Games filed on the device never existed on the host: this is how a saved buffer or a test sees them.  Blocking. */
+int mzreplay_read_games(mzreplay *store, int32_t n, const int32_t *slots, int32_t *lengths, float *observations,
+                        int32_t *actions, double *rewards, int32_t *to_play, double *child_visits, double *root_values,
+                        void *stream);
+
+/* ---- finished self-play games filed on the device ---------------------------------------------------------------------
+ * The producer side of the store without the host: a filer is owned by a store (one per store) and bound to one actor of
+ * E envs.  It keeps, in device memory, one running row per env in the store's own slot layout and the store-wide counters
+ * (next game id, games stored, total_samples, steps played), and turns a whole move batch -- read where the search engine
+ * and the environment kernels left it -- into stored games in three launches with no host decision in between
+ * (csrc/replay_filer.h holds the index arithmetic):
+ *   1. per env and move what mzhist_file does: child_visits[len][legal[i]] = double(visits[i]) / S over a zeroed row,
+ *      root_values[len] = root_value_sum / S (IEEE fp64 divisions), actions / rewards / observations / to_play[len + 1];
+ *      on `done` the row is a finished game of len moves and the next one starts with obs_next, action 0, reward 0 and the
+ *      next move's player;
+ *   2. an env's played moves are a prefix of the batch, ending at its first move whose action reads < 0;
+ *   3. the games a call finishes are numbered env-major, then in move order: id = next id + rank, slot = id % capacity;
+ *   4. a finished game is copied into its slot (length set, Reanalyse's values forgotten), its initial priorities and game
+ *      priority are computed as mzreplay_add_games computes them (bit for bit) and, with the sampler on, adopted by it;
+ *      when a call finishes more games than the store has slots only the last `capacity` are written, and the counters
+ *      move as if all had been stored and evicted in turn;
+ *   5. nothing read from a ring is used as an index before it was checked: a legal count outside [0, A], a legal action
+ *      outside [0, A) or a game longer than max_moves sets a bit in a device error word, NOTHING of that batch is filed,
+ *      and the next mzreplay_filer_sync fails with mzhist_file's message (later calls work).
+ * Errors of these calls are read with mzreplay_last_error(store). */
+typedef struct mzreplay_filer mzreplay_filer;
+
+/* The device twin of mzhist_moves: every pointer a DEVICE pointer, per-move blocks `stride` bytes apart (the engine's
+ * rings as mzmcts_moves_device_ring / mzmcts_moves_inputs_device_ring report them).  There is no moves_done (rule 2) and
+ * no `played` (opponent plies are not filed on the device).  The players to move are given as the searches recorded them:
+ * to_play_after of a move is 1 - to_play for two players and 0 for one, to_play_next of a game's last move is the next
+ * move's to_play (the batch's last move: to_play_last). */
+typedef struct mzreplay_file_moves {
+    int32_t n_moves;               /* M */
+    int32_t num_simulations;       /* S */
+    const void *actions;           /* move m: i32[E] at actions + m * actions_stride */
+    int64_t actions_stride;
+    const void *visits;            /* move m: i32[E][A], root children by child slot */
+    int64_t visits_stride;
+    const void *root_value_sum;    /* move m: f64[E] */
+    int64_t root_value_sum_stride;
+    const void *legal;             /* move m: i32[E][A] child slot -> action; stride 0 = one set for the batch */
+    int64_t legal_stride;
+    const void *num_legal;         /* move m: i32[E] */
+    int64_t num_legal_stride;
+    const void *to_play;           /* move m: i32[E] player to move when move m was searched; NULL = player 0 throughout */
+    int64_t to_play_stride;
+    const int32_t *to_play_last;   /* [E] player to move after the batch's last move (required with to_play) */
+    const float *rewards;          /* [M][E] */
+    const uint8_t *done;           /* [M][E] game over after this move */
+    const float *obs_after;        /* [M][E][obs] observation after the move (terminal one included) */
+    const float *obs_next;         /* [M][E][obs] observation the next search sees (reset where done) */
+    int32_t players;               /* 1 or 2 */
+    int32_t reserved;
+} mzreplay_file_moves;
+
+int mzreplay_filer_create(mzreplay *store, int32_t num_envs, mzreplay_filer **out);
+void mzreplay_filer_destroy(mzreplay_filer *filer);
+/* Every env starts a game: reset observations dev f32[E][obs], to_play dev i32[E] (NULL = player 0).  Asynchronous. */
+int mzreplay_filer_begin(mzreplay_filer *filer, const float *first_observations, const int32_t *first_to_play,
+                         void *stream);
+/* The store-wide counters as the host knows them: counters[4] = next game id, games stored, total_samples, steps played.
+ * At the start, and after every mzreplay_add_games into a store that has a filer.  Asynchronous (the values are copied). */
+int mzreplay_filer_set_counters(mzreplay_filer *filer, const int64_t *counters, void *stream);
+/* File a move batch.  Asynchronous on `stream`: queue it behind the batch's last environment kernel. */
+int mzreplay_filer_file(mzreplay_filer *filer, const mzreplay_file_moves *moves, void *stream);
+/* The games filed since the last sync, as host arrays of 4 bytes per game (valid until the next call on this filer), the
+ * id of the first of them (they are consecutive), the counters (counters[4] as above, may be NULL), and the device error
+ * word turned into a message.  The only data that comes back.  Blocking. */
+int mzreplay_filer_sync(mzreplay_filer *filer, int32_t *n_new, const int32_t **env_index, const int32_t **lengths,
+                        int64_t *first_game_id, int64_t *counters, void *stream);
+/* Moves played so far in every env's running game: host i32[E] (what mzhist_lengths gives for the host filer).  Blocking. */
+int mzreplay_filer_lengths(mzreplay_filer *filer, int32_t *lengths, void *stream);
+/* Initial priorities of stored games for a host-side sampler: host f32[n][max_moves] (zero past the length) and f32[n]
+ * for the games in `slots` (host i32[n]).  Blocking. */
+int mzreplay_filer_priorities(mzreplay_filer *filer, int32_t n, const int32_t *slots, float *priorities,
+                              float *game_priority, void *stream);
 
 /* Bytes of device memory the store occupies. */
 int64_t mzreplay_device_bytes(const mzreplay *store);

@@ -125,6 +125,8 @@ PROTOTYPES = {
     "mzmcts_moves_actions": (c_void, [c_void, ctypes.c_int32]),
     "mzmcts_moves_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p, c_i32_p]),
     "mzmcts_moves_inputs_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p]),
+    "mzmcts_moves_device_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p, c_i32_p]),
+    "mzmcts_moves_inputs_device_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p]),
     "mzmcts_moves_collect": (ctypes.c_int, [c_void, c_i32_p, c_i32_p, c_i32_p, c_f64_p, c_f32_p, c_i32_p, c_void]),
     "mzmcts_set_profiling": (ctypes.c_int, [c_void, ctypes.c_int32]),
     "mzmcts_set_select_queue": (ctypes.c_int, [c_void, ctypes.c_int32]),
@@ -188,6 +190,17 @@ PROTOTYPES = {
     "mzreplay_make_batch_device": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, c_void, c_void, c_void, c_void,
                                                   c_void, c_void, c_void, c_void]),
     "mzreplay_update_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, c_void, c_void]),
+    "mzreplay_read_games": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_i32_p, c_f32_p, c_i32_p, c_f64_p, c_i32_p,
+                                           c_f64_p, c_f64_p, c_void]),
+    "mzreplay_filer_create": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.POINTER(c_void)]),
+    "mzreplay_filer_destroy": (None, [c_void]),
+    "mzreplay_filer_begin": (ctypes.c_int, [c_void, c_void, c_void, c_void]),
+    "mzreplay_filer_set_counters": (ctypes.c_int, [c_void, c_i64_p, c_void]),
+    "mzreplay_filer_file": (ctypes.c_int, [c_void, c_void, c_void]),
+    "mzreplay_filer_sync": (ctypes.c_int, [c_void, c_i32_p, ctypes.POINTER(c_void), ctypes.POINTER(c_void), c_i64_p, c_i64_p,
+                                           c_void]),
+    "mzreplay_filer_lengths": (ctypes.c_int, [c_void, c_i32_p, c_void]),
+    "mzreplay_filer_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_f32_p, c_f32_p, c_void]),
     "mzenv_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_u32_p, ctypes.POINTER(c_void)]),
     "mzenv_destroy": (None, [c_void]),
     "mzenv_last_error": (ctypes.c_char_p, [c_void]),
@@ -296,6 +309,17 @@ class MzHistMoves(ctypes.Structure):
                 ("legal", c_void), ("num_legal", c_void), ("rewards", c_void), ("done", c_void), ("obs_after", c_void),
                 ("obs_next", c_void), ("to_play_after", c_void), ("to_play_next", c_void),
                 ("legal_stride", ctypes.c_int64), ("num_legal_stride", ctypes.c_int64), ("played", c_void)]
+
+
+class MzReplayFileMoves(ctypes.Structure):
+    """mzreplay_file_moves (include/mzreplay.h): a move batch in device memory, as the device filer reads it."""
+    _fields_ = [("n_moves", ctypes.c_int32), ("num_simulations", ctypes.c_int32),
+                ("actions", c_void), ("actions_stride", ctypes.c_int64), ("visits", c_void),
+                ("visits_stride", ctypes.c_int64), ("root_value_sum", c_void), ("root_value_sum_stride", ctypes.c_int64),
+                ("legal", c_void), ("legal_stride", ctypes.c_int64), ("num_legal", c_void),
+                ("num_legal_stride", ctypes.c_int64), ("to_play", c_void), ("to_play_stride", ctypes.c_int64),
+                ("to_play_last", c_void), ("rewards", c_void), ("done", c_void), ("obs_after", c_void),
+                ("obs_next", c_void), ("players", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class HostRng:

@@ -685,6 +685,28 @@ int mzmcts_moves_inputs_ring(mzmcts_engine* eng, void** host_base, int64_t* move
     return MZMCTS_OK;
 }
 
+int mzmcts_moves_device_ring(mzmcts_engine* eng, void** device_base, int64_t* move_stride, int64_t* offsets,
+                             int32_t* capacity) {
+    if (!eng || !device_base || !move_stride || !offsets || !capacity) return MZMCTS_ERR_INVALID;
+    mzmcts_engine::MoveBatch& b = eng->batch;
+    if (!b.d_out) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_device_ring: no batch has been prepared yet");
+    void* host_base = nullptr;
+    const int rc = mzmcts_moves_ring(eng, &host_base, move_stride, offsets, capacity);   // (the same strides and offsets)
+    *device_base = b.d_out;
+    return rc;
+}
+
+int mzmcts_moves_inputs_device_ring(mzmcts_engine* eng, void** device_base, int64_t* move_stride, int64_t* offsets) {
+    if (!eng || !device_base || !move_stride || !offsets) return MZMCTS_ERR_INVALID;
+    mzmcts_engine::MoveBatch& b = eng->batch;
+    if (!b.d_inputs)
+        return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_inputs_device_ring: no device-input batch has been prepared yet");
+    void* host_base = nullptr;
+    const int rc = mzmcts_moves_inputs_ring(eng, &host_base, move_stride, offsets);
+    *device_base = b.d_inputs;
+    return rc;
+}
+
 int mzmcts_moves_collect(mzmcts_engine* eng, int32_t* moves_done, int32_t* actions, int32_t* visits, double* root_value_sum,
                          float* root_predicted, int32_t* max_depth, void* stream_) {
     if (!eng) return MZMCTS_ERR_INVALID;

@@ -20,12 +20,15 @@
 // and update_priorities in two (writes with the reference's later-sample-wins order, then the game maxima).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/mzreplay.h"
+#include "replay_filer.h"
 #include "replay_sampler.h"
 
 namespace {
@@ -80,6 +83,12 @@ __device__ __forceinline__ double target_value(const StoreParams& p, int slot, i
     return value;
 }
 
+// ReplayBuffer.save_game's initial priority of one position (replay_buffer.py:33-50): |root value - target| ** alpha
+__device__ __forceinline__ float position_priority(const StoreParams& p, int slot, int n, int i) {
+    const double rv = p.root_values[static_cast<size_t>(slot) * p.L + i];
+    return static_cast<float>(pow(fabs(rv - target_value(p, slot, n, i)), p.alpha));
+}
+
 __global__ __launch_bounds__(256) void priorities_kernel(StoreParams p, const int32_t* __restrict__ slots,
                                                          float* __restrict__ priorities,  // [n][L]
                                                          float* __restrict__ game_priority) {
@@ -90,8 +99,7 @@ __global__ __launch_bounds__(256) void priorities_kernel(StoreParams p, const in
     for (int i = threadIdx.x; i < p.L; i += blockDim.x) {
         float pr = 0.f;
         if (i < n) {
-            const double rv = p.root_values[static_cast<size_t>(slot) * p.L + i];
-            pr = static_cast<float>(pow(fabs(rv - target_value(p, slot, n, i)), p.alpha));
+            pr = position_priority(p, slot, n, i);
             best = fmaxf(best, pr);
         }
         priorities[static_cast<size_t>(blockIdx.x) * p.L + i] = pr;
@@ -565,6 +573,271 @@ __global__ __launch_bounds__(256) void adopt_games_kernel(StoreParams p, Sampler
     }
 }
 
+// ---- the filer (replay_filer.h; include/mzreplay.h mzreplay_filer_file) ------------------------------------------------
+// Three launches per move batch, no host decision in between:
+//   filer_count_kernel        a thread per env: prefix of played moves, validation of everything later used as an index,
+//                             games finished
+//   filer_scan_kernel         one workgroup: exclusive scan of the E counts in LDS, 1024 at a time; the call's plan
+//                             (first id, games, how many a wrap drops), the lengths of the stored games the call evicts,
+//                             the counters
+//   filer_append_kernel       a wavefront per env walks its moves in order: lanes spread over the policy entries and the
+//                             observation floats; a finished game's row goes to its slot in coalesced copies
+//   filer_priorities_kernel   a fixed grid strides over the call's surviving games: priorities_kernel's arithmetic into the
+//                             priority arrays (the sampler's when it is on, with the game id)
+struct FilerState {                  // one block of device memory, read back whole by mzreplay_filer_sync
+    mz::filer::Counters counters;
+    int32_t pending;                 // games in the list since the last sync
+    int32_t error;                   // mz::filer::kErr* bits
+};
+
+struct FilerParams {
+    int32_t E;
+    float* obs;                      // the running games, one row per env, in the store's slot layout
+    int32_t* actions;
+    double* rewards;
+    int8_t* to_play;
+    double* child_visits;
+    double* root_values;
+    int32_t* length;
+    int32_t* played;                 // [E] scratch of a call: prefix length, games finished, their first rank
+    int32_t* count;
+    int32_t* offset;
+    FilerState* state;
+    mz::filer::Call* call;
+    int32_t* list_env;               // [list_cap] games filed since the last sync
+    int32_t* list_len;
+    int32_t list_cap;
+    float* priorities;               // [G][L], [G]: the sampler's arrays when it is on, else the filer's own
+    float* game_priority;
+    int64_t* game_id;                // the sampler's [G], or null
+};
+
+constexpr int kScanThreads = 1024;
+constexpr int kFilerWave = 64;
+
+template <typename T>
+__device__ __forceinline__ const T* move_block(const void* base, int64_t stride, int m) {
+    return reinterpret_cast<const T*>(static_cast<const uint8_t*>(base) + stride * m);
+}
+
+__global__ __launch_bounds__(256) void filer_count_kernel(StoreParams p, FilerParams f, mzreplay_file_moves mv) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= f.E) return;
+    const int E = f.E, A = p.A, M = mv.n_moves;
+    const int k = mz::filer::prefix_length(M, [&](int m) { return move_block<int32_t>(mv.actions, mv.actions_stride, m)[e]; });
+    bool bad_legal = false;
+    for (int m = 0; m < k; ++m) {
+        const int n_legal = move_block<int32_t>(mv.num_legal, mv.num_legal_stride, m)[e];
+        if (n_legal < 0 || n_legal > A) {
+            bad_legal = true;
+        } else {
+            const int32_t* legal = move_block<int32_t>(mv.legal, mv.legal_stride, m) + static_cast<size_t>(e) * A;
+            for (int i = 0; i < n_legal; ++i) bad_legal |= legal[i] < 0 || legal[i] >= A;
+        }
+    }
+    int len = f.length[e];
+    bool overflow = len < 0 || len > p.L;
+    const int count = mz::filer::count_finished(&len, k, p.L, [&](int m) { return mv.done[static_cast<size_t>(m) * E + e] != 0; },
+                                                &overflow);
+    f.played[e] = k;
+    f.count[e] = count;
+    if (bad_legal) atomicOr(&f.state->error, mz::filer::kErrLegal);
+    if (overflow) atomicOr(&f.state->error, mz::filer::kErrOverflow);
+}
+
+__global__ __launch_bounds__(kScanThreads) void filer_scan_kernel(StoreParams p, FilerParams f) {
+    __shared__ int32_t scan[2][kScanThreads];
+    __shared__ long long evicted_s[kScanThreads];
+    const int t = threadIdx.x;
+    // exclusive scan, a chunk of 1024 counts at a time (mz::filer::exclusive_scan_chunked is its serial statement)
+    int32_t carry = 0;
+    for (int base = 0; base < f.E; base += kScanThreads) {
+        const int e = base + t;
+        const int32_t own = e < f.E ? f.count[e] : 0;
+        int cur = 0;
+        scan[0][t] = own;
+        __syncthreads();
+        for (int step = 1; step < kScanThreads; step <<= 1) {
+            scan[cur ^ 1][t] = scan[cur][t] + (t >= step ? scan[cur][t - step] : 0);
+            cur ^= 1;
+            __syncthreads();
+        }
+        if (e < f.E) f.offset[e] = carry + scan[cur][t] - own;
+        carry += scan[cur][kScanThreads - 1];
+        __syncthreads();
+    }
+    const mz::filer::Counters before = f.state->counters;
+    const bool refused = f.state->error != 0;
+    const int64_t list_room = static_cast<int64_t>(f.list_cap) - f.state->pending;
+    // (the host sized the list for E x M games per unsynced call: a call that does not fit is refused whole)
+    const bool no_room = carry > list_room;
+    const mz::filer::Call call = mz::filer::plan_call(before, carry, p.G, f.state->pending, refused || no_room);
+    // the stored games this call evicts lose their lengths from total_samples: read before any slot is rewritten
+    const int64_t evicted = mz::filer::evicted_old(before, call.n_new, p.G);
+    const int64_t first = mz::filer::first_evicted_id(before);
+    long long sum = 0;
+    for (int64_t j = t; j < evicted; j += kScanThreads) sum += p.length[mz::filer::slot_of(first + j, p.G)];
+    evicted_s[t] = sum;
+    __syncthreads();
+    for (int half = kScanThreads / 2; half > 0; half >>= 1) {
+        if (t < half) evicted_s[t] += evicted_s[t + half];
+        __syncthreads();
+    }
+    if (t == 0) {
+        if (no_room) atomicOr(&f.state->error, mz::filer::kErrList);
+        // (the new games' own lengths are added by the wavefronts that file them)
+        f.state->counters = mz::filer::counters_after(before, call.n_new, p.G, 0, 0, evicted_s[0]);
+        f.state->pending += call.n_new;
+        *f.call = call;
+    }
+}
+
+template <bool kVec4>
+__device__ __forceinline__ void copy_floats(float* __restrict__ dst, const float* __restrict__ src, size_t count, int lane) {
+    if (kVec4) {   // (count % 4 == 0 and both 16-byte aligned: the host checked)
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        for (size_t i = lane; i < count / 4; i += kFilerWave) d4[i] = s4[i];
+    } else {
+        for (size_t i = lane; i < count; i += kFilerWave) dst[i] = src[i];
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void copy_items(T* __restrict__ dst, const T* __restrict__ src, size_t count, int lane) {
+    for (size_t i = lane; i < count; i += kFilerWave) dst[i] = src[i];
+}
+
+template <bool kVec4>
+__global__ __launch_bounds__(kFilerWave) void filer_append_kernel(StoreParams p, FilerParams f, mzreplay_file_moves mv) {
+    extern __shared__ double policy_row[];   // [A] one move's child_visits row, scattered by action, written out in order
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const mz::filer::Call call = *f.call;
+    const int k = f.played[e];
+    if (call.refused || k == 0) return;
+    const int E = f.E, A = p.A, M = mv.n_moves, obs = p.obs_floats;
+    const size_t L = p.L, L1 = L + 1;
+    const double S = static_cast<double>(mv.num_simulations);
+    float* row_obs = f.obs + static_cast<size_t>(e) * L1 * obs;
+    int32_t* row_act = f.actions + static_cast<size_t>(e) * L1;
+    double* row_rew = f.rewards + static_cast<size_t>(e) * L1;
+    int8_t* row_tp = f.to_play + static_cast<size_t>(e) * L1;
+    double* row_cv = f.child_visits + static_cast<size_t>(e) * L * A;
+    double* row_rv = f.root_values + static_cast<size_t>(e) * L;
+    int len = f.length[e];
+    int rank = f.offset[e];   // of the env's next finished game within the call
+    for (int m = 0; m < k; ++m) {
+        const size_t me = static_cast<size_t>(m) * E + e;
+        const int32_t* visits = move_block<int32_t>(mv.visits, mv.visits_stride, m) + static_cast<size_t>(e) * A;
+        const int32_t* legal = move_block<int32_t>(mv.legal, mv.legal_stride, m) + static_cast<size_t>(e) * A;
+        const int n_legal = move_block<int32_t>(mv.num_legal, mv.num_legal_stride, m)[e];   // (checked by filer_count_kernel)
+        for (int a = lane; a < A; a += kFilerWave) policy_row[a] = 0.0;
+        __syncthreads();
+        for (int i = lane; i < n_legal; i += kFilerWave) policy_row[legal[i]] = static_cast<double>(visits[i]) / S;
+        __syncthreads();
+        double* cv = row_cv + static_cast<size_t>(len) * A;
+        for (int a = lane; a < A; a += kFilerWave) cv[a] = policy_row[a];
+        const int to_play = mv.to_play ? move_block<int32_t>(mv.to_play, mv.to_play_stride, m)[e] : 0;
+        if (lane == 0) {
+            row_rv[len] = move_block<double>(mv.root_value_sum, mv.root_value_sum_stride, m)[e] / S;
+            row_act[len + 1] = move_block<int32_t>(mv.actions, mv.actions_stride, m)[e];
+            row_rew[len + 1] = static_cast<double>(mv.rewards[me]);
+            row_tp[len + 1] = static_cast<int8_t>(mv.players > 1 ? 1 - to_play : 0);
+        }
+        copy_floats<kVec4>(row_obs + static_cast<size_t>(len + 1) * obs, mv.obs_after + me * obs, obs, lane);
+        ++len;
+        if (mv.done[me]) {
+            __syncthreads();   // the row is complete (and visible to every lane) before it is copied
+            const int j = rank++;
+            if (mz::filer::survives(call, j)) {
+                const size_t slot = static_cast<size_t>(mz::filer::slot_of(mz::filer::game_id(call, j), p.G));
+                copy_floats<kVec4>(p.obs + slot * L1 * obs, row_obs, static_cast<size_t>(len + 1) * obs, lane);
+                copy_items(p.actions + slot * L1, row_act, len + 1, lane);
+                copy_items(p.rewards + slot * L1, row_rew, len + 1, lane);
+                copy_items(p.to_play + slot * L1, row_tp, len + 1, lane);
+                copy_items(p.child_visits + slot * L * A, row_cv, static_cast<size_t>(len) * A, lane);
+                copy_items(p.root_values + slot * L, row_rv, len, lane);
+                if (lane == 0) {
+                    p.length[slot] = len;
+                    p.has_reanalysed[slot] = 0;
+                }
+            }
+            if (lane == 0) {
+                f.list_env[call.list_base + j] = e;
+                f.list_len[call.list_base + j] = len;
+                atomicAdd(reinterpret_cast<unsigned long long*>(&f.state->counters.steps_played), static_cast<unsigned long long>(len));
+                if (mz::filer::survives(call, j))
+                    atomicAdd(reinterpret_cast<unsigned long long*>(&f.state->counters.total_samples), static_cast<unsigned long long>(len));
+            }
+            __syncthreads();   // the copies have read the row before the next game starts in it
+            len = 0;
+            copy_floats<kVec4>(row_obs, mv.obs_next + me * obs, obs, lane);
+            if (lane == 0) {
+                row_act[0] = 0;
+                row_rew[0] = 0.0;
+                int next = 0;   // the next move's recorded player: the envs' own after the batch's last move
+                if (mv.to_play) next = m + 1 < M ? move_block<int32_t>(mv.to_play, mv.to_play_stride, m + 1)[e] : mv.to_play_last[e];
+                row_tp[0] = static_cast<int8_t>(next);
+            }
+        }
+    }
+    if (lane == 0) f.length[e] = len;
+}
+
+__global__ __launch_bounds__(256) void filer_priorities_kernel(StoreParams p, FilerParams f) {
+    __shared__ float block_max[256];
+    const mz::filer::Call call = *f.call;
+    for (int j = call.dropped + blockIdx.x; j < call.n_new; j += gridDim.x) {
+        const int64_t id = mz::filer::game_id(call, j);
+        const int slot = mz::filer::slot_of(id, p.G);
+        const int n = p.length[slot];
+        float best = -INFINITY;
+        for (int i = threadIdx.x; i < p.L; i += blockDim.x) {
+            float pr = 0.f;
+            if (i < n) {
+                pr = position_priority(p, slot, n, i);
+                best = fmaxf(best, pr);
+            }
+            f.priorities[static_cast<size_t>(slot) * p.L + i] = pr;
+        }
+        block_max[threadIdx.x] = best;
+        __syncthreads();
+        for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+            if (threadIdx.x < s) block_max[threadIdx.x] = fmaxf(block_max[threadIdx.x], block_max[threadIdx.x + s]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            f.game_priority[slot] = block_max[0];
+            if (f.game_id) f.game_id[slot] = id;
+        }
+        __syncthreads();
+    }
+}
+
+// every env starts a game (mzhist_begin)
+__global__ __launch_bounds__(256) void filer_begin_kernel(StoreParams p, FilerParams f, const float* __restrict__ first_obs,
+                                                          const int32_t* __restrict__ first_to_play) {
+    const int e = blockIdx.x;
+    const size_t L1 = static_cast<size_t>(p.L) + 1;
+    for (int t = threadIdx.x; t < p.obs_floats; t += blockDim.x)
+        f.obs[static_cast<size_t>(e) * L1 * p.obs_floats + t] = first_obs[static_cast<size_t>(e) * p.obs_floats + t];
+    if (threadIdx.x == 0) {
+        f.actions[e * L1] = 0;
+        f.rewards[e * L1] = 0.0;
+        f.to_play[e * L1] = static_cast<int8_t>(first_to_play ? first_to_play[e] : 0);
+        f.length[e] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void gather_priorities_kernel(StoreParams p, FilerParams f, const int32_t* __restrict__ slots,
+                                                                float* __restrict__ priorities,
+                                                                float* __restrict__ game_priority) {
+    const int g = blockIdx.x, slot = slots[g];
+    for (int i = threadIdx.x; i < p.L; i += blockDim.x)
+        priorities[static_cast<size_t>(g) * p.L + i] = f.priorities[static_cast<size_t>(slot) * p.L + i];
+    if (threadIdx.x == 0) game_priority[g] = f.game_priority[slot];
+}
+
 }  // namespace
 
 struct mzreplay {
@@ -583,6 +856,20 @@ struct mzreplay {
     SamplerParams sp{};
     int64_t next_game_id = 0;        // id of the next game mzreplay_add_games stores (sampler on)
     size_t sampler_batch = 0;        // samples the per-batch scratch holds
+    mzreplay_filer* filer = nullptr; // the device filer bound to this store (at most one)
+};
+
+struct mzreplay_filer {
+    mzreplay* store = nullptr;
+    FilerParams f{};
+    std::vector<void*> allocs;
+    int64_t pending_bound = 0;       // games the unsynced calls can have filed at most (E x M each)
+    int32_t* d_gather_slots = nullptr;   // mzreplay_filer_priorities' staging
+    float* d_gather = nullptr;
+    size_t gather_games = 0;
+    bool own_priorities = false;     // f.priorities / f.game_priority are the filer's own arrays (sampler off)
+    std::vector<int32_t> h_env, h_len;   // games drained from the device list since the last sync
+    std::vector<int32_t> out_env, out_len;   // what the last mzreplay_filer_sync handed out
 };
 
 namespace {
@@ -670,6 +957,7 @@ int mzreplay_create(const mzreplay_config* c, mzreplay** out) {
 
 void mzreplay_destroy(mzreplay* s) {
     if (!s) return;
+    if (s->filer) mzreplay_filer_destroy(s->filer);
     for (void* ptr : s->allocs) (void)hipFree(ptr);
     delete s;
 }
@@ -945,6 +1233,283 @@ int mzreplay_update_priorities(mzreplay* s, int32_t batch, const int64_t* game_i
     RP_HIP(s, hipGetLastError());
     game_priority_kernel<<<dim3(batch), dim3(64), 0, stream>>>(s->p, s->sp, game_ids);
     RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+// ---- reading games back, and the device filer's entries ----------------------------------------------------------------
+int mzreplay_read_games(mzreplay* s, int32_t n, const int32_t* slots, int32_t* lengths, float* observations, int32_t* actions,
+                        double* rewards, int32_t* to_play, double* child_visits, double* root_values, void* stream_) {
+    if (!s || !slots) return fail(s, "mzreplay_read_games: null argument");
+    if (n <= 0) return 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const StoreParams& p = s->p;
+    const size_t L = p.L, L1 = L + 1, A = p.A, obs = p.obs_floats;
+    for (int g = 0; g < n; ++g)
+        if (slots[g] < 0 || slots[g] >= p.G) return fail(s, "mzreplay_read_games: slot out of range");
+    std::vector<int32_t> all(static_cast<size_t>(p.G));
+    RP_HIP(s, hipMemcpyAsync(all.data(), p.length, sizeof(int32_t) * p.G, hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    std::vector<int8_t> tp8(to_play ? static_cast<size_t>(n) * L1 : 0);
+    if (observations) std::memset(observations, 0, sizeof(float) * n * L1 * obs);
+    if (actions) std::memset(actions, 0, sizeof(int32_t) * n * L1);
+    if (rewards) std::memset(rewards, 0, sizeof(double) * n * L1);
+    if (to_play) std::memset(to_play, 0, sizeof(int32_t) * n * L1);
+    if (child_visits) std::memset(child_visits, 0, sizeof(double) * n * L * A);
+    if (root_values) std::memset(root_values, 0, sizeof(double) * n * L);
+    for (int g = 0; g < n; ++g) {
+        const size_t slot = static_cast<size_t>(slots[g]), o = static_cast<size_t>(g);
+        const int32_t stored = all[slot];
+        if (stored < 0 || stored > p.L) return fail(s, "mzreplay_read_games: a stored length is out of range");
+        const size_t len = static_cast<size_t>(stored);
+        if (lengths) lengths[g] = stored;
+        if (observations)
+            RP_HIP(s, hipMemcpyAsync(observations + o * L1 * obs, p.obs + slot * L1 * obs, sizeof(float) * (len + 1) * obs,
+                                     hipMemcpyDeviceToHost, stream));
+        if (actions)
+            RP_HIP(s, hipMemcpyAsync(actions + o * L1, p.actions + slot * L1, sizeof(int32_t) * (len + 1), hipMemcpyDeviceToHost, stream));
+        if (rewards)
+            RP_HIP(s, hipMemcpyAsync(rewards + o * L1, p.rewards + slot * L1, sizeof(double) * (len + 1), hipMemcpyDeviceToHost, stream));
+        if (to_play) RP_HIP(s, hipMemcpyAsync(tp8.data() + o * L1, p.to_play + slot * L1, len + 1, hipMemcpyDeviceToHost, stream));
+        if (child_visits && len)
+            RP_HIP(s, hipMemcpyAsync(child_visits + o * L * A, p.child_visits + slot * L * A, sizeof(double) * len * A,
+                                     hipMemcpyDeviceToHost, stream));
+        if (root_values && len)
+            RP_HIP(s, hipMemcpyAsync(root_values + o * L, p.root_values + slot * L, sizeof(double) * len, hipMemcpyDeviceToHost, stream));
+    }
+    RP_HIP(s, hipStreamSynchronize(stream));
+    if (to_play)
+        for (int g = 0; g < n; ++g)
+            for (int32_t i = 0; i <= all[static_cast<size_t>(slots[g])]; ++i)
+                to_play[static_cast<size_t>(g) * L1 + i] = tp8[static_cast<size_t>(g) * L1 + i];
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+template <typename T>
+int filer_alloc(mzreplay_filer* fl, T** out, size_t count) {
+    mzreplay* s = fl->store;
+    void* ptr = nullptr;
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    RP_HIP(s, hipMalloc(&ptr, bytes));
+    RP_HIP(s, hipMemset(ptr, 0, bytes));
+    fl->allocs.push_back(ptr);
+    s->bytes += static_cast<int64_t>(bytes);
+    *out = static_cast<T*>(ptr);
+    return 0;
+}
+
+// the games of the unsynced calls, moved from the device list to the host arrays mzreplay_filer_sync hands out
+int filer_drain(mzreplay_filer* fl, FilerState* state_out, hipStream_t stream) {
+    mzreplay* s = fl->store;
+    FilerState st{};
+    RP_HIP(s, hipMemcpyAsync(&st, fl->f.state, sizeof(st), hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    if (st.pending < 0 || st.pending > fl->f.list_cap) return fail(s, "mzreplay_filer_sync: the device list is corrupt");
+    if (st.pending > 0) {
+        const size_t have = fl->h_env.size(), more = static_cast<size_t>(st.pending);
+        fl->h_env.resize(have + more);
+        fl->h_len.resize(have + more);
+        RP_HIP(s, hipMemcpyAsync(fl->h_env.data() + have, fl->f.list_env, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
+        RP_HIP(s, hipMemcpyAsync(fl->h_len.data() + have, fl->f.list_len, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
+    }
+    // pending and error are adjacent: both start again at zero
+    RP_HIP(s, hipMemsetAsync(&fl->f.state->pending, 0, 2 * sizeof(int32_t), stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    fl->pending_bound = 0;
+    if (state_out) *state_out = st;
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mzreplay_filer_create(mzreplay* s, int32_t num_envs, mzreplay_filer** out) {
+    if (!s || !out) return fail(s, "mzreplay_filer_create: null store or output");
+    *out = nullptr;
+    if (num_envs <= 0) return fail(s, "mzreplay_filer_create: num_envs must be positive");
+    if (s->filer) return fail(s, "mzreplay_filer_create: the store already has a filer (one actor files into one store)");
+    if (s->p.stacked != 0) return fail(s, "mzreplay_filer_create: device envs do not stack observations");
+    RP_HIP(s, hipSetDevice(s->cfg.device));
+    mzreplay_filer* fl = new mzreplay_filer();
+    fl->store = s;
+    FilerParams& f = fl->f;
+    const StoreParams& p = s->p;
+    const size_t E = static_cast<size_t>(num_envs), L = p.L, L1 = L + 1;
+    f.E = num_envs;
+    int rc = 0;
+    rc |= filer_alloc(fl, &f.obs, E * L1 * p.obs_floats);
+    rc |= filer_alloc(fl, &f.actions, E * L1);
+    rc |= filer_alloc(fl, &f.rewards, E * L1);
+    rc |= filer_alloc(fl, &f.to_play, E * L1);
+    rc |= filer_alloc(fl, &f.child_visits, E * L * p.A);
+    rc |= filer_alloc(fl, &f.root_values, E * L);
+    rc |= filer_alloc(fl, &f.length, E);
+    rc |= filer_alloc(fl, &f.played, E);
+    rc |= filer_alloc(fl, &f.count, E);
+    rc |= filer_alloc(fl, &f.offset, E);
+    rc |= filer_alloc(fl, &f.state, 1);
+    rc |= filer_alloc(fl, &f.call, 1);
+    if (rc) {
+        const std::string msg = s->error;
+        mzreplay_filer_destroy(fl);
+        return fail(s, msg.empty() ? "mzreplay_filer_create: device allocation failed" : msg);
+    }
+    s->filer = fl;
+    *out = fl;
+    return 0;
+}
+
+void mzreplay_filer_destroy(mzreplay_filer* fl) {
+    if (!fl) return;
+    (void)hipDeviceSynchronize();
+    for (void* ptr : fl->allocs) (void)hipFree(ptr);
+    if (fl->store && fl->store->filer == fl) fl->store->filer = nullptr;
+    delete fl;
+}
+
+int mzreplay_filer_begin(mzreplay_filer* fl, const float* first_observations, const int32_t* first_to_play, void* stream_) {
+    if (!fl || !first_observations) return fail(fl ? fl->store : nullptr, "mzreplay_filer_begin: null argument");
+    mzreplay* s = fl->store;
+    filer_begin_kernel<<<dim3(fl->f.E), dim3(256), 0, static_cast<hipStream_t>(stream_)>>>(s->p, fl->f, first_observations,
+                                                                                          first_to_play);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+int mzreplay_filer_set_counters(mzreplay_filer* fl, const int64_t* counters, void* stream_) {
+    if (!fl || !counters) return fail(fl ? fl->store : nullptr, "mzreplay_filer_set_counters: null argument");
+    mzreplay* s = fl->store;
+    if (counters[0] < 0 || counters[1] < 0 || counters[1] > s->p.G || counters[1] > counters[0] || counters[2] < 0 || counters[3] < 0)
+        return fail(s, "mzreplay_filer_set_counters: counters out of range");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    mz::filer::Counters c{counters[0], counters[1], counters[2], counters[3]};
+    RP_HIP(s, hipMemcpyAsync(&fl->f.state->counters, &c, sizeof(c), hipMemcpyHostToDevice, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));   // (c is a local)
+    s->next_game_id = counters[0];
+    return 0;
+}
+
+int mzreplay_filer_file(mzreplay_filer* fl, const mzreplay_file_moves* mv, void* stream_) {
+    if (!fl || !mv) return fail(fl ? fl->store : nullptr, "mzreplay_filer_file: null argument");
+    mzreplay* s = fl->store;
+    if (!mv->actions || !mv->visits || !mv->root_value_sum || !mv->legal || !mv->num_legal || !mv->rewards || !mv->done ||
+        !mv->obs_after || !mv->obs_next || (mv->to_play && !mv->to_play_last))
+        return fail(s, "mzreplay_filer_file: null argument");
+    const StoreParams& p = s->p;
+    FilerParams& f = fl->f;
+    if (mv->n_moves <= 0) return 0;
+    if (mv->num_simulations <= 0 || mv->players < 1 || mv->players > 2)
+        return fail(s, "mzreplay_filer_file: num_simulations must be positive and players 1 or 2");
+    const int64_t most = static_cast<int64_t>(f.E) * mv->n_moves;   // games the batch can finish
+    if (most > (int64_t{1} << 30)) return fail(s, "mzreplay_filer_file: the batch is too large");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (fl->pending_bound + most > f.list_cap) {
+        // the list grows: what it holds goes to the host first (blocking, like any allocation; a warmed-up actor that
+        // syncs after every batch does not come here again)
+        if (filer_drain(fl, nullptr, stream)) return -1;
+        if (most > f.list_cap) {
+            int32_t *env = nullptr, *len = nullptr;
+            if (filer_alloc(fl, &env, static_cast<size_t>(most)) || filer_alloc(fl, &len, static_cast<size_t>(most))) return -1;
+            f.list_env = env;
+            f.list_len = len;
+            f.list_cap = static_cast<int32_t>(most);
+        }
+    }
+    if (s->sampler_on) {
+        f.priorities = s->sp.priorities;
+        f.game_priority = s->sp.game_priority;
+        f.game_id = s->sp.game_id;
+    } else if (!fl->own_priorities) {
+        if (filer_alloc(fl, &f.priorities, static_cast<size_t>(p.G) * p.L) || filer_alloc(fl, &f.game_priority, static_cast<size_t>(p.G)))
+            return -1;
+        f.game_id = nullptr;
+        fl->own_priorities = true;
+    }
+    fl->pending_bound += most;
+    filer_count_kernel<<<dim3((f.E + 255) / 256), dim3(256), 0, stream>>>(p, f, *mv);
+    RP_HIP(s, hipGetLastError());
+    filer_scan_kernel<<<dim3(1), dim3(kScanThreads), 0, stream>>>(p, f);
+    RP_HIP(s, hipGetLastError());
+    auto aligned = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; };
+    const bool vec4 = p.obs_floats % 4 == 0 && aligned(mv->obs_after) && aligned(mv->obs_next);
+    const size_t lds = sizeof(double) * p.A;
+    if (vec4)
+        filer_append_kernel<true><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+    else
+        filer_append_kernel<false><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+    RP_HIP(s, hipGetLastError());
+    const int64_t grid = std::min<int64_t>(std::min<int64_t>(most, p.G), 2048);
+    filer_priorities_kernel<<<dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream>>>(p, f);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+int mzreplay_filer_sync(mzreplay_filer* fl, int32_t* n_new, const int32_t** env_index, const int32_t** lengths,
+                        int64_t* first_game_id, int64_t* counters, void* stream_) {
+    if (!fl || !n_new) return fail(fl ? fl->store : nullptr, "mzreplay_filer_sync: null argument");
+    mzreplay* s = fl->store;
+    FilerState st{};
+    if (filer_drain(fl, &st, static_cast<hipStream_t>(stream_))) return -1;
+    s->next_game_id = st.counters.next_game_id;
+    if (counters) {
+        counters[0] = st.counters.next_game_id;
+        counters[1] = st.counters.games_stored;
+        counters[2] = st.counters.total_samples;
+        counters[3] = st.counters.steps_played;
+    }
+    if (st.error) {
+        // (the batch that raised it filed nothing; games of earlier, unsynced batches stay for the next sync)
+        *n_new = 0;
+        if (st.error & mz::filer::kErrLegal)
+            return fail(s, "mzhist_file: a legal-action count outside [0, A] or a legal action outside [0, A)");
+        if (st.error & mz::filer::kErrOverflow) return fail(s, "mzhist_file: a game outgrew max_moves");
+        return fail(s, "mzreplay_filer_file: the list of filed games was full");
+    }
+    fl->out_env.swap(fl->h_env);
+    fl->out_len.swap(fl->h_len);
+    fl->h_env.clear();
+    fl->h_len.clear();
+    *n_new = static_cast<int32_t>(fl->out_env.size());
+    if (env_index) *env_index = fl->out_env.data();
+    if (lengths) *lengths = fl->out_len.data();
+    if (first_game_id) *first_game_id = st.counters.next_game_id - static_cast<int64_t>(fl->out_env.size());
+    return 0;
+}
+
+int mzreplay_filer_lengths(mzreplay_filer* fl, int32_t* lengths, void* stream_) {
+    if (!fl || !lengths) return fail(fl ? fl->store : nullptr, "mzreplay_filer_lengths: null argument");
+    mzreplay* s = fl->store;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    RP_HIP(s, hipMemcpyAsync(lengths, fl->f.length, sizeof(int32_t) * fl->f.E, hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int mzreplay_filer_priorities(mzreplay_filer* fl, int32_t n, const int32_t* slots, float* priorities, float* game_priority,
+                              void* stream_) {
+    if (!fl || !slots || !priorities || !game_priority) return fail(fl ? fl->store : nullptr, "mzreplay_filer_priorities: null argument");
+    mzreplay* s = fl->store;
+    if (n <= 0) return 0;
+    if (!fl->f.priorities) return fail(s, "mzreplay_filer_priorities: nothing has been filed yet");
+    const StoreParams& p = s->p;
+    for (int g = 0; g < n; ++g)
+        if (slots[g] < 0 || slots[g] >= p.G) return fail(s, "mzreplay_filer_priorities: slot out of range");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t L = p.L, count = static_cast<size_t>(n);
+    if (count > fl->gather_games) {
+        if (filer_alloc(fl, &fl->d_gather_slots, count) || filer_alloc(fl, &fl->d_gather, count * (L + 1))) return -1;
+        fl->gather_games = count;
+    }
+    float* d_pri = fl->d_gather;
+    float* d_game = fl->d_gather + count * L;
+    RP_HIP(s, hipMemcpyAsync(fl->d_gather_slots, slots, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
+    gather_priorities_kernel<<<dim3(n), dim3(256), 0, stream>>>(p, fl->f, fl->d_gather_slots, d_pri, d_game);
+    RP_HIP(s, hipGetLastError());
+    RP_HIP(s, hipMemcpyAsync(priorities, d_pri, sizeof(float) * count * L, hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipMemcpyAsync(game_priority, d_game, sizeof(float) * count, hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
     return 0;
 }
 

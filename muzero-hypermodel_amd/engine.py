@@ -671,6 +671,25 @@ class BatchedMCTS:
                                                 ctypes.byref(self._ring_moves)))
         return self._pinned_bytes(base.value, stride.value * self._ring_moves.value), stride.value, list(offsets)
 
+    def moves_device_ring(self):
+        """The DEVICE ring moves_collect downloads from: dict(actions, visits, root_value_sum = device addresses of move
+        0's arrays, stride = bytes from one move's block to the next).  A batch's blocks stay until the next batch's
+        searches overwrite them (include/mzmcts.h mzmcts_moves_device_ring)."""
+        base, stride, moves = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int32()
+        offsets = (ctypes.c_int64 * 8)()
+        self._check(self._lib.mzmcts_moves_device_ring(self._h, ctypes.byref(base), ctypes.byref(stride), offsets,
+                                                       ctypes.byref(moves)))
+        return dict(actions=base.value + offsets[0], visits=base.value + offsets[1], root_value_sum=base.value + offsets[2],
+                    stride=stride.value)
+
+    def moves_inputs_device_ring(self):
+        """The same for what moves_inputs unpacks (device-input batches): num_legal, to_play, legal, stride."""
+        base, stride = ctypes.c_void_p(), ctypes.c_int64()
+        offsets = (ctypes.c_int64 * 3)()
+        self._check(self._lib.mzmcts_moves_inputs_device_ring(self._h, ctypes.byref(base), ctypes.byref(stride), offsets))
+        return dict(num_legal=base.value + offsets[0], to_play=base.value + offsets[1], legal=base.value + offsets[2],
+                    stride=stride.value)
+
     def moves_collect(self, copy=True):
         """Wait for the queued searches.  Returns dict(moves_done [E], actions [M,E], visits [M,E,A],
         root_value_sum [M,E], root_predicted [M,E], max_depth [M,E]); M = searches queued.

@@ -12,10 +12,16 @@ csrc/replay_sampler.h): priorities, game priorities and a numpy stream of its ow
 the sampler and the target kernels and returns without waiting, and `update_priorities` takes the trainer's device
 tensor -- draw for draw what the host path returns.
 
+With `DeviceSelfPlay.file_to(replay_buffer)` the producer side is on the device too (include/mzreplay.h mzreplay_filer_*,
+csrc/replay_filer.h): the actor's finished games go from the search engine's and the environment kernels' device rings
+straight into the store's slots, and only their lengths (4 bytes per game) and the counters come back, once per move
+batch (`sync_filing`).  Such games have no host copy: `download_games` reads them back when someone asks.
+
 Not carried over: Ray (`.remote`), `get_buffer()`'s live GameHistory objects are only kept when games
 arrive as GameHistory (save_game), and `update_game_history` (Reanalyse).
 """
 import ctypes
+import itertools
 
 import numpy
 import torch
@@ -106,6 +112,8 @@ class ReplayBuffer:
                 raise NotImplementedError("device sampling draws absorbing actions as indices: action_space must be range(A)")
             self._check(self._lib.mzreplay_sampler_enable(self._h, int(config.seed) & 0xFFFFFFFF, int(self.num_played_games)))
         self.buffer = {}                                  # game_id -> dict(length, priorities, game_priority[, history])
+        self._filer = None                                # device filer handle (attach_filer)
+        self._filing_pending = False                      # a move batch was filed on the device and not synced yet
         for game_history in (initial_buffer or {}).values():
             self.save_game(game_history)
 
@@ -118,6 +126,9 @@ class ReplayBuffer:
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def close(self):
+        if getattr(self, "_filer", None):
+            self._lib.mzreplay_filer_destroy(self._filer)
+            self._filer = None
         if getattr(self, "_h", None):
             self._lib.mzreplay_destroy(self._h)
             self._h = None
@@ -166,6 +177,7 @@ class ReplayBuffer:
                   padded(packed.root_values, self.L, numpy.float64), [None] * n_games, shared_storage)
 
     def _add(self, lengths, obs, act, rew, tp, cv, rv, histories, shared_storage):
+        self._sync_if_pending()
         n_games = len(lengths)
         ids = numpy.arange(self.num_played_games, self.num_played_games + n_games)
         slots = numpy.ascontiguousarray(ids % self.capacity, dtype=numpy.int32)
@@ -199,15 +211,148 @@ class ReplayBuffer:
                 del_id = self.num_played_games - len(self.buffer)
                 self.total_samples -= self.buffer[del_id]["length"]
                 del self.buffer[del_id]
+        if self._filer is not None:
+            self._push_counters()
         if shared_storage:
             shared_storage.set_info("num_played_games", self.num_played_games)
             shared_storage.set_info("num_played_steps", self.num_played_steps)
 
     def get_buffer(self):
-        return {gid: e["history"] for gid, e in self.buffer.items()}
+        """game id -> GameHistory.  Games that were filed on the device have no host copy: they are read back here."""
+        self._sync_if_pending()
+        missing = [gid for gid, e in self.buffer.items() if dict.get(e, "history") is None]
+        packed = self.download_games(missing) if missing else None
+        fetched = {gid: packed.history(i) for i, gid in enumerate(missing)}
+        return {gid: fetched[gid] if gid in fetched else e["history"] for gid, e in self.buffer.items()}
+
+    # ---- games filed on the device (include/mzreplay.h mzreplay_filer_*) ---------------------------------
+    def attach_filer(self, num_envs):
+        """Bind the store's device filer to an actor of `num_envs` envs (DeviceSelfPlay.file_to calls this).  One actor
+        files into one store: ids are handed out in the order of the filings on one stream."""
+        if self._filer is not None:
+            raise NotImplementedError("this replay buffer already receives the games of an actor that called file_to(): "
+                                      "several actors filing into one store are not supported (game ids would depend on "
+                                      "the order of their streams); use on_games -> save_games for the others")
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_create(self._h, int(num_envs), ctypes.byref(handle)))
+        self._filer, self._filer_envs = handle, int(num_envs)
+        self._push_counters()
+
+    def _push_counters(self):
+        counters = numpy.array([self.num_played_games, len(self.buffer), self.total_samples, self.num_played_steps],
+                               dtype=numpy.int64)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_set_counters(self._filer, ptr(counters, _native.c_i64_p), self._stream()))
+
+    def filer_begin(self, first_observations, first_to_play=None):
+        """Every env of the filing actor starts a game: device tensors f32 [E, ...] and int32 [E] (None: player 0)."""
+        assert first_observations.is_cuda and first_observations.dtype == torch.float32 and first_observations.is_contiguous()
+        assert first_observations.numel() == self._filer_envs * self.C * self.H * self.W
+        assert first_to_play is None or (first_to_play.is_cuda and first_to_play.dtype == torch.int32
+                                         and first_to_play.numel() == self._filer_envs)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_begin(self._filer, first_observations.data_ptr(),
+                                                       None if first_to_play is None else first_to_play.data_ptr(),
+                                                       self._stream()))
+
+    def filer_file(self, moves):
+        """Queue the filing of a move batch (a _native.MzReplayFileMoves of device pointers) on the current stream."""
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_file(self._filer, ctypes.byref(moves), self._stream()))
+        self._filing_pending = True
+
+    def filer_lengths(self):
+        """Moves played so far in every env's running game (int32 [E]; waits for the device)."""
+        out = numpy.zeros(self._filer_envs, dtype=numpy.int32)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_lengths(self._filer, ptr(out, c_i32_p), self._stream()))
+        return out
+
+    def _sync_if_pending(self):
+        if self._filing_pending:
+            self.sync_filing()
+
+    def sync_filing(self, shared_storage=None):
+        """The games filed on the device since the last sync join the host bookkeeping: `buffer` entries (length,
+        history=None), num_played_games / num_played_steps / total_samples from the device counters and, for host-side
+        prioritised sampling, the new games' initial priorities.  Returns (env_index, length, game_id) host arrays.
+        Small and blocking: 4 bytes per game come back."""
+        if self._filer is None:
+            raise RuntimeError("sync_filing: no actor files into this buffer (DeviceSelfPlay.file_to)")
+        n, first = ctypes.c_int32(), ctypes.c_int64()
+        env_p, len_p = ctypes.c_void_p(), ctypes.c_void_p()
+        counters = numpy.zeros(4, dtype=numpy.int64)
+        self._filing_pending = False
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_sync(self._filer, ctypes.byref(n), ctypes.byref(env_p), ctypes.byref(len_p),
+                                                      ctypes.byref(first), ptr(counters, _native.c_i64_p), self._stream()))
+        count = n.value
+
+        def arr(p):
+            if count == 0:
+                return numpy.zeros(0, dtype=numpy.int32)
+            return numpy.ctypeslib.as_array(ctypes.cast(p, c_i32_p), shape=(count,)).copy()
+        env_index, lengths = arr(env_p), arr(len_p)
+        ids = first.value + numpy.arange(count, dtype=numpy.int64)
+        if count:
+            keep_from = max(0, count - self.capacity)            # a call can finish more games than there are slots
+            kept_ids, kept_len = ids[keep_from:].tolist(), lengths[keep_from:].tolist()
+            if self.device_sampling:
+                entries = [_DeviceEntry(self, gid, length=n_moves, history=None) for gid, n_moves in zip(kept_ids, kept_len)]
+            else:
+                entries = [dict(length=n_moves, history=None) for n_moves in kept_len]
+                if self.config.PER:
+                    slots = numpy.ascontiguousarray(numpy.asarray(kept_ids) % self.capacity, dtype=numpy.int32)
+                    pri = numpy.zeros((len(kept_ids), self.L), dtype=numpy.float32)
+                    game_pri = numpy.zeros(len(kept_ids), dtype=numpy.float32)
+                    with torch.cuda.device(self.device):
+                        self._check(self._lib.mzreplay_filer_priorities(self._filer, len(kept_ids), ptr(slots, c_i32_p),
+                                                                        ptr(pri, c_f32_p), ptr(game_pri, c_f32_p),
+                                                                        self._stream()))
+                    for g, entry in enumerate(entries):
+                        entry["priorities"] = pri[g, : kept_len[g]].copy()
+                        entry["game_priority"] = game_pri[g]
+            self.buffer.update(zip(kept_ids, entries))
+            oldest = int(counters[0]) - int(counters[1])
+            for gid in [g for g in itertools.takewhile(lambda g: g < oldest, self.buffer)]:
+                del self.buffer[gid]
+        self.num_played_games, stored, self.total_samples, self.num_played_steps = (int(v) for v in counters)
+        assert stored == len(self.buffer), "the device filer's game count left the host's"
+        if shared_storage:
+            shared_storage.set_info("num_played_games", self.num_played_games)
+            shared_storage.set_info("num_played_steps", self.num_played_steps)
+        return env_index, lengths, ids
+
+    def download_games(self, game_ids):
+        """Stored games read back from the device as a self_play.PackedGames (rows max_moves wide; rewards float64 as the
+        store holds them; env_index -1: the store does not keep it)."""
+        from .self_play import PackedGames
+        self._sync_if_pending()
+        game_ids = [int(g) for g in game_ids]
+        for gid in game_ids:
+            if gid not in self.buffer:
+                raise KeyError(f"game {gid} is not in the buffer")
+        n = len(game_ids)
+        slots = numpy.ascontiguousarray([self._slot(g) for g in game_ids], dtype=numpy.int32)
+        lengths = numpy.zeros(n, dtype=numpy.int32)
+        obs = numpy.zeros((n, self.L + 1, self.C, self.H, self.W), dtype=numpy.float32)
+        act = numpy.zeros((n, self.L + 1), dtype=numpy.int32)
+        rew = numpy.zeros((n, self.L + 1), dtype=numpy.float64)
+        tp = numpy.zeros((n, self.L + 1), dtype=numpy.int32)
+        cv = numpy.zeros((n, self.L, self.A), dtype=numpy.float64)
+        rv = numpy.zeros((n, self.L), dtype=numpy.float64)
+        if n:
+            with torch.cuda.device(self.device):
+                self._check(self._lib.mzreplay_read_games(self._h, n, ptr(slots, c_i32_p), ptr(lengths, c_i32_p),
+                                                          ptr(obs, c_f32_p), ptr(act, c_i32_p), ptr(rew, c_f64_p),
+                                                          ptr(tp, c_i32_p), ptr(cv, c_f64_p), ptr(rv, c_f64_p), self._stream()))
+        return PackedGames(env_index=numpy.full(n, -1, dtype=numpy.int32), length=lengths, observations=obs, actions=act,
+                           rewards=rew, to_play=tp, child_visits=cv, root_values=rv)
 
     # ---- sampling (replay_buffer.py:135-195) -----------------------------------------------------------
     def sample_game(self, force_uniform=False):
+        self._sync_if_pending()
         game_prob = None
         if self.config.PER and not force_uniform:
             game_probs = numpy.array([e["game_priority"] for e in self.buffer.values()], dtype="float32")
@@ -220,6 +365,7 @@ class ReplayBuffer:
         return game_id, self.buffer[game_id], game_prob
 
     def sample_n_games(self, n_games, force_uniform=False):
+        self._sync_if_pending()
         ids = list(self.buffer.keys())
         if self.config.PER and not force_uniform:
             game_probs = numpy.array([self.buffer[g]["game_priority"] for g in ids], dtype="float32")
@@ -311,6 +457,7 @@ class ReplayBuffer:
         a DeviceIndexBatch and float32 / int64 CUDA tensors, queued on the current stream without waiting; `out` (a dict
         with the trainer's keys: observations, actions, values, rewards, policies, weights, gradient_scales) receives
         them in place."""
+        self._sync_if_pending()
         if self.device_sampling:
             return self._get_batch_device(out)
         if out is not None:
@@ -362,6 +509,7 @@ class ReplayBuffer:
     # ---- Reanalyse's two ends (replay_buffer.py:335-356) ------------------------------------------------
     def game_observations(self, game_id):
         """Stacked observations of every position of a stored game: CUDA tensor [n, C', H, W]."""
+        self._sync_if_pending()
         n = self.buffer[game_id]["length"]
         stacked = int(self.config.stacked_observations)
         out = torch.empty((n, self.C + stacked * (self.C + 1), self.H, self.W), dtype=torch.float32, device=self.device)
@@ -371,6 +519,7 @@ class ReplayBuffer:
 
     def set_reanalysed_values(self, game_id, values):
         """game_history.reanalysed_predicted_root_values = values (float32 [n], tensor or array)."""
+        self._sync_if_pending()
         if game_id not in self.buffer:      # the game could have been removed since its selection
             return
         n = self.buffer[game_id]["length"]
@@ -383,6 +532,7 @@ class ReplayBuffer:
 
     # ---- priorities (replay_buffer.py:197-220) ---------------------------------------------------------
     def update_priorities(self, priorities, index_info):
+        self._sync_if_pending()
         if self.device_sampling:
             dev = self.device
             if not isinstance(index_info, DeviceIndexBatch):

@@ -592,6 +592,12 @@ class ManyEnvLoop:
             else:
                 temperature = 0                          # best action, no exploration noise in the sampling
             finished = self._play_pass(temperature, cfg.temperature_threshold, moves_per_pass)
+            if getattr(self, "_filed_to", None) is not None:
+                # the pass filed its games on the device: they are in the store, only the counters travel
+                if talker:
+                    shared_storage.set_info("num_played_games", self._filed_to.num_played_games)
+                    shared_storage.set_info("num_played_steps", self._filed_to.num_played_steps)
+                finished = []
             for e, game_history in finished:
                 game_history.weights_version = (int(st["started"][e]), st["version"])
                 st["started"][e] = st["version"]
@@ -876,6 +882,18 @@ class HistoryFiler:
                            root_values=arr(ptrs[7], ct.c_double, (count, W)))
 
 
+class FiledGames(typing.NamedTuple):
+    """The games a move batch finished when the actor files on the device (DeviceSelfPlay.file_to): they are in the replay
+    store already; what comes back is 4 bytes per game and the ids the store gave them.  Host arrays, in the order
+    PackedGames would have had (env-major, then in move order)."""
+    env_index: numpy.ndarray     # int32 [n]
+    length: numpy.ndarray        # int32 [n] moves
+    game_id: numpy.ndarray       # int64 [n] consecutive
+
+    def __len__(self):
+        return len(self.env_index)
+
+
 ENV_OUTPUTS = ("reward", "done", "obs_after", "obs_next")    # what the environment kernels return for a move of a batch
 
 
@@ -931,7 +949,8 @@ class DeviceSelfPlay(ManyEnvLoop):
         # the running games: one packed row per env in the native filer, long enough for a game of config.max_moves moves
         self._filer = HistoryFiler(E, int(config.max_moves) + 1, self.envs.observation_shape, self.envs.A)
         self._filer.begin(self._cur["obs"], self._cur["to_play"])
-        self._len = self._filer.lengths()       # moves played in env e's current game (the filer's own counters)
+        self._host_len = self._filer.lengths()  # moves played in env e's current game (the filer's own counters)
+        self._filed_to = None                   # the ReplayBuffer whose device filer takes the games (file_to)
         self._step_is_batch = False             # step_begin queued the whole move as a one-move batch (an opponent's turn)
         self._batch_ready = None                # (n_moves, temperature) of the batch drawn and uploaded ahead (play_moves)
         self._dev_batch = None                  # DeviceBatch being queued
@@ -939,6 +958,77 @@ class DeviceSelfPlay(ManyEnvLoop):
         self._copy_stream = torch.cuda.Stream(device=self.device)    # downloads of a batch's env outputs
         self._ring = None                       # env outputs of a batch on the device, sized by the first batch (_move_ring)
         self._pinned, self._flip = None, 0      # their two alternating host sets (_next_pinned)
+
+    @property
+    def _len(self):
+        """Moves played in every env's running game: the host filer's counters, or the device filer's (a small download)."""
+        return self._host_len if self._filed_to is None else self._filed_to.filer_lengths()
+
+    def file_to(self, replay_buffer):
+        """From now on finished games go into `replay_buffer`'s store on the device (include/mzreplay.h
+        mzreplay_filer_file): play_moves queues the filing behind the batch's last environment kernel, no observation,
+        policy row or value of a game visits the host, and `on_games` receives a FiledGames (env_index, length, game_id)
+        instead of a PackedGames.  Before the first move only, same device only; step(), on_game and opponent modes are
+        not available afterwards (evaluation games are never saved to a replay buffer)."""
+        if self._filed_to is not None:
+            raise ValueError("file_to was called before")
+        if self.moves_played or self._batch_ready or self._dev_batch is not None or self._unfiled is not None:
+            raise ValueError("file_to comes before the first move: the running games live in the host filer by now")
+        store_device = torch.device(replay_buffer.device)
+        mine = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        if store_device != mine:
+            raise ValueError(f"file_to: the replay buffer lives on {store_device}, the actor on {mine}")
+        if (replay_buffer.L != int(self.config.max_moves) or replay_buffer.A != self.envs.A
+                or (replay_buffer.C, replay_buffer.H, replay_buffer.W) != tuple(self.envs.observation_shape)):
+            raise ValueError("file_to: the replay buffer was built for another game shape or move limit")
+        replay_buffer.attach_filer(self.E)
+        obs, _, _, to_play = self.envs.observe()
+        replay_buffer.filer_begin(obs, to_play)
+        self._filed_to = replay_buffer
+
+    def _filing_refuses(self, what):
+        if self._filed_to is not None:
+            raise NotImplementedError(f"{what} is not available after file_to(): the games are filed on the device from "
+                                      "whole move batches (play_moves with on_games)")
+
+    def _file_on_device(self, n_moves, device_inputs):
+        """Describe the batch just queued for the device filer: the search results where the engine left them, the env
+        outputs in the actor's ring, the legal sets and players to move from the envs' own arrays (a constant legal set)
+        or from the engine's recorded-inputs ring (device-input batches).  The filing itself is queued by _queue_filing
+        -- behind the batch's last environment kernel and ahead of anything that rewrites those arrays: at the start of
+        the next play_moves, or in flush() -- so that a batch's games reach the store, and on_games, exactly when the host
+        path files them (play_moves hands out the batch before's games while the GPU runs the current one)."""
+        eng, envs, ring = self.engine, self.envs, self._ring
+        out = eng.moves_device_ring()
+        mv = _native.MzReplayFileMoves()
+        mv.n_moves, mv.num_simulations = int(n_moves), int(self.config.num_simulations)
+        mv.players = 2 if len(self.config.players) > 1 else 1
+        for name in ("actions", "visits", "root_value_sum"):
+            setattr(mv, name, out[name])
+            setattr(mv, name + "_stride", out["stride"])
+        if device_inputs:
+            inputs = eng.moves_inputs_device_ring()
+            for name in ("legal", "num_legal", "to_play"):
+                setattr(mv, name, inputs[name])
+                setattr(mv, name + "_stride", inputs["stride"])
+            mv.to_play_last = envs.to_play.data_ptr()
+        else:
+            mv.legal, mv.num_legal, mv.legal_stride, mv.num_legal_stride = envs.legal.data_ptr(), envs.num_legal.data_ptr(), 0, 0
+            mv.to_play, mv.to_play_stride, mv.to_play_last = None, 0, None
+        mv.rewards, mv.done = ring["reward"].data_ptr(), ring["done"].data_ptr()
+        mv.obs_after, mv.obs_next = ring["obs_after"].data_ptr(), ring["obs_next"].data_ptr()
+        self._unfiled = (mv, ring)                           # (the ring stays alive with it)
+
+    def _queue_filing(self):
+        if self._filed_to is not None and self._unfiled is not None:
+            self._filed_to.filer_file(self._unfiled[0])
+            self._unfiled = None
+
+    def _sync_filing(self, on_games):
+        """The games of the filing queued last: their lengths and ids join the host bookkeeping (one small sync)."""
+        if self._filed_to._filing_pending:
+            filed = FiledGames(*self._filed_to.sync_filing())
+            self._hand_out(filed if len(filed) else None, None, on_games)
 
     def _observe_host(self):
         obs, legal, num_legal, to_play = self.envs.observe()
@@ -1013,6 +1103,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         (the GPU works; `step_end` waits).  Two actors on streams of their own alternate their halves
         (PipelinedDeviceSelfPlay): one's host work runs under the other's search.  Against an opponent the whole move
         is queued here (search, action sampling, env step: a one-move batch), so the temperature is needed already."""
+        self._filing_refuses("step()")
         mode = self._resolve_opponent(opponent, muzero_player)
         if mode[0] != "self":
             if temperature is None:
@@ -1095,6 +1186,12 @@ class DeviceSelfPlay(ManyEnvLoop):
         batch (always its device-input form; every env then plays all n_moves plies)."""
         E, eng, envs, cfg = self.E, self.engine, self.envs, self.config
         mode = self._resolve_opponent(opponent, muzero_player)
+        if self._filed_to is not None:
+            if on_game is not None:
+                self._filing_refuses("on_game")
+            if mode[0] != "self":
+                self._filing_refuses("an opponent")
+            self._queue_filing()                             # the batch before: ahead of anything this one rewrites
         # Everything but a fused search of a game with a constant legal set takes the device-input form of the batch:
         # board games (legal sets change), residual networks (lock-step searches), and a temperature threshold
         # (play_game drops to temperature 0 once len(action_history) reaches it, self_play.py:152-158: a per-env, per-move
@@ -1118,6 +1215,18 @@ class DeviceSelfPlay(ManyEnvLoop):
             # step, terminal observation, reset of the finished envs, next observation: one call, one launch
             obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
                                   ring["obs_next"][m])
+        if self._filed_to is not None:
+            # the batch is filed where it lies: nothing of the env outputs is downloaded; collect() still waits for the
+            # batch (the RNG mirrors need the engine's own ring) and the filing's few bytes come back right behind it
+            eng.moves_predraw_next(n_moves, cur["legal"], cur["to_play"], temperature, True, num_legal=cur["num_legal"])
+            out = eng.moves_collect(copy=False)
+            self._sync_filing(on_games)                      # the batch before's games (filed ahead of this batch)
+            self._file_on_device(n_moves, device_inputs=False)
+            eng.moves_submit_next()
+            self._batch_ready = params
+            self._cur = dict(cur, obs_dev=obs_in, obs=None)
+            self.moves_played += int(out["moves_done"].sum())
+            return out["moves_done"].copy()
         self.flush(on_game, on_games)                        # the previous batch's games, while this one runs
         eng.moves_predraw_next(n_moves, cur["legal"], cur["to_play"], temperature, True, num_legal=cur["num_legal"])
         out = eng.moves_collect(copy=False)                  # views: filed (flush) before the next collect overwrites them
@@ -1180,6 +1289,8 @@ class DeviceSelfPlay(ManyEnvLoop):
         b.obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
                                 ring["obs_next"][m], played=ring["played"][m] if b.opponent else None,
                                 words=ring["words"][m] if b.opponent else None)
+        if self._filed_to is not None:
+            return                                           # filed on the device: the env outputs stay where they are
         ran = torch.cuda.Event()
         ran.record(torch.cuda.current_stream(self.device))
         self._copy_stream.wait_event(ran)
@@ -1191,6 +1302,13 @@ class DeviceSelfPlay(ManyEnvLoop):
         b, eng, envs = self._dev_batch, self.engine, self.envs
         n_moves = b.n_moves
         self._dev_batch = None
+        if self._filed_to is not None:
+            out = eng.moves_collect(copy=False)
+            self._sync_filing(on_games)                      # the batch before's games (filed ahead of this batch)
+            self._file_on_device(n_moves, device_inputs=True)
+            self._cur = dict(obs_dev=b.obs_in, on_device_only=True)
+            self.moves_played += int(out["moves_done"].sum())
+            return out["moves_done"].copy()
         self.flush(on_game, on_games)                        # the previous batch's games, while this one runs
         # (views of the engine's pinned rings, filled move by move while the batch ran: nothing is unpacked here; they
         # stay valid until the batch after the next one is prepared, and flush() files them before that)
@@ -1229,6 +1347,13 @@ class DeviceSelfPlay(ManyEnvLoop):
     def _play_pass(self, temperature, temperature_threshold, moves_per_pass):
         """ManyEnvLoop's pass: whole move batches on the device when the game, the network and the temperature allow
         it (play_moves), else one move at a time (step)."""
+        if self._filed_to is not None:
+            if not self._batchable(temperature, temperature_threshold, moves_per_pass):
+                raise NotImplementedError("after file_to() a pass must run as one move batch on the device: give "
+                                          "moves_per_pass, and a temperature and root_dirichlet_alpha play_moves accepts")
+            self.play_moves(moves_per_pass, temperature, temperature_threshold=temperature_threshold or 0)
+            self.flush()
+            return []
         if not self._batchable(temperature, temperature_threshold, moves_per_pass):
             return ManyEnvLoop._play_pass(self, temperature, temperature_threshold, moves_per_pass)
         finished = []
@@ -1241,6 +1366,13 @@ class DeviceSelfPlay(ManyEnvLoop):
         """File the moves of the last play_moves batch into the histories (play_moves does this for the
         batch before while the GPU runs the current one; call it once at the end).  Native code
         (HistoryFiler, include/mzhist.h): one pass over the batch on the library's worker pool."""
+        if self._filed_to is not None:
+            # the games are in the store: their lengths and ids join the host bookkeeping (one small sync per batch)
+            if on_game is not None:
+                self._filing_refuses("on_game")
+            self._queue_filing()
+            self._sync_filing(on_games)
+            return
         u, self._unfiled = self._unfiled, None
         if u is None:
             return
@@ -1252,6 +1384,8 @@ class DeviceSelfPlay(ManyEnvLoop):
     @property
     def searched_moves(self):
         """Env-moves filed so far that ran a search (moves_played counts the opponent's plies too)."""
+        if self._filed_to is not None:
+            return self.moves_played                         # self-play only: every ply was searched
         return self._filer.searched_moves()
 
     def _drop_batch(self):
@@ -1272,7 +1406,9 @@ class DeviceSelfPlay(ManyEnvLoop):
                         # opponents consumed
                         played=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev),
                         words=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev))
-            self._pinned = [{k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
+            # (an actor that files on the device downloads none of this: no host sets)
+            self._pinned = [None if self._filed_to is not None else
+                            {k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
             self._ring = ring
         return ring
 
@@ -1309,6 +1445,11 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         self._started = [False] * groups         # group g's next search is queued (step)
         self._batch_queued = [False] * groups    # group g's next move batch is queued (play_moves)
         self.device, self.model = self.actors[0].device, self.actors[0].model   # (what ManyEnvLoop's weight pull addresses)
+
+    def file_to(self, replay_buffer):
+        raise NotImplementedError("PipelinedDeviceSelfPlay cannot file_to() a replay buffer: its groups run on streams of "
+                                  "their own, and game ids would depend on the order the streams happen to run in; use "
+                                  "one DeviceSelfPlay, or on_games -> save_games")
 
     def _pull_weights(self, shared_storage, version):
         self._no_batch_queued("weight pull")

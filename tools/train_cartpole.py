@@ -5,9 +5,12 @@ weights.  Not a benchmark: it shows that the pieces learn together (the referenc
 ~420 reward after ~2000 training steps with one worker).
 
     python tools/train_cartpole.py [--envs 64] [--iterations 30] [--moves 8] [--train-steps 100] [--device-sampling]
+                                   [--device-filing]
 
 --device-sampling: replay batches are drawn on the device and an iteration's training steps are queued without a host
 round trip (Trainer.train_steps); the log is the host-sampling run's, line for line, except the seconds.
+--device-filing: the actor files its finished games into the replay store on the device (DeviceSelfPlay.file_to): no
+game visits the host, only lengths and ids come back; the log is again the same, line for line, except the seconds.
 """
 import argparse
 import importlib
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--eager-trainer", action="store_true", help="launch the training step op by op instead of as one hipGraph replay")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample replay batches on the device; an iteration's training steps run as Trainer.train_steps")
+    ap.add_argument("--device-filing", action="store_true",
+                    help="file finished games into the replay store on the device (DeviceSelfPlay.file_to)")
     args = ap.parse_args()
     sp = importlib.import_module("muzero-hypermodel_amd.self_play")
     rb_mod = importlib.import_module("muzero-hypermodel_amd.replay_buffer")
@@ -55,6 +60,12 @@ def main():
     def on_games(batch):
         replay.save_games(batch)
         finished.extend(batch.rewards[i, 1: n + 1].sum() for i, n in enumerate(batch.length))
+
+    if args.device_filing:
+        actor.file_to(replay)
+
+        def on_games(batch):                         # FiledGames: the games are in the store already
+            finished.extend(np.float32(n) for n in batch.length)   # (CartPole pays 1 per move: the reward sum is the length)
 
     t0 = time.perf_counter()
     log = []
