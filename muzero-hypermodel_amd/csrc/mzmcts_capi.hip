@@ -26,6 +26,11 @@ int mzmcts_create(const mzmcts_config* c, mzmcts_engine** out) {
         return fail(nullptr, MZMCTS_ERR_INVALID, "mzmcts_create: at most 256 actions are supported");
     if (c->num_simulations > 32767)
         return fail(nullptr, MZMCTS_ERR_INVALID, "mzmcts_create: at most 32767 simulations are supported");
+    // the decode (tree_device.h support_to_scalar_pair) weighs entry i with float(i - support_size): exact up to 2^24,
+    // and F = 2 * support_size + 1 has to stay an int32
+    if (c->support_size > (1 << 24))
+        return fail(nullptr, MZMCTS_ERR_INVALID, "mzmcts_create: support_size above 16777216 is not supported (the "
+                                                 "support values would not be exact floats)");
 
     int n_dev = 0;
     hipError_t err = hipGetDeviceCount(&n_dev);

@@ -348,6 +348,9 @@ __device__ __forceinline__ float inverse_value_transform(float x) {
 // operation order per vector; the two reductions are interleaved so their dependent chains overlap.
 // The F logits of a vector are spread over the G lanes of the group; with at most 4 per lane the
 // exponentials are computed once and kept in registers.  A vector's result does not depend on the other.
+// The two forms (register-resident for F <= 4 G, strided and re-computing beyond) add the same terms in the same
+// order; tests/test_gpu_lockstep_decode.py::test_decode_and_priors_vs_float64 holds both to float64 on either side of
+// that limit for every G, and this function bit for bit to support_to_scalar_group below.
 template <int G>
 __device__ __forceinline__ void support_to_scalar_pair(const float* la, const float* lb, int F, int support, int j,
                                                        float& out_a, float& out_b) {

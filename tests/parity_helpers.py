@@ -413,6 +413,78 @@ def value_transform_bound(value, delta_x, eps=0.001):
     return 1.01 * kappa * delta_x + 2.0 * e_v
 
 
+def inverse_value_transform64(x, eps=0.001):
+    """models.py:655-660 in float64: sign(x) * (z**2 - 1), z = (sqrt(1 + 4 eps (|x| + 1 + eps)) - 1) / (2 eps)."""
+    x = np.asarray(x, dtype=np.float64)
+    z = (np.sqrt(1.0 + 4.0 * eps * (np.abs(x) + 1.0 + eps)) - 1.0) / (2.0 * eps)
+    return np.sign(x) * (z * z - 1.0)
+
+
+def support_to_scalar64(logits, support_size):
+    """models.py:641-662 on float32 logits, every operation in float64: the yardstick of the decode tests."""
+    return inverse_value_transform64(categorical_mean(logits, support_size))
+
+
+def _gamma(k):
+    k = np.asarray(k, dtype=np.float64)
+    return k * F32_UNIT / (1.0 - k * F32_UNIT)
+
+
+def _softmax_terms(logits):
+    """float64 soft-max of the rows of `logits` with what its float32 evaluation is charged per entry BEFORE any
+    summation: d_i = fl(l_i - max) carries one rounding, i.e. |d_i| u on the exponent and so a relative |d_i| u on
+    exp(d_i); expf itself is good to one ulp = 2 u.  Returns (p, |d| with the -inf entries at 0, c = sum p (|d| + 2)):
+    c u is the relative error those two leave on the normaliser sum exp(d_k), whatever order it is added in."""
+    logits = np.asarray(logits, dtype=np.float64)
+    d = logits - logits.max(axis=-1, keepdims=True)
+    e = np.exp(d)
+    p = e / e.sum(axis=-1, keepdims=True)
+    absd = np.where(np.isfinite(d), np.abs(d), 0.0)
+    absd = np.where(p > 0, absd, 0.0)                      # (exp underflows in float64 too: the entry is exactly 0 in both)
+    return p, absd, (p * (absd + 2.0)).sum(axis=-1, keepdims=True)
+
+
+def categorical_mean_rounding(logits, support_size, group=1):
+    """delta_x: bound on |x_f32 - x| for x = sum_i (i - s) softmax(l)_i evaluated in float32 by a lane group of `group`
+    lanes (tree_device.h support_to_scalar_pair; group = 1 is any sequential or vectorised sum of F terms: the C oracle,
+    torch), against the float64 value of the same float32 logits.  The usual gamma_n argument, per entry i:
+
+        exp(fl(l_i - max))              |d_i| + 2            (see _softmax_terms; the maximum itself is exact)
+        the normaliser Z                c + n                the entries' own errors, and a sum in which every term
+                                                             passes through at most n = ceil(F / G) + log2(G) additions
+                                                             (a lane's chain, then the butterfly)
+        1 / Z, e_i * (1 / Z), (i - s) * p_i     3            one rounding each; (i - s) is an exact float
+        the weighted sum                n                    the same chain and butterfly
+
+    so x_f32 = sum_i (i - s) p_i (1 + theta_i) with |theta_i| <= gamma(2 n + 5 + |d_i| + c) and
+    delta_x = sum_i |i - s| p_i gamma(...): small when the mass sits near the centre, up to s * gamma for a peaked row.
+    Entries whose exponential leaves float32's normal range (p_i < 2**-126) are charged absolutely.  1 % for the second
+    order.  A single non-zero probability, at the maximum, costs nothing at all: every operation on it is exact."""
+    p, absd, c = _softmax_terms(logits)
+    F = p.shape[-1]
+    n = -(-F // group) + int(np.log2(group))
+    weight = np.abs(np.arange(-support_size, support_size + 1, dtype=np.float64))
+    lone = (p > 0).sum(axis=-1) == 1                       # exp(0) = 1, Z = 1, 1 / Z = 1, (i - s) * 1, + 0: all exact
+    bound = 1.01 * (weight * p * _gamma(2 * n + 5 + absd + c)).sum(axis=-1) + weight.sum() * 2.0 ** -126
+    return np.where(lone, 0.0, bound)
+
+
+def softmax_rounding_bound(logits, group=1, chunks=1):
+    """Per-entry bound on |softmax_f32(l) - softmax(l)| (tree_device.h group_softmax: `chunks` entries per lane, then a
+    butterfly over `group` lanes; group = 1, chunks = n is a sequential sum of n terms: the C oracle, torch): relative
+    gamma(|d_i| + 2 + c + (chunks - 1 + log2(group)) + 2) by the argument of categorical_mean_rounding (own exponential,
+    the normaliser's entries and its sum, the reciprocal and the product), plus 2**-126 where float32 leaves its normal
+    range.  A row with a single non-zero entry is exact."""
+    p, absd, c = _softmax_terms(logits)
+    k = absd + 2.0 + c + (chunks - 1 + int(np.log2(group))) + 2.0
+    lone = ((p > 0).sum(axis=-1, keepdims=True) == 1)
+    return np.where(lone, 0.0, 1.01 * p * _gamma(k) + 2.0 ** -126)
+
+
+def softmax64(logits):
+    return _softmax_terms(logits)[0]
+
+
 # ---- replay store ------------------------------------------------------------------------------
 def history_of(sp, fx, g):
     """Game g of a replay fixture (G12 layout: arrays padded past `lengths[g]`) as a GameHistory with the field types

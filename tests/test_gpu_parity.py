@@ -13,9 +13,9 @@ import numpy as np
 import pytest
 import torch
 
-from parity_helpers import (cartpole_model_and_weights, fixture_config, load_golden, make_search_config,
-                            random_streams, run_injected_on_engine, run_injected_on_oracle,
-                            streams_from_fixture, synthetic_model)
+from parity_helpers import (cartpole_model_and_weights, categorical_mean_rounding, fixture_config, load_golden,
+                            make_search_config, random_streams, run_injected_on_engine, run_injected_on_oracle,
+                            streams_from_fixture, support_to_scalar64, synthetic_model, value_transform_bound)
 
 pytestmark = pytest.mark.gpu
 
@@ -280,6 +280,16 @@ def test_plugin_contract_errors(eng):
 
 
 # ---- device decode kernels vs the reference's torch outputs -----------------------------------------
+def _within_float64_bound(got, logits, support, group):
+    """Beside the comparison with the reference's own float32 output: every decoded value within the derived bound of the
+    float64 value of the same logits (parity_helpers.categorical_mean_rounding -> value_transform_bound; the float32
+    lattice of the inverse transform makes it about 1e-4 sqrt(|v| + 1) near 0, so neither bar is the tighter one
+    everywhere and both are held).  tests/test_gpu_lockstep_decode.py does this at every lane-group width."""
+    want = support_to_scalar64(logits, support)
+    bound = value_transform_bound(want, categorical_mean_rounding(logits, support, group))
+    assert (np.abs(got - want) <= bound).all(), float((np.abs(got - want) / bound).max())
+
+
 def test_support_to_scalar_and_softmax_kernels(eng):
     fx = load_golden("g1_support_to_scalar")
     E = 64
@@ -291,6 +301,7 @@ def test_support_to_scalar_and_softmax_kernels(eng):
     engine.expand_roots(logits, None, policy, torch.zeros(E, 4, device="cuda"))
     st = engine.readout()
     np.testing.assert_allclose(st["root_predicted_value"], fx["out21"][:, 0].astype(np.float64), rtol=1e-5, atol=1e-5)
+    _within_float64_bound(st["root_predicted_value"], fx["logits21"], 10, group=2)
     want_priors = torch.softmax(policy.cpu(), dim=1).numpy().astype(np.float64)
     np.testing.assert_allclose(st["child_prior"], want_priors, rtol=0, atol=1e-6)
     engine.close()
@@ -302,6 +313,7 @@ def test_support_to_scalar_and_softmax_kernels(eng):
                         torch.zeros(8, 4, device="cuda"))
     st = engine.readout()
     np.testing.assert_allclose(st["root_predicted_value"], fx["out601"][:, 0].astype(np.float64), rtol=1e-4, atol=2e-4)
+    _within_float64_bound(st["root_predicted_value"], fx["logits601"], 300, group=4)
     engine.close()
 
 

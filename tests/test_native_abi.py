@@ -66,6 +66,13 @@ def test_create_rejects_bad_configs(native):
     assert b"More than two player mode not implemented." in lib.mzmcts_last_error(None)
     cfg = native.MzConfig(**{**base, "num_envs": 0})
     assert lib.mzmcts_create(ctypes.byref(cfg), ctypes.byref(handle)) == native.ERR_INVALID
+    # support values past 2^24 are not exact floats (and 2 s + 1 leaves int32 soon after): refused before any device work
+    for support in (2 ** 24 + 1, 2 ** 30, 2 ** 31 - 1, -1):
+        cfg = native.MzConfig(**{**base, "support_size": support})
+        assert lib.mzmcts_create(ctypes.byref(cfg), ctypes.byref(handle)) == native.ERR_INVALID and not handle.value
+    cfg = native.MzConfig(**{**base, "support_size": 2 ** 24 + 1})
+    assert lib.mzmcts_create(ctypes.byref(cfg), ctypes.byref(handle)) == native.ERR_INVALID
+    assert b"support_size above 16777216" in lib.mzmcts_last_error(None)
 
 
 def test_downsample_launch_rejects_what_it_does_not_cover(native):
