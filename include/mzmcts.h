@@ -610,6 +610,14 @@ int mzmcts_device_select_action(const uint32_t *seeds, int32_t n_streams, const 
  *                                                        not say so
  *   _PLAIN_RANGE        float64 bits                     counts (and lists) the doubles on which leaves_plain_range fires; the
  *                                                        caller holds the rule
+ *   _LOG                float32 bits of [1, 1024)        no short form: logf as csrc/trainer_kernels.hip calls it on a soft-max
+ *                                                        normaliser (a sum of at most 601 terms in (0, 1], one of them 1);
+ *                                                        distance to float64 log in float32 ulps at the result (log(1) must
+ *                                                        be 0); counts the operands further than 4 ulps
+ *   _POW_HALF, _POW_ONE float32 bits of [+0, FLT_MAX]    no short form: powf(a, 0.5f) / powf(a, 1.0f) as the PER priority
+ *                                                        computes it (the exponent reaches the kernel as an argument, as
+ *                                                        per_alpha does); distance to float64 pow in float32 ulps; counts the
+ *                                                        operands further than 4 ulps
  * count <= MZMCTS_NUMERICS_MAX_COUNT per call (a caller walks a domain in a loop, so no launch is long).  Null pointers,
  * an unknown `which`, count == 0 or over the cap, and patterns outside the check's index space return
  * MZMCTS_ERR_INVALID before the device is touched. */
@@ -620,6 +628,9 @@ int mzmcts_device_select_action(const uint32_t *seeds, int32_t n_streams, const 
 #define MZMCTS_NUMERICS_NORMALIZED 5
 #define MZMCTS_NUMERICS_QUOTIENT_GUARDED 6
 #define MZMCTS_NUMERICS_PLAIN_RANGE 7
+#define MZMCTS_NUMERICS_LOG 8
+#define MZMCTS_NUMERICS_POW_HALF 9
+#define MZMCTS_NUMERICS_POW_ONE 10
 #define MZMCTS_NUMERICS_MAX_COUNT (1ull << 28)
 int mzmcts_device_numerics(int32_t which, uint64_t first, uint64_t count, uint64_t *mismatches_out,
                            uint64_t *first_bad_out, double *worst_out);

@@ -8,6 +8,12 @@
  * with respect to every logit (each unrolled step's share divided by its gradient scale, trainer.py:176-198).
  * The network forward / backward and the optimizer stay with PyTorch-ROCm; this replaces the ~25 element-wise
  * launches per unrolled step between them.  Raw device pointers, fp32, contiguous; no torch types.
+ *
+ * Domain.  Value and reward logits of loss-bearing positions are finite; a `-inf` entry outside the two target entries
+ * does not contribute (the two-hot cross-entropy reads the logits at the two target entries only, where the reference's
+ * sum over all F entries would meet 0 * -inf = NaN).  Step 0's reward row is never read and may hold anything, NaN
+ * included.  Policy rows follow the reference entry by entry: a positive target on a `-inf` logit gives a +inf loss, a
+ * zero target on one gives NaN, and both stay within their sample.
  */
 #ifndef MZTRAIN_H
 #define MZTRAIN_H
@@ -39,7 +45,9 @@ typedef struct mztrain_loss_args {
     float *grad_policy;   /* out [K1][B][A] */
 } mztrain_loss_args;
 
-/* Queues the launch on `stream` (hipStream_t); 0 = ok, < 0 = error (MZMCTS_ERR_*). */
+/* Queues the launch on `stream` (hipStream_t); 0 = ok, < 0 = error (MZMCTS_ERR_*).  Refused with MZMCTS_ERR_INVALID before
+ * anything touches a device: a null `args`, a null pointer among its members (`weight` alone may be null), and a
+ * non-positive batch, steps, support_size or actions (support_size = 0, a one-entry support, is refused too). */
 int mztrain_unroll_loss(const mztrain_loss_args *args, void *stream);
 
 #ifdef __cplusplus

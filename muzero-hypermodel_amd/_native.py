@@ -414,7 +414,7 @@ def device_select_action(seeds, visits, temperature, draws=1):
 
 
 NUMERICS = {"exp": 1, "reciprocal": 2, "inverse_transform": 3, "quotient": 4, "normalized": 5, "quotient_guarded": 6,
-            "plain_range": 7}
+            "plain_range": 7, "log": 8, "pow_half": 9, "pow_one": 10}
 NUMERICS_MAX_COUNT = 1 << 28
 
 

@@ -6,6 +6,10 @@
 // short form and the plain form, compares the result bits and measures the distance to a float64 evaluation; a launch
 // reduces to a mismatch count, a few offending operand patterns and the largest distance.  Nothing per operand leaves
 // the device.  Plain C++ throughout: results go out through ordinary atomics on global memory.
+//
+// Two checks have no short form: logf and powf as trainer_kernels.hip calls them (the soft-max normaliser's logarithm,
+// the PER priority's power), measured against float64 over the whole operand domain the loss kernel can present.  The
+// exponent of powf reaches the kernel as an argument, as per_alpha does there, so the compiler sees the same general call.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -115,7 +119,8 @@ __device__ __forceinline__ void normalized_case(uint64_t i, double& minimum, dou
 
 // One operand per thread: pattern = first + global id.  `bad` is what the call counts (see include/mzmcts.h per check).
 __global__ __launch_bounds__(kCheckThreads) void device_numerics_kernel(int which, unsigned long long first,
-                                                                        unsigned long long count, NumericsResult* out) {
+                                                                        unsigned long long count, float exponent,
+                                                                        NumericsResult* out) {
     const unsigned long long gid = static_cast<unsigned long long>(blockIdx.x) * kCheckThreads + threadIdx.x;
     const bool live = gid < count;
     const unsigned long long pattern = first + (live ? gid : 0ull);
@@ -170,6 +175,20 @@ __global__ __launch_bounds__(kCheckThreads) void device_numerics_kernel(int whic
         const bool in_range = !leaves_plain_range(v) && !leaves_plain_range(mm.minimum) && !leaves_plain_range(mm.maximum);
         bad = !in_range || !fast.fast || !same_f64(single, plain) || !same_f64(pair_a, plain) || !same_f64(pair_b, 1.0);
         if (bad) distance = fmax(f64_ulps_apart(single, plain), f64_ulps_apart(pair_a, plain));
+    } else if (which == MZMCTS_NUMERICS_LOG) {   // "offending" = more than 4 float32 ulps from float64 log
+        const float x = __builtin_bit_cast(float, static_cast<uint32_t>(pattern));
+        const double reference = log(static_cast<double>(x));
+        // log(1) = 0 exactly: anything else there is infinitely many ulps away; elsewhere the spacing at the reference
+        distance = (reference == 0.0) ? (logf(x) == 0.f ? 0.0 : 0x1p62)
+                                      : fabs(static_cast<double>(logf(x)) - reference) / f32_ulp_at(reference);
+        bad = distance > 4.0;
+    } else if (which == MZMCTS_NUMERICS_POW_HALF || which == MZMCTS_NUMERICS_POW_ONE) {
+        const float x = __builtin_bit_cast(float, static_cast<uint32_t>(pattern));
+        const double reference = pow(static_cast<double>(x), static_cast<double>(exponent));
+        const float got = powf(x, exponent);
+        distance = (reference == 0.0) ? (got == 0.f ? 0.0 : 0x1p62)
+                                      : fabs(static_cast<double>(got) - reference) / f32_ulp_at(reference);
+        bad = distance > 4.0;
     } else {   // MZMCTS_NUMERICS_PLAIN_RANGE: "offending" = the guard fires on the double with this bit pattern
         bad = leaves_plain_range(f64_from(pattern));
     }
@@ -203,7 +222,7 @@ int mzmcts_device_numerics(int32_t which, uint64_t first, uint64_t count, uint64
                            double* worst_out) {
     if (!mismatches_out || !first_bad_out || !worst_out) return MZMCTS_ERR_INVALID;
     if (count == 0 || count > MZMCTS_NUMERICS_MAX_COUNT) return MZMCTS_ERR_INVALID;
-    uint64_t domain = 0;
+    uint64_t domain = 0, low = 0;
     switch (which) {
         case MZMCTS_NUMERICS_EXP:
         case MZMCTS_NUMERICS_RECIPROCAL:
@@ -212,8 +231,12 @@ int mzmcts_device_numerics(int32_t which, uint64_t first, uint64_t count, uint64
         case MZMCTS_NUMERICS_QUOTIENT_GUARDED: domain = mz::quotient_cases(true); break;
         case MZMCTS_NUMERICS_NORMALIZED: domain = 1ull << 40; break;                     // seeded cases: any index below
         case MZMCTS_NUMERICS_PLAIN_RANGE: domain = 0; break;                             // float64 bit patterns: all 2^64
+        case MZMCTS_NUMERICS_LOG: low = 0x3F800000ull; domain = 0x44800000ull; break;     // the floats of [1, 1024)
+        case MZMCTS_NUMERICS_POW_HALF:
+        case MZMCTS_NUMERICS_POW_ONE: domain = 0x7F800000ull; break;                     // +0.0 .. the largest finite float
         default: return MZMCTS_ERR_INVALID;
     }
+    if (first < low) return MZMCTS_ERR_INVALID;
     if (domain != 0 && (first >= domain || count > domain - first)) return MZMCTS_ERR_INVALID;
     if (domain == 0 && first + count < first && first + count != 0) return MZMCTS_ERR_INVALID;   // wraps past 2^64
 
@@ -223,7 +246,8 @@ int mzmcts_device_numerics(int32_t which, uint64_t first, uint64_t count, uint64
     MZ_CHECK_HIP(hipMalloc(&d_out, sizeof(host)));
     MZ_CHECK_HIP(hipMemcpy(d_out, &host, sizeof(host), hipMemcpyHostToDevice));
     const unsigned blocks = static_cast<unsigned>((count + mz::kCheckThreads - 1) / mz::kCheckThreads);
-    mz::device_numerics_kernel<<<dim3(blocks), dim3(mz::kCheckThreads)>>>(which, first, count, d_out);
+    mz::device_numerics_kernel<<<dim3(blocks), dim3(mz::kCheckThreads)>>>(
+        which, first, count, which == MZMCTS_NUMERICS_POW_HALF ? 0.5f : 1.0f, d_out);
     MZ_CHECK_HIP(hipGetLastError());
     MZ_CHECK_HIP(hipMemcpy(&host, d_out, sizeof(host), hipMemcpyDeviceToHost));   // (waits for the kernel)
     (void)hipFree(d_out);

@@ -77,7 +77,7 @@ __device__ __forceinline__ float ce_dense(const float* x, const float* target, f
     float mx, log_sum;
     row_stats(x, n, lane, mx, log_sum);
     float total = 0.f;
-    for (int i = 0; i < n; ++i) total += target[i];          // (n <= a few dozen actions: every lane, index order)
+    for (int i = 0; i < n; ++i) total += target[i];          // (every lane walks the whole row in index order: tested up to 129 actions)
     float loss = 0.f;
     for (int i = 0; i < n; ++i) loss += -target[i] * ((x[i] - mx) - log_sum);
     for (int i = lane; i < n; i += kLanes) g[i] = scale * (expf((x[i] - mx) - log_sum) * total - target[i]);

@@ -11,6 +11,11 @@ reduces there; these tests walk the stated domains and hold the claims to them:
   normalized_value / _pair, short     == (v - min) / (max - min)    float32-born bounds, ranges from one ulp to 1e3
   leaves_plain_range                  the rule written beside it, and: wherever the quotient forms differ, it fires
 
+and two library calls of the loss kernel (csrc/trainer_kernels.hip) that have no short form, measured against float64:
+
+  logf(x)                             every float in [1, 1024): what a soft-max normaliser can be
+  powf(a, alpha)                      every non-negative finite float, alpha = 0.5 and 1: the PER priority
+
 Each test prints the patterns it visited, the mismatches, the worst distance to float64 and its run time.
 """
 import ctypes
@@ -113,6 +118,35 @@ def test_normalized_value_short_form_is_the_division(native):
     both members of normalized_pair."""
     visited, mismatches, bad, worst = sweep(native, "normalized", [(0, 1 << 27)], "normalized_value vs the division")
     assert mismatches == 0, f"cases {bad}: the forms are {worst} ulps apart"
+
+
+def test_logf_on_every_normaliser_the_loss_kernel_can_form(native):
+    """logf as csrc/trainer_kernels.hip row_stats calls it, on every float in [1, 1024) (10 * 2^23 patterns): the argument
+    is a sum of at most 601 terms in (0, 1] of which the largest is 1.  The domain is swept completely, so the figure is
+    proven, not sampled: the worst distance to float64 log, in float32 ulps at the result, is at most
+    unroll_loss_reference.LOGF_ULPS (the smallest integer that holds; the loss bounds charge exactly that), and
+    logf(1) is exactly 0.  Measured on the MI355X: worst 1.883 ulps, so L = 2."""
+    from unroll_loss_reference import LOGF_ULPS
+    first, last = f32_pattern(1.0), f32_pattern(1024.0)
+    visited, beyond_four, bad, worst = sweep(native, "log", [(first, last - first)], "logf vs float64 log on [1, 1024)")
+    assert visited == 10 * (1 << 23)
+    assert beyond_four == 0, f"logf more than 4 ulps from float64 at {as_floats(bad)}"
+    assert worst <= LOGF_ULPS, worst
+
+
+@pytest.mark.parametrize("which,alpha", [("pow_half", 0.5), ("pow_one", 1.0)])
+def test_powf_on_every_nonnegative_finite_float(native, which, alpha):
+    """powf(a, alpha) as the PER priority computes it (the exponent a run-time argument), alpha = 0.5 and 1 (the shipped
+    values), on +0.0 and every positive finite float, denormals included (2^31 - 2^23 patterns each): the worst distance
+    to float64 pow in float32 ulps is at most unroll_loss_reference.POWF_ULPS (the smallest integer that holds over both
+    exponents; the priority bound charges exactly that).  Measured on the MI355X: worst 1.500 ulps for alpha = 0.5 and
+    1.0000000019 for alpha = 1 (among the smallest operands powf(a, 1) is a neighbour of a, not a), so P = 2."""
+    from unroll_loss_reference import POWF_ULPS
+    n = f32_pattern(float("inf"))
+    visited, beyond_four, bad, worst = sweep(native, which, [(0, n)], f"powf(a, {alpha}) vs float64 pow")
+    assert visited == (1 << 31) - (1 << 23)
+    assert beyond_four == 0, f"powf(a, {alpha}) more than 4 ulps from float64 at {as_floats(bad)}"
+    assert worst <= POWF_ULPS, worst
 
 
 def plain_by_the_rule(x):

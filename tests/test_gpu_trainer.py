@@ -7,36 +7,14 @@ import numpy as np
 import pytest
 import torch
 
+from unroll_loss_reference import torch_reference
+
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def mods(pkg):
     return (importlib.import_module("muzero-hypermodel_amd.trainer"), importlib.import_module("muzero-hypermodel_amd.models"))
-
-
-def torch_reference(trainer_mod, models, value, reward, policy, b, support, vw, alpha):
-    """The CPU branch of Trainer.update_weights on given logits (lists of per-step tensors that require grad)."""
-    value_targets = models.scalar_to_support(b["values"], support)
-    reward_targets = models.scalar_to_support(b["rewards"], support)
-    priorities = torch.zeros_like(b["values"])
-    sums = {"value": 0, "reward": 0, "policy": 0}
-    for k in range(len(value)):
-        per_head = dict(zip(("value", "reward", "policy"), trainer_mod.Trainer.loss_function(
-            value[k], reward[k], policy[k], value_targets[:, k], reward_targets[:, k], b["policies"][:, k])))
-        if k == 0:
-            del per_head["reward"]
-        for head, term in per_head.items():
-            if k > 0:
-                term = trainer_mod._scale_gradient(term, b["gradient_scales"][:, k])
-            sums[head] = sums[head] + term
-        with torch.no_grad():
-            predicted = models.support_to_scalar(value[k], support).squeeze(-1)
-            priorities[:, k] = torch.abs(predicted - b["values"][:, k]) ** alpha
-    loss = sums["value"] * vw + sums["reward"] + sums["policy"]
-    if b["weights"] is not None:
-        loss = loss * b["weights"]
-    return loss, sums, priorities
 
 
 @pytest.mark.parametrize("B,K1,support,A,per", [(128, 11, 10, 2, True), (32, 6, 10, 9, True), (7, 4, 300, 4, False),

@@ -166,14 +166,20 @@ def test_device_numerics_refuses_bad_arguments_without_a_device(native):
 
     cap = native.NUMERICS_MAX_COUNT
     assert cap == 1 << 28
-    for bad in (dict(n=None), dict(p=None), dict(w=None), dict(which=0), dict(which=8), dict(which=-1), dict(count=0),
+    for bad in (dict(n=None), dict(p=None), dict(w=None), dict(which=0), dict(which=11), dict(which=-1), dict(count=0),
                 dict(count=cap + 1), dict(first=1 << 32), dict(first=(1 << 32) - 8, count=9),
                 dict(which=native.NUMERICS["reciprocal"], first=1 << 32),
                 dict(which=native.NUMERICS["inverse_transform"], first=(1 << 32) - 1, count=2),
                 dict(which=native.NUMERICS["quotient"], first=32768 * 2 * 803 * 4, count=1),
                 dict(which=native.NUMERICS["quotient_guarded"], first=32768 * 2 * 2048 * 4 - 1, count=2),
                 dict(which=native.NUMERICS["normalized"], first=1 << 40, count=1),
-                dict(which=native.NUMERICS["plain_range"], first=(1 << 64) - 4, count=5)):
+                dict(which=native.NUMERICS["plain_range"], first=(1 << 64) - 4, count=5),
+                dict(which=native.NUMERICS["log"], first=0x3F800000 - 1, count=2),          # below 1.0
+                dict(which=native.NUMERICS["log"], first=0x44800000, count=1),              # 1024.0
+                dict(which=native.NUMERICS["log"], first=0x44800000 - 1, count=2),
+                dict(which=native.NUMERICS["pow_half"], first=0x7F800000, count=1),         # +inf
+                dict(which=native.NUMERICS["pow_one"], first=0x7F800000 - 1, count=2),
+                dict(which=native.NUMERICS["pow_one"], first=0x80000000, count=1)):         # negative operands
         assert call(**bad) == native.ERR_INVALID, bad
     with pytest.raises(KeyError):
         native.device_numerics("cosine", 0, 1)
@@ -181,3 +187,31 @@ def test_device_numerics_refuses_bad_arguments_without_a_device(native):
         assert call() == native.ERR_HIP
         with pytest.raises(RuntimeError, match="mzmcts_device_numerics"):
             native.device_numerics("exp", 0, 1)
+
+
+def test_unroll_loss_refuses_bad_arguments_without_a_device(native):
+    """mztrain_unroll_loss (include/mztrain.h) checks its arguments before anything touches the GPU: a null struct, a null
+    pointer among the required members (`weight` alone may be null) and a non-positive batch, steps, support_size or
+    actions come back as MZMCTS_ERR_INVALID; support_size = 0 (a one-entry support) is refused too."""
+    import ctypes
+    lib = native.load()
+    ptr = 0x10000                                  # never dereferenced: every refused call returns before a launch
+    pointers = ("value_logits", "reward_logits", "policy_logits", "target_value", "target_reward", "target_policy",
+                "gradient_scale", "sample_loss", "head_sums", "priorities", "grad_value", "grad_reward", "grad_policy")
+    good = dict({name: ptr for name in pointers}, weight=ptr, batch=4, steps=3, support_size=10, actions=2,
+                value_loss_weight=0.25, per_alpha=0.5)
+    assert {name for name, _ in native.MzTrainLossArgs._fields_} == set(good)
+
+    def call(**changed):
+        args = native.MzTrainLossArgs(**{**good, **changed})
+        return lib.mztrain_unroll_loss(ctypes.byref(args), None)
+
+    assert lib.mztrain_unroll_loss(None, None) == native.ERR_INVALID
+    for name in pointers:
+        assert call(**{name: None}) == native.ERR_INVALID, name
+        assert call(**{name: None, "weight": None}) == native.ERR_INVALID, name
+    for name in ("batch", "steps", "support_size", "actions"):
+        for value in (0, -1, -2 ** 31):
+            assert call(**{name: value}) == native.ERR_INVALID, (name, value)
+    if not torch.cuda.is_available():               # good calls, with and without weights, get as far as the device
+        assert call() == native.ERR_HIP and call(weight=None) == native.ERR_HIP
