@@ -25,6 +25,10 @@
  *   mzreplay_make_batch_device    builds the targets from those device-resident indices, in the trainer's dtypes
  *   mzreplay_update_priorities    ReplayBuffer.update_priorities (replay_buffer.py:197-220) from device tensors
  *
+ *   mzreplay_reanalyse_*          Reanalyse for N games per pass: the games drawn on the device, every position of every
+ *                                 drawn game as one inference batch (csrc/reanalyse_plan.h), for fully-connected networks
+ *                                 the whole pass in one launch
+ *
  *   mzreplay_filer_*              finished self-play games appended straight from the search engine's and the
  *                                 environment kernels' device rings (csrc/replay_filer.h); mzreplay_read_games reads
  *                                 stored games back
@@ -207,6 +211,56 @@ int mzreplay_filer_lengths(mzreplay_filer *filer, int32_t *lengths, void *stream
  * for the games in `slots` (host i32[n]).  Blocking. */
 int mzreplay_filer_priorities(mzreplay_filer *filer, int32_t n, const int32_t *slots, float *priorities,
                               float *game_priority, void *stream);
+
+/* ---- Reanalyse in batches (csrc/reanalyse_plan.h) ------------------------------------------------
+ * N games per pass, queued on one stream: the games drawn on the device, every position of every drawn game evaluated
+ * as one batch, the fresh values written back.  A pass is a PLAN -- device arrays game_ids i64[n], slots i32[n], row_start
+ * i32[n + 1] -- and its consumers:
+ *   1. draw d = numpy.random.choice(n_stored) from the pass's own MT19937 stream (n_stored == 1 consumes no word),
+ *      game_ids[d] = oldest_game_id + index, slot = id % capacity; or the caller's ids, and the stream does not move;
+ *   2. a draw whose game is drawn again later in the pass gets no rows: the last occurrence carries them;
+ *   3. rows = the game's length for a carrying draw, 0 otherwise; row_start = their exclusive prefix sum and
+ *      row_start[n] = R; row r belongs to the draw found by right bisection in row_start, at position r - row_start[d].
+ * mzreplay_reanalyse_enable gives the store the stream, seeded as numpy.random.seed(seed) (calling it again reseeds),
+ * and the pass's scratch.  Blocking, like _get_rng / _set_rng (RandomState.get_state() form: key u32[624], pos 0..624). */
+struct mzmcts_fc_desc;   /* include/mzmcts.h */
+int mzreplay_reanalyse_enable(mzreplay *store, uint32_t seed);
+int mzreplay_reanalyse_get_rng(mzreplay *store, uint32_t *key, int32_t *pos);
+int mzreplay_reanalyse_set_rng(mzreplay *store, const uint32_t *key, int32_t pos);
+/* The plan of a pass of n_games draws (1..4096) in one launch.  given_ids: NULL, or host i64[n_games], each a stored
+ * game (oldest_game_id <= id < oldest_game_id + n_stored).  Lengths are read from the store's own device array, so games
+ * that were filed on the device work unchanged.  n_stored == 0: nothing is drawn, ids and slots are -1, R = 0.  A store
+ * whose n_games * max_moves leaves int32 is refused.  Asynchronous. */
+int mzreplay_reanalyse_plan(mzreplay *store, int32_t n_games, int64_t oldest_game_id, int32_t n_stored,
+                            const int64_t *given_ids, int64_t *game_ids, int32_t *slots, int32_t *row_start, void *stream);
+/* The stacked observation of every row of the plan: observations dev f32[n_rows][C'][H][W], compact, in row order -- the
+ * input batch of initial_inference for any network.  n_rows: the rows the output holds (R, read back by the caller, or
+ * an upper bound of it); rows past row_start[n_games] are not written.  Asynchronous. */
+int mzreplay_reanalyse_observations(mzreplay *store, int32_t n_games, const int32_t *slots, const int32_t *row_start,
+                                    int32_t n_rows, float *observations, void *stream);
+/* values dev f32[R] into reanalysed[slot][0 .. length) of every carrying draw and has_reanalysed[slot] = 1, as
+ * mzreplay_set_reanalysed leaves them; nothing else of the store is written and no slot without rows is touched.
+ * Asynchronous. */
+int mzreplay_reanalyse_store(mzreplay *store, int32_t n_games, const int32_t *slots, const int32_t *row_start,
+                             const float *values, void *stream);
+/* Read Reanalyse's values back (host outputs, each may be NULL): values f32[n][max_moves], the whole row of every slot in
+ * `slots` (host i32[n]) as it sits in the store -- entries past a game's length are whatever was there --, and
+ * has_values u8[n] (1: the slot's targets bootstrap from them).  Blocking. */
+int mzreplay_read_reanalysed(mzreplay *store, int32_t n, const int32_t *slots, float *values, uint8_t *has_values,
+                             void *stream);
+/* The pass for a fully-connected network, in one launch behind the plan.  _fc_configure describes the network as
+ * mzmcts_fc_configure does (weights: dev f32[n_weights] in state_dict order; the pointer is RETAINED, so a publish or a
+ * broadcast into that buffer refreshes the network without a call) plus config.support_size; it refuses what
+ * mzmcts_fc_configure refuses, an observation_floats that is not the store's stacked observation (or wider than 256
+ * floats), and a network whose weights, neuron tables and activations exceed a workgroup's LDS.  Blocking.
+ * _fc: per row the stacked observation is built in the lane group's LDS scratch, fc_initial and support_to_scalar_group
+ * (csrc/fc_net_device.h, tree_device.h) run on it and the float32 value goes where mzreplay_reanalyse_store would put
+ * it; no observation, logit or value passes through device memory on the way.  Asynchronous, allocation-free. */
+int mzreplay_reanalyse_fc_configure(mzreplay *store, const struct mzmcts_fc_desc *desc, int32_t support_size,
+                                    const float *weights, int64_t n_weights);
+int mzreplay_reanalyse_fc(mzreplay *store, int32_t n_games, const int32_t *slots, const int32_t *row_start, void *stream);
+/* Lanes of a wavefront that evaluate one row in mzreplay_reanalyse_fc (the decode's rounding depends on it). */
+int32_t mzreplay_reanalyse_fc_group_width(void);
 
 /* Bytes of device memory the store occupies. */
 int64_t mzreplay_device_bytes(const mzreplay *store);

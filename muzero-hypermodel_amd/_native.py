@@ -201,6 +201,17 @@ PROTOTYPES = {
                                            c_void]),
     "mzreplay_filer_lengths": (ctypes.c_int, [c_void, c_i32_p, c_void]),
     "mzreplay_filer_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_f32_p, c_f32_p, c_void]),
+    "mzreplay_reanalyse_enable": (ctypes.c_int, [c_void, ctypes.c_uint32]),
+    "mzreplay_reanalyse_get_rng": (ctypes.c_int, [c_void, c_u32_p, c_i32_p]),
+    "mzreplay_reanalyse_set_rng": (ctypes.c_int, [c_void, c_u32_p, ctypes.c_int32]),
+    "mzreplay_reanalyse_plan": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_i64_p, c_void, c_void,
+                                               c_void, c_void]),
+    "mzreplay_reanalyse_observations": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, ctypes.c_int32, c_void, c_void]),
+    "mzreplay_reanalyse_store": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, c_void, c_void]),
+    "mzreplay_read_reanalysed": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_f32_p, c_void, c_void]),
+    "mzreplay_reanalyse_fc_configure": (ctypes.c_int, [c_void, ctypes.POINTER(MzFcDesc), ctypes.c_int32, c_void, ctypes.c_int64]),
+    "mzreplay_reanalyse_fc": (ctypes.c_int, [c_void, ctypes.c_int32, c_void, c_void, c_void]),
+    "mzreplay_reanalyse_fc_group_width": (ctypes.c_int32, []),
     "mzenv_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_u32_p, ctypes.POINTER(c_void)]),
     "mzenv_destroy": (None, [c_void]),
     "mzenv_last_error": (ctypes.c_char_p, [c_void]),

@@ -18,6 +18,13 @@
 //                            at a time by ballot; the MT19937 twist runs across the lanes
 //   sample_finish_kernel     positions by bisection, importance weights, batch maximum, all samples in parallel
 // and update_priorities in two (writes with the reference's later-sample-wins order, then the game maxima).
+// Reanalyse in batches (mzreplay_reanalyse_*; index arithmetic in reanalyse_plan.h) is a plan and its consumers:
+//   reanalyse_plan_kernel          one workgroup: the draws (a wavefront consumes 64 words a round, all lanes twist), the last
+//                                  occurrence of every game, the rows' exclusive prefix sum
+//   reanalyse_observations_kernel  a workgroup per row, grid-stride: the network's input batch
+//   reanalyse_store_kernel         a workgroup per draw, grid-stride: values into the slots of the carrying draws
+//   reanalyse_fc_kernel            fully-connected networks: a fixed grid, weights and neuron tables staged once per
+//                                  workgroup, a lane group per row from the observation to the stored value
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +35,8 @@
 #include <vector>
 
 #include "../../include/mzreplay.h"
+#include "fc_net_host.h"
+#include "reanalyse_plan.h"
 #include "replay_filer.h"
 #include "replay_sampler.h"
 
@@ -113,30 +122,25 @@ __global__ __launch_bounds__(256) void priorities_kernel(StoreParams p, const in
     if (threadIdx.x == 0) game_priority[blockIdx.x] = block_max[0];
 }
 
-// GameHistory.get_stacked_observations (self_play.py:514-548) of one position, by the whole workgroup
-__device__ __forceinline__ void stacked_observation(const StoreParams& p, int slot, int pos, float* out) {
+// GameHistory.get_stacked_observations (self_play.py:514-548): float t of the stacked observation of one position
+__device__ __forceinline__ float stacked_element(const StoreParams& p, int slot, int pos, int t) {
     const int32_t* actions = p.actions + static_cast<size_t>(slot) * (p.L + 1);
     const int plane = p.H * p.W;
-    const int out_channels = p.C + p.stacked * (p.C + 1);
     const float* game_obs = p.obs + static_cast<size_t>(slot) * (p.L + 1) * p.obs_floats;
-    for (int t = threadIdx.x; t < out_channels * plane; t += blockDim.x) {
-        const int ch = t / plane, px = t - ch * plane;
-        float v;
-        if (ch < p.C) {
-            v = game_obs[static_cast<size_t>(pos) * p.obs_floats + t];
-        } else {
-            const int k = (ch - p.C) / (p.C + 1);        // k-th past frame: index pos - 1 - k
-            const int c = (ch - p.C) - k * (p.C + 1);    // its channel; c == C is the action plane
-            const int past = pos - 1 - k;
-            if (past < 0)
-                v = 0.f;
-            else if (c < p.C)
-                v = game_obs[static_cast<size_t>(past) * p.obs_floats + c * plane + px];
-            else
-                v = static_cast<float>(actions[past + 1]);
-        }
-        out[t] = v;
-    }
+    const int ch = t / plane, px = t - ch * plane;
+    if (ch < p.C) return game_obs[static_cast<size_t>(pos) * p.obs_floats + t];
+    const int k = (ch - p.C) / (p.C + 1);        // k-th past frame: index pos - 1 - k
+    const int c = (ch - p.C) - k * (p.C + 1);    // its channel; c == C is the action plane
+    const int past = pos - 1 - k;
+    if (past < 0) return 0.f;
+    if (c < p.C) return game_obs[static_cast<size_t>(past) * p.obs_floats + c * plane + px];
+    return static_cast<float>(actions[past + 1]);
+}
+
+// ... of one position, by the whole workgroup
+__device__ __forceinline__ void stacked_observation(const StoreParams& p, int slot, int pos, float* out) {
+    const int floats = (p.C + p.stacked * (p.C + 1)) * p.H * p.W;
+    for (int t = threadIdx.x; t < floats; t += blockDim.x) out[t] = stacked_element(p, slot, pos, t);
 }
 
 // every position of one game, stacked: the input batch of Reanalyse's initial_inference (replay_buffer.py:335-346)
@@ -573,6 +577,209 @@ __global__ __launch_bounds__(256) void adopt_games_kernel(StoreParams p, Sampler
     }
 }
 
+// ---- Reanalyse in batches (reanalyse_plan.h) --------------------------------------------------------------------------
+struct ReanalyseParams {
+    uint32_t* mt_key;        // [624] the pass's own numpy stream
+    int32_t* mt_pos;         // [1]
+    int32_t* last_draw;      // [G] scratch of a plan: the last draw that names the slot
+    int64_t* given_ids;      // [kMaxGames] staging of ids handed in by the caller
+};
+
+constexpr int kPlanThreads = 256;
+constexpr int kReanalyseGroup = 16;    // lanes per row in reanalyse_fc_kernel
+constexpr int kReanalyseThreads = 256;
+constexpr int kReanalyseRowsPerBlock = kReanalyseThreads / kReanalyseGroup;
+
+// One workgroup.  Stored ids are consecutive, so two draws name the same game exactly when they name the same slot: the
+// last occurrence of a game is the largest draw index its slot has seen (an LDS-free atomicMax per draw on a [G] array).
+__global__ __launch_bounds__(kPlanThreads) void reanalyse_plan_kernel(StoreParams p, ReanalyseParams r, int n_games,
+                                                                      int64_t oldest_id, int n_stored, int given,
+                                                                      int64_t* __restrict__ game_ids,
+                                                                      int32_t* __restrict__ slots,
+                                                                      int32_t* __restrict__ row_start) {
+    __shared__ uint32_t key[mz::kMtN], fresh[mz::kMtN];
+    __shared__ int32_t index_s[mz::reanalyse::kMaxGames];   // the draws; then rows per draw
+    __shared__ int32_t part[2][kPlanThreads];
+    __shared__ int32_t pos_s, done_s;
+    const int t = threadIdx.x;
+    if (n_stored <= 0) {
+        for (int d = t; d < n_games; d += kPlanThreads) {
+            game_ids[d] = -1;
+            slots[d] = -1;
+        }
+        for (int d = t; d <= n_games; d += kPlanThreads) row_start[d] = 0;
+        return;
+    }
+    if (!given) {
+        auto sync = [] { __syncthreads(); };
+        for (int k = t; k < mz::kMtN; k += kPlanThreads) key[k] = r.mt_key[k];
+        if (t == 0) {
+            pos_s = r.mt_pos[0];
+            done_s = 0;
+        }
+        __syncthreads();
+        const uint32_t top = static_cast<uint32_t>(n_stored) - 1u;
+        const uint32_t mask = mz::mask_for(top);
+        if (top == 0u) {   // choice(1): no word, index 0
+            for (int d = t; d < n_games; d += kPlanThreads) index_s[d] = 0;
+            if (t == 0) done_s = n_games;
+            __syncthreads();
+        }
+        while (done_s < n_games) {
+            if (pos_s >= mz::kMtN) {
+                twist_parallel(key, fresh, t, kPlanThreads, sync);
+                if (t == 0) pos_s = 0;
+            }
+            __syncthreads();
+            if (t < 64) {   // the first wavefront: masked rejection, up to 64 words per round, accepted words ranked by ballot
+                int pos = pos_s, d = done_s;
+                while (pos < mz::kMtN && d < n_games) {
+                    const int avail = mz::kMtN - pos < 64 ? mz::kMtN - pos : 64;
+                    const uint32_t v = t < avail ? (mz::mt_temper(key[pos + t]) & mask) : 0u;
+                    const bool ok = t < avail && v <= top;
+                    const unsigned long long accepted = __ballot(ok);
+                    const int k = __popcll(accepted);
+                    const int rank = __popcll(accepted & ((1ull << t) - 1ull));
+                    const int need = n_games - d;
+                    int consumed = avail;
+                    if (k >= need) {   // the need-th accepted word ends the pass: the words behind it stay in the stream
+                        unsigned long long m = accepted;
+                        for (int i = 1; i < need; ++i) m &= m - 1ull;
+                        consumed = __ffsll(static_cast<long long>(m));
+                    }
+                    if (ok && rank < need) index_s[d + rank] = static_cast<int32_t>(v);
+                    d += k < need ? k : need;
+                    pos += consumed;
+                }
+                if (t == 0) {
+                    pos_s = pos;
+                    done_s = d;
+                }
+            }
+            __syncthreads();
+        }
+        for (int k = t; k < mz::kMtN; k += kPlanThreads) r.mt_key[k] = key[k];
+        if (t == 0) r.mt_pos[0] = pos_s;
+    }
+    for (int d = t; d < n_games; d += kPlanThreads) {
+        const int64_t id = given ? r.given_ids[d] : oldest_id + index_s[d];
+        const int slot = mz::reanalyse::slot_of(id, p.G);
+        game_ids[d] = id;
+        slots[d] = slot;
+        __hip_atomic_store(&r.last_draw[slot], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    for (int d = t; d < n_games; d += kPlanThreads) atomicMax(&r.last_draw[slots[d]], d);
+    __syncthreads();
+    for (int d = t; d < n_games; d += kPlanThreads) {
+        const int slot = slots[d];
+        int rows = 0;
+        if (__hip_atomic_load(&r.last_draw[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == d) {   // (past the L1)
+            rows = p.length[slot];
+            rows = rows < 0 ? 0 : (rows > p.L ? p.L : rows);
+        }
+        index_s[d] = rows;
+    }
+    __syncthreads();
+    // exclusive prefix sum: a contiguous piece per thread, the pieces' sums scanned across the workgroup
+    const int piece = (n_games + kPlanThreads - 1) / kPlanThreads;
+    const int lo = t * piece < n_games ? t * piece : n_games;
+    const int hi = lo + piece < n_games ? lo + piece : n_games;
+    int32_t sum = 0;
+    for (int d = lo; d < hi; ++d) sum += index_s[d];
+    int cur = 0;
+    part[0][t] = sum;
+    __syncthreads();
+    for (int step = 1; step < kPlanThreads; step <<= 1) {   // inclusive scan of the pieces' sums
+        part[cur ^ 1][t] = part[cur][t] + (t >= step ? part[cur][t - step] : 0);
+        cur ^= 1;
+        __syncthreads();
+    }
+    if (t == kPlanThreads - 1) row_start[n_games] = part[cur][t];
+    int32_t run = part[cur][t] - sum;
+    for (int d = lo; d < hi; ++d) {
+        row_start[d] = run;
+        run += index_s[d];
+    }
+}
+
+// (draw, slot, position) of row r; false where an index read from the plan does not fit the store
+__device__ __forceinline__ bool reanalyse_row(const StoreParams& p, int n_games, const int32_t* __restrict__ slots,
+                                              const int32_t* __restrict__ row_start, int r, int* slot, int* pos) {
+    const int d = mz::reanalyse::draw_of_row([&](int i) { return row_start[i]; }, n_games, r);
+    if (d < 0 || d >= n_games) return false;
+    *slot = slots[d];
+    *pos = r - row_start[d];
+    return *slot >= 0 && *slot < p.G && *pos >= 0 && *pos < p.L;
+}
+
+__global__ __launch_bounds__(128) void reanalyse_observations_kernel(StoreParams p, int n_games,
+                                                                     const int32_t* __restrict__ slots,
+                                                                     const int32_t* __restrict__ row_start, int n_rows,
+                                                                     float* __restrict__ obs_out) {
+    const int total = row_start[n_games] < n_rows ? row_start[n_games] : n_rows;
+    const size_t floats = static_cast<size_t>(p.C + p.stacked * (p.C + 1)) * p.H * p.W;
+    for (int r = blockIdx.x; r < total; r += gridDim.x) {
+        int slot, pos;
+        if (!reanalyse_row(p, n_games, slots, row_start, r, &slot, &pos)) continue;
+        stacked_observation(p, slot, pos, obs_out + static_cast<size_t>(r) * floats);
+    }
+}
+
+__global__ __launch_bounds__(128) void reanalyse_store_kernel(StoreParams p, int n_games, const int32_t* __restrict__ slots,
+                                                              const int32_t* __restrict__ row_start,
+                                                              const float* __restrict__ values) {
+    for (int d = blockIdx.x; d < n_games; d += gridDim.x) {
+        const int first = row_start[d];
+        int rows = row_start[d + 1] - first;
+        const int slot = slots[d];
+        if (rows <= 0 || first < 0 || slot < 0 || slot >= p.G) continue;
+        rows = rows > p.L ? p.L : rows;
+        for (int i = threadIdx.x; i < rows; i += blockDim.x)
+            p.reanalysed[static_cast<size_t>(slot) * p.L + i] = values[static_cast<size_t>(first) + i];
+        if (threadIdx.x == 0) p.has_reanalysed[slot] = 1;
+    }
+}
+
+// Reanalyse for a fully-connected network.  Dynamic LDS: [padded weights][neuron tables of initial_inference]
+// [kReanalyseRowsPerBlock activation scratches].  R is only known on the device: the grid is fixed, every workgroup stages
+// the weights once and walks rows blockIdx.x * 16 + group, stride gridDim.x * 16.  Rows are independent: after the staging
+// nothing is exchanged between lane groups, and a group that runs out of rows leaves.
+template <int G>
+__global__ __launch_bounds__(kReanalyseThreads) void reanalyse_fc_kernel(StoreParams p, mz::FcNet net,
+                                                                         const float* __restrict__ weights, int n_games,
+                                                                         const int32_t* __restrict__ slots,
+                                                                         const int32_t* __restrict__ row_start) {
+    extern __shared__ __attribute__((aligned(16))) float re_smem[];
+    const int total = row_start[n_games];
+    if (static_cast<int>(blockIdx.x) * kReanalyseRowsPerBlock >= total) return;   // (block-uniform: before any barrier)
+    float* w_lds = re_smem;
+    mz::NeuronDesc* table = reinterpret_cast<mz::NeuronDesc*>(re_smem + ((net.n_weights_lds + 3) & ~3));
+    mz::stage_mlp_weights(net.repr, weights, w_lds, threadIdx.x, kReanalyseThreads);
+    mz::stage_mlp_weights(net.policy, weights, w_lds, threadIdx.x, kReanalyseThreads);
+    mz::stage_mlp_weights(net.value, weights, w_lds, threadIdx.x, kReanalyseThreads);
+    __syncthreads();
+    int entries = mz::build_phase_tables(net.init_pre, net.n_init_pre, w_lds, table, G, threadIdx.x, kReanalyseThreads);
+    entries += mz::build_phase_tables(net.init_post, net.n_init_post, w_lds, table + entries, G, threadIdx.x, kReanalyseThreads);
+    __syncthreads();
+    const int group = threadIdx.x / G, j = threadIdx.x % G;
+    float* scratch = reinterpret_cast<float*>(table + entries) + static_cast<size_t>(group) * net.scratch_floats;
+    mz::fc_clear_scratch<G>(net, scratch, j);
+    for (int r = blockIdx.x * kReanalyseRowsPerBlock + group; r < total; r += gridDim.x * kReanalyseRowsPerBlock) {
+        int slot, pos;
+        if (!reanalyse_row(p, n_games, slots, row_start, r, &slot, &pos)) continue;
+        for (int t = j; t < net.obs; t += G) scratch[t] = stacked_element(p, slot, pos, t);
+        mz::group_memory_fence();
+        mz::fc_initial<G>(net, table, w_lds, scratch, scratch, j);   // (the observation is in place: x <- x)
+        const float value = mz::support_to_scalar_group<G>(scratch + net.off_value, net.F, net.support, j);
+        if (j == 0) {
+            p.reanalysed[static_cast<size_t>(slot) * p.L + pos] = value;
+            if (pos == 0) p.has_reanalysed[slot] = 1;
+        }
+        mz::group_memory_fence();   // the logits are read before the next row's layers overwrite them
+    }
+}
+
 // ---- the filer (replay_filer.h; include/mzreplay.h mzreplay_filer_file) ------------------------------------------------
 // Three launches per move batch, no host decision in between:
 //   filer_count_kernel        a thread per env: prefix of played moves, validation of everything later used as an index,
@@ -857,6 +1064,13 @@ struct mzreplay {
     int64_t next_game_id = 0;        // id of the next game mzreplay_add_games stores (sampler on)
     size_t sampler_batch = 0;        // samples the per-batch scratch holds
     mzreplay_filer* filer = nullptr; // the device filer bound to this store (at most one)
+    bool reanalyse_on = false;       // mzreplay_reanalyse_enable: the pass's stream and scratch exist
+    ReanalyseParams rp{};
+    bool re_fc_ready = false;        // mzreplay_reanalyse_fc_configure
+    mz::FcNet re_fc{};
+    const float* re_fc_weights = nullptr;
+    size_t re_fc_lds = 0;
+    int re_fc_grid = 0;
 };
 
 struct mzreplay_filer {
@@ -1510,6 +1724,187 @@ int mzreplay_filer_priorities(mzreplay_filer* fl, int32_t n, const int32_t* slot
     RP_HIP(s, hipMemcpyAsync(priorities, d_pri, sizeof(float) * count * L, hipMemcpyDeviceToHost, stream));
     RP_HIP(s, hipMemcpyAsync(game_priority, d_game, sizeof(float) * count, hipMemcpyDeviceToHost, stream));
     RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- Reanalyse in batches ---------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;   // gfx950
+
+int reanalyse_ready(mzreplay* s, const char* who) {
+    if (!s) return fail(s, std::string(who) + ": null store");
+    if (!s->reanalyse_on) return fail(s, std::string(who) + ": call mzreplay_reanalyse_enable first");
+    return 0;
+}
+
+int plan_arguments(mzreplay* s, const char* who, int32_t n_games, const int32_t* slots, const int32_t* row_start) {
+    if (!s) return fail(s, std::string(who) + ": null store");
+    if (!slots || !row_start) return fail(s, std::string(who) + ": null argument");
+    if (n_games < 1 || n_games > mz::reanalyse::kMaxGames) return fail(s, std::string(who) + ": n_games must be 1..4096");
+    return 0;
+}
+
+int phase_entries(const mz::FcPhase* list, int n, int G) {
+    int total = 0;
+    for (int i = 0; i < n; ++i) total += (list[i].total_out + 4 * G - 1) / (4 * G) * 4 * G;
+    return total;
+}
+
+// dynamic LDS of reanalyse_fc_kernel
+size_t reanalyse_fc_lds_bytes(const mz::FcNet& net) {
+    const int entries = phase_entries(net.init_pre, net.n_init_pre, kReanalyseGroup) +
+                        phase_entries(net.init_post, net.n_init_post, kReanalyseGroup);
+    return sizeof(float) * (static_cast<size_t>((net.n_weights_lds + 3) & ~3) +
+                            static_cast<size_t>(net.scratch_floats) * kReanalyseRowsPerBlock) +
+           sizeof(mz::NeuronDesc) * static_cast<size_t>(entries);
+}
+}  // namespace
+
+extern "C" {
+
+int32_t mzreplay_reanalyse_fc_group_width(void) { return kReanalyseGroup; }
+
+int mzreplay_reanalyse_enable(mzreplay* s, uint32_t seed) {
+    if (!s) return fail(s, "mzreplay_reanalyse_enable: null store");
+    if (!mz::reanalyse::rows_fit(mz::reanalyse::kMaxGames, s->p.L))
+        return fail(s, "mzreplay_reanalyse_enable: 4096 games of max_moves rows do not fit int32");
+    if (!s->reanalyse_on) {
+        ReanalyseParams& rp = s->rp;
+        if (dev_alloc(s, &rp.mt_key, static_cast<size_t>(mz::kMtN)) || dev_alloc(s, &rp.mt_pos, 1) ||
+            dev_alloc(s, &rp.last_draw, static_cast<size_t>(s->p.G)) ||
+            dev_alloc(s, &rp.given_ids, static_cast<size_t>(mz::reanalyse::kMaxGames)))
+            return -1;
+        s->reanalyse_on = true;
+    }
+    uint32_t key[mz::kMtN];
+    int32_t pos;
+    mz::mt_seed(key, &pos, seed);   // numpy.random.seed(seed)
+    return mzreplay_reanalyse_set_rng(s, key, pos);
+}
+
+int mzreplay_reanalyse_set_rng(mzreplay* s, const uint32_t* key, int32_t pos) {
+    if (reanalyse_ready(s, "mzreplay_reanalyse_set_rng")) return -1;
+    if (!key || pos < 0 || pos > mz::kMtN) return fail(s, "mzreplay_reanalyse_set_rng: bad state");
+    RP_HIP(s, hipDeviceSynchronize());
+    RP_HIP(s, hipMemcpy(s->rp.mt_key, key, sizeof(uint32_t) * mz::kMtN, hipMemcpyHostToDevice));
+    RP_HIP(s, hipMemcpy(s->rp.mt_pos, &pos, sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int mzreplay_reanalyse_get_rng(mzreplay* s, uint32_t* key, int32_t* pos) {
+    if (reanalyse_ready(s, "mzreplay_reanalyse_get_rng")) return -1;
+    if (!key || !pos) return fail(s, "mzreplay_reanalyse_get_rng: null argument");
+    RP_HIP(s, hipDeviceSynchronize());
+    RP_HIP(s, hipMemcpy(key, s->rp.mt_key, sizeof(uint32_t) * mz::kMtN, hipMemcpyDeviceToHost));
+    RP_HIP(s, hipMemcpy(pos, s->rp.mt_pos, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mzreplay_reanalyse_plan(mzreplay* s, int32_t n_games, int64_t oldest_game_id, int32_t n_stored, const int64_t* given_ids,
+                            int64_t* game_ids, int32_t* slots, int32_t* row_start, void* stream_) {
+    if (reanalyse_ready(s, "mzreplay_reanalyse_plan")) return -1;
+    if (!game_ids) return fail(s, "mzreplay_reanalyse_plan: null argument");
+    if (plan_arguments(s, "mzreplay_reanalyse_plan", n_games, slots, row_start)) return -1;
+    const StoreParams& p = s->p;
+    if (n_stored < 0 || n_stored > p.G || oldest_game_id < 0)
+        return fail(s, "mzreplay_reanalyse_plan: more stored games than the capacity, or a negative id");
+    if (!mz::reanalyse::rows_fit(n_games, p.L)) return fail(s, "mzreplay_reanalyse_plan: n_games * max_moves does not fit int32");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (given_ids && n_stored > 0) {
+        for (int d = 0; d < n_games; ++d)
+            if (given_ids[d] < oldest_game_id || given_ids[d] >= oldest_game_id + n_stored)
+                return fail(s, "mzreplay_reanalyse_plan: game " + std::to_string(given_ids[d]) + " is not stored");
+        RP_HIP(s, hipMemcpyAsync(s->rp.given_ids, given_ids, sizeof(int64_t) * n_games, hipMemcpyHostToDevice, stream));
+    }
+    reanalyse_plan_kernel<<<dim3(1), dim3(kPlanThreads), 0, stream>>>(p, s->rp, n_games, oldest_game_id, n_stored,
+                                                                     given_ids ? 1 : 0, game_ids, slots, row_start);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+int mzreplay_reanalyse_observations(mzreplay* s, int32_t n_games, const int32_t* slots, const int32_t* row_start,
+                                    int32_t n_rows, float* observations, void* stream_) {
+    if (plan_arguments(s, "mzreplay_reanalyse_observations", n_games, slots, row_start)) return -1;
+    if (n_rows < 0 || (n_rows > 0 && !observations)) return fail(s, "mzreplay_reanalyse_observations: bad argument");
+    if (n_rows == 0) return 0;
+    const int grid = n_rows < 65536 ? n_rows : 65536;
+    reanalyse_observations_kernel<<<dim3(grid), dim3(128), 0, static_cast<hipStream_t>(stream_)>>>(s->p, n_games, slots, row_start,
+                                                                                              n_rows, observations);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+int mzreplay_reanalyse_store(mzreplay* s, int32_t n_games, const int32_t* slots, const int32_t* row_start, const float* values,
+                             void* stream_) {
+    if (plan_arguments(s, "mzreplay_reanalyse_store", n_games, slots, row_start)) return -1;
+    if (!values) return fail(s, "mzreplay_reanalyse_store: null argument");
+    reanalyse_store_kernel<<<dim3(n_games), dim3(128), 0, static_cast<hipStream_t>(stream_)>>>(s->p, n_games, slots, row_start,
+                                                                                          values);
+    RP_HIP(s, hipGetLastError());
+    return 0;
+}
+
+int mzreplay_read_reanalysed(mzreplay* s, int32_t n, const int32_t* slots, float* values, uint8_t* has_values, void* stream_) {
+    if (!s || !slots) return fail(s, "mzreplay_read_reanalysed: null argument");
+    if (n <= 0) return 0;
+    const StoreParams& p = s->p;
+    for (int g = 0; g < n; ++g)
+        if (slots[g] < 0 || slots[g] >= p.G) return fail(s, "mzreplay_read_reanalysed: slot out of range");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t L = p.L;
+    for (int g = 0; g < n; ++g) {
+        if (values)
+            RP_HIP(s, hipMemcpyAsync(values + static_cast<size_t>(g) * L, p.reanalysed + static_cast<size_t>(slots[g]) * L,
+                                     sizeof(float) * L, hipMemcpyDeviceToHost, stream));
+        if (has_values) RP_HIP(s, hipMemcpyAsync(has_values + g, p.has_reanalysed + slots[g], 1, hipMemcpyDeviceToHost, stream));
+    }
+    RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int mzreplay_reanalyse_fc_configure(mzreplay* s, const mzmcts_fc_desc* desc, int32_t support_size, const float* weights,
+                                    int64_t n_weights) {
+    if (!s || !desc || !weights) return fail(s, "mzreplay_reanalyse_fc_configure: null argument");
+    const StoreParams& p = s->p;
+    s->re_fc_ready = false;
+    if (support_size < 1 || 2 * static_cast<int64_t>(support_size) + 1 > mz::kFcMaxWidth)
+        return fail(s, std::string("mzreplay_reanalyse_fc_configure: ") + mz::kFcNetSizesMessage);
+    const int64_t stacked_floats = static_cast<int64_t>(p.C + p.stacked * (p.C + 1)) * p.H * p.W;
+    if (stacked_floats > mz::kFcMaxWidth)
+        return fail(s, std::string("mzreplay_reanalyse_fc_configure: ") + mz::kFcNetSizesMessage);
+    if (desc->observation_floats != stacked_floats)
+        return fail(s, "mzreplay_reanalyse_fc_configure: observation_floats is not the store's stacked observation");
+    mz::FcNet net{};
+    const int rc = mz::build_fc_net(desc, p.A, support_size, n_weights, &net);
+    if (rc == mz::kFcNetSizes) return fail(s, std::string("mzreplay_reanalyse_fc_configure: ") + mz::kFcNetSizesMessage);
+    if (rc == mz::kFcNetWeightCount)
+        return fail(s, std::string("mzreplay_reanalyse_fc_configure: ") + mz::kFcNetWeightCountMessage);
+    const size_t lds = reanalyse_fc_lds_bytes(net);
+    if (lds > kLdsPerWorkgroup)
+        return fail(s, "mzreplay_reanalyse_fc_configure: the network's weights and activations do not fit a workgroup's "
+                       "160 KB of LDS");
+    int cus = 0;
+    RP_HIP(s, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->cfg.device));
+    RP_HIP(s, hipFuncSetAttribute(reinterpret_cast<const void*>(reanalyse_fc_kernel<kReanalyseGroup>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsPerWorkgroup)));
+    const size_t per_cu = kLdsPerWorkgroup / (lds ? lds : 1);
+    s->re_fc = net;
+    s->re_fc_weights = weights;
+    s->re_fc_lds = lds;
+    s->re_fc_grid = (cus > 0 ? cus : 1) * static_cast<int>(per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
+    s->re_fc_ready = true;
+    return 0;
+}
+
+int mzreplay_reanalyse_fc(mzreplay* s, int32_t n_games, const int32_t* slots, const int32_t* row_start, void* stream_) {
+    if (plan_arguments(s, "mzreplay_reanalyse_fc", n_games, slots, row_start)) return -1;
+    if (!s->re_fc_ready) return fail(s, "mzreplay_reanalyse_fc: call mzreplay_reanalyse_fc_configure first");
+    reanalyse_fc_kernel<kReanalyseGroup><<<dim3(s->re_fc_grid), dim3(kReanalyseThreads), s->re_fc_lds,
+                                           static_cast<hipStream_t>(stream_)>>>(s->p, s->re_fc, s->re_fc_weights, n_games, slots,
+                                                                                row_start);
+    RP_HIP(s, hipGetLastError());
     return 0;
 }
 

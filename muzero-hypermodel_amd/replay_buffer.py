@@ -17,8 +17,14 @@ csrc/replay_filer.h): the actor's finished games go from the search engine's and
 straight into the store's slots, and only their lengths (4 bytes per game) and the counters come back, once per move
 batch (`sync_filing`).  Such games have no host copy: `download_games` reads them back when someone asks.
 
+Reanalyse refreshes the stored games' value targets with the current network, one game per call
+(`Reanalyse.reanalyse_game`, the reference's loop body) or N games per pass queued on one stream
+(`Reanalyse.reanalyse_games`; include/mzreplay.h mzreplay_reanalyse_*, csrc/reanalyse_plan.h): the games are drawn on the
+device from a stream of the pass's own, every position of every drawn game is evaluated as one batch and the values go
+back into the store -- for fully-connected networks in one HIP launch with no host round trip at all.
+
 Not carried over: Ray (`.remote`), `get_buffer()`'s live GameHistory objects are only kept when games
-arrive as GameHistory (save_game), and `update_game_history` (Reanalyse).
+arrive as GameHistory (save_game), and `update_game_history` (the values live in the store, not in a GameHistory).
 """
 import ctypes
 import itertools
@@ -49,6 +55,19 @@ class DeviceIndexBatch:
 
     def tolist(self):
         return [list(pair) for pair in zip(self.game_ids.tolist(), self.positions.tolist())]
+
+
+class ReanalysePlan:
+    """The plan of a batched Reanalyse pass (csrc/reanalyse_plan.h), as CUDA tensors: game_ids i64[n], slots i32[n],
+    row_start i32[n + 1] (row_start[n] = the rows R of the pass).  Draws whose game is drawn again later in the pass have
+    no rows.  The tensors belong to the buffer and are rewritten by its next plan of the same size."""
+
+    def __init__(self, n_games, game_ids, slots, row_start, max_rows):
+        self.n_games, self.game_ids, self.slots, self.row_start, self.max_rows = n_games, game_ids, slots, row_start, max_rows
+
+    def rows(self):
+        """R, read back from the device (4 bytes; waits for it)."""
+        return int(self.row_start[self.n_games].item())
 
 
 class _DeviceEntry(dict):
@@ -114,6 +133,10 @@ class ReplayBuffer:
         self.buffer = {}                                  # game_id -> dict(length, priorities, game_priority[, history])
         self._filer = None                                # device filer handle (attach_filer)
         self._filing_pending = False                      # a move batch was filed on the device and not synced yet
+        self._reanalyse_plans = {}                        # n_games -> ReanalysePlan (the pass's device arrays, kept)
+        # the batched Reanalyse pass draws from a stream of its own, seeded like the reference's Reanalyse worker
+        # (numpy.random.seed(config.seed), replay_buffer.py:309); the buffer's and the batch sampler's never move for it
+        self._check(self._lib.mzreplay_reanalyse_enable(self._h, int(config.seed) & 0xFFFFFFFF))
         for game_history in (initial_buffer or {}).values():
             self.save_game(game_history)
 
@@ -530,6 +553,110 @@ class ReplayBuffer:
             self._check(self._lib.mzreplay_set_reanalysed(self._h, self._slot(game_id), v.data_ptr(), n, self._stream()))
         self.buffer[game_id]["reanalysed"] = True
 
+    # ---- Reanalyse in batches (include/mzreplay.h mzreplay_reanalyse_*) ----------------------------------
+    def reanalyse_plan(self, n_games, game_ids=None):
+        """Queue the plan of a pass of `n_games` draws (1..4096) on the current stream and return it (ReanalysePlan).
+        game_ids None: drawn on the device, numpy.random.choice(len(buffer)) each, from the pass's own stream; else the
+        caller's ids (each stored now), and the stream does not move.  An empty buffer gives a plan without rows."""
+        self._sync_if_pending()
+        n_games = int(n_games)
+        if not 1 <= n_games <= 4096:
+            raise ValueError("reanalyse_plan: n_games must be 1..4096")
+        given = None
+        if game_ids is not None:
+            given = numpy.ascontiguousarray(game_ids, dtype=numpy.int64).reshape(-1)
+            if len(given) != n_games:
+                raise ValueError("reanalyse_plan: game_ids must hold n_games ids")
+        plan = self._reanalyse_plans.get(n_games)
+        if plan is None:
+            dev = self.device
+            plan = ReanalysePlan(n_games, torch.empty(n_games, dtype=torch.int64, device=dev),
+                                 torch.empty(n_games, dtype=torch.int32, device=dev),
+                                 torch.zeros(n_games + 1, dtype=torch.int32, device=dev), n_games * self.L)
+            self._reanalyse_plans[n_games] = plan
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_reanalyse_plan(
+                self._h, n_games, self.num_played_games - len(self.buffer), len(self.buffer), ptr(given, _native.c_i64_p),
+                plan.game_ids.data_ptr(), plan.slots.data_ptr(), plan.row_start.data_ptr(), self._stream()))
+        return plan
+
+    def reanalyse_observations(self, plan, n_rows=None):
+        """The stacked observation of every row of the plan, CUDA tensor [R, C', H, W] in row order: the input batch of
+        initial_inference.  n_rows: R when the caller has read it already (else it is read here: 4 bytes, blocking)."""
+        self._sync_if_pending()
+        n_rows = plan.rows() if n_rows is None else int(n_rows)
+        stacked = int(self.config.stacked_observations)
+        out = torch.empty((n_rows, self.C + stacked * (self.C + 1), self.H, self.W), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_reanalyse_observations(self._h, plan.n_games, plan.slots.data_ptr(),
+                                                                  plan.row_start.data_ptr(), n_rows, out.data_ptr(),
+                                                                  self._stream()))
+        return out
+
+    def reanalyse_store(self, plan, values):
+        """values (float32 CUDA tensor [R], row order) become the reanalysed root values of the plan's games."""
+        self._sync_if_pending()
+        v = values.reshape(-1)
+        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+            raise ValueError("reanalyse_store: values must be a contiguous float32 CUDA tensor")
+        if v.numel() == 0:
+            return
+        self._keep_values = v
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_reanalyse_store(self._h, plan.n_games, plan.slots.data_ptr(),
+                                                           plan.row_start.data_ptr(), v.data_ptr(), self._stream()))
+
+    def reanalyse_fc_configure(self, flat):
+        """Describe config's fully-connected network to the store; `flat` (weights.FlatWeights) is the buffer the pass
+        reads from then on -- a publish or a broadcast into it refreshes the network.  Raises what the library refuses."""
+        cfg = self.config
+        desc = _native.MzFcDesc()
+        desc.observation_floats = self.C * self.H * self.W * (cfg.stacked_observations + 1) + cfg.stacked_observations * self.H * self.W
+        desc.encoding_size = int(cfg.encoding_size)
+        for i, layers in enumerate((cfg.fc_representation_layers, cfg.fc_dynamics_layers, cfg.fc_reward_layers,
+                                    cfg.fc_policy_layers, cfg.fc_value_layers)):
+            if len(layers) > 3:
+                raise RuntimeError("mzreplay_reanalyse_fc_configure: layer sizes outside the supported range "
+                                   "(<= 3 hidden layers per MLP, widths <= 256)")
+            desc.n_hidden[i] = len(layers)
+            for k, width in enumerate(layers):
+                desc.hidden[i][k] = int(width)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_reanalyse_fc_configure(self._h, ctypes.byref(desc), int(cfg.support_size),
+                                                                  flat.flat.data_ptr(), int(flat.numel)))
+        self._reanalyse_flat = flat
+
+    def reanalyse_fc(self, plan):
+        """The whole pass for the configured fully-connected network, one launch behind the plan; nothing comes back."""
+        self._sync_if_pending()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_reanalyse_fc(self._h, plan.n_games, plan.slots.data_ptr(),
+                                                        plan.row_start.data_ptr(), self._stream()))
+
+    def download_reanalysed(self, game_ids):
+        """(values float32 [n, max_moves], has_values bool [n]) of stored games, read from the device (waits for it): the
+        whole reanalysed row of each game's slot -- entries past the game's length are not the game's."""
+        self._sync_if_pending()
+        slots = numpy.ascontiguousarray([self._slot(int(g)) for g in game_ids], dtype=numpy.int32)
+        values = numpy.zeros((len(slots), self.L), dtype=numpy.float32)
+        has = numpy.zeros(len(slots), dtype=numpy.uint8)
+        if len(slots):
+            with torch.cuda.device(self.device):
+                self._check(self._lib.mzreplay_read_reanalysed(self._h, len(slots), ptr(slots, c_i32_p), ptr(values, c_f32_p),
+                                                               has.ctypes.data, self._stream()))
+        return values, has.astype(bool)
+
+    def reanalyse_state(self):
+        """The pass's stream as numpy.random.get_state() gives it."""
+        key = numpy.zeros(624, dtype=numpy.uint32)
+        pos = ctypes.c_int32()
+        self._check(self._lib.mzreplay_reanalyse_get_rng(self._h, ptr(key, _native.c_u32_p), ctypes.byref(pos)))
+        return ("MT19937", key, pos.value, 0, 0.0)
+
+    def set_reanalyse_state(self, state):
+        key = numpy.ascontiguousarray(state[1], dtype=numpy.uint32)
+        self._check(self._lib.mzreplay_reanalyse_set_rng(self._h, ptr(key, _native.c_u32_p), int(state[2])))
+
     # ---- priorities (replay_buffer.py:197-220) ---------------------------------------------------------
     def update_priorities(self, priorities, index_info):
         self._sync_if_pending()
@@ -558,10 +685,15 @@ class ReplayBuffer:
 
 
 class Reanalyse:
-    """Reanalyse (reference replay_buffer.py:297-361) against the device store: one batched initial_inference
-    over all positions of a sampled game, support_to_scalar, values written back into the store."""
+    """Reanalyse (reference replay_buffer.py:297-361) against the device store.  `reanalyse_game`: the reference's loop
+    body, one batched initial_inference over all positions of a sampled game, support_to_scalar, values written back.
+    `reanalyse_games`: N games per pass, queued on one stream (module docstring)."""
 
-    def __init__(self, initial_checkpoint, config, device=None):
+    def __init__(self, initial_checkpoint, config, device=None, flat=None, max_rows=8192):
+        """flat: the weights.FlatWeights the fully-connected pass reads (e.g. the actor's buffer `Trainer.publish` writes
+        into); without one the model's own weights are flattened at the first pass and `model.set_weights` keeps
+        reaching them (a buffer handed in is refreshed by whoever owns it).  max_rows: rows per
+        initial_inference call on the torch path of `reanalyse_games`."""
         from . import models
         self._models = models
         self.config = config
@@ -572,6 +704,10 @@ class Reanalyse:
         self.model.to(self.device)
         self.model.eval()
         self.num_reanalysed_games = initial_checkpoint.get("num_reanalysed_games", 0)
+        self.flat = flat
+        self.max_rows = int(max_rows)
+        self._fc_store = None            # (store, flat buffer) the FC pass is configured for
+        self._fc_refused = None          # the library's message where it refused this network
 
     @torch.no_grad()
     def reanalyse_game(self, replay_buffer, game_id=None):
@@ -587,13 +723,75 @@ class Reanalyse:
         self.num_reanalysed_games += 1
         return game_id, values
 
-    def reanalyse(self, replay_buffer, shared_storage, max_games=None):
-        """The reference's loop without Ray: runs until shared_storage reports the end of training."""
+    def _fc_pass_ready(self, replay_buffer):
+        """True when the HIP pass covers this network on this store (configured on first use).  The choice follows the
+        network kind and shape alone: a shape the library refuses takes the torch path, its message is kept."""
+        if self.config.network != "fullyconnected":
+            return False
+        if self._fc_store is not None and self._fc_store[0] is replay_buffer:
+            return True
+        if self._fc_refused is not None and self._fc_refused[0] is replay_buffer:
+            return False
+        if self.flat is None:
+            from .weights import FlatWeights
+            self.flat = FlatWeights(self.model)
+        try:
+            replay_buffer.reanalyse_fc_configure(self.flat)
+        except RuntimeError as err:
+            self._fc_refused = (replay_buffer, str(err))
+            return False
+        self._fc_store = (replay_buffer, self.flat)
+        return True
+
+    @torch.no_grad()
+    def _pass_torch(self, replay_buffer, plan, max_rows=None):
+        """The pass of a plan through the torch model (any network); returns the values (CUDA float32 [R]) or None."""
+        rows = plan.rows()                                   # the pass's one host round trip
+        if not rows:
+            return None
+        observations = replay_buffer.reanalyse_observations(plan, rows)
+        step = int(max_rows if max_rows is not None else self.max_rows)
+        values = torch.empty(rows, dtype=torch.float32, device=observations.device)
+        for at in range(0, rows, step):
+            logits = self.model.initial_inference(observations[at: at + step])[0]
+            values[at: at + step] = self._models.support_to_scalar(logits, self.config.support_size).reshape(-1)
+        replay_buffer.reanalyse_store(plan, values)
+        return values
+
+    @torch.no_grad()
+    def reanalyse_games(self, replay_buffer, n_games, game_ids=None, max_rows=None):
+        """A pass over `n_games` games (drawn uniformly on the device from the pass's own stream, or `game_ids`); every
+        position of every game is evaluated once with the current weights and the values are written into the store.
+        Returns the number of draws.  While the store is empty or use_last_model_value is false it only counts.
+
+        Fully-connected networks the library admits: plan + one HIP launch on the flat weights -- no blocking call, no
+        allocation, no host-side decision (the pass can be captured in a graph).  Any other network: plan -> ONE 4-byte
+        readback of the row count -> stacked observations -> model.initial_inference in chunks of at most `max_rows`
+        rows -> support_to_scalar -> store: one host round trip per PASS, where reanalyse_game makes several per game."""
+        n_games = int(n_games)
+        if not 1 <= n_games <= 4096:
+            raise ValueError("reanalyse_games: n_games must be 1..4096")
+        replay_buffer._sync_if_pending()
+        if self.config.use_last_model_value and len(replay_buffer.buffer) > 0:
+            plan = replay_buffer.reanalyse_plan(n_games, game_ids)
+            if self._fc_pass_ready(replay_buffer):
+                replay_buffer.reanalyse_fc(plan)
+            else:
+                self._pass_torch(replay_buffer, plan, max_rows)
+        self.num_reanalysed_games += n_games
+        return n_games
+
+    def reanalyse(self, replay_buffer, shared_storage, max_games=None, games_per_pass=1):
+        """The reference's loop without Ray: runs until shared_storage reports the end of training.  games_per_pass > 1:
+        every turn is a `reanalyse_games` pass of that many games."""
         done = 0
         while shared_storage.get_info("training_step") < self.config.training_steps and not shared_storage.get_info("terminate"):
             self.model.set_weights(shared_storage.get_info("weights"))
-            self.reanalyse_game(replay_buffer)
+            if games_per_pass == 1:
+                self.reanalyse_game(replay_buffer)
+            else:
+                self.reanalyse_games(replay_buffer, games_per_pass)
             shared_storage.set_info("num_reanalysed_games", self.num_reanalysed_games)
-            done += 1
+            done += games_per_pass
             if max_games is not None and done >= max_games:
                 break

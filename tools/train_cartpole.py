@@ -5,12 +5,15 @@ weights.  Not a benchmark: it shows that the pieces learn together (the referenc
 ~420 reward after ~2000 training steps with one worker).
 
     python tools/train_cartpole.py [--envs 64] [--iterations 30] [--moves 8] [--train-steps 100] [--device-sampling]
-                                   [--device-filing]
+                                   [--device-filing] [--reanalyse N]
 
 --device-sampling: replay batches are drawn on the device and an iteration's training steps are queued without a host
 round trip (Trainer.train_steps); the log is the host-sampling run's, line for line, except the seconds.
 --device-filing: the actor files its finished games into the replay store on the device (DeviceSelfPlay.file_to): no
 game visits the host, only lengths and ids come back; the log is again the same, line for line, except the seconds.
+--reanalyse N: every iteration, between the training steps and the publish, one batched Reanalyse pass refreshes the value
+targets of N stored games (Reanalyse.reanalyse_games on the actor's flat weights: one HIP launch behind the plan); the log
+gains a num_reanalysed_games column.  0 (default): no pass, the log is today's line for line.
 """
 import argparse
 import importlib
@@ -38,6 +41,8 @@ def main():
                     help="sample replay batches on the device; an iteration's training steps run as Trainer.train_steps")
     ap.add_argument("--device-filing", action="store_true",
                     help="file finished games into the replay store on the device (DeviceSelfPlay.file_to)")
+    ap.add_argument("--reanalyse", type=int, default=0,
+                    help="games per iteration whose value targets are refreshed by a batched Reanalyse pass (0: none)")
     args = ap.parse_args()
     sp = importlib.import_module("muzero-hypermodel_amd.self_play")
     rb_mod = importlib.import_module("muzero-hypermodel_amd.replay_buffer")
@@ -55,6 +60,7 @@ def main():
     trainer = tr_mod.Trainer({"weights": weights, "training_step": 0, "optimizer_state": None}, config, device="cuda",
                                 graph=not args.eager_trainer)   # the step as one hipGraph replay
     flat = actor.engine._fc_flat                     # the buffer the actor's network (and the fused kernel) alias
+    reanalyse = rb_mod.Reanalyse({"weights": weights}, config, flat=flat) if args.reanalyse > 0 else None
     finished = []
 
     def on_games(batch):
@@ -75,6 +81,8 @@ def main():
         losses = None
         if replay.num_played_games > 0 and args.device_sampling:
             losses = list(trainer.train_steps(replay, args.train_steps))
+            if reanalyse is not None:
+                reanalyse.reanalyse_games(replay, args.reanalyse)
             trainer.publish(flat)
         elif replay.num_played_games > 0:
             for _ in range(args.train_steps):
@@ -83,13 +91,19 @@ def main():
                 priorities, *losses = trainer.update_weights(batch)
                 if config.PER:
                     replay.update_priorities(priorities, index_batch)
+            if reanalyse is not None:
+                reanalyse.reanalyse_games(replay, args.reanalyse)
             trainer.publish(flat)                    # fresh weights for the next batch of searches
+        elif reanalyse is not None:
+            reanalyse.reanalyse_games(replay, args.reanalyse)   # (an empty store: the pass only counts)
         recent = finished[-50:]
         row = dict(iteration=it, training_step=trainer.training_step, played_steps=int(actor.moves_played),
                    games=len(finished), mean_reward_last_50=float(np.mean(recent)) if recent else None,
                    max_reward=float(np.max(finished)) if finished else None,
                    mean_length_of_running_games=float(np.mean(actor._len)), temperature=temperature,
                    total_loss=losses[0] if losses else None, seconds=time.perf_counter() - t0)
+        if reanalyse is not None:
+            row["num_reanalysed_games"] = reanalyse.num_reanalysed_games
         log.append(row)
         print(json.dumps(row), flush=True)
     actor.flush(on_games=on_games)
