@@ -285,6 +285,11 @@ class ReplayBuffer:
             self._check(self._lib.mzreplay_filer_file(self._filer, ctypes.byref(moves), self._stream()))
         self._filing_pending = True
 
+    @property
+    def filing_pending(self):
+        """A move batch was filed on the device (filer_file) and sync_filing has not fetched its games yet."""
+        return self._filing_pending
+
     def filer_lengths(self):
         """Moves played so far in every env's running game (int32 [E]; waits for the device)."""
         out = numpy.zeros(self._filer_envs, dtype=numpy.int32)

@@ -569,6 +569,10 @@ class ManyEnvLoop:
             if (moves_per_pass is None and finished) or (moves_per_pass is not None and moves >= moves_per_pass):
                 return finished
 
+    def _filed_counters(self):
+        """(num_played_games, num_played_steps) of the replay store an actor files its games into itself, else None."""
+        return None
+
     def continuous_self_play(self, shared_storage, replay_buffer, test_mode=False, moves_per_pass=None):
         cfg = self.config
         st = self._loop_state()
@@ -592,12 +596,11 @@ class ManyEnvLoop:
             else:
                 temperature = 0                          # best action, no exploration noise in the sampling
             finished = self._play_pass(temperature, cfg.temperature_threshold, moves_per_pass)
-            if getattr(self, "_filed_to", None) is not None:
+            counters = self._filed_counters()
+            if counters is not None and talker:
                 # the pass filed its games on the device: they are in the store, only the counters travel
-                if talker:
-                    shared_storage.set_info("num_played_games", self._filed_to.num_played_games)
-                    shared_storage.set_info("num_played_steps", self._filed_to.num_played_steps)
-                finished = []
+                shared_storage.set_info("num_played_games", counters[0])
+                shared_storage.set_info("num_played_steps", counters[1])
             for e, game_history in finished:
                 game_history.weights_version = (int(st["started"][e]), st["version"])
                 st["started"][e] = st["version"]
@@ -898,8 +901,8 @@ ENV_OUTPUTS = ("reward", "done", "obs_after", "obs_next")    # what the environm
 
 
 class UnfiledBatch(typing.NamedTuple):
-    """A collected move batch that DeviceSelfPlay.flush has yet to file: HistoryFiler.file's arguments, as views of the
-    engine's download ring and of the actor's pinned buffers (nothing is copied until the filer reads them)."""
+    """A collected move batch that HostRows.flush has yet to file: HistoryFiler.file's arguments, as views of the
+    engine's download ring and of the rows' pinned host sets (nothing is copied until the filer reads them)."""
     out: dict                                               # engine.moves_collect(copy=False)
     host: dict                                              # ENV_OUTPUTS -> [M, E, ...] host arrays
     legal: numpy.ndarray                                    # [E, A] for the whole batch or [M, E, A] per move
@@ -916,12 +919,218 @@ class DeviceBatch:
     ring: dict                   # the environment kernels' outputs on the device, [n_moves, E, ...] each
     obs_in: torch.Tensor         # what the next move's search reads (the move before's next observation, where it lies)
     threshold: int               # play_game's temperature threshold (0 / None: none)
-    pinned: dict                 # the host set the outputs are downloaded into, move by move
+    pinned: typing.Optional[dict]    # the host set the outputs are downloaded into, move by move (HostRows.next_set)
     opponent: bool               # evaluation games: the kernels also return the played actions and the words drawn
 
     @property
     def keys(self):
         return ENV_OUTPUTS + (("played", "words") if self.opponent else ())
+
+
+class HostRows:
+    """Where DeviceSelfPlay's games go by default: the rows of the running games on the host (HistoryFiler), with all a
+    move batch needs on its way there -- the two alternating pinned host sets its env outputs are downloaded into, the
+    copy stream of those downloads, and the collected batch that waits to be filed.  The actor holds one rows owner and
+    never asks which; StoreRows answers the same calls."""
+
+    def __init__(self, engine, envs, config, device, first):
+        self.engine, self.envs, self.config, self.device = engine, envs, config, device
+        # the running games: one packed row per env in the native filer, long enough for a game of config.max_moves moves
+        self.filer = HistoryFiler(envs.E, int(config.max_moves) + 1, envs.observation_shape, envs.A)
+        self.filer.begin(first["obs"], first["to_play"])
+        self.lengths = self.filer.lengths()     # moves played in env e's current game (the filer's own counters)
+        self.pending = None                     # UnfiledBatch: collected, not filed yet
+        self._copy_stream = torch.cuda.Stream(device=device)    # downloads of a batch's env outputs
+        self._sets, self._flip = None, 0        # their two alternating host sets (next_set)
+
+    def admit(self, step=False, on_game=None, opponent="self", batched_pass=True):
+        pass                                    # host rows take every way of playing
+
+    def per_game(self, on_game):
+        return on_game
+
+    def counters(self):
+        return None                             # (no store of its own: the loop's replay buffer counts)
+
+    def searched_moves(self, moves_played):
+        return self.filer.searched_moves()
+
+    def ring_resized(self, ring):
+        self._sets = [{k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
+
+    def next_set(self):
+        """The host set a batch's env outputs are downloaded into (after ring_resized): two alternate, so that the batch
+        waiting to be filed keeps its own."""
+        self._flip ^= 1
+        return self._sets[self._flip]
+
+    def download_move(self, b, m):
+        # the env outputs of a move (reward, done, the observations the history rows need) go to pinned host memory on a
+        # copy stream as soon as the move's env kernel has run: the downloads ride under the batch's remaining searches
+        ran = torch.cuda.Event()
+        ran.record(torch.cuda.current_stream(self.device))
+        self._copy_stream.wait_event(ran)
+        with torch.cuda.stream(self._copy_stream):
+            for k in b.keys:
+                b.pinned[k][m].copy_(b.ring[k][m], non_blocking=True)
+
+    def file_move(self, one, legal, num_legal, reward, over, after, nxt):
+        # step_end's move, filed natively (include/mzhist.h, the library's worker pool): a batch of one move whose legal
+        # sets are this move's
+        return self.filer.file(one, legal, num_legal, self.config.num_simulations, reward[None], over.astype(numpy.uint8)[None],
+                               after["obs"][None], nxt["obs"][None], to_play_after=after["to_play"][None],
+                               to_play_next=nxt["to_play"][None])
+
+    def queue(self):
+        pass
+
+    def flush(self):
+        """File the batch that waits (native code, one pass on the library's worker pool): the games it finished as
+        PackedGames, or None."""
+        u, self.pending = self.pending, None
+        if u is None:
+            return None
+        return self.filer.file(u.out, u.legal, u.num_legal, self.config.num_simulations, u.host["reward"], u.host["done"],
+                               u.host["obs_after"], u.host["obs_next"], to_play_after=u.to_play_after,
+                               to_play_next=u.to_play_next, played=u.played)
+
+    # the batch before's games leave once the current batch has been enqueued, so that host filing runs under the GPU,
+    # and before moves_collect overwrites the engine ring the UnfiledBatch views
+    games_before_collect = flush
+
+    def games_after_collect(self):
+        return None
+
+    def keep_predrawn(self, out, ring, n_moves, cur):
+        """A collected batch of the pre-drawn form becomes the batch that waits; returns the envs' current observations."""
+        # env outputs of the batch: one asynchronous copy each into pinned host buffers (alternating sets, so that
+        # the batch waiting to be filed keeps its own), one wait
+        pinned = self.next_set()
+        for k in ENV_OUTPUTS:
+            pinned[k][:n_moves].copy_(ring[k][:n_moves], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        host = {k: pinned[k][:n_moves].numpy() for k in ENV_OUTPUTS}
+        self.pending = UnfiledBatch(out=out, host=host, legal=cur["legal"], num_legal=cur["num_legal"])
+        return host["obs_next"][n_moves - 1]
+
+    def keep_device_inputs(self, out, b):
+        """A collected batch of the device-input form becomes the batch that waits."""
+        # (views of the engine's pinned rings, filled move by move while the batch ran: nothing is unpacked here; they
+        # stay valid until the batch after the next one is prepared, and flush() files them before that)
+        inputs = self.engine.moves_inputs(b.n_moves, copy=False)
+        last_to_play = self.envs.to_play.cpu().numpy()
+        self._copy_stream.synchronize()                  # (the last move's downloads)
+        host = {k: b.pinned[k][:b.n_moves].numpy() for k in b.keys}
+        played = None
+        if b.opponent:
+            # the opponents drew on the device copies of the streams: the host mirrors step over those words
+            played = host["played"]
+            self.engine.rng_consumed(host["words"].view(numpy.uint32).sum(axis=0, dtype=numpy.uint64))
+        two_players = len(self.config.players) > 1
+        to_play = inputs["to_play"]
+        to_play_after = (1 - to_play) if two_players else numpy.zeros_like(to_play)
+        to_play_next = numpy.concatenate([to_play[1:], last_to_play[None]], axis=0)
+        self.pending = UnfiledBatch(out=out, host=host, legal=inputs["legal"], num_legal=inputs["num_legal"],
+                                    to_play_after=to_play_after, to_play_next=to_play_next, played=played)
+
+
+class StoreRows:
+    """Where DeviceSelfPlay's games go after file_to(): rows in `replay_buffer`'s store, filed on the device
+    (include/mzreplay.h mzreplay_filer_*).  Owns the buffer's reference and the described batch that waits to be queued,
+    with the ring it points into.  Nothing of a batch is downloaded; a batch's games reach the store, and on_games,
+    exactly when HostRows would hand them out: its filing is queued at the start of the next play_moves -- behind the
+    batch's last environment kernel, ahead of anything that rewrites the rings -- or in flush(), and its few bytes are
+    synchronised right behind the current batch's moves_collect; the new batch is described only then."""
+
+    def __init__(self, replay_buffer, engine, envs, config):
+        self.replay_buffer, self.engine, self.envs, self.config = replay_buffer, engine, envs, config
+        replay_buffer.attach_filer(envs.E)
+        obs, _, _, to_play = envs.observe()
+        replay_buffer.filer_begin(obs, to_play)
+        self.pending = None                     # (MzReplayFileMoves, ring): described, not queued yet (the ring stays alive with it)
+
+    @property
+    def lengths(self):
+        return self.replay_buffer.filer_lengths()           # (a small download)
+
+    def admit(self, step=False, on_game=None, opponent="self", batched_pass=True):
+        """Evaluation games are never saved to a replay buffer, and the device filer takes whole move batches."""
+        if not batched_pass:
+            raise NotImplementedError("after file_to() a pass must run as one move batch on the device: give "
+                                      "moves_per_pass, and a temperature and root_dirichlet_alpha play_moves accepts")
+        what = "step()" if step else "on_game" if on_game is not None else "an opponent" if opponent != "self" else None
+        if what is not None:
+            raise NotImplementedError(f"{what} is not available after file_to(): the games are filed on the device from "
+                                      "whole move batches (play_moves with on_games)")
+
+    def per_game(self, on_game):
+        return None                             # the games are in the store: none is rebuilt on the host
+
+    def counters(self):
+        return self.replay_buffer.num_played_games, self.replay_buffer.num_played_steps
+
+    def searched_moves(self, moves_played):
+        return moves_played                     # self-play only: every ply was searched
+
+    def ring_resized(self, ring):
+        pass                                    # (an actor that files on the device downloads none of it: no host sets)
+
+    def next_set(self):
+        return None
+
+    def download_move(self, b, m):
+        pass                                    # filed on the device: the env outputs stay where they are
+
+    def queue(self):
+        if self.pending is not None:
+            self.replay_buffer.filer_file(self.pending[0])
+            self.pending = None
+
+    def flush(self):
+        self.queue()
+        return self.games_after_collect()
+
+    def games_before_collect(self):
+        return None
+
+    def games_after_collect(self):
+        """The games of the filing queued last: their lengths and ids join the host bookkeeping (one small sync)."""
+        if not self.replay_buffer.filing_pending:
+            return None
+        filed = FiledGames(*self.replay_buffer.sync_filing())
+        return filed if len(filed) else None
+
+    def keep_predrawn(self, out, ring, n_moves, cur):
+        self._describe(n_moves, ring, device_inputs=False)
+        return None                             # (the observations stay on the device)
+
+    def keep_device_inputs(self, out, b):
+        self._describe(b.n_moves, b.ring, device_inputs=True)
+
+    def _describe(self, n_moves, ring, device_inputs):
+        """Describe the batch just collected for the device filer: the search results where the engine left them, the env
+        outputs in the actor's ring, the legal sets and players to move from the envs' own arrays (a constant legal set)
+        or from the engine's recorded-inputs ring (device-input batches)."""
+        eng, envs = self.engine, self.envs
+        out = eng.moves_device_ring()
+        mv = _native.MzReplayFileMoves()
+        mv.n_moves, mv.num_simulations = int(n_moves), int(self.config.num_simulations)
+        mv.players = 2 if len(self.config.players) > 1 else 1
+        for name in ("actions", "visits", "root_value_sum"):
+            setattr(mv, name, out[name])
+            setattr(mv, name + "_stride", out["stride"])
+        if device_inputs:
+            inputs = eng.moves_inputs_device_ring()
+            for name in ("legal", "num_legal", "to_play"):
+                setattr(mv, name, inputs[name])
+                setattr(mv, name + "_stride", inputs["stride"])
+            mv.to_play_last = envs.to_play.data_ptr()
+        else:
+            mv.legal, mv.num_legal, mv.legal_stride, mv.num_legal_stride = envs.legal.data_ptr(), envs.num_legal.data_ptr(), 0, 0
+            mv.to_play, mv.to_play_stride, mv.to_play_last = None, 0, None
+        mv.rewards, mv.done = ring["reward"].data_ptr(), ring["done"].data_ptr()
+        mv.obs_after, mv.obs_next = ring["obs_after"].data_ptr(), ring["obs_next"].data_ptr()
+        self.pending = (mv, ring)
 
 
 class DeviceSelfPlay(ManyEnvLoop):
@@ -946,23 +1155,19 @@ class DeviceSelfPlay(ManyEnvLoop):
         self.moves_played = 0
         self.games_finished = 0
         self._cur = self._observe_host()
-        # the running games: one packed row per env in the native filer, long enough for a game of config.max_moves moves
-        self._filer = HistoryFiler(E, int(config.max_moves) + 1, self.envs.observation_shape, self.envs.A)
-        self._filer.begin(self._cur["obs"], self._cur["to_play"])
-        self._host_len = self._filer.lengths()  # moves played in env e's current game (the filer's own counters)
-        self._filed_to = None                   # the ReplayBuffer whose device filer takes the games (file_to)
+        self._row_moves = int(config.max_moves)  # moves a running game's row holds, whoever owns the rows
+        # where the games are filed: HostRows, until file_to() swaps StoreRows in; the rows of the running games, the
+        # batch waiting to be filed and everything on the way there live in the owner and nowhere else
+        self._rows = HostRows(self.engine, self.envs, config, self.device, self._cur)
         self._step_is_batch = False             # step_begin queued the whole move as a one-move batch (an opponent's turn)
         self._batch_ready = None                # (n_moves, temperature) of the batch drawn and uploaded ahead (play_moves)
         self._dev_batch = None                  # DeviceBatch being queued
-        self._unfiled = None                    # UnfiledBatch: collected, not filed yet
-        self._copy_stream = torch.cuda.Stream(device=self.device)    # downloads of a batch's env outputs
         self._ring = None                       # env outputs of a batch on the device, sized by the first batch (_move_ring)
-        self._pinned, self._flip = None, 0      # their two alternating host sets (_next_pinned)
 
     @property
     def _len(self):
         """Moves played in every env's running game: the host filer's counters, or the device filer's (a small download)."""
-        return self._host_len if self._filed_to is None else self._filed_to.filer_lengths()
+        return self._rows.lengths
 
     def file_to(self, replay_buffer):
         """From now on finished games go into `replay_buffer`'s store on the device (include/mzreplay.h
@@ -970,9 +1175,9 @@ class DeviceSelfPlay(ManyEnvLoop):
         policy row or value of a game visits the host, and `on_games` receives a FiledGames (env_index, length, game_id)
         instead of a PackedGames.  Before the first move only, same device only; step(), on_game and opponent modes are
         not available afterwards (evaluation games are never saved to a replay buffer)."""
-        if self._filed_to is not None:
+        if isinstance(self._rows, StoreRows):
             raise ValueError("file_to was called before")
-        if self.moves_played or self._batch_ready or self._dev_batch is not None or self._unfiled is not None:
+        if self.moves_played or self._batch_ready or self._dev_batch is not None or self._rows.pending is not None:
             raise ValueError("file_to comes before the first move: the running games live in the host filer by now")
         store_device = torch.device(replay_buffer.device)
         mine = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
@@ -981,54 +1186,10 @@ class DeviceSelfPlay(ManyEnvLoop):
         if (replay_buffer.L != int(self.config.max_moves) or replay_buffer.A != self.envs.A
                 or (replay_buffer.C, replay_buffer.H, replay_buffer.W) != tuple(self.envs.observation_shape)):
             raise ValueError("file_to: the replay buffer was built for another game shape or move limit")
-        replay_buffer.attach_filer(self.E)
-        obs, _, _, to_play = self.envs.observe()
-        replay_buffer.filer_begin(obs, to_play)
-        self._filed_to = replay_buffer
+        self._rows = StoreRows(replay_buffer, self.engine, self.envs, self.config)
 
-    def _filing_refuses(self, what):
-        if self._filed_to is not None:
-            raise NotImplementedError(f"{what} is not available after file_to(): the games are filed on the device from "
-                                      "whole move batches (play_moves with on_games)")
-
-    def _file_on_device(self, n_moves, device_inputs):
-        """Describe the batch just queued for the device filer: the search results where the engine left them, the env
-        outputs in the actor's ring, the legal sets and players to move from the envs' own arrays (a constant legal set)
-        or from the engine's recorded-inputs ring (device-input batches).  The filing itself is queued by _queue_filing
-        -- behind the batch's last environment kernel and ahead of anything that rewrites those arrays: at the start of
-        the next play_moves, or in flush() -- so that a batch's games reach the store, and on_games, exactly when the host
-        path files them (play_moves hands out the batch before's games while the GPU runs the current one)."""
-        eng, envs, ring = self.engine, self.envs, self._ring
-        out = eng.moves_device_ring()
-        mv = _native.MzReplayFileMoves()
-        mv.n_moves, mv.num_simulations = int(n_moves), int(self.config.num_simulations)
-        mv.players = 2 if len(self.config.players) > 1 else 1
-        for name in ("actions", "visits", "root_value_sum"):
-            setattr(mv, name, out[name])
-            setattr(mv, name + "_stride", out["stride"])
-        if device_inputs:
-            inputs = eng.moves_inputs_device_ring()
-            for name in ("legal", "num_legal", "to_play"):
-                setattr(mv, name, inputs[name])
-                setattr(mv, name + "_stride", inputs["stride"])
-            mv.to_play_last = envs.to_play.data_ptr()
-        else:
-            mv.legal, mv.num_legal, mv.legal_stride, mv.num_legal_stride = envs.legal.data_ptr(), envs.num_legal.data_ptr(), 0, 0
-            mv.to_play, mv.to_play_stride, mv.to_play_last = None, 0, None
-        mv.rewards, mv.done = ring["reward"].data_ptr(), ring["done"].data_ptr()
-        mv.obs_after, mv.obs_next = ring["obs_after"].data_ptr(), ring["obs_next"].data_ptr()
-        self._unfiled = (mv, ring)                           # (the ring stays alive with it)
-
-    def _queue_filing(self):
-        if self._filed_to is not None and self._unfiled is not None:
-            self._filed_to.filer_file(self._unfiled[0])
-            self._unfiled = None
-
-    def _sync_filing(self, on_games):
-        """The games of the filing queued last: their lengths and ids join the host bookkeeping (one small sync)."""
-        if self._filed_to._filing_pending:
-            filed = FiledGames(*self._filed_to.sync_filing())
-            self._hand_out(filed if len(filed) else None, None, on_games)
+    def _filed_counters(self):
+        return self._rows.counters()
 
     def _observe_host(self):
         obs, legal, num_legal, to_play = self.envs.observe()
@@ -1075,9 +1236,9 @@ class DeviceSelfPlay(ManyEnvLoop):
         switch between self-play and an opponent; the positions stay, the legal counts the searches read are observed
         again in the new mode."""
         limit = int(self.config.max_moves)
-        if limit + 1 > self._filer.L:
+        if limit > self._row_moves:
             raise ValueError(f"config.max_moves was raised to {limit} on a built actor whose history rows hold "
-                             f"{self._filer.L - 1} moves; build a new actor")
+                             f"{self._row_moves} moves; build a new actor")
         limit = limit if limit < self.envs.max_episode_steps else 0
         if self.envs.max_moves != limit:
             self.envs.set_max_moves(limit)
@@ -1103,7 +1264,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         (the GPU works; `step_end` waits).  Two actors on streams of their own alternate their halves
         (PipelinedDeviceSelfPlay): one's host work runs under the other's search.  Against an opponent the whole move
         is queued here (search, action sampling, env step: a one-move batch), so the temperature is needed already."""
-        self._filing_refuses("step()")
+        self._rows.admit(step=True)
         mode = self._resolve_opponent(opponent, muzero_player)
         if mode[0] != "self":
             if temperature is None:
@@ -1148,19 +1309,15 @@ class DeviceSelfPlay(ManyEnvLoop):
         if over.any():
             self.envs.reset(torch.from_numpy(over.astype(numpy.uint8)).to(self.device))
             nxt = self._observe_host()
-        # file the move natively (include/mzhist.h, the library's worker pool): a batch of one move whose legal sets are
-        # this move's; child visits by action and root values as store_search_statistics computes them (self_play.py:497-512)
+        # child visits by action and root values as store_search_statistics computes them (self_play.py:497-512)
         one = {"actions": actions.astype(numpy.int32)[None], "visits": stats["visits"][None],
                "root_value_sum": stats["root_value_sum"][None], "moves_done": numpy.ones(self.E, dtype=numpy.int32)}
-        batch = self._filer.file(one, cur["legal"], cur["num_legal"], self.config.num_simulations, reward[None],
-                                 over.astype(numpy.uint8)[None], after["obs"][None], nxt["obs"][None],
-                                 to_play_after=after["to_play"][None], to_play_next=nxt["to_play"][None])
-        self._hand_out(batch, on_game, on_games)
+        self._hand_out(self._rows.file_move(one, cur["legal"], cur["num_legal"], reward, over, after, nxt), on_game, on_games)
         self._cur = nxt
         self.moves_played += self.E
 
     def _hand_out(self, batch, on_game, on_games):
-        """The games a filing finished (PackedGames or None) leave: counted, then as one batch, then one by one."""
+        """The games a filing finished (PackedGames, FiledGames or None) leave: counted, then as one batch, then one by one."""
         if batch is None:
             return
         self.games_finished += len(batch)
@@ -1186,12 +1343,8 @@ class DeviceSelfPlay(ManyEnvLoop):
         batch (always its device-input form; every env then plays all n_moves plies)."""
         E, eng, envs, cfg = self.E, self.engine, self.envs, self.config
         mode = self._resolve_opponent(opponent, muzero_player)
-        if self._filed_to is not None:
-            if on_game is not None:
-                self._filing_refuses("on_game")
-            if mode[0] != "self":
-                self._filing_refuses("an opponent")
-            self._queue_filing()                             # the batch before: ahead of anything this one rewrites
+        self._rows.admit(on_game=on_game, opponent=mode[0])
+        self._rows.queue()                                   # (store rows) the batch before: ahead of anything this one rewrites
         # Everything but a fused search of a game with a constant legal set takes the device-input form of the batch:
         # board games (legal sets change), residual networks (lock-step searches), and a temperature threshold
         # (play_game drops to temperature 0 once len(action_history) reaches it, self_play.py:152-158: a per-env, per-move
@@ -1215,32 +1368,17 @@ class DeviceSelfPlay(ManyEnvLoop):
             # step, terminal observation, reset of the finished envs, next observation: one call, one launch
             obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
                                   ring["obs_next"][m])
-        if self._filed_to is not None:
-            # the batch is filed where it lies: nothing of the env outputs is downloaded; collect() still waits for the
-            # batch (the RNG mirrors need the engine's own ring) and the filing's few bytes come back right behind it
-            eng.moves_predraw_next(n_moves, cur["legal"], cur["to_play"], temperature, True, num_legal=cur["num_legal"])
-            out = eng.moves_collect(copy=False)
-            self._sync_filing(on_games)                      # the batch before's games (filed ahead of this batch)
-            self._file_on_device(n_moves, device_inputs=False)
-            eng.moves_submit_next()
-            self._batch_ready = params
-            self._cur = dict(cur, obs_dev=obs_in, obs=None)
-            self.moves_played += int(out["moves_done"].sum())
-            return out["moves_done"].copy()
-        self.flush(on_game, on_games)                        # the previous batch's games, while this one runs
+        # host rows: the previous batch's games, while this one runs
+        self._hand_out(self._rows.games_before_collect(), on_game, on_games)
         eng.moves_predraw_next(n_moves, cur["legal"], cur["to_play"], temperature, True, num_legal=cur["num_legal"])
-        out = eng.moves_collect(copy=False)                  # views: filed (flush) before the next collect overwrites them
-        # env outputs of the batch: one asynchronous copy each into pinned host buffers (alternating sets, so that
-        # the batch waiting to be filed keeps its own), one wait
-        pinned = self._next_pinned()
-        for k in ENV_OUTPUTS:
-            pinned[k][:n_moves].copy_(ring[k][:n_moves], non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        host = {k: pinned[k][:n_moves].numpy() for k in ENV_OUTPUTS}
+        out = eng.moves_collect(copy=False)                  # views: kept by the rows, filed before the next collect
+        # store rows: the batch before's games, filed ahead of this batch (collect() has waited for it: the RNG mirrors
+        # need the engine's own ring); the filing's few bytes come back right behind it
+        self._hand_out(self._rows.games_after_collect(), on_game, on_games)
+        obs = self._rows.keep_predrawn(out, ring, n_moves, cur)
         eng.moves_submit_next()
         self._batch_ready = params
-        self._unfiled = UnfiledBatch(out=out, host=host, legal=cur["legal"], num_legal=cur["num_legal"])
-        self._cur = dict(cur, obs_dev=obs_in, obs=host["obs_next"][n_moves - 1])
+        self._cur = dict(cur, obs_dev=obs_in, obs=obs)
         self.moves_played += int(out["moves_done"].sum())
         return out["moves_done"].copy()
 
@@ -1271,11 +1409,9 @@ class DeviceSelfPlay(ManyEnvLoop):
             eng.moves_sit_out(True)        # the opponent's plies: played by the environment kernels, filed from `played`
         if temperature_threshold:
             eng.moves_temperature_threshold(temperature_threshold, self._len)
-        # the env outputs of a move (reward, done, the observations the history rows need) go to pinned host memory on a
-        # copy stream as soon as the move's env kernel has run: the downloads ride under the batch's remaining searches
         ring = self._move_ring(n_moves)
-        self._dev_batch = DeviceBatch(n_moves=n_moves, ring=ring, obs_in=self._cur["obs_dev"],
-                                      threshold=temperature_threshold, pinned=self._next_pinned(), opponent=mode[0] != "self")
+        self._dev_batch = DeviceBatch(n_moves=n_moves, ring=ring, obs_in=self._cur["obs_dev"], threshold=temperature_threshold,
+                                      pinned=self._rows.next_set(), opponent=mode[0] != "self")
 
     def _device_batch_move(self, m):
         b, eng, envs = self._dev_batch, self.engine, self.envs
@@ -1289,45 +1425,16 @@ class DeviceSelfPlay(ManyEnvLoop):
         b.obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
                                 ring["obs_next"][m], played=ring["played"][m] if b.opponent else None,
                                 words=ring["words"][m] if b.opponent else None)
-        if self._filed_to is not None:
-            return                                           # filed on the device: the env outputs stay where they are
-        ran = torch.cuda.Event()
-        ran.record(torch.cuda.current_stream(self.device))
-        self._copy_stream.wait_event(ran)
-        with torch.cuda.stream(self._copy_stream):
-            for k in b.keys:
-                b.pinned[k][m].copy_(ring[k][m], non_blocking=True)
+        self._rows.download_move(b, m)
 
     def _device_batch_end(self, on_game, on_games):
-        b, eng, envs = self._dev_batch, self.engine, self.envs
-        n_moves = b.n_moves
-        self._dev_batch = None
-        if self._filed_to is not None:
-            out = eng.moves_collect(copy=False)
-            self._sync_filing(on_games)                      # the batch before's games (filed ahead of this batch)
-            self._file_on_device(n_moves, device_inputs=True)
-            self._cur = dict(obs_dev=b.obs_in, on_device_only=True)
-            self.moves_played += int(out["moves_done"].sum())
-            return out["moves_done"].copy()
-        self.flush(on_game, on_games)                        # the previous batch's games, while this one runs
-        # (views of the engine's pinned rings, filled move by move while the batch ran: nothing is unpacked here; they
-        # stay valid until the batch after the next one is prepared, and flush() files them before that)
-        out = eng.moves_collect(copy=False)
-        inputs = eng.moves_inputs(n_moves, copy=False)
-        last_to_play = envs.to_play.cpu().numpy()
-        self._copy_stream.synchronize()                  # (the last move's downloads)
-        host = {k: b.pinned[k][:n_moves].numpy() for k in b.keys}
-        played = None
-        if b.opponent:
-            # the opponents drew on the device copies of the streams: the host mirrors step over those words
-            played = host["played"]
-            eng.rng_consumed(host["words"].view(numpy.uint32).sum(axis=0, dtype=numpy.uint64))
-        two_players = len(self.config.players) > 1
-        to_play = inputs["to_play"]
-        to_play_after = (1 - to_play) if two_players else numpy.zeros_like(to_play)
-        to_play_next = numpy.concatenate([to_play[1:], last_to_play[None]], axis=0)
-        self._unfiled = UnfiledBatch(out=out, host=host, legal=inputs["legal"], num_legal=inputs["num_legal"],
-                                     to_play_after=to_play_after, to_play_next=to_play_next, played=played)
+        b, self._dev_batch = self._dev_batch, None
+        # host rows: the previous batch's games, while this one runs
+        self._hand_out(self._rows.games_before_collect(), on_game, on_games)
+        out = self.engine.moves_collect(copy=False)
+        # store rows: the batch before's games (filed ahead of this batch)
+        self._hand_out(self._rows.games_after_collect(), on_game, on_games)
+        self._rows.keep_device_inputs(out, b)
         # the envs' current positions stay on the device: the next batch starts from the last move's observation (the
         # kernels' output, where it lies); a step() fetches what it needs first (_current)
         self._cur = dict(obs_dev=b.obs_in, on_device_only=True)
@@ -1347,46 +1454,27 @@ class DeviceSelfPlay(ManyEnvLoop):
     def _play_pass(self, temperature, temperature_threshold, moves_per_pass):
         """ManyEnvLoop's pass: whole move batches on the device when the game, the network and the temperature allow
         it (play_moves), else one move at a time (step)."""
-        if self._filed_to is not None:
-            if not self._batchable(temperature, temperature_threshold, moves_per_pass):
-                raise NotImplementedError("after file_to() a pass must run as one move batch on the device: give "
-                                          "moves_per_pass, and a temperature and root_dirichlet_alpha play_moves accepts")
-            self.play_moves(moves_per_pass, temperature, temperature_threshold=temperature_threshold or 0)
-            self.flush()
-            return []
         if not self._batchable(temperature, temperature_threshold, moves_per_pass):
+            self._rows.admit(batched_pass=False)
             return ManyEnvLoop._play_pass(self, temperature, temperature_threshold, moves_per_pass)
         finished = []
-        self.play_moves(moves_per_pass, temperature, on_game=lambda e, gh: finished.append((e, gh)),
-                        temperature_threshold=temperature_threshold or 0)
-        self.flush(on_game=lambda e, gh: finished.append((e, gh)))
+        collect = self._rows.per_game(lambda e, gh: finished.append((e, gh)))
+        self.play_moves(moves_per_pass, temperature, on_game=collect, temperature_threshold=temperature_threshold or 0)
+        self.flush(on_game=collect)
         return finished
 
     def flush(self, on_game=None, on_games=None):
         """File the moves of the last play_moves batch into the histories (play_moves does this for the
-        batch before while the GPU runs the current one; call it once at the end).  Native code
-        (HistoryFiler, include/mzhist.h): one pass over the batch on the library's worker pool."""
-        if self._filed_to is not None:
-            # the games are in the store: their lengths and ids join the host bookkeeping (one small sync per batch)
-            if on_game is not None:
-                self._filing_refuses("on_game")
-            self._queue_filing()
-            self._sync_filing(on_games)
-            return
-        u, self._unfiled = self._unfiled, None
-        if u is None:
-            return
-        batch = self._filer.file(u.out, u.legal, u.num_legal, self.config.num_simulations, u.host["reward"], u.host["done"],
-                                 u.host["obs_after"], u.host["obs_next"], to_play_after=u.to_play_after,
-                                 to_play_next=u.to_play_next, played=u.played)
-        self._hand_out(batch, on_game, on_games)
+        batch before while the GPU runs the current one; call it once at the end).  Host rows: native code
+        (HistoryFiler, include/mzhist.h), one pass over the batch on the library's worker pool.  Store rows: the filing
+        is queued and its games' lengths and ids join the host bookkeeping (one small sync per batch)."""
+        self._rows.admit(on_game=on_game)
+        self._hand_out(self._rows.flush(), on_game, on_games)
 
     @property
     def searched_moves(self):
         """Env-moves filed so far that ran a search (moves_played counts the opponent's plies too)."""
-        if self._filed_to is not None:
-            return self.moves_played                         # self-play only: every ply was searched
-        return self._filer.searched_moves()
+        return self._rows.searched_moves(self.moves_played)
 
     def _drop_batch(self):
         """Forget the batch that was drawn and uploaded ahead (its noise goes back into the RNG streams)."""
@@ -1406,17 +1494,9 @@ class DeviceSelfPlay(ManyEnvLoop):
                         # opponents consumed
                         played=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev),
                         words=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev))
-            # (an actor that files on the device downloads none of this: no host sets)
-            self._pinned = [None if self._filed_to is not None else
-                            {k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
+            self._rows.ring_resized(ring)                    # (host rows: their host sets are sized with it)
             self._ring = ring
         return ring
-
-    def _next_pinned(self):
-        """The host set a batch's env outputs are downloaded into (after _move_ring): two alternate, so that the batch
-        waiting to be filed keeps its own."""
-        self._flip ^= 1
-        return self._pinned[self._flip]
 
     def close(self):
         self.envs.close()
