@@ -461,7 +461,8 @@ int mzmcts_board_conv3x3(const float *x, const float *packed, const float *scale
  *   dynamics    conv(C+1 -> C), N residual blocks; last layer: export_raw -> reward head, export_unit -> next state
  *   prediction  N residual blocks; last layer: export_raw -> value / policy heads
  * (models.py:399-420, 500-522, 586-602).  n_layers <= 16; shapes as mzmcts_board_conv_supported; MZMCTS_ERR_INVALID
- * when two activation buffers of the workgroup do not fit in LDS (the caller keeps the per-layer path). */
+ * when two activation buffers of the workgroup do not fit in LDS (the caller keeps the per-layer path) -- which is always
+ * the case for 64 channels on 3 x 3 boards, in both forms: that shape has the single-layer kernel only. */
 typedef struct mzmcts_tower_layer {
     const void *packed;        /* mzmcts_board_conv_pack (fp32 tower) or mzmcts_board_conv_pack_split (split tower) */
     const float *scale, *shift; /* dev f32[channels] each, 16-byte aligned (the towers read four channels at a time) */
@@ -504,7 +505,8 @@ int mzmcts_board_tower_heads(const float *x, const struct mzmcts_tower_gather *g
  * mzmcts_board_conv_pack_split (mzmcts_board_conv_split_halfs(cin_conv, cout) 16-bit words; cin_conv = cin - 1 when
  * const_plane).  const_plane != 0: the LAST input plane of x is one constant per sample (the dynamics input's action
  * plane, models.py:553-568); it is not convolved, its contribution comes from `const_table` (dev f32[cout, height *
- * width], written by the pack call).  |activation| must stay below 8188 (larger values turn into inf / NaN): with
+ * width], written by the pack call; a skip on layer 1 would have to read that plane when cin0 <= channels: refused,
+ * MZMCTS_ERR_INVALID).  |activation| must stay below 8188 (larger values turn into inf / NaN): with
  * layers[0].gate set the launch reports the blocks where that happened, for the exact-fp32 tower to re-run. */
 int64_t mzmcts_board_conv_split_halfs(int32_t cin_conv, int32_t cout);
 int mzmcts_board_conv_pack_split(const float *weight, void *packed, float *const_table, int32_t cin, int32_t cout,

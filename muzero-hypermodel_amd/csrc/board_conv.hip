@@ -45,6 +45,15 @@ __host__ __device__ inline int conv_packed_floats(int cin, int cout) {  // [9 * 
     return (9 * conv_groups(cin) + 2) * 4 * cout * 4;
 }
 
+// The staging loops turn a plane index sc = s * cin + ci (below 2^16) into the sample s with ONE __umulhi by
+// ceil(2^32 / cin): exact for 2 <= cin <= 80 (the error term sc * (magic * cin - 2^32) < 2^16 * 80 stays below 2^32).  A
+// divisor of 1 has no such 32-bit reciprocal -- 2^32 wraps to 0, which sent every plane to sample 0 -- so 0 stands for it:
+// the quotient is the index itself.
+inline uint32_t plane_div_magic(int cin) { return cin == 1 ? 0u : 0xFFFFFFFFu / static_cast<uint32_t>(cin) + 1u; }
+__device__ __forceinline__ int plane_div(int sc, uint32_t magic) {
+    return magic ? static_cast<int>(__umulhi(static_cast<uint32_t>(sc), magic)) : sc;
+}
+
 // Packed weights: wt[(((tap * NG + grp) * 4 + kk) * cout + n) * 4 + g] = w[n][grp * 16 + 4 * kk + g][tap]
 // (0 for channels >= cin and for the spare group): lane (n, kk) of a wave reads the four weights of its four k-steps of
 // a group with ONE 16-byte load, 16 lanes x 16 B contiguous per kk.
@@ -102,7 +111,7 @@ __global__ __launch_bounds__(64 * kConvWaves) void board_conv3x3_kernel(const fl
     auto place = [&](int i, float v) {
         const int p = i % P;
         const int sc = i / P;                           // s * cin + ci
-        const int s = static_cast<int>(__umulhi(static_cast<uint32_t>(sc), cin_magic));   // sc / cin (sc < 2^16: exact)
+        const int s = plane_div(sc, cin_magic);         // sc / cin
         const int ci = sc - s * cin;
         lds[(s * PP + (p / W + 1) * PW + (p % W) + 1) * CP + ci] = v;
     };
@@ -389,7 +398,7 @@ __device__ __forceinline__ void board_tower_block(const float* __restrict__ x, i
                     at[k] = -1;
                     v[k] = 0.f;
                     if (sc < planes) {
-                        const int s = static_cast<int>(__umulhi(static_cast<uint32_t>(sc), cin0_magic));
+                        const int s = plane_div(sc, cin0_magic);
                         const int ci = sc - s * cin0;
                         v[k] = (ci * P < gather.hidden) ? in_row[s][ci * P + p] : act_plane[s];
                         at[k] = s * PP * cp0 + at_p + ci;
@@ -406,7 +415,7 @@ __device__ __forceinline__ void board_tower_block(const float* __restrict__ x, i
         auto place = [&](int i, float v) {
             const int p = i % P;
             const int sc = i / P;
-            const int s = static_cast<int>(__umulhi(static_cast<uint32_t>(sc), cin0_magic));
+            const int s = plane_div(sc, cin0_magic);
             const int ci = sc - s * cin0;
             lds[(s * PP + (p / W + 1) * PW + (p % W) + 1) * cp0 + ci] = v;
         };
@@ -1408,7 +1417,7 @@ static int launch_board_tower(const float* x, int batch, int cin0, const TowerAr
         return MZMCTS_ERR_HIP;
     const int blocks = (batch + SB - 1) / SB;
     const dim3 grid(static_cast<unsigned>(args.gate ? std::min(blocks, 256) : blocks)), block(64 * kConvWaves);
-    kernel<<<grid, block, lds, stream>>>(x, batch, cin0, 0xFFFFFFFFu / static_cast<uint32_t>(cin0) + 1u, cp0, cp1, args, gather);
+    kernel<<<grid, block, lds, stream>>>(x, batch, cin0, plane_div_magic(cin0), cp0, cp1, args, gather);
     return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
 }
 
@@ -1585,7 +1594,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
                 at[k] = -1;
                 v[k] = 0.f;
                 if (sc < planes) {
-                    const int sidx = static_cast<int>(__umulhi(static_cast<uint32_t>(sc), cin_load_magic));
+                    const int sidx = plane_div(sc, cin_load_magic);
                     const int ci = sc - sidx * cin_load;
                     v[k] = in_row[sidx][ci * P + p];
                     at[k] = sidx * PP * 2 * cph0 + at_p + ci;
@@ -1865,7 +1874,7 @@ static int launch_board_tower_split(const float* x, int batch, int cin0, int con
         return MZMCTS_ERR_HIP;
     const dim3 grid(static_cast<unsigned>((batch + SB - 1) / SB)), block(64 * WAVES);
     const int cin_load = cin0 - const_plane;
-    kernel<<<grid, block, lds, stream>>>(x, batch, cin0, const_plane, 0xFFFFFFFFu / static_cast<uint32_t>(cin_load) + 1u, cph0,
+    kernel<<<grid, block, lds, stream>>>(x, batch, cin0, const_plane, plane_div_magic(cin_load), cph0,
                                          cph1, args, gather);
     return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
 }
@@ -1887,7 +1896,7 @@ static int launch_board_conv(const float* x, const float* wt, const float* scale
             hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,      \
                                 static_cast<int>(lds)) != hipSuccess)                                                   \
             return MZMCTS_ERR_HIP;                                                                                      \
-        kernel<<<grid, block, lds, stream>>>(x, wt, scale, shift, residual, out, batch, cin, 0xFFFFFFFFu / static_cast<uint32_t>(cin) + 1u);                           \
+        kernel<<<grid, block, lds, stream>>>(x, wt, scale, shift, residual, out, batch, cin, plane_div_magic(cin));                           \
     } while (0)
     if (residual) {
         if (relu) MZ_CONV_LAUNCH(true, true); else MZ_CONV_LAUNCH(true, false);
@@ -2016,7 +2025,10 @@ static int board_tower_impl(const float* x, const mz::TowerGather& gather, int64
         if (many) return mz::launch_board_tower<1, 6, 6, 3>(x, b, cin0, args, stream, gather);
         return mz::launch_board_tower<1, 6, 6, 4>(x, b, cin0, args, stream, gather);
     }
-    if (channels == 64) return mz::launch_board_tower<4, 3, 3, 16>(x, b, cin0, args, stream, gather);
+    // 64 channels on 3 x 3 boards have no tower: a workgroup's 8 wavefronts want the row tiles of 16 boards, and two
+    // activation buffers of 16 padded planes x (64 + 4) channels are 179 KB -- over the 160 KB of a workgroup whatever cin0
+    // is.  Refused here by name (the caller keeps the per-layer kernels) instead of by a launch line that could never run.
+    if (channels == 64) return MZMCTS_ERR_INVALID;
     if (mz::tower_cols_applies(channels, height, width, cin0, args)) {
         const int rc = mz::launch_board_tower_cols(x, b, cin0, args, stream, gather, th);
         if (rc != MZMCTS_ERR_INVALID || n_heads > 0) return rc;
@@ -2101,6 +2113,11 @@ static int board_tower_split_impl(const float* x, const mz::TowerGather& gather,
                                        (l == 0 && const_plane) ? d.const_table : nullptr, d.export_raw, d.export_unit,
                                        cin_conv, d.relu, d.skip, 0};
     }
+    // The constant plane is never staged into LDS (its contribution comes from the table).  A skip on layer 1 -- a tower
+    // that starts with a residual block -- adds the input's first `channels` planes: with cin0 <= channels the constant
+    // plane is one of them and would be read as zeros.  Refused; no network builds such a tower (the dynamics input has
+    // channels + 1 planes and starts with a plain convolution).
+    if (const_plane && n_layers > 1 && layers[1].skip && cin0 <= channels) return MZMCTS_ERR_INVALID;
     args.gate = layers[0].gate;
     {
         static const int slot_priority = [] {
@@ -2122,7 +2139,8 @@ static int board_tower_split_impl(const float* x, const mz::TowerGather& gather,
         return mz::launch_board_tower_split<6, 7, 4>(x, b, cin0, const_plane, args, stream, gather);
     }
     if (height == 6 && width == 6) return mz::launch_board_tower_split<6, 6, 4>(x, b, cin0, const_plane, args, stream, gather);
-    return mz::launch_board_tower_split<3, 3, 16>(x, b, cin0, const_plane, args, stream, gather);
+    // 3 x 3 boards: refused as in board_tower_impl (16 boards x two buffers of two fp16 halves x (64 + 8) channels = 189 KB)
+    return MZMCTS_ERR_INVALID;
 }
 
 extern "C" int mzmcts_board_tower_split(const float* x, int64_t batch, int32_t cin0, int32_t const_plane, int32_t channels,

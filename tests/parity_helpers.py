@@ -485,6 +485,42 @@ def softmax64(logits):
     return _softmax_terms(logits)[0]
 
 
+TOWER_CHAIN_BAR = 4e-7       # |fp32 k-ordered chain - float64| / sum |a b|: the bar tests/test_gpu_board_conv.py holds a
+                             # single layer of both tower forms to (test_random_data_within_one_fp32_chain_of_fp64,
+                             # test_split_tower_single_layer_against_fp64)
+
+
+def tower_layer_rounding_bound(magnitude, conv, scale, shift, skip=None, split_store=False):
+    """Per-element bound on |tower layer in float32 - the same layer in float64 on the same float32 input| for
+    csrc/board_conv.hip's layer  v = conv * scale + shift; v += skip; relu(v)  (the epilogue's operation order, separate
+    multiply and add: the library is built without contraction):
+
+        the accumulation     TOWER_CHAIN_BAR * sum |a b| (`magnitude`), carried through the multiply: * |scale|
+        conv * scale         one rounding, half an ulp of the product:        u (|conv scale| + e)
+        + shift              one rounding of the sum:                         u (|conv scale + shift| + e)
+        + skip               one more where the layer has one (the skip planes are the run's own float32 values)
+        ReLU                 1-Lipschitz, exact
+
+    with u = 2^-24 and e the error carried so far (second order, kept so that the bound is one).  `split_store`: the split
+    form keeps the result as two fp16 halves of 8 v (h0 to 11 bits, the remainder to 11 more: a relative 2^-22; a
+    remainder in fp16's subnormal range is held to 2^-25, that is 2^-28 of v) -- what its export shows carries that too.
+    conv, magnitude: float64 [b, cout, h, w]; scale, shift: [cout]; skip: as conv, or None."""
+    cout = conv.shape[1]
+    scale = np.asarray(scale, dtype=np.float64).reshape(1, cout, 1, 1)
+    shift = np.asarray(shift, dtype=np.float64).reshape(1, cout, 1, 1)
+    e = TOWER_CHAIN_BAR * np.asarray(magnitude, dtype=np.float64) * np.abs(scale)
+    t = conv * scale
+    e = e + F32_UNIT * (np.abs(t) + e)
+    t = t + shift
+    e = e + F32_UNIT * (np.abs(t) + e)
+    if skip is not None:
+        t = t + skip
+        e = e + F32_UNIT * (np.abs(t) + e)
+    if split_store:
+        e = e + 2.0 ** -22 * (np.abs(t) + e) + 2.0 ** -28
+    return e
+
+
 # ---- replay store ------------------------------------------------------------------------------
 def history_of(sp, fx, g):
     """Game g of a replay fixture (G12 layout: arrays padded past `lengths[g]`) as a GameHistory with the field types

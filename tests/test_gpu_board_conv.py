@@ -19,6 +19,8 @@ pytestmark = pytest.mark.gpu
 SHAPES = [  # batch, cin, cout, h, w -- every kernel instantiation, ragged batches, padded channel counts
     (37, 64, 64, 6, 7), (1024, 65, 64, 6, 7), (3, 3, 64, 6, 7), (9, 16, 16, 6, 7), (50, 17, 16, 6, 6), (21, 16, 16, 6, 6),
     (7, 64, 64, 6, 6), (130, 17, 16, 3, 3), (64, 16, 16, 3, 3), (33, 64, 64, 3, 3), (1, 16, 16, 3, 3),
+    # one and two input channels: the staging code's division by cin (a divisor of 1 is its own quotient)
+    (5, 1, 16, 3, 3), (3, 1, 64, 6, 7), (40, 2, 16, 6, 6),
 ]
 
 
