@@ -145,7 +145,7 @@ __device__ __forceinline__ void stage_copy(float* dst, const float* __restrict__
     }
 }
 
-// Up to two heads that read the same board (value and policy) share a launch: blockIdx.y picks the head.
+// Up to three heads (kMaxHeads) share a launch, each reading its own tensor: blockIdx.y picks the head.
 constexpr int kMaxHeads = 3;
 struct HeadSet {
     const float* x[kMaxHeads];   // the tensor each head reads (value / policy share one, the reward head has its own)

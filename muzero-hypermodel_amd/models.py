@@ -312,7 +312,9 @@ def conv_heads(x, heads):
     read the same tensor (reference models.py:467-480, 500-522).  Inference on the GPU with the usual
     one-hidden-layer MLPs: ONE HIP launch for up to two heads (include/mzmcts.h mzmcts_conv_heads) reading the
     modules' own parameters; anything else (training, autograd, CPU, deeper MLPs, heads too large for LDS)
-    evaluates the torch modules."""
+    evaluates the torch modules.  The entry takes three heads; this wrapper stays at two because no network has
+    three heads on ONE tensor (value and policy share the prediction features, the reward head reads the dynamics
+    output): three heads go through conv_heads_multi, which admits them."""
     if 1 <= len(heads) <= 2 and all(_head_is_native(x, conv, fc) for conv, fc, _ in heads):
         x = x.contiguous()
         b, c, h, w = x.shape

@@ -521,6 +521,56 @@ def tower_layer_rounding_bound(magnitude, conv, scale, shift, skip=None, split_s
     return e
 
 
+def dot_layer_rounding_bound(x, e, w, b):
+    """_mlp_rounding_bound's layer in numpy, for one affine layer y = x w^T + b of the conv heads (csrc/net_kernels.hip,
+    board_heads_cols_kernel) and of the down-sampler's two convolutions seen as rows of patches: x [n, K] float64 with a
+    bound e [n, K] on the float32 evaluation's distance from it, w [m, K], b [m].  Returns (y, e_out).
+
+    Every term of a K-term dot product plus bias passes through at most K + 1 roundings in each of the kernels' forms:
+      * the matrix cores' k-ordered chain of fused multiply-adds (conv_head_mfma_kernel, the cols heads, the down-sampler):
+        the first term is rounded K times by the chain and once by the bias; k-steps padded with zeros round nothing;
+      * Linear-1's four `kParts` chains and their three additions: a term of a chain of n terms sees n roundings there, at
+        most m - 1 additions of the m <= 4 chains that hold anything (a chain of exact zeros adds exactly) and the bias;
+        each of the other m - 1 chains holds a term or more, so n + m - 1 <= K;
+      * conv_head_kernel (no contraction): the product rounds once, is added to 0 exactly, then n - 1 additions of its
+        `split` partial sum, at most m - 1 additions of the partial sums in order and the bias: n + m <= K + 1 again.
+    So the layer's error is at most gamma(K + 2) (|w| (|x| + e) + |b|) on top of |w| e, with K counted per output as the
+    products that are not zero (adding an exact zero rounds nothing), and nothing at all where no product is non-zero."""
+    x, e, w, b = (np.asarray(a, dtype=np.float64) for a in (x, e, w, b))
+    y = x @ w.T + b
+    magnitude = (np.abs(x) + e) @ np.abs(w).T + np.abs(b)
+    products = (x != 0).astype(np.float64) @ (w != 0).astype(np.float64).T
+    rounding = np.where(products > 0, _gamma(products + 2.0) * magnitude, 0.0)
+    return y, e @ np.abs(w).T + rounding
+
+
+def head_rounding_bound(x, conv_w, conv_b, w1, b1, w2, b2):
+    """Per-logit bound on |float32 head - float64 head| for float32 boards x [B, C, P] and float32 parameters:
+    dot_layer_rounding_bound for the 1x1 convolution (rows = (sample, position) pairs, K = C), Linear-1 (K = R P) and
+    Linear-2 (K = Hd); ELU is 1-Lipschitz and its exponential and `- 1` stay within 2^-23 of the exact value on the
+    negative side (charged on every unit, as _mlp_rounding_bound does; tests/test_gpu_device_numerics.py's
+    MZMCTS_NUMERICS_EXP sweep holds expf to that).  Returns e [B, O]."""
+    x = np.asarray(x, dtype=np.float64)
+    batch, channels, plane = x.shape
+    rows = x.transpose(0, 2, 1).reshape(batch * plane, channels)
+    y, e = dot_layer_rounding_bound(rows, np.zeros_like(rows), conv_w, conv_b)
+    reduced = y.shape[1]
+    flat = y.reshape(batch, plane, reduced).transpose(0, 2, 1).reshape(batch, reduced * plane)
+    e = e.reshape(batch, plane, reduced).transpose(0, 2, 1).reshape(batch, reduced * plane)
+    pre, e = dot_layer_rounding_bound(flat, e, w1, b1)
+    hidden = np.where(pre > 0, pre, np.expm1(np.minimum(pre, 0.0)))
+    _, e = dot_layer_rounding_bound(hidden, e + 2.0 ** -23, w2, b2)
+    return e
+
+
+def window_mean_rounding_bound(values, e):
+    """The adaptive average of the down-sampler: `values` [..., n] are a window's n float64 numbers, e the bounds they
+    carry.  The float32 kernel adds them one by one (the first to an exact 0: n - 1 roundings) and divides once: the
+    mean of e, and gamma(n) of the mean of (|v| + e)."""
+    n = values.shape[-1]
+    return e.mean(axis=-1) + _gamma(n) * (np.abs(values) + e).mean(axis=-1)
+
+
 # ---- replay store ------------------------------------------------------------------------------
 def history_of(sp, fx, g):
     """Game g of a replay fixture (G12 layout: arrays padded past `lengths[g]`) as a GameHistory with the field types
