@@ -25,25 +25,17 @@
 // global load.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
 #include <type_traits>
 
 #include "../../include/mzmcts.h"
+#include "board_launch.h"
 
 namespace mz {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kConvWaves = 8;   // two per SIMD: one wave's LDS reads and weight loads hide under the other's MFMAs
-constexpr int kConvGroup = 16;  // input channels per group = 4 k-steps; a lane fetches its 4 channels with one 16-byte read
-
-__host__ __device__ inline int conv_groups(int cin) { return (cin + kConvGroup - 1) / kConvGroup; }
-__host__ __device__ inline int conv_packed_floats(int cin, int cout) {  // [9 * groups + 2 spare][4 kk][cout][4 g]
-    return (9 * conv_groups(cin) + 2) * 4 * cout * 4;
-}
 
 // The staging loops turn a plane index sc = s * cin + ci (below 2^16) into the sample s with ONE __umulhi by
 // ceil(2^32 / cin): exact for 2 <= cin <= 80 (the error term sc * (magic * cin - 2^32) < 2^16 * 80 stays below 2^32).  A
@@ -648,10 +640,6 @@ __global__ __launch_bounds__(64 * kConvWaves) void board_tower_kernel(const floa
 // outputs (tests/test_gpu_board_conv.py compares the two kernels).  Reads the weights as mzmcts_board_conv_pack lays them
 // out (its [tap][group][kk][cout][g] order is this kernel's operand order).
 // -------------------------------------------------------------------------------------------------------------------
-constexpr int kColWaves = 4;                  // wavefronts per workgroup (independent of each other): 64 boards
-constexpr int kColBoardStride = 148;          // floats between two boards' [9][16] activations (+4: bank spread of 16-byte reads)
-constexpr int kColActStride = 12;             // floats between two boards' 17th-channel values [9]
-constexpr int kColWaveFloats = 16 * (kColBoardStride + kColActStride) + 32;   // + the boards' input rows (16 pointers)
 
 // Where value idx = lane + 64 it of a wavefront's NCHW boards ([board][16 channels][P positions]) lives in the
 // [board][position][channel] LDS image (boards STRIDE floats apart).  64 * 9 = 576 is a whole number of boards both for
@@ -716,8 +704,6 @@ __device__ __forceinline__ void cols_head_load_conv(const mzmcts_head_desc& d, i
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) w.conv_bias[rr] = 4 * kk + rr < d.reduced ? d.conv_b[4 * kk + rr] : 0.f;
 }
-
-constexpr int kColHeadW1Floats = 16 * (16 * 9 + 1);          // LDS floats of one head's Linear-1 weights, worst case
 
 // Linear-1 weights of a head -> LDS [unit][R P + 1] by the whole workgroup (rows beyond `hidden` are never read)
 __device__ __forceinline__ void cols_stage_head(const mzmcts_head_desc& d, float* dst, int P, int tid, int nthreads) {
@@ -1079,17 +1065,6 @@ __global__ __launch_bounds__(64 * kColWaves) __attribute__((amdgpu_waves_per_eu(
 // by the 25 halo operands).
 // -------------------------------------------------------------------------------------------------------------------
 template <int H, int W>
-struct PatchGeometry {
-    static constexpr int P = H * W;
-    static constexpr int NPX = W / 3, NPY = H / 3, NP = NPX * NPY;    // patches per board
-    static constexpr int BPW = 16 / NP;                                // boards per wavefront
-    static constexpr int BS = P * 16 + 4;                              // floats between two boards' [P][16] activations
-    static constexpr int WAVE_FLOATS = 2 * BPW * BS + BPW * P + 32;    // activations | skip | 17th channel | input rows
-    static_assert(H % 3 == 0 && W % 3 == 0 && 16 % NP == 0 && NP > 1, "boards of 2, 4, 8 or 16 patches of 3 x 3");
-    static_assert((BPW * 16 * P) % 64 == 0, "the fill walks whole wavefronts");
-};
-
-template <int H, int W>
 __global__ __launch_bounds__(64 * kColWaves) __attribute__((amdgpu_waves_per_eu(2, 2))) void board_tower_patch_kernel(
     const float* __restrict__ x, int batch, int cin0, TowerArgs args, TowerGather gather) {
     using G = PatchGeometry<H, W>;
@@ -1260,22 +1235,6 @@ __global__ __launch_bounds__(64 * kColWaves) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
-static int launch_board_tower_patch66(const float* x, int batch, int cin0, const TowerArgs& args, hipStream_t stream,
-                                      const TowerGather& gather) {
-    using G = PatchGeometry<6, 6>;
-    for (int l = 0; l < args.n_layers; ++l)
-        if (reinterpret_cast<uintptr_t>(args.layer[l].wt) & 15u) return MZMCTS_ERR_INVALID;   // (read as float4)
-    const size_t lds = sizeof(float) * static_cast<size_t>(kColWaves) * G::WAVE_FLOATS;
-    auto kernel = board_tower_patch_kernel<6, 6>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(lds)) != hipSuccess)
-        return MZMCTS_ERR_HIP;
-    const int per_group = G::BPW * kColWaves;
-    kernel<<<dim3(static_cast<unsigned>((batch + per_group - 1) / per_group)), dim3(64 * kColWaves), lds, stream>>>(x, batch, cin0,
-                                                                                                                  args, gather);
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
-}
-
 // -------------------------------------------------------------------------------------------------------------------
 // The heads of a 16-channel 3 x 3 network as a launch of their own in the board-column shape (round 3): a wavefront takes
 // 16 boards, brings their NCHW planes into LDS as [board][position][channel] with coalesced loads, and runs cols_head_* --
@@ -1330,95 +1289,23 @@ __global__ __launch_bounds__(64 * kColWaves) void board_heads_cols_kernel(HeadsC
     cols_head_finish<P>(hd, c0, f0, y0, ys, hs, b0, n_boards, lane);
 }
 
-// mzmcts_conv_heads_multi's fast path (net_kernels.hip calls it first): MZMCTS_ERR_INVALID = this launch does not cover
-// the shapes, the caller takes conv_head_mfma_kernel.
-int launch_board_heads_cols(const float* const* xs, const mzmcts_head_desc* heads, int n_heads, float* const* outs,
-                            int64_t batch, hipStream_t stream) {
-    const char* env = std::getenv("MZ_HEADS_COLS");
-    if (env && std::string(env) == "off") return MZMCTS_ERR_INVALID;
-    if (n_heads < 1 || n_heads > 3 || batch > 0x3fffffff) return MZMCTS_ERR_INVALID;
+// pointers present, and a shape the board-column heads take (launch_plan.h cols_head_ok)
+static bool cols_head_desc_ok(const mzmcts_head_desc& d, const float* out) {
+    return out && d.conv_w && d.conv_b && d.fc1_w && d.fc1_b && d.fc2_w && d.fc2_b &&
+           cols_head_ok(HeadDims{d.channels, d.plane, d.reduced, d.hidden, d.outputs});
+}
+
+// mzmcts_conv_heads_multi's board-column form (net_kernels.hip validates the descriptors and asks plan_heads)
+int launch_board_heads_cols(const HeadsPlan& plan, const float* const* xs, const mzmcts_head_desc* heads, int n_heads,
+                            float* const* outs, int64_t batch, hipStream_t stream) {
     HeadsColsArgs a{};
     a.n = n_heads;
     for (int h = 0; h < n_heads; ++h) {
-        const mzmcts_head_desc& d = heads[h];
-        if (!xs[h] || !outs[h] || !d.conv_w || !d.conv_b || !d.fc1_w || !d.fc1_b || !d.fc2_w || !d.fc2_b || d.channels != 16 ||
-            d.plane != 9 || d.reduced < 1 || d.reduced > 16 || d.hidden < 1 || d.hidden > 16 || d.outputs < 1 || d.outputs > 32)
-            return MZMCTS_ERR_INVALID;
         a.x[h] = xs[h];
-        a.head[h] = TowerHead{d, outs[h], 0, 0};
+        a.head[h] = TowerHead{heads[h], outs[h], 0, 0};
     }
-    if (batch == 0) return MZMCTS_OK;
-    const size_t lds = sizeof(float) * (static_cast<size_t>(kColWaves) * kColWaveFloats + kColHeadW1Floats);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(board_heads_cols_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-        return MZMCTS_ERR_HIP;
-    const int per_group = 16 * kColWaves;
-    board_heads_cols_kernel<<<dim3(static_cast<unsigned>((batch + per_group - 1) / per_group), static_cast<unsigned>(n_heads)),
-                              dim3(64 * kColWaves), lds, stream>>>(a, static_cast<int>(batch));
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
-}
-
-static bool tower_cols_applies(int channels, int height, int width, int cin0, const TowerArgs& args) {
-    const char* env = std::getenv("MZ_TOWER_COLS");              // "off": the row-tile kernel (A/B runs, the equality test)
-    const bool off = env && std::string(env) == "off";
-    const bool board = (height == 3 && width == 3) || (height == 6 && width == 6);
-    if (off || channels != 16 || !board || (cin0 != 16 && cin0 != 17)) return false;
-    for (int l = 1; l < args.n_layers; ++l)
-        if (args.layer[l].cin != 16) return false;
-    return true;
-}
-
-static int launch_board_tower_cols(const float* x, int batch, int cin0, const TowerArgs& args, hipStream_t stream,
-                                   const TowerGather& gather, const TowerHeads& heads = TowerHeads{}) {
-    static_assert(16 * (16 * 9 + 1) + 16 * 17 <= kColWaveFloats, "a head's y and h take the place of the activations");
-    auto head_ok = [&](const TowerHead& hd) {
-        const mzmcts_head_desc& d = hd.d;
-        return hd.out && d.conv_w && d.conv_b && d.fc1_w && d.fc1_b && d.fc2_w && d.fc2_b && d.channels == 16 && d.plane == 9 &&
-               d.reduced >= 1 && d.reduced <= 16 && d.hidden >= 1 && d.hidden <= 16 && d.outputs >= 1 && d.outputs <= 32;
-    };
-    if (heads.has_mid && !(head_ok(heads.mid) && heads.mid.layer >= 0 && heads.mid.layer < args.n_layers - 1 &&
-                           args.layer[heads.mid.layer].export_unit))
-        return MZMCTS_ERR_INVALID;
-    if (heads.n_last < 0 || heads.n_last > 2 || (heads.n_last > 0 && !head_ok(heads.last0)) || (heads.n_last > 1 && !head_ok(heads.last1)))
-        return MZMCTS_ERR_INVALID;
-    const bool with_heads = heads.has_mid || heads.n_last > 0;
-    const size_t lds = sizeof(float) * (static_cast<size_t>(kColWaves) * kColWaveFloats + (with_heads ? 3 * kColHeadW1Floats : 0));
-    const int per_group = 16 * kColWaves;
-    const dim3 grid(static_cast<unsigned>((batch + per_group - 1) / per_group)), block(64 * kColWaves);
-    if (with_heads) {
-        auto kernel = board_tower_cols_kernel<3, 3, true>;
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   static_cast<int>(lds)) != hipSuccess)
-            return MZMCTS_ERR_HIP;
-        kernel<<<grid, block, lds, stream>>>(x, batch, cin0, args, gather, heads);
-    } else {
-        board_tower_cols_kernel<3, 3, false><<<grid, block, lds, stream>>>(x, batch, cin0, args, gather, heads);
-    }
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
-}
-
-template <int NT, int H, int W, int SB>
-static int launch_board_tower(const float* x, int batch, int cin0, const TowerArgs& args, hipStream_t stream,
-                              const TowerGather& gather = TowerGather{}) {
-    constexpr int PP = (H + 2) * (W + 1) + 1;
-    int cp0 = conv_groups(cin0) * kConvGroup + 4;
-    int cp1 = 4;
-    for (int l = 0; l < args.n_layers; ++l) {             // layer l reads buffer l & 1
-        int& cp = (l & 1) ? cp1 : cp0;
-        cp = std::max(cp, conv_groups(args.layer[l].cin) * kConvGroup + 4);
-    }
-    cp0 = std::max(cp0, 16 * NT + 4);                     // outputs (16 NT channels) land in either buffer
-    cp1 = std::max(cp1, 16 * NT + 4);
-    const size_t lds = sizeof(float) * static_cast<size_t>(SB) * PP * (cp0 + cp1) + (sizeof(float*) + sizeof(float)) * SB;
-    if (lds > 160 * 1024) return MZMCTS_ERR_INVALID;
-    auto kernel = board_tower_kernel<NT, H, W, SB>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(lds)) != hipSuccess)
-        return MZMCTS_ERR_HIP;
-    const int blocks = (batch + SB - 1) / SB;
-    const dim3 grid(static_cast<unsigned>(args.gate ? std::min(blocks, 256) : blocks)), block(64 * kConvWaves);
-    kernel<<<grid, block, lds, stream>>>(x, batch, cin0, plane_div_magic(cin0), cp0, cp1, args, gather);
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
+    return launch_with_lds(board_heads_cols_kernel, dim3(plan.grid_x, plan.grid_y), dim3(plan.block), plan.lds, stream, a,
+                           static_cast<int>(batch));
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -1438,12 +1325,6 @@ static int launch_board_tower(const float* x, int batch, int cin0, const TowerAr
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 constexpr float kActScale = 8.f, kWtScale = 64.f;
-constexpr int kSplitGroup = 32;   // input channels per MFMA (K of v_mfma_f32_16x16x32_f16)
-
-__host__ __device__ inline int split_groups(int cin) { return (cin + kSplitGroup - 1) / kSplitGroup; }
-__host__ __device__ inline int64_t split_packed_halfs(int cin, int cout) {   // [9 NG + 2 spare][2 q][4 kk][cout][8 j]
-    return static_cast<int64_t>(9 * split_groups(cin) + 2) * 2 * 4 * cout * 8;
-}
 
 // wh[((((tap * NG + grp) * 2 + q) * 4 + kk) * cout + n) * 8 + j] = half q of 64 * w[n][grp * 32 + 8 kk + j][tap]
 // over the first `cin_conv` input channels of a [cout, cin_total, 3, 3] weight (0 beyond, and in the spare groups).
@@ -1857,54 +1738,183 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
     MZ_TSTAMP_FLUSH;
 }
 
-template <int H, int W, int SB, int WAVES = kConvWaves>
-static int launch_board_tower_split(const float* x, int batch, int cin0, int const_plane, const SplitArgs& args,
-                                    hipStream_t stream, const TowerGather& gather = TowerGather{}) {
-    constexpr int PP = (H + 2) * (W + 1) + 1;
-    int cph0 = 64 + 8, cph1 = 64 + 8;                     // outputs are 64 channels in either buffer
-    for (int l = 0; l < args.n_layers; ++l) {
-        int& cp = (l & 1) ? cph1 : cph0;
-        cp = std::max(cp, split_groups(args.layer[l].cin) * kSplitGroup + 8);
+// -------------------------------------------------------------------------------------------------------------------
+// Host side.  An entry point validates its descriptors into the kernel's argument structs (one function per family:
+// layers, gather, heads), asks launch_plan.h what to launch, and switches from the plan to the instantiation.
+// -------------------------------------------------------------------------------------------------------------------
+constexpr int form_key(int a, int h, int w, int sb) { return ((a * 8 + h) * 8 + w) * 64 + sb; }   // template arguments as a case label
+
+static bool env_is_off(const char* name) {
+    const char* env = std::getenv(name);
+    return env && std::string(env) == "off";
+}
+
+static int split_boards_env() {                                      // MZ_SPLIT_BOARDS=4|2|1 (A/B measurements), once per process
+    static const int chosen = [] {
+        const char* env = std::getenv("MZ_SPLIT_BOARDS");
+        return env ? std::atoi(env) : 2;
+    }();
+    return chosen;
+}
+
+// mzmcts_tower_layer[] -> the kernel's layer table (Args = TowerArgs or SplitArgs): every pointer present, scale and shift
+// readable four channels at a time.  For the plan: cin[l] as the descriptors state it, and whether every packed weight
+// pointer is 16-byte aligned.
+template <typename Args>
+static int tower_args_from(const mzmcts_tower_layer* layers, int32_t n_layers, bool const_plane, Args* args, int32_t* cin,
+                           bool* aligned16) {
+    if (!layers || n_layers < 1 || n_layers > kMaxTowerLayers) return MZMCTS_ERR_INVALID;
+    *args = Args{};
+    args->n_layers = n_layers;
+    args->gate = layers[0].gate;
+    *aligned16 = true;
+    for (int l = 0; l < n_layers; ++l) {
+        const mzmcts_tower_layer& d = layers[l];
+        const bool table = l == 0 && const_plane;           // (split form: the constant plane's contribution comes from it)
+        if (!d.packed || !d.scale || !d.shift || (table && !d.const_table)) return MZMCTS_ERR_INVALID;
+        if ((reinterpret_cast<uintptr_t>(d.scale) | reinterpret_cast<uintptr_t>(d.shift)) & 15u)
+            return MZMCTS_ERR_INVALID;                      // (read four channels at a time)
+        cin[l] = d.cin;
+        if (reinterpret_cast<uintptr_t>(d.packed) & 15u) *aligned16 = false;
+        if constexpr (std::is_same<Args, SplitArgs>::value)
+            args->layer[l] = SplitLayer{static_cast<const _Float16*>(d.packed), d.scale, d.shift, table ? d.const_table : nullptr,
+                                        d.export_raw, d.export_unit, d.cin - (table ? 1 : 0), d.relu, d.skip, 0};
+        else
+            args->layer[l] = TowerLayer{static_cast<const float*>(d.packed), d.scale, d.shift, d.export_raw, d.export_unit, d.cin,
+                                        d.relu, d.skip, 0};
     }
-    const size_t lds = sizeof(_Float16) * static_cast<size_t>(SB) * PP * 2 * (cph0 + cph1) + (sizeof(float) + sizeof(float*)) * SB;
-    if (lds > 160 * 1024) return MZMCTS_ERR_INVALID;
-    auto kernel = board_tower_split_kernel<H, W, SB, WAVES>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(lds)) != hipSuccess)
-        return MZMCTS_ERR_HIP;
-    const dim3 grid(static_cast<unsigned>((batch + SB - 1) / SB)), block(64 * WAVES);
-    const int cin_load = cin0 - const_plane;
-    kernel<<<grid, block, lds, stream>>>(x, batch, cin0, const_plane, plane_div_magic(cin_load), cph0,
-                                         cph1, args, gather);
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
+    return MZMCTS_OK;
+}
+
+// mzmcts_tower_gather -> TowerGather: the pools of a search whose hidden state is this tower's first `channels` planes
+static int gather_from(const mzmcts_tower_gather* g, int64_t batch, int32_t cin0, int32_t channels, int32_t height,
+                       int32_t width, TowerGather* out) {
+    if (!g || !g->pool || !g->parent || !g->action || g->envs < batch || !(g->action_space > 0.f) ||
+        g->hidden_floats != channels * height * width || cin0 != channels + 1)
+        return MZMCTS_ERR_INVALID;
+    *out = TowerGather{g->pool, g->parent, g->action, static_cast<long long>(g->envs), g->hidden_floats, g->action_space};
+    return MZMCTS_OK;
+}
+
+// mzmcts_tower_head[] -> TowerHeads: at most two heads on the last layer, at most one on an earlier one
+static int tower_heads_from(const mzmcts_tower_head* heads, int32_t n_heads, int32_t n_layers, TowerHeads* th) {
+    *th = TowerHeads{};
+    for (int q = 0; q < n_heads; ++q) {
+        const TowerHead hd{heads[q].head, heads[q].out, heads[q].layer, 0};
+        if (hd.layer == n_layers - 1) {
+            if (th->n_last >= 2) return MZMCTS_ERR_INVALID;
+            (th->n_last == 0 ? th->last0 : th->last1) = hd;
+            ++th->n_last;
+        } else {
+            if (th->has_mid) return MZMCTS_ERR_INVALID;
+            th->mid = hd;
+            th->has_mid = 1;
+        }
+    }
+    return MZMCTS_OK;
+}
+
+// what board_tower_cols_kernel<3, 3, true> needs of its heads (checked when the launch is certain)
+static bool tower_heads_ok(const TowerHeads& th, const TowerArgs& args) {
+    static_assert(16 * (16 * 9 + 1) + 16 * 17 <= kColWaveFloats, "a head's y and h take the place of the activations");
+    if (th.has_mid && !(cols_head_desc_ok(th.mid.d, th.mid.out) && th.mid.layer >= 0 && th.mid.layer < args.n_layers - 1 &&
+                        args.layer[th.mid.layer].export_unit))
+        return false;
+    return !(th.n_last > 0 && !cols_head_desc_ok(th.last0.d, th.last0.out)) &&
+           !(th.n_last > 1 && !cols_head_desc_ok(th.last1.d, th.last1.out));
+}
+
+// Every tower entry point ends here.  split: the split-precision form (const_plane: its input's last plane is constant).
+static int board_tower_impl(const float* x, const TowerGather& gather, bool split, int32_t const_plane, int64_t batch,
+                            int32_t cin0, int32_t channels, int32_t height, int32_t width, const mzmcts_tower_layer* layers,
+                            int32_t n_layers, void* stream_, const mzmcts_tower_head* heads = nullptr, int32_t n_heads = 0) {
+    if ((!x && !gather.pool) || (n_heads > 0 && !heads)) return MZMCTS_ERR_INVALID;
+    TowerArgs args{};
+    SplitArgs sargs{};
+    int32_t cin[kMaxTowerLayers];
+    bool aligned16;
+    int rc = split ? tower_args_from(layers, n_layers, const_plane != 0, &sargs, cin, &aligned16)
+                   : tower_args_from(layers, n_layers, false, &args, cin, &aligned16);
+    if (rc != MZMCTS_OK) return rc;
+    TowerShape s{};
+    s.batch = batch;
+    s.cin0 = cin0;
+    s.channels = channels;
+    s.height = height;
+    s.width = width;
+    s.n_layers = n_layers;
+    s.layer_cin = cin;
+    s.split = split;
+    s.const_plane = const_plane != 0;
+    s.layer1_skip = n_layers > 1 && layers[1].skip;
+    s.gated = layers[0].gate != nullptr;
+    s.n_heads = n_heads;
+    s.weights_aligned16 = aligned16;
+    s.cols_on = !env_is_off("MZ_TOWER_COLS");                        // "off": the row-tile kernel (A/B runs, the equality test)
+    s.split_boards = (height == 6 && width == 7) ? split_boards_env() : 2;   // (read at the first 6 x 7 tower, as ever)
+    TowerPlan p;
+    TowerHeads th;
+    if ((rc = plan_tower(s, &p)) != MZMCTS_OK || (rc = tower_heads_from(heads, n_heads, n_layers, &th)) != MZMCTS_OK) return rc;
+    if (split) {                                                     // (read at the first split tower, once per process)
+        static const int slot_priority = env_is_off("MZ_SPLIT_PRIORITY") ? 0 : 1;
+        sargs.slot_priority = slot_priority;
+    }
+    if (batch == 0) return MZMCTS_OK;
+    args.gate_samples = p.gate_samples;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int b = static_cast<int>(batch);
+    const dim3 grid(p.grid), block(p.block);
+#define MZ_ROW_TILE(NT, H, W, SB)  \
+    case form_key(NT, H, W, SB):   \
+        return launch_with_lds(board_tower_kernel<NT, H, W, SB>, grid, block, p.lds, stream, x, b, cin0, plane_div_magic(cin0), p.cp0, p.cp1, args, gather)
+#define MZ_SPLIT(H, W, SB, WAVES)     \
+    case form_key(WAVES, H, W, SB):   \
+        return launch_with_lds(board_tower_split_kernel<H, W, SB, WAVES>, grid, block, p.lds, stream, x, b, cin0, const_plane, plane_div_magic(cin0 - const_plane), p.cp0, p.cp1, sargs, gather)
+    switch (p.kernel) {
+        case TowerKernel::kRowTile:
+            switch (form_key(p.nt, p.h, p.w, p.sb)) {
+                MZ_ROW_TILE(4, 6, 7, 4);
+                MZ_ROW_TILE(1, 6, 7, 6);
+                MZ_ROW_TILE(1, 6, 7, 4);
+                MZ_ROW_TILE(4, 6, 6, 4);
+                MZ_ROW_TILE(1, 6, 6, 3);
+                MZ_ROW_TILE(1, 6, 6, 4);
+                MZ_ROW_TILE(1, 3, 3, 14);
+                MZ_ROW_TILE(1, 3, 3, 16);
+            }
+            break;
+        case TowerKernel::kSplit:
+            switch (form_key(p.waves, p.h, p.w, p.sb)) {
+                MZ_SPLIT(6, 7, 2, 4);
+                MZ_SPLIT(6, 7, 1, 2);
+                MZ_SPLIT(6, 7, 4, 8);
+                MZ_SPLIT(6, 6, 4, 8);
+            }
+            break;
+        case TowerKernel::kCols:
+            return launch_with_lds(board_tower_cols_kernel<3, 3, false>, grid, block, p.lds, stream, x, b, cin0, args, gather, th);
+        case TowerKernel::kColsHeads:
+            if (!tower_heads_ok(th, args)) return MZMCTS_ERR_INVALID;
+            return launch_with_lds(board_tower_cols_kernel<3, 3, true>, grid, block, p.lds, stream, x, b, cin0, args, gather, th);
+        case TowerKernel::kPatch:
+            return launch_with_lds(board_tower_patch_kernel<6, 6>, grid, block, p.lds, stream, x, b, cin0, args, gather);
+        case TowerKernel::kNone:
+            break;
+    }
+#undef MZ_ROW_TILE
+#undef MZ_SPLIT
+    return MZMCTS_ERR_INVALID;                                       // (a plan without an instantiation: cannot happen)
 }
 
 template <int NT, int H, int W, int SB>
-static int launch_board_conv(const float* x, const float* wt, const float* scale, const float* shift, const float* residual,
-                             float* out, int batch, int cin, int relu, hipStream_t stream) {
-    constexpr int PP = (H + 2) * (W + 1) + 1;
-    const int cp = conv_groups(cin) * kConvGroup + 4;
-    const size_t planes = static_cast<size_t>(SB) * PP * cp;
-    const size_t stage = static_cast<size_t>(16 * NT) * (SB * H * W + 1) + 2 * 16 * NT;
-    const size_t lds = sizeof(float) * std::max(planes, stage);
-    if (lds > 160 * 1024) return MZMCTS_ERR_INVALID;
-    const dim3 grid(static_cast<unsigned>((batch + SB - 1) / SB)), block(64 * kConvWaves);
-#define MZ_CONV_LAUNCH(RES, ACT)                                                                                        \
-    do {                                                                                                                \
-        auto kernel = board_conv3x3_kernel<NT, H, W, SB, RES, ACT>;                                                     \
-        if (lds > 64 * 1024 &&                                                                                          \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                static_cast<int>(lds)) != hipSuccess)                                                   \
-            return MZMCTS_ERR_HIP;                                                                                      \
-        kernel<<<grid, block, lds, stream>>>(x, wt, scale, shift, residual, out, batch, cin, plane_div_magic(cin));                           \
-    } while (0)
-    if (residual) {
-        if (relu) MZ_CONV_LAUNCH(true, true); else MZ_CONV_LAUNCH(true, false);
-    } else {
-        if (relu) MZ_CONV_LAUNCH(false, true); else MZ_CONV_LAUNCH(false, false);
-    }
-#undef MZ_CONV_LAUNCH
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
+static int launch_board_conv(const ConvPlan& p, hipStream_t stream, const float* x, const float* wt, const float* scale,
+                             const float* shift, const float* residual, float* out, int batch, int cin, int relu) {
+    auto go = [&](auto kernel) {
+        return launch_with_lds(kernel, dim3(p.grid), dim3(p.block), p.lds, stream, x, wt, scale, shift, residual, out, batch, cin,
+                               plane_div_magic(cin));
+    };
+    if (residual) return relu ? go(board_conv3x3_kernel<NT, H, W, SB, true, true>) : go(board_conv3x3_kernel<NT, H, W, SB, true, false>);
+    return relu ? go(board_conv3x3_kernel<NT, H, W, SB, false, true>) : go(board_conv3x3_kernel<NT, H, W, SB, false, false>);
 }
 
 }  // namespace mz
@@ -1923,140 +1933,41 @@ extern "C" int mzmcts_board_conv_pack(const float* weight, float* packed, int32_
 }
 
 extern "C" int mzmcts_board_conv_supported(int32_t cin, int32_t cout, int32_t height, int32_t width) {
-    const bool shape = (height == 6 && width == 7) || (height == 6 && width == 6) || (height == 3 && width == 3);
-    return shape && (cout == 64 || cout == 16) && cin >= 1 && cin <= 80 ? 1 : 0;
+    return mz::board_conv_supported(cin, cout, height, width) ? 1 : 0;
 }
 
 extern "C" int mzmcts_board_conv3x3(const float* x, const float* packed, const float* scale, const float* shift,
                                     const float* residual, float* out, int64_t batch, int32_t cin, int32_t cout,
                                     int32_t height, int32_t width, int32_t relu, void* stream_) {
-    if (!x || !packed || !scale || !shift || !out || batch < 0 || batch > 0x3fffffff ||
-        !mzmcts_board_conv_supported(cin, cout, height, width) || out == x)
-        return MZMCTS_ERR_INVALID;
-    if (batch == 0) return MZMCTS_OK;
+    if (!x || !packed || !scale || !shift || !out || out == x) return MZMCTS_ERR_INVALID;
+    mz::ConvPlan p;
+    const int rc = mz::plan_board_conv(batch, cin, cout, height, width, &p);
+    if (rc != MZMCTS_OK || batch == 0) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int b = static_cast<int>(batch);
-    // samples per workgroup: 8 waves x <= 6 row tiles each, planes within LDS
-    if (height == 6 && width == 7) {
-        if (cout == 64) return mz::launch_board_conv<4, 6, 7, 4>(x, packed, scale, shift, residual, out, b, cin, relu, stream);
-        return mz::launch_board_conv<1, 6, 7, 8>(x, packed, scale, shift, residual, out, b, cin, relu, stream);
+#define MZ_CONV(NT, H, W, SB)         \
+    case mz::form_key(NT, H, W, SB):  \
+        return mz::launch_board_conv<NT, H, W, SB>(p, stream, x, packed, scale, shift, residual, out, b, cin, relu)
+    switch (mz::form_key(p.nt, p.h, p.w, p.sb)) {
+        MZ_CONV(4, 6, 7, 4);
+        MZ_CONV(1, 6, 7, 8);
+        MZ_CONV(4, 6, 6, 4);
+        MZ_CONV(1, 6, 6, 16);
+        MZ_CONV(4, 3, 3, 16);
+        MZ_CONV(1, 3, 3, 32);
     }
-    if (height == 6 && width == 6) {
-        if (cout == 64) return mz::launch_board_conv<4, 6, 6, 4>(x, packed, scale, shift, residual, out, b, cin, relu, stream);
-        return mz::launch_board_conv<1, 6, 6, 16>(x, packed, scale, shift, residual, out, b, cin, relu, stream);
-    }
-    if (cout == 64) return mz::launch_board_conv<4, 3, 3, 16>(x, packed, scale, shift, residual, out, b, cin, relu, stream);
-    return mz::launch_board_conv<1, 3, 3, 32>(x, packed, scale, shift, residual, out, b, cin, relu, stream);
-}
-
-// Boards per workgroup of the split-precision 64-channel tower.  6 x 7: TWO boards on FOUR wavefronts (84 rows = 6 tiles,
-// three per wavefront, as with 4 boards on 8), because half the LDS lets two workgroups share a CU: one's fill / epilogue
-// / barrier / export phases (55 % of a workgroup's life, profiles/r02_tower_phase_stamps.jsonl) run under the other's MFMAs.
-// MZ_SPLIT_BOARDS=4|2|1 selects the shape (A/B measurements).
-static int split_block_samples(int32_t height, int32_t width) {
-    if (height == 6 && width == 7) {
-        static const int chosen = [] {
-            const char* env = std::getenv("MZ_SPLIT_BOARDS");
-            const int v = env ? std::atoi(env) : 2;
-            return (v == 4 || v == 2 || v == 1) ? v : 2;
-        }();
-        return chosen;
-    }
-    return height == 3 ? 16 : 4;
-}
-
-static int board_tower_impl(const float* x, const mz::TowerGather& gather, int64_t batch, int32_t cin0, int32_t channels,
-                            int32_t height, int32_t width, const mzmcts_tower_layer* layers, int32_t n_layers, void* stream_,
-                            const mzmcts_tower_head* heads = nullptr, int32_t n_heads = 0) {
-    if ((!x && !gather.pool) || !layers || batch < 0 || batch > 0x3fffffff || n_layers < 1 || n_layers > mz::kMaxTowerLayers ||
-        !mzmcts_board_conv_supported(cin0, channels, height, width) || n_heads < 0 || n_heads > 3 || (n_heads > 0 && !heads))
-        return MZMCTS_ERR_INVALID;
-    mz::TowerHeads th{};
-    for (int q = 0; q < n_heads; ++q) {
-        const mz::TowerHead hd{heads[q].head, heads[q].out, heads[q].layer, 0};
-        if (hd.layer == n_layers - 1) {
-            if (th.n_last >= 2) return MZMCTS_ERR_INVALID;
-            (th.n_last == 0 ? th.last0 : th.last1) = hd;
-            ++th.n_last;
-        } else {
-            if (th.has_mid) return MZMCTS_ERR_INVALID;
-            th.mid = hd;
-            th.has_mid = 1;
-        }
-    }
-    mz::TowerArgs args{};
-    args.n_layers = n_layers;
-    for (int l = 0; l < n_layers; ++l) {
-        const mzmcts_tower_layer& d = layers[l];
-        if (!d.packed || !d.scale || !d.shift || d.cin != (l == 0 ? cin0 : channels)) return MZMCTS_ERR_INVALID;
-        if ((reinterpret_cast<uintptr_t>(d.scale) | reinterpret_cast<uintptr_t>(d.shift)) & 15u)
-            return MZMCTS_ERR_INVALID;                   // (read four channels at a time)
-        args.layer[l] = mz::TowerLayer{static_cast<const float*>(d.packed), d.scale, d.shift, d.export_raw, d.export_unit, d.cin, d.relu, d.skip, 0};
-    }
-    args.gate = layers[0].gate;
-    if (args.gate && channels != 64) return MZMCTS_ERR_INVALID;   // (the hand-over exists between the two 64-channel forms)
-    args.gate_samples = split_block_samples(height, width);
-    // heads inside the launch: the 3 x 3 board-column kernel only -- decided before anything is launched
-    if (n_heads > 0 && !(height == 3 && width == 3 && mz::tower_cols_applies(channels, height, width, cin0, args)))
-        return MZMCTS_ERR_INVALID;
-    if (batch == 0) return MZMCTS_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int b = static_cast<int>(batch);
-    // Samples per workgroup.  A 16-channel tower has ONE column tile, so its 8 wavefronts split the SB x H x W output
-    // rows into 16-row tiles and every wavefront runs ceil(tiles / 8) of them per k-step: 16 x 9 = 144 rows = 9 tiles
-    // cost two rounds for little more than one round's work.  With few boards that choice stands (more workgroups than
-    // CUs matters most); with many, SB is the count whose rows fit ONE round and whose LDS lets two or more workgroups
-    // share a CU, so that one's fill / epilogue / export phases run under another's MFMAs: 14 x 9 = 126 rows = 8 tiles,
-    // a tile for every wavefront (measured at 65536 TicTacToe boards: SB 16 / 28 / 12 / 8 = 318 / 313 / 300 / 353 us per
-    // launch, and 12 -> 14: 374 -> 338 us with heads -- 12 x 9 = 108 rows are 7 tiles and leave the eighth wavefront
-    // idle; 6x6, 16384 boards: SB 4 / 7 / 3 = 513 / 513 / 428 us).
-    const bool many = b >= 16384;
-    if (height == 6 && width == 7) {
-        if (channels == 64) return mz::launch_board_tower<4, 6, 7, 4>(x, b, cin0, args, stream, gather);
-        if (many && (cin0 * 42) % 2 == 0) return mz::launch_board_tower<1, 6, 7, 6>(x, b, cin0, args, stream, gather);
-        return mz::launch_board_tower<1, 6, 7, 4>(x, b, cin0, args, stream, gather);
-    }
-    if (height == 6 && width == 6) {
-        if (channels == 64) return mz::launch_board_tower<4, 6, 6, 4>(x, b, cin0, args, stream, gather);
-        if (mz::tower_cols_applies(channels, height, width, cin0, args)) {
-            const int rc = mz::launch_board_tower_patch66(x, b, cin0, args, stream, gather);
-            if (rc != MZMCTS_ERR_INVALID) return rc;
-        }
-        if (many) return mz::launch_board_tower<1, 6, 6, 3>(x, b, cin0, args, stream, gather);
-        return mz::launch_board_tower<1, 6, 6, 4>(x, b, cin0, args, stream, gather);
-    }
-    // 64 channels on 3 x 3 boards have no tower: a workgroup's 8 wavefronts want the row tiles of 16 boards, and two
-    // activation buffers of 16 padded planes x (64 + 4) channels are 179 KB -- over the 160 KB of a workgroup whatever cin0
-    // is.  Refused here by name (the caller keeps the per-layer kernels) instead of by a launch line that could never run.
-    if (channels == 64) return MZMCTS_ERR_INVALID;
-    if (mz::tower_cols_applies(channels, height, width, cin0, args)) {
-        const int rc = mz::launch_board_tower_cols(x, b, cin0, args, stream, gather, th);
-        if (rc != MZMCTS_ERR_INVALID || n_heads > 0) return rc;
-    }
-    if (n_heads > 0) return MZMCTS_ERR_INVALID;                      // (heads inside the launch: the board-column kernel only)
-    if (many) return mz::launch_board_tower<1, 3, 3, 14>(x, b, cin0, args, stream, gather);
-    return mz::launch_board_tower<1, 3, 3, 16>(x, b, cin0, args, stream, gather);
-}
-
-// samples per workgroup of the tower launches of a given shape (the table board_tower_impl / board_tower_split_impl use;
-// for 64 channels: of the SPLIT launch, whose workgroups are the units of the overflow hand-over)
-static int tower_block_samples(int64_t batch, int32_t channels, int32_t height, int32_t width) {
-    const bool many = batch >= 16384;
-    if (height == 6 && width == 7) return channels == 64 ? split_block_samples(height, width) : 0;   // (16 channels: depends on the input's parity too)
-    if (height == 6 && width == 6) return channels == 64 ? 4 : (many ? 3 : 4);
-    return channels == 64 ? 16 : (many ? 14 : 16);
+#undef MZ_CONV
+    return MZMCTS_ERR_INVALID;                                       // (a plan without an instantiation: cannot happen)
 }
 
 extern "C" int64_t mzmcts_board_tower_blocks(int64_t batch, int32_t channels, int32_t height, int32_t width) {
-    const int sb = tower_block_samples(batch, channels, height, width);
-    if (batch < 0 || sb <= 0 || !mzmcts_board_conv_supported(channels, channels, height, width)) return -1;
-    return (batch + sb - 1) / sb;
+    return mz::board_tower_blocks(batch, channels, height, width, (height == 6 && width == 7) ? mz::split_boards_env() : 2);
 }
 
 extern "C" int mzmcts_board_tower(const float* x, int64_t batch, int32_t cin0, int32_t channels, int32_t height, int32_t width,
                                   const mzmcts_tower_layer* layers, int32_t n_layers, void* stream) {
     if (!x) return MZMCTS_ERR_INVALID;
-    return board_tower_impl(x, mz::TowerGather{}, batch, cin0, channels, height, width, layers, n_layers, stream);
+    return mz::board_tower_impl(x, mz::TowerGather{}, false, 0, batch, cin0, channels, height, width, layers, n_layers, stream);
 }
 
 extern "C" int mzmcts_board_tower_heads(const float* x, const mzmcts_tower_gather* g, int64_t batch, int32_t cin0,
@@ -2064,13 +1975,8 @@ extern "C" int mzmcts_board_tower_heads(const float* x, const mzmcts_tower_gathe
                                         int32_t n_layers, const mzmcts_tower_head* heads, int32_t n_heads, void* stream) {
     if ((!x) == (!g) || n_heads < 1) return MZMCTS_ERR_INVALID;     // exactly one input form
     mz::TowerGather gather{};
-    if (g) {
-        if (!g->pool || !g->parent || !g->action || g->envs < batch || !(g->action_space > 0.f) ||
-            g->hidden_floats != channels * height * width || cin0 != channels + 1)
-            return MZMCTS_ERR_INVALID;
-        gather = mz::TowerGather{g->pool, g->parent, g->action, static_cast<long long>(g->envs), g->hidden_floats, g->action_space};
-    }
-    return board_tower_impl(x, gather, batch, cin0, channels, height, width, layers, n_layers, stream, heads, n_heads);
+    if (g && mz::gather_from(g, batch, cin0, channels, height, width, &gather) != MZMCTS_OK) return MZMCTS_ERR_INVALID;
+    return mz::board_tower_impl(x, gather, false, 0, batch, cin0, channels, height, width, layers, n_layers, stream, heads, n_heads);
 }
 
 extern "C" int64_t mzmcts_board_conv_split_halfs(int32_t cin_conv, int32_t cout) {
@@ -2093,75 +1999,21 @@ extern "C" int mzmcts_board_conv_pack_split(const float* weight, void* packed, f
     return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
 }
 
-static int board_tower_split_impl(const float* x, const mz::TowerGather& gather, int64_t batch, int32_t cin0,
-                                  int32_t const_plane, int32_t channels, int32_t height, int32_t width,
-                                  const mzmcts_tower_layer* layers, int32_t n_layers, void* stream_) {
-    if ((!x && !gather.pool) || !layers || batch < 0 || batch > 0x3fffffff || n_layers < 1 || n_layers > mz::kMaxTowerLayers || channels != 64 ||
-        !mzmcts_board_conv_supported(cin0, channels, height, width) || (const_plane && cin0 < 2))
-        return MZMCTS_ERR_INVALID;
-    mz::SplitArgs args{};
-    args.n_layers = n_layers;
-    for (int l = 0; l < n_layers; ++l) {
-        const mzmcts_tower_layer& d = layers[l];
-        const int cin_conv = l == 0 ? cin0 - (const_plane ? 1 : 0) : channels;
-        if (!d.packed || !d.scale || !d.shift || d.cin != (l == 0 ? cin0 : channels) ||
-            (l == 0 && const_plane && !d.const_table))
-            return MZMCTS_ERR_INVALID;
-        if ((reinterpret_cast<uintptr_t>(d.scale) | reinterpret_cast<uintptr_t>(d.shift)) & 15u)
-            return MZMCTS_ERR_INVALID;                   // (read four channels at a time)
-        args.layer[l] = mz::SplitLayer{static_cast<const _Float16*>(d.packed), d.scale, d.shift,
-                                       (l == 0 && const_plane) ? d.const_table : nullptr, d.export_raw, d.export_unit,
-                                       cin_conv, d.relu, d.skip, 0};
-    }
-    // The constant plane is never staged into LDS (its contribution comes from the table).  A skip on layer 1 -- a tower
-    // that starts with a residual block -- adds the input's first `channels` planes: with cin0 <= channels the constant
-    // plane is one of them and would be read as zeros.  Refused; no network builds such a tower (the dynamics input has
-    // channels + 1 planes and starts with a plain convolution).
-    if (const_plane && n_layers > 1 && layers[1].skip && cin0 <= channels) return MZMCTS_ERR_INVALID;
-    args.gate = layers[0].gate;
-    {
-        static const int slot_priority = [] {
-            const char* env = std::getenv("MZ_SPLIT_PRIORITY");
-            return (env && std::string(env) == "off") ? 0 : 1;
-        }();
-        args.slot_priority = slot_priority;
-    }
-    if (batch == 0) return MZMCTS_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int b = static_cast<int>(batch);
-    // (4 boards per workgroup: 3 fill the MFMA rounds better -- 126 rows = 8 tiles -- and 2 let two workgroups share a
-    // CU, but both measured slower at 4096 Connect4 boards: 700 / 744 / 900 us per launch for 4 / 3 / 2; again after the
-    // packed epilogue, 8192 boards with heads: 1289 us for 4, 1366 us for 3)
-    if (height == 6 && width == 7) {
-        const int sb = split_block_samples(height, width);
-        if (sb == 2) return mz::launch_board_tower_split<6, 7, 2, 4>(x, b, cin0, const_plane, args, stream, gather);
-        if (sb == 1) return mz::launch_board_tower_split<6, 7, 1, 2>(x, b, cin0, const_plane, args, stream, gather);
-        return mz::launch_board_tower_split<6, 7, 4>(x, b, cin0, const_plane, args, stream, gather);
-    }
-    if (height == 6 && width == 6) return mz::launch_board_tower_split<6, 6, 4>(x, b, cin0, const_plane, args, stream, gather);
-    // 3 x 3 boards: refused as in board_tower_impl (16 boards x two buffers of two fp16 halves x (64 + 8) channels = 189 KB)
-    return MZMCTS_ERR_INVALID;
-}
-
 extern "C" int mzmcts_board_tower_split(const float* x, int64_t batch, int32_t cin0, int32_t const_plane, int32_t channels,
                                         int32_t height, int32_t width, const mzmcts_tower_layer* layers, int32_t n_layers,
                                         void* stream) {
     if (!x) return MZMCTS_ERR_INVALID;
-    return board_tower_split_impl(x, mz::TowerGather{}, batch, cin0, const_plane, channels, height, width, layers, n_layers,
-                                  stream);
+    return mz::board_tower_impl(x, mz::TowerGather{}, true, const_plane, batch, cin0, channels, height, width, layers,
+                                n_layers, stream);
 }
 
 extern "C" int mzmcts_board_tower_gathered(const mzmcts_tower_gather* g, int64_t batch, int32_t cin0, int32_t split,
                                            int32_t channels, int32_t height, int32_t width, const mzmcts_tower_layer* layers,
                                            int32_t n_layers, void* stream) {
-    if (!g || !g->pool || !g->parent || !g->action || g->envs < batch || !(g->action_space > 0.f) ||
-        g->hidden_floats != channels * height * width || cin0 != channels + 1)
-        return MZMCTS_ERR_INVALID;
-    const mz::TowerGather gather{g->pool, g->parent, g->action, static_cast<long long>(g->envs), g->hidden_floats,
-                                 g->action_space};
-    if (split)
-        return board_tower_split_impl(nullptr, gather, batch, cin0, 1, channels, height, width, layers, n_layers, stream);
-    return board_tower_impl(nullptr, gather, batch, cin0, channels, height, width, layers, n_layers, stream);
+    mz::TowerGather gather{};
+    if (mz::gather_from(g, batch, cin0, channels, height, width, &gather) != MZMCTS_OK) return MZMCTS_ERR_INVALID;
+    return mz::board_tower_impl(nullptr, gather, split != 0, split ? 1 : 0, batch, cin0, channels, height, width, layers, n_layers,
+                                stream);
 }
 
 #ifdef MZ_TOWER_STAMPS

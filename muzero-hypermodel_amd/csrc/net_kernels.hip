@@ -11,8 +11,10 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 
 #include "../../include/mzmcts.h"
+#include "board_launch.h"
 
 namespace mz {
 
@@ -101,23 +103,6 @@ __global__ __launch_bounds__(kRescaleRows) void unit_rescale_kernel(const float*
 // banks whatever the row length.  A hidden layer narrower than the wave splits its dot products over the idle
 // lanes.  fp32 throughout; hipBLASLt's
 // summation order is its own, so the two agree to fp32 rounding, not bit for bit (tests/test_gpu_net.py: 1e-5).
-constexpr int kHeadWaves = 4;
-
-struct HeadShape {
-    int C, P, R, Hd, O;  // channels, board positions, reduced channels, hidden units, outputs
-    int split;           // lanes sharing one hidden unit's dot product: 64 / pow2(Hd), at least 1
-    __host__ __device__ int RP() const { return R * P; }
-    __host__ __device__ int conv_w() const { return 0; }
-    __host__ __device__ int conv_b() const { return conv_w() + R * C; }
-    __host__ __device__ int fc1_w() const { return conv_b() + R; }
-    __host__ __device__ int fc1_b() const { return fc1_w() + Hd * RP(); }
-    __host__ __device__ int fc2_w() const { return fc1_b() + Hd; }
-    __host__ __device__ int fc2_b() const { return fc2_w() + O * Hd; }
-    __host__ __device__ int per_wave() const { return (fc2_b() + O + 3) & ~3; }  // 16-byte aligned boards
-    // per wave: [x C*P | y R*P | partial sums split*Hd | h Hd], padded to a multiple of 4 words
-    __host__ __device__ int wave_floats() const { return (C * P + RP() + split * Hd + Hd + 3) & ~3; }
-    __host__ __device__ int total() const { return per_wave() + kHeadWaves * wave_floats(); }
-};
 
 // Orders this wave's LDS writes before its following LDS reads (other lanes' data), for the compiler and the
 // memory counters; no other wave is involved.
@@ -146,7 +131,6 @@ __device__ __forceinline__ void stage_copy(float* dst, const float* __restrict__
 }
 
 // Up to three heads (kMaxHeads) share a launch, each reading its own tensor: blockIdx.y picks the head.
-constexpr int kMaxHeads = 3;
 struct HeadSet {
     const float* x[kMaxHeads];   // the tensor each head reads (value / policy share one, the reward head has its own)
     mzmcts_head_desc desc[kMaxHeads];
@@ -270,27 +254,6 @@ __global__ __launch_bounds__(64 * kHeadWaves) void conv_head_kernel(HeadSet set,
 // and from hipBLASLt: equal to fp32 rounding, tests/test_gpu_net.py).
 // -------------------------------------------------------------------------------------------------------------------
 typedef float head_f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kTileSamples = 16;
-constexpr int kMaxConvSteps = 16;   // channels / 4 <= 16: the 1x1 convolution's weights stay in registers (4 or 16 k-steps)
-
-struct MfmaHeadShape {
-    int C, P, R, Hd, O;
-    __host__ __device__ int RP() const { return R * P; }
-    __host__ __device__ int ys_stride() const { return RP() + 1; }      // (+1: the 16 sample rows fall into different banks)
-    __host__ __device__ int hs_stride() const { return Hd + 1; }
-    __host__ __device__ int w1_stride() const { return RP() + 1; }
-    __host__ __device__ int w2_stride() const { return Hd + 1; }
-    __host__ __device__ int nt1() const { return (Hd + 15) / 16; }
-    __host__ __device__ int nt2() const { return (O + 15) / 16; }
-    // LDS (floats): W1 [16 nt1][w1_stride] | b1 [16 nt1] | W2 [16 nt2][w2_stride] | b2 [16 nt2] | per wave { ys, hs }
-    __host__ __device__ int off_b1() const { return 16 * nt1() * w1_stride(); }
-    __host__ __device__ int off_w2() const { return off_b1() + 16 * nt1(); }
-    __host__ __device__ int off_b2() const { return off_w2() + 16 * nt2() * w2_stride(); }
-    __host__ __device__ int off_waves() const { return off_b2() + 16 * nt2(); }
-    __host__ __device__ int wave_floats() const { return kTileSamples * (ys_stride() + hs_stride()); }
-    __host__ __device__ int total() const { return off_waves() + kHeadWaves * wave_floats(); }
-};
-
 struct MfmaHeadSet {
     const float* x[kMaxHeads];
     mzmcts_head_desc desc[kMaxHeads];
@@ -522,11 +485,6 @@ __global__ __launch_bounds__(64 * kHeadWaves) void conv_head_mfma_kernel(MfmaHea
     else mfma_head_dispatch<16, 2>(s, d, x, out, lds, batch, lane, wave);
 }
 
-// shapes the matrix-core heads take: reduced channels <= 16 (one column tile), channels <= 64, hidden <= 64, outputs <= 32
-static bool mfma_head_ok(const mzmcts_head_desc& d) {
-    return d.reduced <= 16 && d.channels <= 4 * kMaxConvSteps && d.hidden <= 64 && d.outputs <= 32;
-}
-
 // The dynamics network's input (reference models.py:553-568): the hidden state's planes followed by one plane
 // holding action / action_space_size -- through torch a cast, a division, an expand and a concatenation.
 __global__ __launch_bounds__(256) void state_action_planes_kernel(const float* __restrict__ state,
@@ -576,82 +534,55 @@ extern "C" int mzmcts_unit_rescale(const float* x, float* out, int64_t rows, int
 
 namespace mz {
 // board_conv.hip: the heads of 16-channel 3 x 3 networks in the board-column shape (same bits as conv_head_mfma_kernel)
-int launch_board_heads_cols(const float* const* xs, const mzmcts_head_desc* heads, int n_heads, float* const* outs,
-                            int64_t batch, hipStream_t stream);
+int launch_board_heads_cols(const HeadsPlan& plan, const float* const* xs, const mzmcts_head_desc* heads, int n_heads,
+                            float* const* outs, int64_t batch, hipStream_t stream);
 }
 
 extern "C" int mzmcts_conv_heads_multi(const float* const* xs, const mzmcts_head_desc* heads, int32_t n_heads,
                                        float* const* outs, int64_t batch, void* stream_) {
-    if (!xs || !heads || !outs || n_heads < 1 || n_heads > mz::kMaxHeads || batch < 0 || batch > 0x7fffffff)
-        return MZMCTS_ERR_INVALID;
-    for (int h = 0; h < n_heads; ++h)
-        if (!xs[h] || (reinterpret_cast<uintptr_t>(xs[h]) & 15u)) return MZMCTS_ERR_INVALID;
-    {
-        const int rc = mz::launch_board_heads_cols(xs, heads, n_heads, outs, batch, static_cast<hipStream_t>(stream_));
-        if (rc != MZMCTS_ERR_INVALID) return rc;
+    if (!xs || !heads || !outs || n_heads < 1 || n_heads > mz::kMaxHeads) return MZMCTS_ERR_INVALID;
+    mz::HeadDims dims[mz::kMaxHeads];
+    for (int h = 0; h < n_heads; ++h) {
+        const mzmcts_head_desc& d = heads[h];
+        if (!xs[h] || (reinterpret_cast<uintptr_t>(xs[h]) & 15u) || !outs[h] || !d.conv_w || !d.conv_b || !d.fc1_w || !d.fc1_b ||
+            !d.fc2_w || !d.fc2_b)
+            return MZMCTS_ERR_INVALID;
+        dims[h] = mz::HeadDims{d.channels, d.plane, d.reduced, d.hidden, d.outputs};
     }
     static const bool use_mfma = std::getenv("MZ_HEADS_WAVE_PER_SAMPLE") == nullptr;
-    bool mfma = use_mfma;      // (any batch: a sample's logits do not depend on how many samples share its launch)
-    for (int h = 0; h < n_heads && mfma; ++h) mfma = mz::mfma_head_ok(heads[h]);
-    if (mfma) {
-        mz::MfmaHeadSet mset{};
-        size_t mlds = 0;
-        for (int h = 0; h < n_heads; ++h) {
-            const mzmcts_head_desc* d = heads + h;
-            if (!outs[h] || !d->conv_w || !d->conv_b || !d->fc1_w || !d->fc1_b || !d->fc2_w || !d->fc2_b || d->channels <= 0 ||
-                d->plane <= 0 || d->reduced <= 0 || d->hidden <= 0 || d->outputs <= 0 || d->channels != heads[0].channels ||
-                d->plane != heads[0].plane)
-                return MZMCTS_ERR_INVALID;
-            mset.x[h] = xs[h];
-            mset.desc[h] = *d;
-            mset.shape[h] = mz::MfmaHeadShape{d->channels, d->plane, d->reduced, d->hidden, d->outputs};
-            mset.out[h] = outs[h];
-            mlds = std::max(mlds, sizeof(float) * static_cast<size_t>(mset.shape[h].total()));
+    const char* cols_env = std::getenv("MZ_HEADS_COLS");
+    mz::HeadsPlan p;
+    const int rc = mz::plan_heads(dims, n_heads, batch, !(cols_env && std::string(cols_env) == "off"), use_mfma, &p);
+    if (rc != MZMCTS_OK || batch == 0) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    switch (p.kernel) {
+        case mz::HeadsKernel::kCols:
+            return mz::launch_board_heads_cols(p, xs, heads, n_heads, outs, batch, stream);
+        case mz::HeadsKernel::kMfma: {
+            mz::MfmaHeadSet set{};
+            for (int h = 0; h < n_heads; ++h) {
+                set.x[h] = xs[h];
+                set.desc[h] = heads[h];
+                set.shape[h] = p.mfma[h];
+                set.out[h] = outs[h];
+            }
+            return mz::launch_with_lds(mz::conv_head_mfma_kernel, grid, block, p.lds, stream, set, static_cast<int>(batch));
         }
-        if (mlds <= 160 * 1024) {
-            if (batch == 0) return MZMCTS_OK;
-            if (mlds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(mz::conv_head_mfma_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mlds)) != hipSuccess)
-                return MZMCTS_ERR_HIP;
-            const int64_t tiles = (batch + mz::kTileSamples - 1) / mz::kTileSamples;
-            const int64_t rounds = (tiles + mz::kHeadWaves - 1) / mz::kHeadWaves;
-            const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / mlds)));
-            const dim3 grid(static_cast<unsigned>(std::min<int64_t>(rounds, 256 * per_cu)), static_cast<unsigned>(n_heads));
-            mz::conv_head_mfma_kernel<<<grid, dim3(64 * mz::kHeadWaves), mlds, static_cast<hipStream_t>(stream_)>>>(
-                mset, static_cast<int>(batch));
-            return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
+        case mz::HeadsKernel::kWave: {
+            mz::HeadSet set{};
+            for (int h = 0; h < n_heads; ++h) {
+                set.x[h] = xs[h];
+                set.desc[h] = heads[h];
+                set.shape[h] = p.wave[h];
+                set.out[h] = outs[h];
+            }
+            return mz::launch_with_lds(mz::conv_head_kernel, grid, block, p.lds, stream, set, static_cast<int>(batch));
         }
+        case mz::HeadsKernel::kNone:
+            break;
     }
-    mz::HeadSet set{};
-    size_t lds = 0;
-    for (int h = 0; h < n_heads; ++h) {
-        const mzmcts_head_desc* d = heads + h;
-        if (!outs[h] || !d->conv_w || !d->conv_b || !d->fc1_w || !d->fc1_b || !d->fc2_w || !d->fc2_b || d->channels <= 0 ||
-            d->plane <= 0 || d->reduced <= 0 || d->hidden <= 0 || d->outputs <= 0 || d->channels != heads[0].channels ||
-            d->plane != heads[0].plane)
-            return MZMCTS_ERR_INVALID;
-        int split = 1;
-        while (split * 2 * d->hidden <= 64) split *= 2;  // lanes per hidden unit (a power of two; 1 from 33 units on)
-        set.x[h] = xs[h];
-        set.desc[h] = *d;
-        set.shape[h] = mz::HeadShape{d->channels, d->plane, d->reduced, d->hidden, d->outputs, split};
-        set.out[h] = outs[h];
-        lds = std::max(lds, sizeof(float) * static_cast<size_t>(set.shape[h].total()));
-    }
-    if (lds > 160 * 1024) return MZMCTS_ERR_INVALID;  // the caller keeps the torch modules
-    if (batch == 0) return MZMCTS_OK;
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(mz::conv_head_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (err != hipSuccess) return MZMCTS_ERR_HIP;
-    }
-    const int64_t rounds = (batch + mz::kHeadWaves - 1) / mz::kHeadWaves;
-    const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds)));
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(rounds, 256 * per_cu)), static_cast<unsigned>(n_heads));
-    mz::conv_head_kernel<<<grid, dim3(64 * mz::kHeadWaves), lds, static_cast<hipStream_t>(stream_)>>>(set,
-                                                                                                    static_cast<int>(batch));
-    return hipGetLastError() == hipSuccess ? MZMCTS_OK : MZMCTS_ERR_HIP;
+    return MZMCTS_ERR_INVALID;
 }
 
 extern "C" int mzmcts_conv_heads(const float* x, const mzmcts_head_desc* heads, int32_t n_heads, float* const* outs,

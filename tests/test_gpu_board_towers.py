@@ -12,15 +12,13 @@ _split, _gathered, _heads; no network module in between) and compared with a yar
              rescales the float32 values h0 + h1 with the same two operations and writes the quotient back as two fp16
              halves before it exports it: its unit export must be split22 of that expression, bit for bit.
 
-Every launch line of the dispatch tables (board_tower_impl, board_tower_split_impl) is a test id below:
-  launch_board_tower<4,6,7,4> <4,6,6,4> <1,6,7,4> <1,6,7,6> <1,6,6,4> <1,6,6,3> <1,3,3,16> <1,3,3,14>,
-  launch_board_tower_cols (plain and with heads), launch_board_tower_patch66,
-  launch_board_tower_split<6,7,2,4> <6,6,4>.
-Not reached: launch_board_tower_split<6,7,1,2> and <6,7,4>.  MZ_SPLIT_BOARDS selects them and is read once per process;
-this file tests the default (2 boards on 4 wavefronts) only.
-Gone: launch_board_tower<4,3,3,16> and launch_board_tower_split<3,3,16>.  Their activation buffers never fitted the 160 KB
-of a workgroup (179 KB / 189 KB whatever cin0 is), so every call came back MZMCTS_ERR_INVALID from the launcher's size
-check; the dispatch now refuses 64 channels on 3 x 3 boards by name (tests/test_board_tower_reference.py holds the refusal).
+Every launch line of the tower plan (csrc/launch_plan.h plan_tower) is a test id below; the ids live in
+tests/board_tower_cases.py (FP32_FORMS, SPLIT_FORMS, MANY), and tests/test_launch_plan_cpu.py holds every one of them, at
+every cin0 and batch it is run with here, to the kernel and template arguments it names -- on the CPU, from the header
+itself.  Not reached on the GPU: launch_board_tower_split<6,7,1,2> and <6,7,4>.  MZ_SPLIT_BOARDS selects them and is read
+once per process; this file tests the default (2 boards on 4 wavefronts) only, the CPU test holds the plan of all three.
+64 channels on 3 x 3 boards have no tower (179 KB / 189 KB of activation buffers whatever cin0 is): the plan refuses them by
+name (tests/test_board_tower_reference.py holds the refusal).
 """
 import ctypes
 import importlib
@@ -231,18 +229,8 @@ def exercise(lib, native, form, h, w, channels, cin0s, S, wide=None, split=False
         report(form)
 
 
-FP32_FORMS = [
-    # id (the launch line), channels, h, w, MZ_TOWER_COLS, samples per workgroup / wavefront, wider unit, cin0s
-    ("launch_board_tower<4,6,7,4>", 64, 6, 7, None, 4, None, (65, 3, 64, 80)),          # 80 -> 64: 158 KB of LDS, the largest admitted
-    ("launch_board_tower<4,6,6,4>", 64, 6, 6, None, 4, None, (65, 2, 64, 80)),
-    ("launch_board_tower<1,6,7,4>", 16, 6, 7, None, 4, None, (17, 1, 15, 16)),
-    ("launch_board_tower<1,6,6,4>", 16, 6, 6, "off", 4, None, (17, 2, 16, 20)),
-    ("launch_board_tower<1,3,3,16>", 16, 3, 3, "off", 16, None, (17, 1, 3, 15, 16)),
-    ("launch_board_tower<1,6,6,4>-cin0-outside-16-17", 16, 6, 6, None, 4, None, (20, 15)),   # (the patch kernel does not apply)
-    ("launch_board_tower<1,3,3,16>-cin0-outside-16-17", 16, 3, 3, None, 16, None, (20, 2)),
-    ("launch_board_tower_cols", 16, 3, 3, None, 16, 64, (17, 16)),                      # a wavefront: 16 boards, a workgroup: 64
-    ("launch_board_tower_patch66", 16, 6, 6, None, 4, 16, (17, 16)),                    # BPW = 4 boards, a workgroup: 16
-]
+FP32_FORMS, SPLIT_FORMS, MANY = cases.FP32_FORMS, cases.SPLIT_FORMS, cases.MANY    # (the launch lines; tests/test_launch_plan_cpu.py
+                                                                                    #  holds every id to the kernel it names)
 
 
 @pytest.mark.parametrize("form", FP32_FORMS, ids=[f[0] for f in FP32_FORMS])
@@ -257,29 +245,12 @@ def test_fp32_tower_forms(lib, native, monkeypatch, form):
     exercise(lib, native, name, h, w, channels, cin0s, S, wide)
 
 
-SPLIT_FORMS = [
-    ("launch_board_tower_split<6,7,2,4>", 6, 7, 2, (65, 2, 64, 80)),
-    ("launch_board_tower_split<6,6,4>", 6, 6, 4, (65, 2, 64)),
-]
-
-
 @pytest.mark.parametrize("form", SPLIT_FORMS, ids=[f[0] for f in SPLIT_FORMS])
 def test_split_tower_forms(lib, native, form):
     """cin0 in {2, 64, 65, 80} with and without a constant last plane; cin0 = 2 with one is a ONE-channel convolution."""
     name, h, w, S, cin0s = form
     assert lib.mzmcts_board_tower_blocks(2 * S + 1, 64, h, w) == 3          # (S is the form's block)
     exercise(lib, native, name, h, w, 64, cin0s, S, split=True)
-
-
-MANY = [
-    # id, h, w, MZ_TOWER_COLS, cin0 -- the 16-channel forms across the `many` switch at 16384 boards
-    ("launch_board_tower<1,6,7,6>", 6, 7, None, 17),
-    ("launch_board_tower<1,6,6,3>", 6, 6, "off", 17),
-    ("launch_board_tower<1,3,3,14>", 3, 3, "off", 17),
-    ("launch_board_tower<1,3,3,14>-cin0-1", 3, 3, None, 1),
-    ("launch_board_tower_cols-many", 3, 3, None, 17),
-    ("launch_board_tower_patch66-many", 6, 6, None, 16),
-]
 
 
 @pytest.mark.parametrize("form", MANY, ids=[f[0] for f in MANY])
