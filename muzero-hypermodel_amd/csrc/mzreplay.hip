@@ -218,7 +218,10 @@ struct SamplerParams {
     double* tables;          // [Bcap][L] normalised running sums of the sampled games' position probabilities
 };
 
-constexpr int kMaxLeaves = 512;        // pairwise leaves summed in parallel (covers 32 768 games; beyond: one lane)
+// pairwise leaves summed in parallel.  64 leaves per full piece of 8192: every store of up to 65 032 games has at most 512,
+// 65 033 has 513, and the count is not monotone after that (65 040 and 65 536 are back at 512, 65 537 has 513).  More
+// leaves than this: one lane adds them up.
+constexpr int kMaxLeaves = 512;
 constexpr int kSampleThreads = 256;
 
 // the next block of 624 words, across the workgroup's (or the wavefront's) lanes: three ranges that each read only

@@ -55,7 +55,8 @@ def f32_of_bits(values):
 def test_pairwise_sum_equals_numpy_sum(check):
     rs = np.random.RandomState(5)
     arrays = []
-    for n in list(range(1, 301)) + [1000, 4096, 8191, 8192, 8200, 9999, 10000, 20001]:
+    for n in list(range(1, 301)) + [1000, 4096, 8191, 8192, 8200, 9999, 10000, 20001,
+              65032, 65033, 65040, 65536, 65537, 70001, 140001]:
         for kind in range(3):
             exponents = rs.uniform(-12, 3, size=n) if kind < 2 else rs.uniform(-1, 0, size=n)
             a = (10.0 ** exponents).astype(np.float32)
