@@ -43,6 +43,10 @@ bool plan_fused_layout(const TreeParams& p, const FcNet& net, bool want_hidden_i
                        FusedLayout* out);
 bool narrow_supported(const TreeParams& p, const FcNet& net);
 bool plan_narrow_layout(const TreeParams& p, const FcNet& net, size_t lds_limit, NarrowLayout* out);
+// The (N, n) exploration table of `mode` (NarrowLayout::pbc2_mode 1 or 2) in device memory, with the expression
+// stage_narrow_tables evaluates; narrow_table_doubles: its size, rounded up to whole 16-byte loads.
+size_t narrow_table_doubles(int S, int mode);
+hipError_t build_narrow_table(const TreeParams& p, int mode, double* out, hipStream_t stream);
 hipError_t launch_search_fused_narrow(const TreeParams& p, const FcNet& net, const NarrowLayout& lay, const float* weights,
                                       const float* observations, const MoveCtl& ctl, int n_sims, int publish_tree,
                                       hipStream_t stream, const LaunchTiming* timing);
@@ -266,6 +270,14 @@ struct mzmcts_engine {
     bool tree_published = true;             // false after a root-only fused search
     mz::FcNet fc{};
     const float* fc_weights = nullptr;
+    // the narrow kernel's per-engine choices, read from the environment once, at mzmcts_create (A/B measurements and
+    // tests/test_gpu_fused_stream_edges.py run both forms of each from one build):
+    //   MZMCTS_NARROW_SERIAL_TWIST=1      lane 0 alone draws from the tree's stream and regenerates its block
+    //   MZMCTS_NARROW_TABLE_PER_LAUNCH=1  every workgroup of every launch computes the (N, n) table
+    //   MZMCTS_NARROW_NO_PREFETCH=1       the per-tree inputs are read where they are needed, after the staging barrier
+    bool narrow_row_rng = true;
+    bool narrow_prefetch = true;
+    double* narrow_table[3] = {nullptr, nullptr, nullptr};   // by pbc2_mode; built at create (S and pb_c never change)
 
     // profiling
     bool profiling = false;

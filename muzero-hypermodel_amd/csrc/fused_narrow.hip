@@ -104,6 +104,45 @@ bool plan_narrow_layout(const TreeParams& p, const FcNet& net, size_t lds_limit,
     return false;
 }
 
+// doubles of the (N, n) table of `mode`, rounded up to whole 16-byte words (0: the mode has no table at this S)
+size_t narrow_table_doubles(int S, int mode) {
+    const size_t K = static_cast<size_t>(S) + 1;
+    size_t n = 0;
+    if (mode == 2 && S <= 63) n = K * 64;
+    if (mode == 1) n = K * (K + 1) / 2;
+    return (n + 1) / 2 * 2;
+}
+
+// The table in device memory, once per engine: entry by entry what stage_narrow_tables computes in a launch (the same
+// two IEEE operations on the same operands; entries the kernel never reads stay zero).
+__global__ void narrow_table_kernel(const double* __restrict__ pbc_log, const double* __restrict__ pbc_sqrt, int S, int mode,
+                                    double* __restrict__ out) {
+    const int K = S + 1;
+    const int total = mode == 2 ? K * 64 : K * (K + 1) / 2;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
+        int N, n;
+        if (mode == 2) {
+            N = t >> 6;
+            n = t & 63;
+            if (n > N) continue;
+        } else {
+            N = 0;
+            int row = 0;  // N(N+1)/2
+            while (row + N + 1 <= t) {
+                row += N + 1;
+                ++N;
+            }
+            n = t - row;
+        }
+        out[t] = pbc_log[N] * (pbc_sqrt[N] / static_cast<double>(n + 1));
+    }
+}
+
+hipError_t build_narrow_table(const TreeParams& p, int mode, double* out, hipStream_t stream) {
+    narrow_table_kernel<<<dim3(16), dim3(256), 0, stream>>>(p.pbc_log, p.pbc_sqrt, p.S, mode, out);
+    return hipGetLastError();
+}
+
 __device__ __forceinline__ void stage_narrow_tables(const TreeParams& p, const NarrowLayout& lay, uint8_t* smem, int tid,
                                                     int nthreads) {
     double* pbc = reinterpret_cast<double*>(smem + lay.off_pbc);
@@ -111,7 +150,28 @@ __device__ __forceinline__ void stage_narrow_tables(const TreeParams& p, const N
         pbc[i] = p.pbc_log[i];
         pbc[p.S + 1 + i] = p.pbc_sqrt[i];
     }
-    if (lay.pbc2_mode == 2) {
+    if (lay.pbc2_table && lay.pbc2_mode != 0) {
+        // the engine's copy: 16-byte loads, a batch of them in flight per thread, then the LDS stores
+        const int K = p.S + 1;
+        const int doubles = lay.pbc2_mode == 2 ? K * 64 : K * (K + 1) / 2;
+        const int n16 = (doubles + 1) / 2;
+        const uint4* src = reinterpret_cast<const uint4*>(lay.pbc2_table);
+        uint4* dst = reinterpret_cast<uint4*>(smem + lay.off_pbc2);
+        constexpr int kBatch = 8;
+        for (int base = tid; base < n16; base += nthreads * kBatch) {
+            uint4 v[kBatch];
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                const int i = base + b * nthreads;
+                v[b] = src[i < n16 ? i : n16 - 1];
+            }
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                const int i = base + b * nthreads;
+                if (i < n16) dst[i] = v[b];
+            }
+        }
+    } else if (lay.pbc2_mode == 2) {
         // rows of 64: entry (N << 6) + n, n <= N -- the triangular table's values, addressed by shifts
         double* pbc2 = reinterpret_cast<double*>(smem + lay.off_pbc2);
         for (int t = tid; t < (p.S + 1) * 64; t += nthreads) {
@@ -148,22 +208,40 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
     const double* pbc2 = reinterpret_cast<const double*>(smem + (PBC2 ? lay.off_pbc2 : 0u));
     float4* units = reinterpret_cast<float4*>(smem + lay.off_units);
     float* bias = reinterpret_cast<float*>(smem + lay.off_bias);
+    const int j = threadIdx.x % kRow;
+    const int group_base = (threadIdx.x & 63) - j;  // lane of the row's first lane inside its wavefront
+    const int row = group_base / kRow;
+    const int tree_in_block = (threadIdx.x / 64) * lay.rows + row;
+    const int e = blockIdx.x * (blockDim.x / 64) * lay.rows + tree_in_block;
+    const bool prefetch = lay.prefetch != 0;
+    NarrowInputs in{};
+    // (a lane without a tree asks for env 0's: it stages with the others and leaves after the barrier)
+    if (prefetch) in = narrow_load_inputs(p, net, ctl, observations, (row < lay.rows && e < p.E) ? e : 0, j);
     stage_narrow_tables(p, lay, smem, threadIdx.x, blockDim.x);
     stage_narrow_units(net, weights, units, bias, threadIdx.x, blockDim.x);
     __syncthreads();
     MZ_STAMP(0);
 
-    const int j = threadIdx.x % kRow;
-    const int group_base = (threadIdx.x & 63) - j;  // lane of the row's first lane inside its wavefront
-    const int row = group_base / kRow;
     if (row >= lay.rows) return;                    // this wavefront carries fewer than four trees
-    const int tree_in_block = (threadIdx.x / 64) * lay.rows + row;
-    const int e = blockIdx.x * (blockDim.x / 64) * lay.rows + tree_in_block;
     if (e >= p.E) return;
-    const int n_root = p.root_children[e];
-    if (move_stalled(p, ctl, e, j)) return;
+    const int n_root = prefetch ? in.n_root : p.root_children[e];
+    if (prefetch ? narrow_move_stalled(ctl, in, e, j) : move_stalled(p, ctl, e, j)) return;
     const double* noise = ctl.noise;
-    if (j == 0) reset_search_state(p, e, ctl.rng_skip);
+    const bool row_rng = lay.row_rng != 0;
+    uint32_t* mt_key = p.mt_key + static_cast<size_t>(e) * kMtN;
+    int32_t mt_pos = 0;   // row_rng: in every lane of the row; else lane 0's
+    if (row_rng) {
+        // the words the host mirror consumed (reset_search_state's loop), stepped over by the row: every lane reads
+        // the position, the block is regenerated by all of them when the skip crosses its end
+        const uint32_t skip = prefetch ? in.skip : (ctl.rng_skip ? ctl.rng_skip[e] : 0u);
+        mt_pos = mt_skip_row(mt_key, prefetch ? in.mt_pos : p.mt_pos[e], skip, j);
+        if (j == 0) {
+            if (skip) p.mt_pos[e] = mt_pos;
+            reset_search_state(p, e, nullptr);
+        }
+    } else if (j == 0) {
+        reset_search_state(p, e, ctl.rng_skip);
+    }
     if (n_root == 0) {
         if (j == 0 && ctl.actions) ctl.actions[e] = -1;
         return;
@@ -187,20 +265,23 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
     // ---- root: initial inference, root.expand over the legal actions, exploration noise ----------
     float predicted;
     {
-        const float obs = (j < net.obs) ? observations[static_cast<size_t>(e) * net.obs + j] : 0.f;
+        const float obs = prefetch ? in.obs : ((j < net.obs) ? observations[static_cast<size_t>(e) * net.obs + j] : 0.f);
         const NarrowHeads h = narrow_initial(units, bias, enc, wide_support, net.repr.n_layers == 2, obs, j);
         float unused;
         narrow_support_pair(h.value_a, h.value_b, h.value_a, h.value_b, net.F, net.support, j, predicted, unused);
         // child slot c of the root is action root_action[c]: fetch its logit across the lanes through LDS
-        const int my_action = (j < n_root) ? p.root_action[static_cast<size_t>(e) * p.A + j] : 0;
+        const int my_action = (j < n_root) ? (prefetch ? in.root_action : p.root_action[static_cast<size_t>(e) * p.A + j]) : 0;
         root_action_lds[j] = my_action;
         root_logit_lds[j] = h.policy;
         if (j < enc) hidden_lds[j] = h.norm;  // slab 0
         group_memory_fence();
         const bool valid = j < n_root;
         double prior[1] = {narrow_softmax(valid ? root_logit_lds[my_action] : 0.f, valid)};
-        write_root_children<kRow, 1>(tree, p.A, n_root, prior, noise ? noise + static_cast<size_t>(e) * p.A : nullptr,
-                                     p.noise_frac, j);
+        if (prefetch)
+            write_root_children_row(tree, p.A, n_root, prior[0], noise != nullptr, in.noise, p.noise_frac, j);
+        else
+            write_root_children<kRow, 1>(tree, p.A, n_root, prior, noise ? noise + static_cast<size_t>(e) * p.A : nullptr,
+                                         p.noise_frac, j);
         if constexpr (SPAN == 2) {  // the prior moves aside; the block holds table[0][0] * prior (see LdsTreeV)
             if (j == 0) *reinterpret_cast<uint4*>(region + lay.off_desc) = uint4{0u, 0u, 0u, 0u};   // (the root, at position 1 of its own table)
             if (j < p.A) {
@@ -217,12 +298,11 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
     MinMax mm{INFINITY, -INFINITY};  // replicated in every lane of the row
     double root_value_sum = 0.0;     // lane 0
     const double root_reward = 0.0;  // log(one_hot(centre)) decodes to exactly 0
-    int32_t mt_pos = (j == 0) ? p.mt_pos[e] : 0;
+    if (!row_rng) mt_pos = (j == 0) ? p.mt_pos[e] : 0;
     uint32_t words = 0;
     int max_depth = 0;
     int64_t depth_sum = 0;
     unsigned long long exotic = lay.exact_division ? 1ull : 0ull;   // (per wavefront) a backed-up value left normalized_value's plain range
-    uint32_t* mt_key = p.mt_key + static_cast<size_t>(e) * kMtN;
     MZ_STAMP(1);
 
     const ResidentWeights resident = load_resident_weights(units, bias, j);
@@ -234,11 +314,11 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
         Descent d;
         float state;
         if constexpr (SPAN == 2)
-            d = descend_window(tree, region + lay.off_desc, root_entry, sim, n_root, mm, exotic, mt_key, mt_pos, words, j, group_base,
-                               p.error_flag);
+            d = descend_window(tree, region + lay.off_desc, root_entry, sim, n_root, mm, exotic, mt_key, mt_pos, words, row_rng, j,
+                               group_base, p.error_flag);
         else
-            d = descend_row<SPAN, PBC2>(tree, pbc, pbc2, p.S, p.A, sim, n_root, mm, exotic, mt_key, mt_pos, words, j,
-                                        group_base, p.error_flag MZ_DSTAMP_ARGS);
+            d = descend_row<SPAN, PBC2>(tree, pbc, pbc2, p.S, p.A, sim, n_root, mm, exotic, mt_key, mt_pos, words, row_rng,
+                                        j, group_base, p.error_flag MZ_DSTAMP_ARGS);
         state = hidden_lds[d.parent * enc + (j < enc ? j : 0)];
         // the backup's operands (leaf-side round) and the path entries the new node is linked under: asked for here and
         // between the layers of the network, needed after it
@@ -276,6 +356,16 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
     }
 
     // ---- publish: per-tree statistics, the root's child block, and on request the whole tree -----------
+    uint32_t sample_words = 0;
+    int slot = 0;
+    if (ctl.temperature && row_rng) {
+        // SelfPlay.select_action on the tree's own stream (kernel_common.h), by every lane of the row alike: its words
+        // are drawn row-wide, a block that ends here is regenerated by the row
+        const ChildLinks* root_links = tree.links(0);
+        slot = device_select_action_from([&](int i) { return root_links[i].visits; }, n_root,
+                                         prefetch ? narrow_move_temperature(ctl, in) : move_temperature(ctl, e),
+                                         [&]() { return mt_next_row(mt_key, mt_pos, j); }, &sample_words);
+    }
     if (j == 0) {
         p.root_reward[e] = root_reward;
         p.root_predicted[e] = predicted;
@@ -283,11 +373,12 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
         p.min_max[e] = mm;
         p.max_depth[e] = max_depth;
         p.depth_sum[e] = depth_sum;
-        uint32_t sample_words = 0;
-        if (ctl.temperature) {  // SelfPlay.select_action on the tree's own stream (kernel_common.h)
-            const ChildLinks* root_links = tree.links(0);
-            const int slot = device_select_action([&](int i) { return root_links[i].visits; }, n_root, move_temperature(ctl, e),
-                                                  mt_key, &mt_pos, &sample_words);
+        if (ctl.temperature) {
+            if (!row_rng) {
+                const ChildLinks* root_links = tree.links(0);
+                slot = device_select_action([&](int i) { return root_links[i].visits; }, n_root, move_temperature(ctl, e),
+                                            mt_key, &mt_pos, &sample_words);
+            }
             if (ctl.actions) ctl.actions[e] = slot >= 0 ? root_action_lds[slot] : slot;
             if (ctl.game_moves) ctl.game_moves[e] += 1;        // this env's game is one move longer
         }

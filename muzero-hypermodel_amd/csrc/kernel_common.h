@@ -125,9 +125,10 @@ __device__ __forceinline__ bool move_stalled(const TreeParams& p, const MoveCtl&
 // sum, one legacy double, right-bisect: RandomState.choice(p=...)).  exact_inverse_temperature: np_legacy_rng.h.
 // Returns the chosen child slot, or -2 for any other temperature: the host samples it (mzmcts_sample_actions), or, in a
 // move batch, select_action_general_kernel right behind the search (select_action.h, mzmcts_rng.hip).
-template <typename VisitOf>
-__device__ __forceinline__ int device_select_action(VisitOf visit_of, int n, double temperature, uint32_t* key,
-                                                    int32_t* pos, uint32_t* words) {
+// `next_word()` yields the stream's next tempered word (mt_next on one lane; the narrow kernel's row-wide form).
+template <typename VisitOf, typename NextWord>
+__device__ __forceinline__ int device_select_action_from(VisitOf visit_of, int n, double temperature, NextWord next_word,
+                                                         uint32_t* words) {
     if (temperature == 0.0) {
         int best = 0, best_v = visit_of(0);
         for (int i = 1; i < n; ++i) {
@@ -139,7 +140,17 @@ __device__ __forceinline__ int device_select_action(VisitOf visit_of, int n, dou
         }
         return best;
     }
-    if (isinf(temperature)) return static_cast<int>(mt_below(key, pos, static_cast<uint32_t>(n), words));
+    if (isinf(temperature)) {  // mt_below
+        const uint32_t top = static_cast<uint32_t>(n) - 1u;
+        if (top == 0u) return 0;
+        const uint32_t mask = mask_for(top);
+        uint32_t v;
+        do {
+            v = next_word() & mask;
+            ++*words;
+        } while (v > top);
+        return static_cast<int>(v);
+    }
     const int k = exact_inverse_temperature(temperature);
     if (k == 0) return -2;
     auto weight = [&](int i) {
@@ -152,8 +163,8 @@ __device__ __forceinline__ int device_select_action(VisitOf visit_of, int n, dou
     for (int i = 0; i < n; ++i) total = total + weight(i);
     double total_p = 0.0;
     for (int i = 0; i < n; ++i) total_p += weight(i) / total;
-    const int32_t a = static_cast<int32_t>(mt_next(key, pos) >> 5);
-    const int32_t b = static_cast<int32_t>(mt_next(key, pos) >> 6);
+    const int32_t a = static_cast<int32_t>(next_word() >> 5);
+    const int32_t b = static_cast<int32_t>(next_word() >> 6);
     *words += 2u;
     const double u = (a * 67108864.0 + b) / 9007199254740992.0;
     double run = 0.0;
@@ -163,6 +174,12 @@ __device__ __forceinline__ int device_select_action(VisitOf visit_of, int n, dou
         if (!(run / total_p <= u)) break;
     }
     return idx;
+}
+
+template <typename VisitOf>
+__device__ __forceinline__ int device_select_action(VisitOf visit_of, int n, double temperature, uint32_t* key,
+                                                    int32_t* pos, uint32_t* words) {
+    return device_select_action_from(visit_of, n, temperature, [&]() { return mt_next(key, pos); }, words);
 }
 
 // Launch with optional HIP events bound to the dispatch itself (hipExtLaunchKernel records the

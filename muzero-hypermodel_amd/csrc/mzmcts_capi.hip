@@ -177,6 +177,26 @@ int mzmcts_create(const mzmcts_config* c, mzmcts_engine** out) {
         p.pbc_sqrt = d_tab + K;
     }
 
+    // the narrow whole-move kernel's (N, n) exploration tables, once per engine (fused_narrow.hip stage_narrow_tables)
+    {
+        const char* serial = std::getenv("MZMCTS_NARROW_SERIAL_TWIST");
+        eng->narrow_row_rng = !(serial && std::atoi(serial) != 0);
+        const char* no_prefetch = std::getenv("MZMCTS_NARROW_NO_PREFETCH");
+        eng->narrow_prefetch = !(no_prefetch && std::atoi(no_prefetch) != 0);
+        const char* per_launch = std::getenv("MZMCTS_NARROW_TABLE_PER_LAUNCH");
+        if (!(per_launch && std::atoi(per_launch) != 0)) {
+            for (int mode = 1; mode <= 2; ++mode) {
+                const size_t doubles = mz::narrow_table_doubles(S, mode);
+                if (doubles == 0 || doubles * sizeof(double) > kLdsPerWorkgroup) continue;   // no layout can hold it
+                if ((rc = dev_alloc(eng, &eng->narrow_table[mode], doubles))) return cleanup_on(rc);
+                err = mz::build_narrow_table(p, mode, eng->narrow_table[mode], nullptr);
+                if (err != hipSuccess) return cleanup_on(hip_fail(eng, err, "build_narrow_table"));
+            }
+            err = hipDeviceSynchronize();
+            if (err != hipSuccess) return cleanup_on(hip_fail(eng, err, "build_narrow_table"));
+        }
+    }
+
     if ((rc = pinned_alloc(eng, &eng->h_slab0, static_cast<size_t>(E) * p.line_stride))) return cleanup_on(rc);
 
     eng->streams.resize(E);
@@ -844,6 +864,9 @@ int mzhost_launch_fused_move(mzmcts_engine* eng, const float* observations, cons
     if (mzhost_use_narrow(eng)) {
         mz::NarrowLayout nl{};
         mz::plan_narrow_layout(eng->p, eng->fc, kLdsPerWorkgroup, &nl);
+        nl.row_rng = eng->narrow_row_rng ? 1 : 0;
+        nl.prefetch = eng->narrow_prefetch ? 1 : 0;
+        nl.pbc2_table = eng->narrow_table[nl.pbc2_mode];
         ProfScope scope(eng, stream, kProfFused);
         MZ_HIP(eng, mz::launch_search_fused_narrow(eng->p, eng->fc, nl, eng->fc_weights, observations, ctl, eng->p.S,
                                                    eng->publish_tree ? 1 : 0, stream, scope.get()));

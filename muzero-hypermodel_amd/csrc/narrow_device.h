@@ -64,6 +64,10 @@ struct NarrowLayout {
     int32_t pbc2_mode;     // exploration table over (N, n): 0 none, 1 triangular, 2 rows of 64 (index = N << 6 | n; S <= 63)
     int32_t exact_division; // != 0: every quotient by the division itself (MZMCTS_NARROW_EXACT_DIV=1; the tests' A/B of the
                            // reciprocal-prepared forms, see Normalizer)
+    // set by the engine after planning (mzhost_launch_fused_move), not by plan_narrow_layout
+    int32_t row_rng;       // != 0: the tree's row draws from its stream together (mt_regenerate_row); 0: lane 0 alone
+    const double* pbc2_table;  // the (N, n) table of pbc2_mode, built once per engine; null: every launch computes it
+    int32_t prefetch;      // != 0: the per-tree inputs are asked for ahead of the staging (NarrowInputs)
 };
 
 template <int R>
@@ -106,6 +110,147 @@ __device__ __forceinline__ int row_or(int v) {
     v |= partner_bits<4>(v);
     v |= partner_bits<8>(v);
     return v;
+}
+
+// ---- the tree's MT19937 stream, drawn by the whole row -------------------------------------------------
+// mt_next (np_legacy_rng.h) on lane 0 regenerates the 624-word block with one dependent global round trip per few
+// words while the row's other lanes -- and, with one wavefront per SIMD, the whole SIMD -- wait.  Here every lane of
+// the row holds the stream position, so "the block is used up" is a row-uniform branch, and the row regenerates the
+// block together: per phase (np_legacy_rng.h: mt_twist_*) each lane takes the sources of its elements with all loads
+// in flight, waits for them, stores its words, and the stores are released to the row before the next phase reads.
+// Same words, same block, same position as the serial form.  Rows of one wavefront come here independently: nothing in
+// here crosses lanes.
+__device__ __forceinline__ void mt_regenerate_row(uint32_t* key, int j) {
+    constexpr int kPerLane = (kMtTwistPhaseMax + kRow - 1) / kRow;
+#pragma unroll 1
+    for (int phase = 0; phase < kMtTwistPhases; ++phase) {
+        const int begin = mt_twist_phase_begin(phase), end = mt_twist_phase_end(phase);
+        MtTwistSources src[kPerLane];
+#pragma unroll
+        for (int t = 0; t < kPerLane; ++t) {
+            const int k = begin + t * kRow + j;
+            src[t] = mt_twist_load(key, k < end ? k : begin);   // (unconditional: a guarded load is a branch and a wait each)
+        }
+        // every lane's sources have arrived before any lane stores: key[k + 1] is another lane's element
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int t = 0; t < kPerLane; ++t) {
+            const int k = begin + t * kRow + j;
+            if (k < end) key[k] = mt_twist_word(src[t]);
+        }
+        // the phase's words are visible to the row's other lanes before anyone reads them (the next phase, the draw)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
+// mt_next for the row: every lane passes the same position and receives the same word
+__device__ __forceinline__ uint32_t mt_next_row(uint32_t* key, int32_t& pos, int j) {
+    if (__builtin_expect(pos >= kMtN, 0)) {
+        mt_regenerate_row(key, j);
+        pos = 0;
+    }
+    const uint32_t y = key[pos];
+    ++pos;
+    return mt_temper(y);
+}
+
+// mt_below for the row
+__device__ __forceinline__ uint32_t mt_below_row(uint32_t* key, int32_t& pos, uint32_t n, uint32_t& words, int j) {
+    const uint32_t top = n - 1u;
+    if (top == 0u) return 0u;
+    const uint32_t mask = mask_for(top);
+    uint32_t v;
+    do {
+        v = mt_next_row(key, pos, j) & mask;
+        ++words;
+    } while (v > top);
+    return v;
+}
+
+// `skip` draws whose values nobody looks at (HostStream::skip): the position they leave behind, the block regenerated
+// when they cross its end
+__device__ __forceinline__ int32_t mt_skip_row(uint32_t* key, int32_t pos, uint32_t skip, int j) {
+    while (skip > 0u) {
+        if (pos >= kMtN) {
+            mt_regenerate_row(key, j);
+            pos = 0;
+        }
+        const uint32_t room = static_cast<uint32_t>(kMtN - pos);
+        const uint32_t step = skip < room ? skip : room;
+        pos += static_cast<int32_t>(step);
+        skip -= step;
+    }
+    return pos;
+}
+
+// ---- the per-tree inputs of a move, asked for at the kernel's first instructions ----------------------------
+// Every address is known there.  Read where they are needed, each is an exposed global round trip between the staging
+// barrier and the first simulation (load, wait, branch, nine times in a row) and again in the epilogue; asked for
+// before the staging they arrive underneath it.  The decisions taken from them are move_stalled's, move_temperature's
+// and reset_search_state's skip, unchanged.
+struct NarrowInputs {
+    int32_t n_root, mt_pos, move_limit, root_action, game_moves;
+    uint32_t stall, tie_words, expected_ties, skip;
+    float obs;
+    double noise, temperature;
+};
+
+__device__ __forceinline__ NarrowInputs narrow_load_inputs(const TreeParams& p, const FcNet& net, const MoveCtl& ctl,
+                                                           const float* __restrict__ observations, int e, int j) {
+    NarrowInputs in{};
+    in.n_root = p.root_children[e];
+    in.mt_pos = p.mt_pos[e];
+    in.tie_words = p.tie_words[e];
+    if (ctl.stall) in.stall = ctl.stall[e];
+    if (ctl.expected_ties) in.expected_ties = ctl.expected_ties[e];
+    if (ctl.move_limit) in.move_limit = ctl.move_limit[e];
+    if (ctl.rng_skip) in.skip = ctl.rng_skip[e];
+    if (ctl.temperature) in.temperature = ctl.temperature[e];
+    if (ctl.game_moves) in.game_moves = ctl.game_moves[e];
+    const int a = j < p.A ? j : 0;
+    in.root_action = p.root_action[static_cast<size_t>(e) * p.A + a];
+    if (ctl.noise) in.noise = ctl.noise[static_cast<size_t>(e) * p.A + a];
+    in.obs = observations[static_cast<size_t>(e) * net.obs + (j < net.obs ? j : 0)];
+    if (j >= net.obs) in.obs = 0.f;
+    return in;
+}
+
+// move_stalled (kernel_common.h) from the registers
+__device__ __forceinline__ bool narrow_move_stalled(const MoveCtl& ctl, const NarrowInputs& in, int e, int j) {
+    if (!ctl.stall) return false;
+    bool stalled = in.stall != 0;
+    if (!stalled && ctl.expected_ties && in.tie_words != in.expected_ties) stalled = true;
+    if (!stalled && ctl.move_limit && ctl.move_index >= in.move_limit) stalled = true;
+    if (stalled && j == 0) {
+        ctl.stall[e] = 1;
+        if (ctl.actions) ctl.actions[e] = -1;
+    }
+    return stalled;
+}
+
+// move_temperature (kernel_common.h) from the registers
+__device__ __forceinline__ double narrow_move_temperature(const MoveCtl& ctl, const NarrowInputs& in) {
+    if (ctl.game_moves && ctl.temperature_threshold > 0 && in.game_moves + 1 >= ctl.temperature_threshold) return 0.0;
+    return in.temperature;
+}
+
+// write_root_children<kRow, 1> (tree_device.h) with the child's noise entry in a register
+template <typename Acc>
+__device__ __forceinline__ void write_root_children_row(const Acc& acc, int A, int n_children, double prior, bool add_noise,
+                                                        double noise, double noise_frac, int j) {
+    if (j < A) {
+        double pr = (j < n_children) ? prior : 0.0;
+        if (j < n_children && add_noise) {
+            // prior * (1 - frac) + n * frac   (self_play.py:477)
+            const double keep = pr * (1 - noise_frac);
+            const double add = noise * noise_frac;
+            pr = keep + add;
+        }
+        acc.stats(0)[j] = ChildStats{0.0, pr};
+        acc.links(0)[j] = ChildLinks{0.f, 0, -1, 0};
+    }
 }
 
 // ---- weights in rotation order -----------------------------------------------------------------------
@@ -610,8 +755,8 @@ __device__ __forceinline__ double exploration_factor(const double* pbc, const do
 template <int SPAN, int MODE>
 __device__ __forceinline__ Descent descend_row(const LdsTreeV<SPAN>& acc, const double* pbc, const double* pbc2, int S, int A,
                                                int sim, int n_root_children, const MinMax& mm, unsigned long long exotic,
-                                               uint32_t* mt_key, int32_t& mt_pos, uint32_t& words, int j, int group_base,
-                                               int32_t* error_flag MZ_DSTAMP_PARAMS) {
+                                               uint32_t* mt_key, int32_t& mt_pos, uint32_t& words, bool row_rng, int j,
+                                               int group_base, int32_t* error_flag MZ_DSTAMP_PARAMS) {
     const Normalizer norm = make_normalizer(mm, exotic);
     int n_children = n_root_children;
     int k = 0, N = sim, depth = 0, slot = 0;
@@ -641,8 +786,12 @@ __device__ __forceinline__ Descent descend_row(const LdsTreeV<SPAN>& acc, const 
         if (n_ties != 1) {
             if (n_ties > 1) {  // numpy.random.choice over the tie list (self_play.py:372-378)
                 int r = 0;
-                if (j == 0) r = static_cast<int>(mt_below(mt_key, &mt_pos, static_cast<uint32_t>(n_ties), &words));
-                r = row_or(r);
+                if (row_rng) {
+                    r = static_cast<int>(mt_below_row(mt_key, mt_pos, static_cast<uint32_t>(n_ties), words, j));
+                } else {
+                    if (j == 0) r = static_cast<int>(mt_below(mt_key, &mt_pos, static_cast<uint32_t>(n_ties), &words));
+                    r = row_or(r);
+                }
                 for (int i = 0; i < r; ++i) mask &= mask - 1u;
             } else {  // NaN scores: the reference would raise; flag and take slot 0
                 if (j == 0) atomicOr(error_flag, 1);
@@ -699,8 +848,8 @@ __device__ __forceinline__ int window_root_entry(const uint8_t* desc, int j) {
 
 __device__ __forceinline__ Descent descend_window(const LdsTreeV<2>& acc, const uint8_t* desc, int root_entry, int sim,
                                                   int n_root_children, const MinMax& mm, unsigned long long exotic,
-                                                  uint32_t* mt_key, int32_t& mt_pos, uint32_t& words, int j, int group_base,
-                                                  int32_t* error_flag) {
+                                                  uint32_t* mt_key, int32_t& mt_pos, uint32_t& words, bool row_rng, int j,
+                                                  int group_base, int32_t* error_flag) {
     const Normalizer norm = make_normalizer(mm, exotic);
     const int h = j > 0 ? j : 1;   // heap position inside the window (lane 0 doubles lane 1)
     const int my_level = h >= 8 ? 3 : h >= 4 ? 2 : h >= 2 ? 1 : 0;
@@ -750,9 +899,13 @@ __device__ __forceinline__ Descent descend_window(const LdsTreeV<2>& acc, const 
         slot = (packed >> 24) & 1;
         if (packed & (1 << 25)) {          // (the same for every lane of the row)
             if (packed & (1 << 26)) {      // tie: numpy.random.choice over [0, 1]
-                int r = 0;
-                if (j == 0) r = static_cast<int>(mt_below(mt_key, &mt_pos, 2u, &words));
-                slot = row_or(r);
+                if (row_rng) {
+                    slot = static_cast<int>(mt_below_row(mt_key, mt_pos, 2u, words, j));
+                } else {
+                    int r = 0;
+                    if (j == 0) r = static_cast<int>(mt_below(mt_key, &mt_pos, 2u, &words));
+                    slot = row_or(r);
+                }
             } else {                       // NaN scores: the reference would raise; flag and take slot 0
                 if (j == 0) atomicOr(error_flag, 1);
                 slot = 0;

@@ -57,6 +57,33 @@ MZ_HD inline void mt_regenerate(uint32_t* key) {
     key[kMtN - 1] = mt_mix(key[kMtN - 1], key[0], key[kMtM - 1]);
 }
 
+// ---- the same regeneration, split for several lanes working on one block ------------------------------------
+// The recurrence new[k] = mix(old[k], key[k + 1], key[k + 397 mod 624]) falls into three phases whose elements do not
+// depend on one another:
+//   phase 0, k in [0, 227):   old words only (k + 397 stays inside the block);
+//   phase 1, k in [227, 454): the new [0, 227) and old words;
+//   phase 2, k in [454, 624): the new [227, 397) and old words; word 623 closes it with the new key[0] and key[396].
+// INSIDE a phase an element still reads its neighbour key[k + 1] as the OLD word, and that neighbour is rewritten by
+// the same phase (by the next one when k is the phase's last element): whoever runs a phase on several lanes takes
+// every lane's sources before any lane stores, and finishes the phase's stores before the next phase reads.
+// mt_regenerate and the three phases run in order leave the same block (tests/test_mt_twist_cpu.py).
+constexpr int kMtTwistPhases = 3;
+MZ_HD inline int mt_twist_phase_begin(int phase) { return phase * (kMtN - kMtM); }
+MZ_HD inline int mt_twist_phase_end(int phase) { return phase == kMtTwistPhases - 1 ? kMtN : (phase + 1) * (kMtN - kMtM); }
+constexpr int kMtTwistPhaseMax = kMtN - kMtM;   // elements of the longest phase
+
+struct MtTwistSources {
+    uint32_t hi, lo, far;
+};
+// what element k of its phase reads from the block as it stands when the phase begins
+MZ_HD inline MtTwistSources mt_twist_load(const uint32_t* key, int k) {
+    const int next = k + 1 < kMtN ? k + 1 : 0;
+    const int far = k + kMtM < kMtN ? k + kMtM : k + kMtM - kMtN;
+    return MtTwistSources{key[k], key[next], key[far]};
+}
+// ... and the word it leaves at key[k]
+MZ_HD inline uint32_t mt_twist_word(const MtTwistSources& s) { return mt_mix(s.hi, s.lo, s.far); }
+
 MZ_HD inline uint32_t mt_temper(uint32_t y) {
     y ^= (y >> 11);
     y ^= (y << 7) & 0x9d2c5680u;
