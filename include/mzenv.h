@@ -16,6 +16,22 @@
  *                    when the board is full.  Scripted opponent: "random" only -- the reference defines no expert
  *                    agent for Gomoku and mzenv_set_opponent refuses MZENV_OPPONENT_EXPERT there.  A wavefront per
  *                    env, two cells per lane (csrc/env_kernels.hip); games 0-2 run one thread per env.
+ *   MZENV_TWENTYONE  games/twentyone.py:227-299 (rules), :144-155 (reward x10).  One player, actions 0 = hit, 1 = stand,
+ *                    both legal in every state.  A card is RandomState(seed).randint(1, 13) on the env's OWN stream
+ *                    (10, 11 and 12 count 10): masked rejection, one 32-bit word per attempt, so a ply consumes a variable
+ *                    number of words -- a hit one card, a stand (or a hit to exactly 21) as many as bring the dealer
+ *                    above 16, a bust none beyond its own card.  `Game(seed)` deals two cards in its constructor, which
+ *                    mzenv_create therefore draws and discards; every reset deals the player's card, then the dealer's.
+ *                    Reward +10 / 0 / -10 on the ply that ends the game.  Observation (3,3,3): a plane of the player's
+ *                    hand, a plane of the dealer's, a plane of zeros.  The game's own length is at most 20 plies.  A hit
+ *                    that only the move limit ends is no stand: the dealer does not play and the reward is 0.
+ *   MZENV_SIMPLEGRID games/simple_grid.py:190-227 (rules), :132-143 (reward x10).  One player on a 3 x 3 grid from (0, 0);
+ *                    0 = down, 1 = right, both legal in every state as far as Game.legal_actions() says; a move off the
+ *                    grid moves nothing and still counts as a ply.  Reward 10 and done exactly on reaching (2, 2).
+ *                    Observation (1,1,9): one-hot of 3 * row + column.  The game has no length of its own: play that
+ *                    dawdles ends at the move limit (mzenv_set_max_moves).
+ *                    Neither game has an opponent or a board: mzenv_set_opponent (other than SELF) and mzenv_set_boards
+ *                    are errors.  One thread per env (csrc/solo_rules.h, shared with a CPU check).
  *   MZENV_CARTPOLE   games/cartpole.py wraps gym's CartPole-v1; gym is not vendored by the reference, so
  *                    this restates the published classic-control equations (Euler, tau = 0.02) exactly as
  *                    muzero-hypermodel_amd/games/cartpole.py does on the host -- parity UNPINNED against gym
@@ -36,6 +52,9 @@ extern "C" {
 #define MZENV_TICTACTOE 1
 #define MZENV_CONNECT4 2
 #define MZENV_GOMOKU 3
+/* 4 is no game and stays refused by mzenv_create ("bad argument"): an existing check pins that, so the ids go on at 5 */
+#define MZENV_TWENTYONE 5
+#define MZENV_SIMPLEGRID 6
 
 typedef struct mzenv mzenv;
 

@@ -3,6 +3,7 @@
 // One thread per env: a move is a handful of byte operations per game, far below any roofline that
 // matters; what these kernels buy is that E games advance without E host-side Python calls per move.
 // Gomoku's 121 cells do not fit that shape: its kernels (further down) give an env a wavefront and a lane two cells.
+// TwentyOne and SimpleGrid (solo_rules.h, shared with a CPU check) take the same shape; TwentyOne's plies draw cards from the env's stream.
 // Rules restate the reference's in-repo envs (games/tictactoe.py:242-305, games/connect4.py:219-304)
 // with the Game wrappers' reward scaling; CartPole restates the classic-control equations (unpinned).  The board rules
 // and the scripted opponents of evaluation games live in board_rules.h (also compiled for the host by a CPU check).
@@ -11,9 +12,13 @@
 #include "board_rules.h"
 #include "env_layout.h"
 #include "np_legacy_rng.h"
+#include "solo_rules.h"
 
 namespace mz {
 
+// games 1..3 keep a board and a player to move (and can face a scripted opponent); 0, 5 and 6 are one-player games
+// with a state of their own (4 is no game: include/mzenv.h)
+__device__ __forceinline__ bool board_game(int game) { return game >= 1 && game <= 3; }
 
 __device__ __forceinline__ double mt_uniform(uint32_t* key, int32_t* pos) {
     const int32_t a = static_cast<int32_t>(mt_next(key, pos) >> 5);
@@ -28,6 +33,12 @@ __device__ __forceinline__ void env_reset_one(const EnvParams& p, int e) {
         int32_t pos = p.mt_pos[e];
         for (int i = 0; i < 4; ++i) p.state[4 * e + i] = -0.05 + (0.05 - -0.05) * mt_uniform(key, &pos);
         p.mt_pos[e] = pos;
+    } else if (solo_game(p.game)) {
+        // TwentyOne.reset() deals two fresh cards from the env's stream; GridEnv.reset() goes back to (0, 0)
+        int32_t pos = p.game == kGameTwentyOne ? p.mt_pos[e] : 0;
+        uint32_t words = 0;
+        solo_reset(p.game, p.solo + kSoloState * e, p.mt_key + static_cast<size_t>(e) * kMtN, &pos, &words);
+        if (words) p.mt_pos[e] = pos;
     } else {
         int8_t* b = p.board + static_cast<size_t>(e) * p.cells;
         for (int i = 0; i < p.cells; ++i) b[i] = 0;
@@ -50,7 +61,7 @@ __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, f
                                              uint8_t* __restrict__ done_out, int32_t* __restrict__ played_out = nullptr,
                                              uint32_t* __restrict__ words_out = nullptr) {
     uint32_t words = 0;
-    if (p.game != 0 && opponent_to_move(p, e)) {
+    if (board_game(p.game) && opponent_to_move(p, e)) {
         int32_t pos = p.opp_pos[e];
         a = opponent_action(p.game, p.opp_kind, p.board + static_cast<size_t>(e) * p.cells, p.player[e],
                             p.opp_key + static_cast<size_t>(e) * kMtN, &pos, &words);
@@ -86,6 +97,15 @@ __device__ __forceinline__ bool env_step_one(const EnvParams& p, int e, int a, f
         const double theta_limit = 12 * 2 * 3.141592653589793 / 360;
         done = fabs(s[0]) > 2.4 || fabs(s[2]) > theta_limit || steps >= 500;
         reward = 1.0f;
+    } else if (solo_game(p.game)) {
+        // (a ply draws zero or more cards from the env's stream: the position is stored only when words were consumed)
+        int32_t pos = p.game == kGameTwentyOne ? p.mt_pos[e] : 0;
+        uint32_t drawn = 0;
+        int r = 0;
+        done = solo_ply(p.game, p.solo + kSoloState * e, a, steps, p.max_moves, p.mt_key + static_cast<size_t>(e) * kMtN,
+                        &pos, &drawn, &r);
+        if (drawn) p.mt_pos[e] = pos;
+        reward = static_cast<float>(r);
     } else {
         int8_t* b = p.board + static_cast<size_t>(e) * p.cells;
         const int pl = p.player[e];
@@ -127,6 +147,14 @@ __device__ __forceinline__ void env_observe_one(const EnvParams& p, int e, float
         to_play[e] = 0;
         return;
     }
+    if (solo_game(p.game)) {
+        solo_observe(p.game, p.solo + kSoloState * e, o);
+        l[0] = 0;  // Game.legal_actions() is [0, 1] in every state of both games
+        l[1] = 1;
+        num_legal[e] = 2;
+        to_play[e] = 0;
+        return;
+    }
     const int8_t* b = p.board + static_cast<size_t>(e) * p.cells;
     const int pl = p.player[e];
     for (int i = 0; i < p.cells; ++i) {
@@ -144,6 +172,16 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvParams p, const uint8
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.E || (mask && !mask[e])) return;
     env_reset_one(p, e);
+}
+
+// TwentyOne(seeds[e]): the constructor seeds env e's stream and deals two cards (mzenv_create; Game.reset() follows)
+__global__ __launch_bounds__(256) void env_construct_kernel(EnvParams p, const uint32_t* __restrict__ seeds) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.E) return;
+    int32_t pos = 0;
+    uint32_t words = 0;
+    t21_construct(p.solo + kSoloState * e, p.mt_key + static_cast<size_t>(e) * kMtN, &pos, seeds[e], &words);
+    p.mt_pos[e] = pos;
 }
 
 __global__ __launch_bounds__(256) void env_step_kernel(EnvParams p, const int32_t* __restrict__ actions,
@@ -440,6 +478,10 @@ hipError_t launch_gomoku(const EnvParams& p, const uint8_t* mask, const int32_t*
     return hipGetLastError();
 }
 
+hipError_t launch_env_construct(const EnvParams& p, const uint32_t* seeds, hipStream_t stream) {
+    env_construct_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, seeds);
+    return hipGetLastError();
+}
 hipError_t launch_env_reset(const EnvParams& p, const uint8_t* mask, hipStream_t stream) {
     if (p.game == 3)
         return launch_gomoku<kGmkReset>(p, mask, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,

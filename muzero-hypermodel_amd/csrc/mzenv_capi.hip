@@ -18,6 +18,7 @@ hipError_t launch_env_advance(const EnvParams& p, const int32_t* actions, float*
                               uint32_t* words, hipStream_t stream);
 hipError_t launch_env_observe(const EnvParams& p, float* obs, int32_t* legal, int32_t* num_legal, int32_t* to_play,
                               hipStream_t stream);
+hipError_t launch_env_construct(const EnvParams& p, const uint32_t* seeds, hipStream_t stream);
 hipError_t launch_seed_streams(uint32_t* keys, int32_t* pos, const uint32_t* seeds, int E, hipStream_t stream);
 }  // namespace mz
 
@@ -59,7 +60,7 @@ extern "C" {
 const char* mzenv_last_error(const mzenv* env) { return env ? env->error.c_str() : g_env_error.c_str(); }
 
 int mzenv_create(int32_t game, int32_t num_envs, int32_t device, const uint32_t* seeds, mzenv** out) {
-    if (!out || !seeds || num_envs <= 0 || game < 0 || game > MZENV_GOMOKU) return env_fail(nullptr, -1, "mzenv_create: bad argument");
+    if (!out || !seeds || num_envs <= 0 || game < 0 || game > MZENV_SIMPLEGRID || game == 4) return env_fail(nullptr, -1, "mzenv_create: bad argument");
     *out = nullptr;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
@@ -93,6 +94,27 @@ int mzenv_create(int32_t game, int32_t num_envs, int32_t device, const uint32_t*
         if (err == hipSuccess) err = mz::launch_seed_streams(p.mt_key, p.mt_pos, d_seeds, num_envs, nullptr);
         if (err == hipSuccess) err = hipDeviceSynchronize();
         if (err != hipSuccess) return bail(env_fail(env, -2, std::string("seeding: ") + hipGetErrorString(err)));
+    } else if (game == MZENV_TWENTYONE || game == MZENV_SIMPLEGRID) {
+        p.A = 2;
+        p.cells = 0;
+        env->players = 1;
+        if (game == MZENV_TWENTYONE)
+            env->shape[0] = 3, env->shape[1] = 3, env->shape[2] = 3;
+        else
+            env->shape[0] = 1, env->shape[1] = 1, env->shape[2] = 9;
+        p.obs_floats = env->shape[0] * env->shape[1] * env->shape[2];
+        if ((rc = env_alloc(env, &p.solo, static_cast<size_t>(num_envs) * 2))) return bail(rc);  // (zeroed: the grid's start)
+        if (game == MZENV_TWENTYONE) {
+            // TwentyOne(seeds[e]): seed the card stream and deal the constructor's two cards
+            if ((rc = env_alloc(env, &p.mt_key, static_cast<size_t>(num_envs) * mz::kMtN))) return bail(rc);
+            if ((rc = env_alloc(env, &p.mt_pos, num_envs))) return bail(rc);
+            uint32_t* d_seeds = nullptr;
+            if ((rc = env_alloc(env, &d_seeds, num_envs))) return bail(rc);
+            hipError_t err = hipMemcpy(d_seeds, seeds, sizeof(uint32_t) * num_envs, hipMemcpyHostToDevice);
+            if (err == hipSuccess) err = mz::launch_env_construct(p, d_seeds, nullptr);
+            if (err == hipSuccess) err = hipDeviceSynchronize();
+            if (err != hipSuccess) return bail(env_fail(env, -2, std::string("seeding: ") + hipGetErrorString(err)));
+        }
     } else {
         const int rows = game == MZENV_TICTACTOE ? 3 : (game == MZENV_CONNECT4 ? 6 : 11);
         const int cols = game == MZENV_TICTACTOE ? 3 : (game == MZENV_CONNECT4 ? 7 : 11);

@@ -10,8 +10,14 @@ import torch
 
 from .. import _native
 
-GAME_IDS = {"cartpole": 0, "tictactoe": 1, "connect4": 2, "gomoku": 3}
-MAX_EPISODE_STEPS = {"cartpole": 500, "tictactoe": 9, "connect4": 42, "gomoku": 121}   # the games' own lengths
+# (include/mzenv.h: 4 is no game and stays refused, the two numpy-only one-player games go on at 5)
+GAME_IDS = {"cartpole": 0, "tictactoe": 1, "connect4": 2, "gomoku": 3, "twentyone": 5, "simple_grid": 6}
+# the games' own lengths.  A TwentyOne player holds at least 1 and is done at 21: 20 plies at most.  SimpleGrid has no
+# length of its own (an illegal move is a no-op ply): a value above any config.max_moves, so that the actors always hand
+# the move limit to the env kernels
+MAX_EPISODE_STEPS = {"cartpole": 500, "tictactoe": 9, "connect4": 42, "gomoku": 121, "twentyone": 20,
+                     "simple_grid": 2 ** 31 - 1}
+ONE_PLAYER_GAMES = ("cartpole", "twentyone", "simple_grid")   # every action legal in every state, nobody to play against
 OPPONENT_KINDS = {"self": 0, "expert": 1, "random": 2}      # include/mzenv.h MZENV_OPPONENT_*
 
 
@@ -36,7 +42,7 @@ class DeviceEnvs:
         shape = (ctypes.c_int32 * 3)()
         self._lib.mzenv_shape(self._h, ctypes.byref(a), ctypes.byref(p), shape)
         self.A, self.players, self.observation_shape = a.value, p.value, tuple(shape)
-        self.constant_legal_actions = game == "cartpole"     # every action legal in every state
+        self.constant_legal_actions = game in ONE_PLAYER_GAMES     # every action legal in every state
         self.max_episode_steps = MAX_EPISODE_STEPS[game]
         with torch.cuda.device(self.device):
             self.obs = torch.zeros((self.E, *self.observation_shape), dtype=torch.float32, device=self.device)
@@ -80,6 +86,8 @@ class DeviceEnvs:
         action actually played) and `words` (stream words consumed: hand their sums to engine.rng_consumed)."""
         if kind not in OPPONENT_KINDS:
             raise NotImplementedError('device envs play opponent "self", "expert" or "random" ("human": use SelfPlay)')
+        if kind != "self" and self.game in ("twentyone", "simple_grid"):
+            raise NotImplementedError(f"{self.game} is a one-player game: it has no opponent")
         if kind == "expert" and self.game == "gomoku":
             # (AbstractGame.expert_agent raises the same for a host Game: the reference's games/gomoku.py defines none)
             raise NotImplementedError('gomoku has no expert agent; its scripted opponent is "random"')
@@ -95,6 +103,8 @@ class DeviceEnvs:
     def set_boards(self, boards, players):
         """Put the envs of a board game into given positions: boards int8 [E, cells] (0 / +1 / -1; connect four row 0
         = bottom; gomoku cell = 11 * row + column), players int8 [E] (+1 / -1 to move).  An env's ply count (game_moves) becomes its number of stones."""
+        if self.game in ("twentyone", "simple_grid"):
+            raise NotImplementedError(f"{self.game} has no board to set")
         boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(self.E, -1)
         players = np.ascontiguousarray(players, dtype=np.int8).reshape(self.E)
         self._check(self._lib.mzenv_set_boards(self._h, boards.ctypes.data, players.ctypes.data))

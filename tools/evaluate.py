@@ -37,7 +37,7 @@ def run(args, config, checkpoint, opponent, num_tests):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--game", default="tictactoe", choices=["tictactoe", "connect4", "gomoku", "cartpole"])
+    ap.add_argument("--game", default="tictactoe", choices=["tictactoe", "connect4", "gomoku", "cartpole", "twentyone", "simple_grid"])
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--tests", type=int, default=20000, help="games to average (the first N started)")
     ap.add_argument("--opponent", default=None, choices=["self", "expert", "random"], help="default: the config's")

@@ -64,7 +64,8 @@ def search_only(args, config, weights):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--game", default="cartpole")
+    ap.add_argument("--game", default="cartpole",
+                    choices=["cartpole", "tictactoe", "connect4", "gomoku", "twentyone", "simple_grid"])
     ap.add_argument("--envs", type=int, default=None, help="default 4096; gomoku 256 (a tree is ~26 MB at its config)")
     ap.add_argument("--moves", type=int, default=60)
     ap.add_argument("--kinds", default="host,device")
