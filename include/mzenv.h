@@ -36,6 +36,9 @@
  *                    this restates the published classic-control equations (Euler, tau = 0.02) exactly as
  *                    muzero-hypermodel_amd/games/cartpole.py does on the host -- parity UNPINNED against gym
  *
+ * The last section is the frame stack (mzenv_stack_*): an object of its own that keeps every env's n previous frames on the
+ * GPU and turns these kernels' plain observations into the stacked search input of config.stacked_observations = n.
+ *
  * Conventions as in mzmcts.h: raw device / host pointers, hipStream_t as void*, 0 = ok, < 0 = error,
  * mzenv_last_error() for the text.  All launch functions are asynchronous and allocation-free.
  */
@@ -146,6 +149,43 @@ int mzenv_set_boards(mzenv *env, const int8_t *boards, const int8_t *players);
  * mzenv_game_moves: copies the counters to out_dev (dev i32[E]) on `stream`; asynchronous and allocation-free. */
 int mzenv_set_max_moves(mzenv *env, int32_t max_moves);
 int mzenv_game_moves(mzenv *env, int32_t *out_dev, void *stream);
+
+/* ---- stacked observations: config.stacked_observations = n (reference self_play.py:514-548) -------------------------
+ * The search of a position reads GameHistory.get_stacked_observations(-1, n): the current frame (C planes), then the n
+ * previous frames newest first, each as its C planes followed by one constant plane holding float(action played from
+ * it); positions before the game's start are zeros: (C + n (C + 1)) H W floats per env.  A frame stack keeps, per env,
+ * a ring of the n previous frames (stored with the action plane filled, so a frame of the output is one contiguous
+ * copy), a head and a count saturating at n, and turns the environment kernels' plain observations into that search
+ * input on the device.  It is an object of its own: the env handle, its kernels and their outputs are what they were,
+ * and the plain observations stay what is filed and stored (the replay store stacks on its own when it samples).
+ * The rule lives once in csrc/obs_stack.h (kernel and CPU check compile it); csrc/obs_stack.hip says how one launch
+ * pushes and emits without reading anything it writes.
+ *
+ * mzenv_stack_create   blocking; the only place that allocates.  n <= 0, a non-positive shape or env count, a null
+ *                      `out` and a stacked float count beyond int32 are refused (-1) before any device work; without a
+ *                      device a good call returns -2.
+ * mzenv_stack_floats   (C + n (C + 1)) H W
+ * mzenv_stack_reset    envs whose mask byte is non-zero (mask dev u8[E], NULL = all) forget their frames; obs dev
+ *                      f32[E,C,H,W] is every env's current frame; stacked_out dev f32[E, floats] becomes, for EVERY env,
+ *                      the current frame followed by the frames it holds, then zeros.
+ * mzenv_stack_push     one self-play move of every env, one launch, asynchronous and allocation-free: obs_before dev
+ *                      f32[E,C,H,W] the frames the move was played from, actions dev i32[E], done dev u8[E] (the game is
+ *                      over: by its rules or by the move limit), obs_next dev f32[E,C,H,W] the observation the next search
+ *                      sees (mzenv_advance's obs_next_out).  Per env: actions[e] < 0 = the env was left untouched (a
+ *                      stalled env of a pre-drawn batch, a full board on the opponent's turn): nothing is pushed;
+ *                      otherwise done[e] != 0: the env forgets its frames; otherwise (obs_before[e], actions[e]) is
+ *                      pushed.  In every case stacked_out[e] = [obs_next[e], frames newest to oldest, zeros].
+ *                      In opponent mode pass played_out as `actions`: the opponent's plies are plies of the game.
+ * Null pointers are refused (-1) before the handle is looked at. */
+typedef struct mzenv_stack mzenv_stack;
+int mzenv_stack_create(int32_t num_envs, int32_t channels, int32_t height, int32_t width, int32_t n, int32_t device,
+                       mzenv_stack **out);
+void mzenv_stack_destroy(mzenv_stack *stack);
+const char *mzenv_stack_last_error(const mzenv_stack *stack);
+int64_t mzenv_stack_floats(const mzenv_stack *stack);
+int mzenv_stack_reset(mzenv_stack *stack, const uint8_t *mask, const float *obs, float *stacked_out, void *stream);
+int mzenv_stack_push(mzenv_stack *stack, const float *obs_before, const int32_t *actions, const uint8_t *done,
+                     const float *obs_next, float *stacked_out, void *stream);
 
 #ifdef __cplusplus
 }

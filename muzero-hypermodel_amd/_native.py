@@ -225,6 +225,13 @@ PROTOTYPES = {
     "mzenv_set_boards": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzenv_set_max_moves": (ctypes.c_int, [c_void, ctypes.c_int32]),
     "mzenv_game_moves": (ctypes.c_int, [c_void, c_void, c_void]),
+    # the device frame stack (config.stacked_observations)
+    "mzenv_stack_create": (ctypes.c_int, [ctypes.c_int32] * 6 + [ctypes.POINTER(c_void)]),
+    "mzenv_stack_destroy": (None, [c_void]),
+    "mzenv_stack_last_error": (ctypes.c_char_p, [c_void]),
+    "mzenv_stack_floats": (ctypes.c_int64, [c_void]),
+    "mzenv_stack_reset": (ctypes.c_int, [c_void] * 5),
+    "mzenv_stack_push": (ctypes.c_int, [c_void] * 7),
     "mzmcts_rng_create": (c_void, [ctypes.c_uint32]),
     "mzmcts_rng_destroy": (None, [c_void]),
     "mzmcts_rng_reseed": (None, [c_void, ctypes.c_uint32]),

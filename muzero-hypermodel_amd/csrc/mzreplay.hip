@@ -1547,7 +1547,8 @@ int mzreplay_filer_create(mzreplay* s, int32_t num_envs, mzreplay_filer** out) {
     *out = nullptr;
     if (num_envs <= 0) return fail(s, "mzreplay_filer_create: num_envs must be positive");
     if (s->filer) return fail(s, "mzreplay_filer_create: the store already has a filer (one actor files into one store)");
-    if (s->p.stacked != 0) return fail(s, "mzreplay_filer_create: device envs do not stack observations");
+    // (a store with stacked_observations > 0 is filed like any other: the rows hold the plain observations the env
+    // kernels produced, and stacked_element stacks them when a batch is built; the actor's frame stack feeds the searches)
     RP_HIP(s, hipSetDevice(s->cfg.device));
     mzreplay_filer* fl = new mzreplay_filer();
     fl->store = s;

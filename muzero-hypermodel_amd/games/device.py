@@ -180,3 +180,81 @@ class DeviceEnvs:
         self._check(self._lib.mzenv_observe(self._h, obs.data_ptr(), self.legal.data_ptr(),
                                             self.num_legal.data_ptr(), self.to_play.data_ptr(), self._stream()))
         return obs, self.legal, self.num_legal, self.to_play
+
+
+class DeviceFrameStack:
+    """The n previous frames of every env on the GPU (include/mzenv.h mzenv_stack_*): turns the environment kernels'
+    plain observations into the search input of config.stacked_observations = n --
+    GameHistory.get_stacked_observations(-1, n) of every env, [E, C + n (C + 1), H, W] -- with no host round trip.
+    reset / push write into the caller's `out` tensor and return it; both are one launch on the current stream."""
+
+    def __init__(self, num_envs, observation_shape, n, device=None):
+        self._lib = _native.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceFrameStack needs a HIP device; GameHistory.get_stacked_observations stacks on the host")
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.E, self.n = int(num_envs), int(n)
+        self.observation_shape = tuple(int(v) for v in observation_shape)
+        c, h, w = self.observation_shape
+        handle = ctypes.c_void_p()
+        if self._lib.mzenv_stack_create(self.E, c, h, w, self.n, self.device.index, ctypes.byref(handle)) != 0:
+            raise RuntimeError(self._lib.mzenv_stack_last_error(None).decode())
+        self._h = handle
+        self.stacked_shape = (c + self.n * (c + 1), h, w)
+        assert self._lib.mzenv_stack_floats(self._h) == self.stacked_shape[0] * h * w
+
+    def new_output(self, *leading):
+        """A zeroed device tensor [*leading, E, C + n (C + 1), H, W] for reset / push to write."""
+        return torch.zeros(tuple(leading) + (self.E,) + self.stacked_shape, dtype=torch.float32, device=self.device)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._lib.mzenv_stack_last_error(self._h).decode())
+
+    def _checked(self, t, dtype, shape, what):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"DeviceFrameStack: {what} must be a contiguous {dtype} device tensor of shape {shape}")
+        return t
+
+    def reset(self, obs, out, mask=None):
+        """Envs whose mask entry is non-zero (uint8 [E] device tensor; None = all) forget their frames; `out` becomes
+        every env's stacked observation with `obs` [E, C, H, W] as the current frame."""
+        plain, stacked = (self.E,) + self.observation_shape, (self.E,) + self.stacked_shape
+        self._checked(obs, torch.float32, plain, "obs")
+        self._checked(out, torch.float32, stacked, "out")
+        if mask is not None:
+            self._checked(mask, torch.uint8, (self.E,), "mask")
+        self._keep = (mask, obs, out)
+        self._check(self._lib.mzenv_stack_reset(self._h, None if mask is None else mask.data_ptr(), obs.data_ptr(),
+                                                out.data_ptr(), self._stream()))
+        return out
+
+    def push(self, obs_before, actions, done, obs_next, out):
+        """One self-play move of every env: actions[e] < 0 = untouched (nothing pushed), else done[e] = the game is over
+        (frames forgotten), else (obs_before[e], actions[e]) is pushed; `out` becomes [obs_next, frames newest first]."""
+        plain, stacked = (self.E,) + self.observation_shape, (self.E,) + self.stacked_shape
+        self._checked(obs_before, torch.float32, plain, "obs_before")
+        self._checked(actions, torch.int32, (self.E,), "actions")
+        self._checked(done, torch.uint8, (self.E,), "done")
+        self._checked(obs_next, torch.float32, plain, "obs_next")
+        self._checked(out, torch.float32, stacked, "out")
+        self._keep = (obs_before, actions, done, obs_next, out)
+        self._check(self._lib.mzenv_stack_push(self._h, obs_before.data_ptr(), actions.data_ptr(), done.data_ptr(),
+                                               obs_next.data_ptr(), out.data_ptr(), self._stream()))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mzenv_stack_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1146,8 +1146,7 @@ class DeviceSelfPlay(ManyEnvLoop):
     Python lists, which costs more than the search itself at thousands of envs)."""
 
     def __init__(self, initial_checkpoint, game_name, config, seed, num_envs, device=None, use_graph=True):
-        from .games.device import DeviceEnvs
-        assert config.stacked_observations == 0, "device envs do not stack past observations yet"
+        from .games.device import DeviceEnvs, DeviceFrameStack
         self._build_search(initial_checkpoint, config, seed, num_envs, device, use_graph)
         E = self.E
         self.envs = DeviceEnvs(game_name, E, seeds=[seed + e for e in range(E)], device=self.device)
@@ -1163,6 +1162,33 @@ class DeviceSelfPlay(ManyEnvLoop):
         self._batch_ready = None                # (n_moves, temperature) of the batch drawn and uploaded ahead (play_moves)
         self._dev_batch = None                  # DeviceBatch being queued
         self._ring = None                       # env outputs of a batch on the device, sized by the first batch (_move_ring)
+        # config.stacked_observations = n > 0: the n previous frames of every env live in a device frame stack
+        # (include/mzenv.h mzenv_stack_*).  The plain observations stay what is filed and stored everywhere; only what
+        # the searches read changes: `_stacked`, which every move's push rewrites on the actor's stream.  n = 0: no
+        # stack, no launch, today's code.
+        self._stack = self._stacked = self._stack_ring = None
+        if int(config.stacked_observations) > 0:
+            self._stack = DeviceFrameStack(E, self.envs.observation_shape, int(config.stacked_observations), self.device)
+            self._step_stacked = self._stack.new_output()    # step()'s search input (a batch's lie in _stack_ring)
+            self._stacked = self._stack.reset(self._cur["obs_dev"], self._step_stacked)
+            # step(): the frame a move is played from (the observe after the move rewrites the envs' own buffer),
+            # and the done mask of a move that ends no game
+            self._plain_before = torch.zeros_like(self._cur["obs_dev"])
+            self._no_done = torch.zeros(E, dtype=torch.uint8, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()    # (a pipelined actor moves to a stream of its own)
+
+    def stacked_observation(self):
+        """What the next search reads: the device tensor [E, C + n (C + 1), H, W] of every env's
+        GameHistory.get_stacked_observations(-1, n) (n = config.stacked_observations); the plain observation [E, C, H, W]
+        when n = 0.  Valid until the next move is queued."""
+        return self._cur["obs_dev"] if self._stack is None else self._stacked
+
+    def _frame_before(self, obs_in, obs_next_slot):
+        """The frame a batch's move is played from, where the push can still read it after the move's env kernel has
+        run: a batch that follows a one-move batch starts from the ring slot its own first move rewrites."""
+        if self._stack is not None and obs_in.data_ptr() == obs_next_slot.data_ptr():
+            return self._plain_before.copy_(obs_in)
+        return obs_in
 
     @property
     def _len(self):
@@ -1278,11 +1304,15 @@ class DeviceSelfPlay(ManyEnvLoop):
         self._drop_batch()
         self._set_env_mode(mode)
         cur = self._current()
+        search_input = cur["obs_dev"]
+        if self._stack is not None:
+            search_input = self._stacked
+            self._plain_before.copy_(cur["obs_dev"])         # the frame step_end pushes
         if self.engine._fc_model is not None:
-            self.engine.search_fused_begin(cur["obs_dev"].reshape(self.E, -1), cur["legal"], cur["to_play"], True,
+            self.engine.search_fused_begin(search_input.reshape(self.E, -1), cur["legal"], cur["to_play"], True,
                                            num_legal=cur["num_legal"])
         else:
-            self.engine.search_begin(self.model, cur["obs_dev"], cur["legal"], cur["to_play"], True,
+            self.engine.search_begin(self.model, search_input, cur["legal"], cur["to_play"], True,
                                      num_legal=cur["num_legal"])
 
     def step_end(self, temperature, temperature_threshold=None, on_game=None, on_games=None):
@@ -1301,14 +1331,24 @@ class DeviceSelfPlay(ManyEnvLoop):
             temps = numpy.full(self.E, float(temperature))
         actions, _ = self.engine.sample_actions(numpy.ascontiguousarray(temps, dtype=numpy.float64))
         stats = self.engine.stats
-        reward, done = self.envs.step(actions)
+        played = actions
+        if self._stack is not None:                          # (the push reads the actions on the device as well)
+            played = torch.from_numpy(numpy.ascontiguousarray(actions, dtype=numpy.int32)).to(self.device)
+        reward, done = self.envs.step(played)
         after = self._observe_host()
         reward, done = reward.cpu().numpy(), done.cpu().numpy().astype(bool)
         over = done | (self._len + 2 > self.config.max_moves)   # len(action_history) > max_moves ends the game
         nxt = after
+        over_dev = None
         if over.any():
-            self.envs.reset(torch.from_numpy(over.astype(numpy.uint8)).to(self.device))
+            over_dev = torch.from_numpy(over.astype(numpy.uint8)).to(self.device)
+            self.envs.reset(over_dev)
             nxt = self._observe_host()
+        if self._stack is not None:
+            # the games that are over -- by their rules or by play_game's move limit -- forget their frames; queued
+            # here, ahead of the next step_begin on this stream
+            self._stacked = self._stack.push(self._plain_before, played, self._no_done if over_dev is None else over_dev,
+                                             nxt["obs_dev"], self._step_stacked)
         # child visits by action and root values as store_search_statistics computes them (self_play.py:497-512)
         one = {"actions": actions.astype(numpy.int32)[None], "visits": stats["visits"][None],
                "root_value_sum": stats["root_value_sum"][None], "moves_done": numpy.ones(self.E, dtype=numpy.int32)}
@@ -1364,10 +1404,16 @@ class DeviceSelfPlay(ManyEnvLoop):
         ring = self._move_ring(n_moves)
         obs_in = cur["obs_dev"]
         for m in range(n_moves):
-            eng.moves_enqueue(obs_in.reshape(E, -1))
+            eng.moves_enqueue((obs_in if self._stack is None else self._stacked).reshape(E, -1))
+            obs_in = self._frame_before(obs_in, ring["obs_next"][m])
             # step, terminal observation, reset of the finished envs, next observation: one call, one launch
-            obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
-                                  ring["obs_next"][m])
+            obs_next = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
+                                    ring["obs_next"][m])
+            if self._stack is not None:
+                # (a stalled env's action reads -1: the env kernels left it alone and nothing is pushed)
+                self._stacked = self._stack.push(obs_in, eng.moves_actions(m), ring["done"][m], obs_next,
+                                                 self._stack_ring[m])
+            obs_in = obs_next
         # host rows: the previous batch's games, while this one runs
         self._hand_out(self._rows.games_before_collect(), on_game, on_games)
         eng.moves_predraw_next(n_moves, cur["legal"], cur["to_play"], temperature, True, num_legal=cur["num_legal"])
@@ -1418,13 +1464,21 @@ class DeviceSelfPlay(ManyEnvLoop):
         ring = b.ring
         if b.threshold and m > 0:
             eng.moves_finished(ring["done"][m - 1])          # games that ended with the move before restart their count
+        search_input = b.obs_in if self._stack is None else self._stacked
         if eng._fc_model is not None:
-            eng.moves_enqueue(b.obs_in.reshape(self.E, -1).contiguous())
+            eng.moves_enqueue(search_input.reshape(self.E, -1).contiguous())
         else:
-            eng.moves_enqueue_lockstep(self.model, b.obs_in)
-        b.obs_in = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
+            eng.moves_enqueue_lockstep(self.model, search_input)
+        b.obs_in = self._frame_before(b.obs_in, ring["obs_next"][m])
+        obs_next = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
                                 ring["obs_next"][m], played=ring["played"][m] if b.opponent else None,
                                 words=ring["words"][m] if b.opponent else None)
+        if self._stack is not None:
+            # an opponent's ply is a ply of the game: the action the env kernels played, not the search's (-1 there:
+            # a full board on the opponent's turn leaves the env alone)
+            self._stacked = self._stack.push(b.obs_in, ring["played"][m] if b.opponent else eng.moves_actions(m),
+                                             ring["done"][m], obs_next, self._stack_ring[m])
+        b.obs_in = obs_next
         self._rows.download_move(b, m)
 
     def _device_batch_end(self, on_game, on_games):
@@ -1496,9 +1550,16 @@ class DeviceSelfPlay(ManyEnvLoop):
                         words=torch.zeros((n_moves, self.E), dtype=torch.int32, device=dev))
             self._rows.ring_resized(ring)                    # (host rows: their host sets are sized with it)
             self._ring = ring
+            if self._stack is not None:
+                # every move's stacked search input, kept like its obs_next: the engine holds the tensors it was handed
+                # until the batch is collected (never downloaded, so not part of `ring`, which sizes the host sets; an
+                # earlier ring that `_stacked` still views stays alive through that reference)
+                self._stack_ring = self._stack.new_output(n_moves)
         return ring
 
     def close(self):
+        if self._stack is not None:
+            self._stack.close()
         self.envs.close()
         self.engine.close()
 
@@ -1542,6 +1603,12 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             stream.wait_stream(current)
             with torch.cuda.stream(stream):
                 actor.model.set_weights(state)
+
+    def stacked_observation(self):
+        """DeviceSelfPlay.stacked_observation of all groups, env-major (a copy, once every group's stream has run)."""
+        for stream in self.streams:
+            stream.synchronize()
+        return torch.cat([a.stacked_observation() for a in self.actors])
 
     def set_device_temperatures(self, enabled=True):
         """DeviceSelfPlay.set_device_temperatures for every group's engine."""

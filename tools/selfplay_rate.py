@@ -3,6 +3,7 @@
     python tools/selfplay_rate.py [--game cartpole] [--envs 4096] [--moves 60] [--max-moves N]
     python tools/selfplay_rate.py --game gomoku --kinds search,device-batch [--simulations S --channels C --blocks B]
     python tools/selfplay_rate.py --kinds device-batch --temperature 0.35 --device-temperatures
+    python tools/selfplay_rate.py --game tictactoe --fc 16 --stacked 2 --kinds host,device-batch
 
 Prints one JSON line per actor kind: moves/s, simulations/s, finished games, the engine's device bytes.  This is the
 loop the reference runs in self_play.py:34-113 (continuous_self_play), without the replay buffer hand-off.  Kind
@@ -85,7 +86,11 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0, help="softmax temperature of the action sampling")
     ap.add_argument("--device-temperatures", action="store_true", help="device actors: batches sample at any temperature on "
                     "the GPU (set_device_temperatures); without it the batch kinds take 0 and 1 / k, k = 1..4, only")
+    ap.add_argument("--stacked", type=int, default=0, help="config.stacked_observations: the searches read the current frame "
+                    "and the N previous ones (device actors: the frame stack on the GPU; random weights only)")
     args = ap.parse_args()
+    if args.stacked and (args.weights == "checkpoint" or "search" in args.kinds.split(",")):
+        ap.error("--stacked changes the network's input: random weights, and no search-only kind (it has no history to stack)")
     if args.envs is None:
         args.envs = 256 if args.game == "gomoku" else 4096
     mod = importlib.import_module(f"muzero-hypermodel_amd.games.{args.game}")
@@ -95,6 +100,7 @@ def main():
             setattr(config, name, value)
     if args.max_moves is not None:
         config.max_moves = args.max_moves
+    config.stacked_observations = args.stacked
     if args.fc:
         config.network, config.encoding_size = "fullyconnected", args.fc
         config.fc_representation_layers, config.fc_dynamics_layers = [], [args.fc]
@@ -161,6 +167,7 @@ def main():
                           "simulations_per_s": moves * config.num_simulations / dt, "ms_per_move_step": 1e3 * dt * args.envs / moves,
                           "games_finished": done[0], "weights": args.weights, "max_moves": config.max_moves,
                           "num_simulations": config.num_simulations, "engine_device_bytes": engine_bytes(actor),
+                          "stacked_observations": config.stacked_observations, "seconds": dt, "network": config.network,
                           "temperature": args.temperature, "device_temperatures": bool(args.device_temperatures and kind != "host"),
                           **({"moves_per_call": args.batch, "prefetch": not args.no_prefetch} if kind == "device-pipelined-batch" else {}),
                           **({"moves_per_call": args.batch} if kind == "device-batch" else {})}), flush=True)
