@@ -34,7 +34,11 @@
  *                    are errors.  One thread per env (csrc/solo_rules.h, shared with a CPU check).
  *   MZENV_CARTPOLE   games/cartpole.py wraps gym's CartPole-v1; gym is not vendored by the reference, so
  *                    this restates the published classic-control equations (Euler, tau = 0.02) exactly as
- *                    muzero-hypermodel_amd/games/cartpole.py does on the host -- parity UNPINNED against gym
+ *                    muzero-hypermodel_amd/games/cartpole.py does on the host.  Pinned to the published equations:
+ *                    given sin(theta) and cos(theta), a step is IEEE double + - * / in a fixed order and equals a numpy
+ *                    float64 restatement bit for bit; sin / cos are the device library's, within L ulps of the true values
+ *                    (tests/cartpole_reference.py: L and how it was measured).  Still unpinned against gym itself, which
+ *                    is absent here.  mzenv_get_state / mzenv_set_state read and write the fp64 state.
  *
  * The last section is the frame stack (mzenv_stack_*): an object of its own that keeps every env's n previous frames on the
  * GPU and turns these kernels' plain observations into the stacked search input of config.stacked_observations = n.
@@ -129,6 +133,19 @@ int mzenv_advance_opponent(mzenv *env, const int32_t *actions, float *reward_out
  * step does with a finished position).  The ply counter of each env (below) becomes the number of stones on its board:
  * a position handed in continues the game it came from. */
 int mzenv_set_boards(mzenv *env, const int8_t *boards, const int8_t *players);
+
+/* The fp64 state of every MZENV_CARTPOLE env, in the order x, x_dot, theta, theta_dot, and its ply counter.  Blocking,
+ * host arrays, modelled on mzenv_set_boards; every other game is refused with a message.
+ *   mzenv_get_state  state_out host f64[E][4]; steps_out host i32[E], may be NULL.
+ *   mzenv_set_state  state host f64[E][4], stored as given: non-finite values included (what a step answers on them is
+ *                    plain IEEE arithmetic: a NaN compares false at both limits, so such a state is not "fallen");
+ *                    steps host i32[E], NULL = leave the counters as they are; a negative count is refused.
+ * A handed-in step count is the game's ply counter (below): the state continues a game that has played that many plies.
+ * CartPole's own 500-step cap and mzenv_set_max_moves both read it: the next ply brings it to steps + 1 and ends the
+ * game when that reaches 500 or the move limit.  The env's stream is untouched: the next reset draws what it would have
+ * drawn anyway. */
+int mzenv_get_state(mzenv *env, double *state_out, int32_t *steps_out);
+int mzenv_set_state(mzenv *env, const double *state, const int32_t *steps);
 
 /* ---- move limit: games end at config.max_moves (reference self_play.py:129-131) ------------------------------------
  * play_game() leaves its loop once len(action_history) exceeds max_moves, whatever the game's own rules say.  Every env

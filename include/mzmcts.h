@@ -561,6 +561,10 @@ int64_t mzmcts_device_bytes(const mzmcts_engine *engine);
 int mzmcts_set_device_noise(mzmcts_engine *engine, int32_t enabled);
 int mzmcts_get_noise(mzmcts_engine *engine, double *noise_out);
 int mzmcts_device_libm(const double *x, const double *y, int64_t n, double *log_out, double *pow_out);
+/* The same kind of self-check for the two library calls of CartPole's step (csrc/env_kernels.hip): sin_out[i] = sin(x[i]),
+ * cos_out[i] = cos(x[i]) as that kernel computes them (the device library's fp64 sin and cos, same compiler flags), any
+ * double accepted.  They are the one inexact part of that step: tests/cartpole_reference.py bounds them. */
+int mzmcts_device_sincos(const double *x, int64_t n, double *sin_out, double *cos_out);
 int mzmcts_device_dirichlet(const uint32_t *seeds, int32_t n_streams, double alpha, int32_t k, int32_t draws,
                             double *out, uint32_t *words_out);
 

@@ -223,6 +223,8 @@ PROTOTYPES = {
     "mzenv_step_opponent": (ctypes.c_int, [c_void] * 7),
     "mzenv_advance_opponent": (ctypes.c_int, [c_void] * 12),
     "mzenv_set_boards": (ctypes.c_int, [c_void, c_void, c_void]),
+    "mzenv_get_state": (ctypes.c_int, [c_void, c_void, c_void]),
+    "mzenv_set_state": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzenv_set_max_moves": (ctypes.c_int, [c_void, ctypes.c_int32]),
     "mzenv_game_moves": (ctypes.c_int, [c_void, c_void, c_void]),
     # the device frame stack (config.stacked_observations)
@@ -245,6 +247,7 @@ PROTOTYPES = {
     "mzmcts_set_device_noise": (ctypes.c_int, [c_void, ctypes.c_int32]),
     "mzmcts_get_noise": (ctypes.c_int, [c_void, c_f64_p]),
     "mzmcts_device_libm": (ctypes.c_int, [c_f64_p, c_f64_p, ctypes.c_int64, c_f64_p, c_f64_p]),
+    "mzmcts_device_sincos": (ctypes.c_int, [c_f64_p, ctypes.c_int64, c_f64_p, c_f64_p]),
     "mzmcts_device_dirichlet": (ctypes.c_int, [c_u32_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
                                                c_f64_p, c_u32_p]),
     "mzmcts_set_device_temperatures": (ctypes.c_int, [c_void, ctypes.c_int32]),

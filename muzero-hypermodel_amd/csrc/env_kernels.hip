@@ -5,7 +5,7 @@
 // Gomoku's 121 cells do not fit that shape: its kernels (further down) give an env a wavefront and a lane two cells.
 // TwentyOne and SimpleGrid (solo_rules.h, shared with a CPU check) take the same shape; TwentyOne's plies draw cards from the env's stream.
 // Rules restate the reference's in-repo envs (games/tictactoe.py:242-305, games/connect4.py:219-304)
-// with the Game wrappers' reward scaling; CartPole restates the classic-control equations (unpinned).  The board rules
+// with the Game wrappers' reward scaling; CartPole restates the classic-control equations (pinned to them bit for bit but for sin / cos: include/mzenv.h).  The board rules
 // and the scripted opponents of evaluation games live in board_rules.h (also compiled for the host by a CPU check).
 #include <hip/hip_runtime.h>
 

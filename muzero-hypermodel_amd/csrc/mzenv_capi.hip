@@ -206,6 +206,31 @@ int mzenv_set_boards(mzenv* env, const int8_t* boards, const int8_t* players) {
     return 0;
 }
 
+int mzenv_get_state(mzenv* env, double* state_out, int32_t* steps_out) {
+    if (!env || !state_out) return env_fail(env, -1, "mzenv_get_state: null argument");
+    if (env->p.game != MZENV_CARTPOLE) return env_fail(env, -1, "mzenv_get_state: only cartpole keeps an fp64 state");
+    const size_t E = static_cast<size_t>(env->p.E);
+    MZENV_HIP(env, hipSetDevice(env->device));
+    MZENV_HIP(env, hipDeviceSynchronize());
+    MZENV_HIP(env, hipMemcpy(state_out, env->p.state, E * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (steps_out) MZENV_HIP(env, hipMemcpy(steps_out, env->p.steps, E * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mzenv_set_state(mzenv* env, const double* state, const int32_t* steps) {
+    if (!env || !state) return env_fail(env, -1, "mzenv_set_state: null argument");
+    if (env->p.game != MZENV_CARTPOLE) return env_fail(env, -1, "mzenv_set_state: only cartpole keeps an fp64 state");
+    const size_t E = static_cast<size_t>(env->p.E);
+    if (steps)
+        for (size_t e = 0; e < E; ++e)
+            if (steps[e] < 0) return env_fail(env, -1, "mzenv_set_state: a step count is a number of plies played (>= 0)");
+    MZENV_HIP(env, hipSetDevice(env->device));
+    MZENV_HIP(env, hipDeviceSynchronize());
+    MZENV_HIP(env, hipMemcpy(env->p.state, state, E * 4 * sizeof(double), hipMemcpyHostToDevice));
+    if (steps) MZENV_HIP(env, hipMemcpy(env->p.steps, steps, E * sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
 int mzenv_set_max_moves(mzenv* env, int32_t max_moves) {
     // (the argument is judged before the handle, as in mzenv_set_opponent)
     if (max_moves < 0) return env_fail(env, -1, "mzenv_set_max_moves: the limit is a number of plies (0 = none)");

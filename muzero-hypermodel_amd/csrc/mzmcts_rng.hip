@@ -17,6 +17,17 @@ __global__ void device_libm_kernel(const double* __restrict__ x, const double* _
     out_pow[i] = mz::libm::glibc_pow(x[i], y[i]);
 }
 
+// the two library calls of CartPole's step, made exactly as env_step_one (env_kernels.hip) makes them
+__global__ void device_sincos_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ out_sin,
+                                     double* __restrict__ out_cos) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double theta = x[i];
+    const double cos_t = cos(theta), sin_t = sin(theta);
+    out_sin[i] = sin_t;
+    out_cos[i] = cos_t;
+}
+
 // stream s = numpy.random.seed(seeds[s]); then `draws` x numpy.random.dirichlet([alpha] * k), all on the device
 __global__ void device_dirichlet_kernel(const uint32_t* __restrict__ seeds, int n_streams, double alpha, int k, int draws,
                                         uint32_t* __restrict__ keys, double* __restrict__ out,
@@ -124,6 +135,24 @@ int mzmcts_device_libm(const double* x, const double* y, int64_t n, double* log_
     (void)hipFree(d_y);
     (void)hipFree(d_l);
     (void)hipFree(d_p);
+    return MZMCTS_OK;
+}
+
+int mzmcts_device_sincos(const double* x, int64_t n, double* sin_out, double* cos_out) {
+    if (!x || !sin_out || !cos_out || n <= 0) return MZMCTS_ERR_INVALID;
+    double *d_x = nullptr, *d_s = nullptr, *d_c = nullptr;
+    const size_t bytes = sizeof(double) * static_cast<size_t>(n);
+    MZ_RNG_HIP(hipMalloc(&d_x, bytes));
+    MZ_RNG_HIP(hipMalloc(&d_s, bytes));
+    MZ_RNG_HIP(hipMalloc(&d_c, bytes));
+    MZ_RNG_HIP(hipMemcpy(d_x, x, bytes, hipMemcpyHostToDevice));
+    device_sincos_kernel<<<dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256)>>>(d_x, n, d_s, d_c);
+    MZ_RNG_HIP(hipGetLastError());
+    MZ_RNG_HIP(hipMemcpy(sin_out, d_s, bytes, hipMemcpyDeviceToHost));
+    MZ_RNG_HIP(hipMemcpy(cos_out, d_c, bytes, hipMemcpyDeviceToHost));
+    (void)hipFree(d_x);
+    (void)hipFree(d_s);
+    (void)hipFree(d_c);
     return MZMCTS_OK;
 }
 

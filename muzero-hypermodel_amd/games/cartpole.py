@@ -3,8 +3,12 @@
 Config values: games/cartpole.py:15-127.  The reference's Game wraps `gym.make("CartPole-v1")`
 (games/cartpole.py:136-151); gym is a third-party dependency that is absent from this image and is
 not vendored by the reference, so the environment below restates gym's published classic-control
-CartPole equations (Barto, Sutton & Anderson; Euler integration, tau = 0.02).  Env-side parity is
-therefore UNPINNED; the MCTS path and its benchmarks use synthetic observations.
+CartPole equations (Barto, Sutton & Anderson; Euler integration, tau = 0.02).  This class and the device
+kernel (csrc/env_kernels.hip) are the same restatement, pinned to those equations: given sin and cos, a
+step is IEEE double arithmetic in a fixed order and equals tests/cartpole_reference.py bit for bit; sin
+and cos lie within L ulps of the true values (L is measured there).  Parity with gym itself stays
+unpinned, gym being absent; the MCTS path and its benchmarks use synthetic
+observations.
 """
 import math
 

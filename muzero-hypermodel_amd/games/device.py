@@ -1,7 +1,9 @@
 """Device-resident batched environments (include/mzenv.h): E games of one kind advance on the GPU with
 one kernel per move instead of E host `Game.step` calls.  Same plugin semantics as the host `Game`
 classes of this package (and therefore as the reference's games/*.py): observations, reward scaling,
-legal-action order, `to_play`.  CartPole's physics is the unpinned restatement of games/cartpole.py.
+legal-action order, `to_play`.  CartPole's physics is the restatement of games/cartpole.py: pinned to the
+published equations, exact but for sin / cos within L ulps (tests/cartpole_reference.py); still unpinned against
+gym itself, which is absent here.  get_state / set_state read and write its fp64 state.
 """
 import ctypes
 
@@ -108,6 +110,26 @@ class DeviceEnvs:
         boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(self.E, -1)
         players = np.ascontiguousarray(players, dtype=np.int8).reshape(self.E)
         self._check(self._lib.mzenv_set_boards(self._h, boards.ctypes.data, players.ctypes.data))
+
+    def get_state(self):
+        """CartPole only: (state float64 [E, 4] in the order x, x_dot, theta, theta_dot, steps int32 [E]) as host arrays
+        (copies; blocking)."""
+        state, steps = np.empty((self.E, 4), np.float64), np.empty(self.E, np.int32)
+        self._check(self._lib.mzenv_get_state(self._h, state.ctypes.data, steps.ctypes.data))
+        return state, steps
+
+    def set_state(self, state, steps=None):
+        """CartPole only: every env's fp64 state becomes `state` [E, 4], stored as given (non-finite values included);
+        `steps` int [E] becomes the ply counters, which the game's 500-step cap and the move limit read (None = the
+        counters stay; negative = error).  The envs' streams are untouched.  Blocking."""
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        if state.shape != (self.E, 4):
+            raise ValueError(f"set_state: state must have shape ({self.E}, 4)")
+        if steps is not None:
+            steps = np.ascontiguousarray(steps, dtype=np.int32)
+            if steps.shape != (self.E,):
+                raise ValueError(f"set_state: steps must have shape ({self.E},)")
+        self._check(self._lib.mzenv_set_state(self._h, state.ctypes.data, None if steps is None else steps.ctypes.data))
 
     def set_max_moves(self, max_moves):
         """Games end at `max_moves` plies (config.max_moves, reference self_play.py:129-131): the ply that brings an

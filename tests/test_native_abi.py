@@ -189,6 +189,30 @@ def test_device_numerics_refuses_bad_arguments_without_a_device(native):
             native.device_numerics("exp", 0, 1)
 
 
+def test_cartpole_state_and_sincos_entries_are_declared_and_refuse_bad_arguments(native):
+    """mzenv_get_state / mzenv_set_state (include/mzenv.h) and mzmcts_device_sincos (include/mzmcts.h) are declared,
+    exported and bound; null arguments are refused with a message before anything touches the GPU (the refusals that need
+    a handle -- other games, negative counters -- are in tests/test_gpu_cartpole.py)."""
+    lib = native.load()
+    for name in ("mzenv_get_state", "mzenv_set_state", "mzmcts_device_sincos"):
+        assert name in declared_symbols() and name in native.PROTOTYPES and hasattr(lib, name)
+    assert lib.mzmcts_abi_version() == 2
+    state, steps = numpy.zeros((3, 4)), numpy.zeros(3, numpy.int32)
+    assert lib.mzenv_get_state(None, state.ctypes.data, steps.ctypes.data) == -1
+    assert b"mzenv_get_state: null argument" in lib.mzenv_last_error(None)
+    assert lib.mzenv_set_state(None, state.ctypes.data, steps.ctypes.data) == -1
+    assert b"mzenv_set_state: null argument" in lib.mzenv_last_error(None)
+    assert lib.mzenv_set_state(None, None, None) == -1 and lib.mzenv_get_state(None, None, None) == -1
+    P = native.c_f64_p
+    x, s, c = numpy.zeros(4), numpy.zeros(4), numpy.zeros(4)
+    for bad in ((None, 4, native.ptr(s, P), native.ptr(c, P)), (native.ptr(x, P), 4, None, native.ptr(c, P)),
+                (native.ptr(x, P), 4, native.ptr(s, P), None), (native.ptr(x, P), 0, native.ptr(s, P), native.ptr(c, P)),
+                (native.ptr(x, P), -1, native.ptr(s, P), native.ptr(c, P))):
+        assert lib.mzmcts_device_sincos(*bad) == native.ERR_INVALID
+    if not torch.cuda.is_available():               # a good call gets as far as the device and says so
+        assert lib.mzmcts_device_sincos(native.ptr(x, P), 4, native.ptr(s, P), native.ptr(c, P)) == native.ERR_HIP
+
+
 def test_unroll_loss_refuses_bad_arguments_without_a_device(native):
     """mztrain_unroll_loss (include/mztrain.h) checks its arguments before anything touches the GPU: a null struct, a null
     pointer among the required members (`weight` alone may be null) and a non-positive batch, steps, support_size or
