@@ -453,6 +453,28 @@ int mzmcts_board_conv3x3(const float *x, const float *packed, const float *scale
                          const float *residual, float *out, int64_t batch, int32_t cin, int32_t cout, int32_t height,
                          int32_t width, int32_t relu, void *stream);
 
+/* The same layer for 11 x 11 boards with 128 output channels (Gomoku's residual networks: models.py:213-229,
+ * 318-330, 399-420), one board per workgroup on the 16-bit matrix path at fp32 accuracy: every operand is carried as
+ * two fp16 halves, a product as three fp16 MFMAs with fp32 accumulation (csrc/wide_conv.hip; the arithmetic of
+ * mzmcts_board_tower_split).  A board holding a value outside that form's range (|x| * 8 >= 65504, inf, NaN) is
+ * computed in the SAME launch as plain fp32 fmaf chains in k order (tap-major, then channel) from x and the unpacked
+ * `weight`: never a silently wrong number, no second launch.  exact_boards (dev i32[1] or NULL) is incremented once per
+ * such board.
+ *   mzmcts_board_conv_wide_supported (models.py:213-229): height = width = 11, cout = 128, 1 <= cin <= 160.
+ *   mzmcts_board_conv_wide_halfs (models.py:213-229): 16-bit words of the packed weight.
+ *   mzmcts_board_conv_wide_pack (models.py:213-229): weight dev f32[cout, cin, 3, 3] -> packed (16-byte aligned); repack
+ *   after every weight change, into the same buffer, so a captured hipGraph follows.
+ *   mzmcts_board_conv_wide (models.py:213-229, 318-330, 399-420): x, residual (or NULL), out, scale, shift as
+ *   mzmcts_board_conv3x3; `weight` is the tensor `packed` was made from.
+ * Asynchronous, no allocation, capturable; batch == 0 launches nothing; anything outside the shapes above returns
+ * MZMCTS_ERR_INVALID before any launch. */
+int mzmcts_board_conv_wide_supported(int32_t cin, int32_t cout, int32_t height, int32_t width);
+int64_t mzmcts_board_conv_wide_halfs(int32_t cin, int32_t cout);
+int mzmcts_board_conv_wide_pack(const float *weight, void *packed, int32_t cin, int32_t cout, void *stream);
+int mzmcts_board_conv_wide(const float *x, const void *packed, const float *weight, const float *scale, const float *shift,
+                           const float *residual, float *out, int32_t *exact_boards, int64_t batch, int32_t cin,
+                           int32_t cout, int32_t height, int32_t width, int32_t relu, void *stream);
+
 /* A whole tower of such layers in ONE launch, activations resident in LDS from layer to layer (csrc/board_conv.hip):
  * layer 0 reads x dev f32[batch, cin0, height, width]; every layer produces `channels` planes; `skip` adds the input of
  * the layer BEFORE (the residual block's input, models.py:226-229) ahead of the ReLU.  export_raw / export_unit (either

@@ -149,6 +149,10 @@ PROTOTYPES = {
     "mzmcts_board_tower_heads": (ctypes.c_int, [c_void, c_void, ctypes.c_int64] + [ctypes.c_int32] * 4 +
                                  [c_void, ctypes.c_int32, c_void, ctypes.c_int32, c_void]),
     "mzmcts_board_tower": (ctypes.c_int, [c_void, ctypes.c_int64] + [ctypes.c_int32] * 4 + [c_void, ctypes.c_int32, c_void]),
+    "mzmcts_board_conv_wide_supported": (ctypes.c_int, [ctypes.c_int32] * 4),
+    "mzmcts_board_conv_wide_halfs": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "mzmcts_board_conv_wide_pack": (ctypes.c_int, [c_void, c_void, ctypes.c_int32, ctypes.c_int32, c_void]),
+    "mzmcts_board_conv_wide": (ctypes.c_int, [c_void] * 8 + [ctypes.c_int64] + [ctypes.c_int32] * 5 + [c_void]),
     "mzmcts_board_conv_split_halfs": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
     "mzmcts_board_conv_pack_split": (ctypes.c_int, [c_void, c_void, c_void] + [ctypes.c_int32] * 5 + [c_void]),
     "mzmcts_tower_gather_args": (ctypes.c_int, [c_void, c_void, ctypes.c_int32, ctypes.POINTER(MzTowerGather)]),

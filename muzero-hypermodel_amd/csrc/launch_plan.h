@@ -2,7 +2,8 @@
 // gets, how many samples a workgroup takes, how much LDS it asks for and how wide the grid is.  Plain C++17 with no HIP
 // include: board_conv.hip and net_kernels.hip validate their descriptors, ask a plan_* function here and switch from its
 // answer to the instantiation; tests/launch_plan_check.cpp builds the same text with g++ and
-// tests/test_launch_plan_cpu.py holds it to a restatement in Python (tests/board_tower_cases.py, tests/net_head_cases.py).
+// tests/test_launch_plan_cpu.py holds it to a restatement in Python (tests/board_tower_cases.py, tests/net_head_cases.py);
+// wide_conv.hip asks plan_wide_conv (tests/wide_conv_check.cpp, tests/test_wide_conv_cpu.py).
 // The constants and layout structs the kernels share with these plans live here too, so a launcher and its kernel
 // cannot count differently.
 //
@@ -14,6 +15,7 @@
 
 #include "../../include/mzmcts.h"
 #include "np_legacy_rng.h"   // MZ_HD
+#include "wide_conv.h"
 
 namespace mz {
 
@@ -130,6 +132,34 @@ inline int plan_board_conv(int64_t batch, int cin, int cout, int height, int wid
     if (batch == 0) return MZMCTS_OK;
     if (p.lds > kLdsLimit) return MZMCTS_ERR_INVALID;
     p.grid = static_cast<unsigned>(ceil_div(batch, p.sb));
+    return MZMCTS_OK;
+}
+
+// ============================================================================================================================
+// The 128-channel layer of 11 x 11 boards (mzmcts_board_conv_wide): wide_conv_split_kernel, one board per workgroup
+// ============================================================================================================================
+// A shape of its own beside board_conv_supported (whose answers stay as they are): the geometry is wide_conv.h's.
+inline bool wide_conv_supported(int cin, int cout, int height, int width) {
+    return height == kWideH && width == kWideW && cout == kWideCout && cin >= 1 && cin <= kWideMaxCin;
+}
+
+struct WidePlan {
+    int groups, cph;        // groups of 32 input channels (the last zero-padded); halves per (position, half) in LDS
+    unsigned grid, block;
+    size_t lds;             // bytes: the board as two fp16 halves, later the output staging tile
+};
+
+inline int plan_wide_conv(int64_t batch, int cin, int cout, int height, int width, WidePlan* out) {
+    *out = WidePlan{};
+    if (batch < 0 || batch > kMaxBoardBatch || !wide_conv_supported(cin, cout, height, width)) return MZMCTS_ERR_INVALID;
+    WidePlan& p = *out;
+    p.groups = wide_groups(cin);
+    p.cph = wide_cph(cin);
+    p.lds = wide_lds_bytes(cin);
+    p.block = kWideThreads;
+    if (batch == 0) return MZMCTS_OK;
+    if (p.lds > kLdsLimit) return MZMCTS_ERR_INVALID;
+    p.grid = static_cast<unsigned>(batch);
     return MZMCTS_OK;
 }
 

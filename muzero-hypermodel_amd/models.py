@@ -366,6 +366,11 @@ def conv_head(x, conv, fc, flat_size):
     return conv_heads(x, [(conv, fc, flat_size)])[0]
 
 
+# MZ_BOARD_CONV_WIDE where the environment does not set it.  "on": the whole Gomoku loop measured faster with the kernel than
+# without it in every pair of an A/B (457 against 179 moves/s search only, 394 against 167 whole loop)
+WIDE_CONV_DEFAULT = "on"
+
+
 class BoardConv2d(torch.nn.Conv2d):
     """torch.nn.Conv2d(c_in, c_out, 3, padding=1, bias=False) (same parameter and state-dict key) whose inference
     forward on small boards (expanded matrix of at most `DENSE_MAX_ELEMENTS` entries) is ONE GEMM: on a 3x3 board a padded 3x3 convolution
@@ -441,6 +446,66 @@ class BoardConv2d(torch.nn.Conv2d):
             raise RuntimeError(f"mzmcts_board_conv_pack_split failed ({rc})")
         self.__dict__["_packed_split"][key][2] = self._dense_key()
 
+    # ---- 128 output channels on 11 x 11 boards (include/mzmcts.h mzmcts_board_conv_wide) -------------------------
+    def takes_wide_path(self, x):
+        """Inference on the GPU on the shape the one-board-per-workgroup split-precision kernel covers (Gomoku's
+        128-channel layers).  MZ_BOARD_CONV=off and MZ_BOARD_CONV_WIDE=off keep torch's convolution; both are read per call."""
+        if os.environ.get("MZ_BOARD_CONV", "auto") == "off" or os.environ.get("MZ_BOARD_CONV_WIDE", WIDE_CONV_DEFAULT) != "on" \
+                or self.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 \
+                or x.dim() != 4 or self.stride != (1, 1) or self.kernel_size != (3, 3):
+            return False
+        return bool(_native.load().mzmcts_board_conv_wide_supported(self.in_channels, self.out_channels, x.shape[2], x.shape[3]))
+
+    def takes_fused_path(self, x):
+        """One of the two matrix-core kernels `fused()` dispatches to covers this call."""
+        return self.takes_mfma_path(x) or self.takes_wide_path(x)
+
+    def packed_wide(self):
+        """The weight as two fp16 halves in mzmcts_board_conv_wide's layout; same buffer for the module's lifetime (a
+        captured hipGraph keeps reading it), refilled in place when the weight changes or on refold()."""
+        buf = self.__dict__.get("_packed_wide")
+        if buf is None or buf.device != self.weight.device:
+            n = _native.load().mzmcts_board_conv_wide_halfs(self.in_channels, self.out_channels)
+            buf = self.__dict__["_packed_wide"] = torch.empty(n, dtype=torch.float16, device=self.weight.device)
+            self._packed_wide_version = None
+        if getattr(self, "_packed_wide_version", None) != self._dense_key():
+            self._repack_wide()
+        return buf
+
+    def _repack_wide(self):
+        buf = self.__dict__["_packed_wide"]
+        with torch.cuda.device(buf.device):
+            rc = _native.load().mzmcts_board_conv_wide_pack(self.weight.data_ptr(), buf.data_ptr(), self.in_channels,
+                                                            self.out_channels, torch.cuda.current_stream(buf.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mzmcts_board_conv_wide_pack failed ({rc})")
+        self._packed_wide_version = self._dense_key()
+
+    def _wide_counter(self, device):
+        """The model's count of boards the wide kernel computed in plain fp32 (MuZeroResidualNetwork hands every layer the
+        same holder); None for a convolution outside such a model."""
+        holder = self.__dict__.get("_wide_counters")
+        if holder is None:
+            return None
+        key = str(device)
+        if key not in holder:
+            holder[key] = torch.zeros(1, dtype=torch.int32, device=device)
+        return holder[key]
+
+    def _fused_wide(self, x, scale, shift, residual, relu, out):
+        b, _, h, w = x.shape
+        packed = self.packed_wide()
+        counter = self._wide_counter(x.device)
+        with torch.cuda.device(x.device):
+            rc = _native.load().mzmcts_board_conv_wide(
+                x.data_ptr(), packed.data_ptr(), self.weight.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                residual.data_ptr() if residual is not None else None, out.data_ptr(),
+                counter.data_ptr() if counter is not None else None, b, self.in_channels, self.out_channels, h, w,
+                1 if relu else 0, torch.cuda.current_stream(x.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mzmcts_board_conv_wide failed ({rc}) on a tensor of shape {tuple(x.shape)}")
+        return out
+
     def fused(self, x, bn, residual=None, relu=True):
         """relu(bn(conv(x)) [+ residual]) in one launch on the matrix cores."""
         scale, shift = bn.folded()
@@ -449,6 +514,8 @@ class BoardConv2d(torch.nn.Conv2d):
             residual = residual.contiguous()
         b, _, h, w = x.shape
         out = torch.empty((b, self.out_channels, h, w), dtype=torch.float32, device=x.device)
+        if _native.load().mzmcts_board_conv_wide_supported(self.in_channels, self.out_channels, h, w):
+            return self._fused_wide(x, scale, shift, residual, relu, out)
         packed = self.packed()
         with torch.cuda.device(x.device):
             rc = _native.load().mzmcts_board_conv3x3(
@@ -487,6 +554,8 @@ class BoardConv2d(torch.nn.Conv2d):
         them), in place."""
         if self.__dict__.get("_packed") is not None:
             self._repack()
+        if self.__dict__.get("_packed_wide") is not None:
+            self._repack_wide()
         for key in self.__dict__.get("_packed_split", {}):
             self._repack_split(key)
         with torch.no_grad():
@@ -549,7 +618,7 @@ class BoardConv2d(torch.nn.Conv2d):
 def conv_bn_relu(conv, bn, x):
     """relu(bn(conv(x))) (reference models.py:215-225, 318-330).  On the dense small-board path in inference: ONE
     GEMM -- batch-norm scale folded into the expanded matrix, shift and ReLU in the GEMM's epilogue."""
-    if isinstance(conv, BoardConv2d) and not bn.training and conv.takes_mfma_path(x):
+    if isinstance(conv, BoardConv2d) and not bn.training and conv.takes_fused_path(x):
         return conv.fused(x, bn)
     if isinstance(conv, BoardConv2d) and conv.takes_dense_path(x) and not bn.training:
         b, _, h, w = x.shape
@@ -572,7 +641,7 @@ class ResidualBlock(torch.nn.Module):
 
     def forward(self, x):
         y = conv_bn_relu(self.conv1, self.bn1, x)
-        if not self.bn2.training and self.conv2.takes_mfma_path(y):
+        if not self.bn2.training and self.conv2.takes_fused_path(y):
             return self.conv2.fused(y, self.bn2, residual=x)
         return conv_epilogue(self.conv2(y), self.bn2, residual=x)
 
@@ -747,9 +816,29 @@ class MuZeroResidualNetwork(AbstractNetwork):
             action_space_size, num_blocks, num_channels, reduced_channels_value,
             reduced_channels_policy, fc_value_layers, fc_policy_layers, self.full_support_size,
             reduced_channels_value * plane, reduced_channels_policy * plane))
+        self._share_wide_counter()
 
     def prediction(self, encoded_state):
         return self.prediction_network(encoded_state)
+
+    # ---- 128-channel layers on 11 x 11 boards (include/mzmcts.h mzmcts_board_conv_wide) -------------------------------
+    def _share_wide_counter(self):
+        """One holder {device: i32[1]} for every 3 x 3 convolution of the model: the wide kernel adds to it the boards it
+        computed in plain fp32.  Kept out of the state dict; same tensor for the model's lifetime (captured graphs)."""
+        holder = self.__dict__.setdefault("_wide_counters", {})
+        for module in self.modules():
+            if isinstance(module, BoardConv2d):
+                module.__dict__["_wide_counters"] = holder
+
+    def wide_conv_exact_boards(self, reset=True):
+        """Boards the 128-channel layers computed as plain fp32 fmaf chains since the last call (a value of their input
+        left the two-halves form's range, |x| >= 8188, or was not finite).  Waits for the device."""
+        total = 0
+        for counter in self.__dict__.get("_wide_counters", {}).values():
+            total += int(counter.item())
+            if reset:
+                counter.zero_()
+        return total
 
     # ---- whole towers in one launch (include/mzmcts.h mzmcts_board_tower) ----------------------------------------
     @staticmethod

@@ -2,14 +2,44 @@
 game's network at a given batch, from a hipGraph of 10 launches; environment variables select kernel variants
 (MZ_TOWER_COLS=off: the row-tile kernel for 3x3 boards; MZ_BOARD_CONV_PRECISION=fp32; MZ_SPLIT_FALLBACK=off).
 
-    python tools/tower_time.py [game=tictactoe] [batch=65536]        -> one JSON line"""
+    python tools/tower_time.py [game=tictactoe] [batch=65536]        -> one JSON line
+    python tools/tower_time.py wide-layer [batch=256]                -> one JSON line
+
+wide-layer: Gomoku's two layer shapes on 11 x 11 boards -- 129 -> 128 (the dynamics input) and 128 -> 128 with a skip --
+through mzmcts_board_conv_wide and through the path it replaces (torch's convolution + mzmcts_affine_act), 20 eager
+launches of each after a warm-up (what a `rocprofv3 --kernel-trace --stats` run averages per kernel name) and the time
+per layer from events around them."""
 import importlib, json, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]
 from parity_helpers import synthetic_model
 game = sys.argv[1] if len(sys.argv) > 1 else "tictactoe"
-b = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
+b = int(sys.argv[2]) if len(sys.argv) > 2 else (256 if game == "wide-layer" else 65536)
 models = importlib.import_module("muzero-hypermodel_amd.models")
+if game == "wide-layer":
+    torch.manual_seed(0)
+    result = {"mode": game, "batch": b}
+    with torch.no_grad():
+        for name, cin, skip in (("129->128", 129, False), ("128->128+skip", 128, True)):
+            conv, bn = models.conv3x3(cin, 128).cuda().eval(), models.BatchNorm2d(128).cuda().eval()
+            x = torch.rand(b, cin, 11, 11, device="cuda")
+            res = torch.rand(b, 128, 11, 11, device="cuda") if skip else None
+            for path in ("wide", "torch"):
+                os.environ["MZ_BOARD_CONV_WIDE"] = "on" if path == "wide" else "off"
+                assert conv.takes_wide_path(x) == (path == "wide")
+                run = (lambda: conv.fused(x, bn, residual=res)) if path == "wide" else (lambda: models.conv_epilogue(conv(x), bn, residual=res))
+                for _ in range(5):
+                    run()
+                torch.cuda.synchronize()
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(20):
+                    run()
+                e.record(); torch.cuda.synchronize()
+                result[f"{name} {path}_us"] = 1e3 * a.elapsed_time(e) / 20
+    result["algorithmic_TFLOPs_128_wide"] = 2 * 9 * 121 * 128 * 128 * b / result["128->128+skip wide_us"] / 1e6
+    print(json.dumps(result))
+    sys.exit(0)
 engine = importlib.import_module("muzero-hypermodel_amd.engine")
 if game == "atari84":
     config = importlib.import_module("muzero-hypermodel_amd.games.breakout").atari84_config()
