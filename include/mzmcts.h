@@ -153,11 +153,17 @@ int mzmcts_expand_roots_injected(mzmcts_engine *engine, const double *root_rewar
 /* select: the `while node.expanded()` descent with select_child / ucb_score for all E trees
  * (self_play.py:321-335, 364-405) plus the gather of the parent hidden states into one contiguous
  * batch for recurrent_inference (self_play.py:339-343):
- *   parent_hidden_out dev f32[E,H] or NULL (skip the gather), action_out dev i64[E] or NULL */
+ *   parent_hidden_out dev f32[E,H] or NULL (skip the gather), action_out dev i64[E] or NULL
+ * The batch row of an inactive env (num_legal = 0) is defined, never read outside the pool; zeros from the in-kernel
+ * gather, slab 0's row from the stand-alone kernels: H <= 64 (the descent gathers, with or without a select queue)
+ * stores H zeros, H > 64 (gather_hidden_kernel) copies row e of slab 0 -- whatever the last search with that env
+ * active, or nobody, left there.  action_out[e] is 0 in both (tests/test_gpu_hidden_gather.py pins each). */
 int mzmcts_select(mzmcts_engine *engine, float *parent_hidden_out, int64_t *action_out, void *stream);
 /* The same, with the gather laid out as the residual networks' dynamics input (models.py:553-568): row e of
  * planes_out = [parent hidden state, hidden_floats = channels x plane | one plane of action / action_space]:
- *   planes_out dev f32[E, channels + 1, plane], action_out dev i64[E] (also written, as by mzmcts_select). */
+ *   planes_out dev f32[E, channels + 1, plane], action_out dev i64[E] (also written, as by mzmcts_select).
+ * Both planes kernels are stand-alone: the row of an inactive env is slab 0's row e followed by a plane of zeros
+ * (action 0 over action_space) -- defined, never read outside the pool. */
 int mzmcts_select_planes(mzmcts_engine *engine, float *planes_out, int64_t *action_out, int32_t plane,
                          int32_t action_space, void *stream);
 
