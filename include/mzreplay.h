@@ -157,7 +157,12 @@ int mzreplay_read_games(mzreplay *store, int32_t n, const int32_t *slots, int32_
  *      move as if all had been stored and evicted in turn;
  *   5. nothing read from a ring is used as an index before it was checked: a legal count outside [0, A], a legal action
  *      outside [0, A) or a game longer than max_moves sets a bit in a device error word, NOTHING of that batch is filed,
- *      and the next mzreplay_filer_sync fails with mzhist_file's message (later calls work).
+ *      and the next mzreplay_filer_sync fails with mzhist_file's message (calls after that sync work).
+ * A call queued after a refused one and before the sync that reports it is refused too, whatever it holds: the running
+ * rows would otherwise have a hole.  The error word stands on the device until that sync (the list's drain inside
+ * mzreplay_filer_file leaves it alone).  The games of the calls BEFORE the refused one are not lost: the failing sync keeps
+ * them, the following sync hands them out, and the store and the counters are those of a filer that was given only those
+ * calls (tests/test_gpu_replay_filer_forms.py).
  * Errors of these calls are read with mzreplay_last_error(store). */
 typedef struct mzreplay_filer mzreplay_filer;
 

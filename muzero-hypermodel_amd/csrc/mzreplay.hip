@@ -1531,8 +1531,9 @@ int filer_drain(mzreplay_filer* fl, FilerState* state_out, hipStream_t stream) {
         RP_HIP(s, hipMemcpyAsync(fl->h_env.data() + have, fl->f.list_env, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
         RP_HIP(s, hipMemcpyAsync(fl->h_len.data() + have, fl->f.list_len, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
     }
-    // pending and error are adjacent: both start again at zero
-    RP_HIP(s, hipMemsetAsync(&fl->f.state->pending, 0, 2 * sizeof(int32_t), stream));
+    // pending starts again at zero; the error word (adjacent) only for the sync, which reports it: a drain between two
+    // unsynced calls leaves it standing, so the device goes on refusing and the next sync still sees it
+    RP_HIP(s, hipMemsetAsync(&fl->f.state->pending, 0, (state_out ? 2 : 1) * sizeof(int32_t), stream));
     RP_HIP(s, hipStreamSynchronize(stream));
     fl->pending_bound = 0;
     if (state_out) *state_out = st;

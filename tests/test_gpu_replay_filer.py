@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from parity_helpers import synthetic_model
+from replay_filer_cases import file_moves
 
 pytestmark = pytest.mark.gpu
 START = {"num_played_games": 0, "num_played_steps": 0}
@@ -291,16 +292,7 @@ def test_bad_legal_sets_are_refused_without_touching_the_store(mods):
                 obs_after=torch.ones((M, E) + obs_shape, device=dev), obs_next=torch.zeros((M, E) + obs_shape, device=dev))
 
     def moves():
-        mv = native.MzReplayFileMoves()
-        mv.n_moves, mv.num_simulations, mv.players = M, 10, 2
-        for name, t in (("actions", keep["actions"]), ("visits", keep["visits"]), ("root_value_sum", keep["rvs"]),
-                        ("legal", keep["legal"]), ("num_legal", keep["num_legal"]), ("to_play", keep["to_play"])):
-            setattr(mv, name, t.data_ptr())
-            setattr(mv, name + "_stride", t.stride(0) * t.element_size())
-        mv.to_play_last = keep["last"].data_ptr()
-        mv.rewards, mv.done = keep["rewards"].data_ptr(), keep["done"].data_ptr()
-        mv.obs_after, mv.obs_next = keep["obs_after"].data_ptr(), keep["obs_next"].data_ptr()
-        return mv
+        return file_moves(native, keep, M, 10, 2)
     store.filer_file(moves())
     env, length, ids = store.sync_filing()
     assert env.tolist() == list(range(E)) and length.tolist() == [2] * E and ids.tolist() == list(range(E))
