@@ -6,8 +6,10 @@
  * per-sample total with the value-loss weight and the PER importance weight, the new PER priorities
  * (|support_to_scalar(value logits) - target value| ** PER_alpha, trainer.py:199-209) and the gradient of the total
  * with respect to every logit (each unrolled step's share divided by its gradient scale, trainer.py:176-198).
- * The network forward / backward and the optimizer stay with PyTorch-ROCm; this replaces the ~25 element-wise
- * launches per unrolled step between them.  Raw device pointers, fp32, contiguous; no torch types.
+ * It replaces the ~25 element-wise launches per unrolled step between the network's forward and backward.  For
+ * fully-connected networks the forward and the backward are HIP launches too (mztrain_fc_*, below); residual networks
+ * keep both with PyTorch-ROCm, and the optimizer stays there for every network.  Raw device pointers, fp32, contiguous;
+ * no torch types.
  *
  * Domain.  Value and reward logits of loss-bearing positions are finite; a `-inf` entry outside the two target entries
  * does not contribute (the two-hot cross-entropy reads the logits at the two target entries only, where the reference's
@@ -18,6 +20,8 @@
 #ifndef MZTRAIN_H
 #define MZTRAIN_H
 #include <stdint.h>
+
+#include "mzmcts.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -49,6 +53,53 @@ typedef struct mztrain_loss_args {
  * anything touches a device: a null `args`, a null pointer among its members (`weight` alone may be null), and a
  * non-positive batch, steps, support_size or actions (support_size = 0, a one-entry support, is refused too). */
 int mztrain_unroll_loss(const mztrain_loss_args *args, void *stream);
+
+/* ---- the training step of a fully-connected network (csrc/fc_train.hip, csrc/fc_backward.h) ----------------------------
+ * Four launches queued on the caller's stream, no allocation, no host decision, no synchronisation (capturable):
+ *   forward   a lane group of 16 per sample walks its K1 positions with the search's own fc_initial / fc_recurrent,
+ *             writes the logits step-major and saves per position what the backward reads
+ *   loss      mztrain_unroll_loss on those logits
+ *   backward  the same lane group walks k = K1-1 .. 0: the gradient of every layer's pre-activation (csrc/fc_backward.h)
+ *   weights   every entry of `grads` = sum over (b, k), b-major, of delta * input: exact float64 products accumulated in
+ *             float64 in one fixed order, rounded once; no atomics, the same bits from run to run, every entry written
+ * `grads` is the gradient of mean_b(sample_loss[b]) in the layout of `weights` (every Linear's weight then bias in
+ * state_dict order, as mzmcts_fc_configure).  Both pointers are retained.  Messages through mzmcts_last_error(NULL). */
+typedef struct mztrain_fc mztrain_fc;
+
+typedef struct mztrain_fc_args {
+    const float *observations;   /* [B][obs]  the (stacked) observations of the root positions */
+    const int64_t *actions;      /* [B][K1]   column k is the action of unroll step k (column 0 is unread); an action
+                                              outside [0, A) is an all-zero one-hot */
+    const float *target_value;   /* the seven batch pointers and the three outputs of mztrain_loss_args */
+    const float *target_reward;
+    const float *target_policy;
+    const float *gradient_scale;
+    const float *weight;         /* or NULL */
+    int32_t batch;               /* B  <= max_batch */
+    int32_t steps;               /* K1 <= max_steps */
+    float value_loss_weight;
+    float per_alpha;
+    float *sample_loss;          /* out [B] */
+    float *head_sums;            /* out [3][B] */
+    float *priorities;           /* out [B][K1] */
+} mztrain_fc_args;
+
+/* weights / grads: dev f32[n_weights].  MZMCTS_ERR_INVALID before anything touches a device: a null pointer, a
+ * non-positive actions, support_size, max_batch or max_steps, build_fc_net's refusals (layer sizes, n_weights), a
+ * network whose weights and per-group activations do not fit a workgroup's 160 KB of LDS, and max_batch * max_steps
+ * beyond int32 (the kernels count the positions b * K1 + k in int32). */
+int mztrain_fc_create(const mzmcts_fc_desc *desc, int32_t actions, int32_t support_size, const float *weights,
+                      int64_t n_weights, float *grads, int32_t max_batch, int32_t max_steps, int32_t device,
+                      mztrain_fc **out);
+void mztrain_fc_destroy(mztrain_fc *handle);
+int64_t mztrain_fc_workspace_bytes(const mztrain_fc *handle);   /* device memory the handle owns; -1 for a null handle */
+/* MZMCTS_ERR_INVALID before anything touches a device: a null handle, `args` or member (`weight` alone may be null),
+ * non-positive batch or steps, batch or steps above the created maxima. */
+int mztrain_fc_step(mztrain_fc *handle, const mztrain_fc_args *args, void *stream);
+/* The last step's logits inside the workspace: value [K1][B][F], reward [K1][B][F] (step 0's row unspecified), policy
+ * [K1][B][A], with the B and K1 of that step. */
+int mztrain_fc_logits(const mztrain_fc *handle, const float **value_logits, const float **reward_logits,
+                      const float **policy_logits);
 
 #ifdef __cplusplus
 }

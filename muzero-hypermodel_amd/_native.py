@@ -65,6 +65,15 @@ class MzTowerGather(ctypes.Structure):
                 ("envs", ctypes.c_int64), ("hidden_floats", ctypes.c_int32), ("action_space", ctypes.c_float)]
 
 
+class MzTrainFcArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_fc_args: one training step of a fully-connected network."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("observations", "actions", "target_value", "target_reward",
+                                                     "target_policy", "gradient_scale", "weight")] + \
+               [("batch", ctypes.c_int32), ("steps", ctypes.c_int32), ("value_loss_weight", ctypes.c_float),
+                ("per_alpha", ctypes.c_float)] + \
+               [(name, ctypes.c_void_p) for name in ("sample_loss", "head_sums", "priorities")]
+
+
 class MzFcDesc(ctypes.Structure):
     _fields_ = [("observation_floats", ctypes.c_int32), ("encoding_size", ctypes.c_int32),
                 ("n_hidden", ctypes.c_int32 * 5), ("hidden", (ctypes.c_int32 * 3) * 5)]
@@ -166,6 +175,12 @@ PROTOTYPES = {
     # include/mzenv.h
     "mzenv_advance": (ctypes.c_int, [c_void] * 10),
     "mztrain_unroll_loss": (ctypes.c_int, [ctypes.POINTER(MzTrainLossArgs), c_void]),
+    "mztrain_fc_create": (ctypes.c_int, [ctypes.POINTER(MzFcDesc), ctypes.c_int32, ctypes.c_int32, c_void, ctypes.c_int64,
+                                         c_void, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
+    "mztrain_fc_destroy": (None, [c_void]),
+    "mztrain_fc_workspace_bytes": (ctypes.c_int64, [c_void]),
+    "mztrain_fc_step": (ctypes.c_int, [c_void, ctypes.POINTER(MzTrainFcArgs), c_void]),
+    "mztrain_fc_logits": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), ctypes.POINTER(c_void), ctypes.POINTER(c_void)]),
     "mzhist_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
     "mzhist_destroy": (None, [c_void]),
     "mzhist_last_error": (ctypes.c_char_p, [c_void]),

@@ -1,7 +1,8 @@
 """Trainer with the reference's interface (trainer.py:11-298), SURVEY.md section 8(f) row 4: the unroll that
 turns a replay batch into a gradient step, and the producer side of the weight hand-over to the actors.
 
-The arithmetic is PyTorch-ROCm (fp32, the reference's operation order); what changes is the plumbing around it:
+The arithmetic is PyTorch-ROCm (fp32, the reference's operation order) -- or, for fully-connected networks with
+Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_*); what changes is the plumbing around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -10,6 +11,7 @@ instead of a state_dict through shared storage.
 import copy
 import ctypes
 import time
+import weakref
 
 import numpy
 import torch
@@ -72,11 +74,17 @@ class _UnrollLoss(torch.autograd.Function):
 class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
-    def __init__(self, initial_checkpoint, config, device=None, graph=False):
+    def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False):
         """graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
         hipGraph at the first update_weights and replayed afterwards (the step is launch-bound: ~1 500 launches of
-        microsecond kernels for the CartPole network); batches are copied into the capture's static buffers."""
+        microsecond kernels for the CartPole network); batches are copied into the capture's static buffers.
+
+        fc_step=True (GPU, fully-connected networks): forward, loss, backward and weight gradients are four HIP launches
+        (include/mztrain.h mztrain_fc_step) that differentiate the arithmetic the search evaluates; the parameters are
+        views of one flat buffer (weights.FlatWeights, `self.flat_weights`), every p.grad a view of one flat gradient buffer
+        the launches overwrite whole, and the optimizer stays torch's.  Combines with graph=True."""
         self.config = config
+        self._fc = None
         self._graph_mode = bool(graph)
         self._graph = None
         numpy.random.seed(self.config.seed)
@@ -87,6 +95,8 @@ class Trainer:
             device = torch.device("cuda" if self.config.train_on_gpu else "cpu")
         self.model.to(torch.device(device))
         self.model.train()
+        if fc_step:
+            self._fc_setup(torch.device(device))      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]
         if self.config.optimizer == "SGD":
             self.optimizer = torch.optim.SGD(self.model.parameters(), lr=self.config.lr_init,
@@ -121,6 +131,133 @@ class Trainer:
                 for state in self.optimizer.state.values():
                     if "step" in state:
                         state["step"] = torch.as_tensor(state["step"], dtype=torch.float32).to(dev).reshape(())
+
+    # ---- the fully-connected step as HIP launches (include/mztrain.h mztrain_fc_*) -------------------------
+    def _fc_setup(self, device):
+        from . import _native, weights
+        cfg = self.config
+        if cfg.network != "fullyconnected":
+            raise NotImplementedError(f"Trainer(fc_step=True) differentiates fully-connected networks; config.network is "
+                                      f"{cfg.network!r}")
+        if device.type != "cuda":
+            raise NotImplementedError(f"Trainer(fc_step=True) runs HIP kernels: the model must be on the GPU, not on {device}")
+        layers = (cfg.fc_representation_layers, cfg.fc_dynamics_layers, cfg.fc_reward_layers, cfg.fc_policy_layers,
+                  cfg.fc_value_layers)
+        if any(len(widths) > 3 for widths in layers):
+            raise NotImplementedError("Trainer(fc_step=True): layer sizes outside the supported range (<= 3 hidden layers "
+                                      "per MLP, widths <= 256)")
+        c, h, w = cfg.observation_shape
+        desc = _native.MzFcDesc()
+        desc.observation_floats = c * h * w * (cfg.stacked_observations + 1) + cfg.stacked_observations * h * w
+        desc.encoding_size = int(cfg.encoding_size)
+        for i, widths in enumerate(layers):
+            desc.n_hidden[i] = len(widths)
+            for k, width in enumerate(widths):
+                desc.hidden[i][k] = int(width)
+        self._fc_lib = _native.load()
+        self._fc_desc = desc
+        self._fc_device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.flat_weights = weights.FlatWeights(self.model)
+        self._flat_grad = torch.zeros(self.flat_weights.numel, dtype=torch.float32, device=device)
+        for name, parameter in self.model.named_parameters():
+            at = self.flat_weights.offsets[name]
+            parameter.grad = self._flat_grad[at: at + parameter.numel()].view(parameter.shape)
+        self._fc_max = (0, 0)
+        self._fc_live = [None]
+        weakref.finalize(self, self._fc_destroy, self._fc_lib, self._fc_live, self._fc_device)
+        self._fc_handle(int(cfg.batch_size), int(cfg.num_unroll_steps) + 1)
+
+    def _fc_handle(self, batch, steps):
+        """The handle, made again (outside any capture) when a batch is larger than the one it was sized for."""
+        if self._fc is not None and batch <= self._fc_max[0] and steps <= self._fc_max[1]:
+            return self._fc
+        if self._graph is not None:
+            raise RuntimeError("Trainer(fc_step=True, graph=True): the captured step was sized for a smaller batch")
+        batch, steps = max(batch, self._fc_max[0]), max(steps, self._fc_max[1])
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self._fc_device):
+            rc = self._fc_lib.mztrain_fc_create(
+                ctypes.byref(self._fc_desc), len(self.config.action_space), int(self.config.support_size),
+                self.flat_weights.flat.data_ptr(), self.flat_weights.numel, self._flat_grad.data_ptr(), batch, steps,
+                self._fc_device.index, ctypes.byref(handle))
+        if rc != 0:
+            message = (self._fc_lib.mzmcts_last_error(None) or b"").decode()
+            if rc == -1:
+                raise NotImplementedError(f"Trainer(fc_step=True): {message}")
+            raise RuntimeError(f"mztrain_fc_create failed ({rc}): {message}")
+        self._fc_release()
+        self._fc, self._fc_max = handle, (batch, steps)
+        self._fc_live[0] = handle
+        return handle
+
+    def _fc_release(self):
+        self._fc_destroy(self._fc_lib, self._fc_live, self._fc_device)
+        self._fc = None
+
+    @staticmethod
+    def _fc_destroy(lib, live, device):
+        """Free the handle in `live` (a one-entry list, so that the finalizer registered in _fc_setup sees a handle made
+        later without holding the trainer)."""
+        if live[0] is not None:
+            torch.cuda.synchronize(device)
+            lib.mztrain_fc_destroy(live[0])
+            live[0] = None
+
+    def _fc_queue(self, b):
+        """Queue forward, loss, backward and weight gradients of batch `b` on the current stream: the flat gradient buffer
+        is overwritten whole.  Returns (per-sample loss [B], head sums [3, B], priorities [B, K+1]) as device tensors."""
+        from . import _native
+        values = b["values"]
+        size, steps = values.shape
+        handle = self._fc_handle(size, steps)
+        dev = values.device
+        obs = b["observations"].reshape(size, -1).contiguous().float()
+        actions = b["actions"].reshape(size, steps).contiguous()
+        assert actions.dtype == torch.int64 and obs.shape[1] == self._fc_desc.observation_floats
+        tv, tr, tp, gs = (b[key].contiguous() for key in ("values", "rewards", "policies", "gradient_scales"))
+        weight = b["weights"].contiguous() if b["weights"] is not None else None
+        sample_loss = torch.empty(size, device=dev)
+        head_sums = torch.empty((3, size), device=dev)
+        priorities = torch.empty((size, steps), device=dev)
+        args = _native.MzTrainFcArgs(
+            observations=obs.data_ptr(), actions=actions.data_ptr(), target_value=tv.data_ptr(), target_reward=tr.data_ptr(),
+            target_policy=tp.data_ptr(), gradient_scale=gs.data_ptr(),
+            weight=weight.data_ptr() if weight is not None else None, batch=size, steps=steps,
+            value_loss_weight=float(self.config.value_loss_weight), per_alpha=float(self.config.PER_alpha),
+            sample_loss=sample_loss.data_ptr(), head_sums=head_sums.data_ptr(), priorities=priorities.data_ptr())
+        rc = self._fc_lib.mztrain_fc_step(handle, ctypes.byref(args), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mztrain_fc_step failed ({rc}): {(self._fc_lib.mzmcts_last_error(None) or b'').decode()}")
+        return sample_loss, head_sums, priorities
+
+    def _fc_step(self, b):
+        """One eager step: the four launches, then the optimizer; the report tensor and the priorities stay on the device."""
+        sample_loss, head_sums, priorities = self._fc_queue(b)
+        self.optimizer.step()
+        return torch.cat([sample_loss.mean().reshape(1), head_sums.mean(dim=1)]), priorities
+
+    def _capture_fc(self, b):
+        """_capture for the fc_step path: the gradient buffer is overwritten by every step, so nothing is zeroed."""
+        self._fc_handle(*b["values"].shape)
+        self._static = {k: (v.clone() if v is not None else None) for k, v in b.items()}
+        dev = b["values"].device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        state = (copy.deepcopy(self.model.state_dict()), copy.deepcopy(self.optimizer.state_dict()))
+        with torch.cuda.stream(side):
+            for _ in range(3):                       # warm-up steps, undone below
+                self._fc_step(self._static)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.model.load_state_dict(state[0])         # in place: the parameters stay views of the flat buffer
+        live = self.optimizer.state_dict()["state"]
+        for index, entry in live.items():
+            saved = state[1]["state"].get(index)
+            for name, value in entry.items():
+                if torch.is_tensor(value):
+                    value.copy_(saved[name]) if saved is not None else value.zero_()
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self._graph_out = self._fc_step(self._static)
 
     @staticmethod
     def _portable_optimizer_state(state):
@@ -197,6 +334,8 @@ class Trainer:
                             self._static[key].copy_(value)
                 self._graph.replay()
                 report, priorities = self._graph_out
+            elif self._fc is not None:
+                report, priorities = self._fc_step(b)
             else:
                 steps = self._unroll(b["observations"], b["actions"])
                 sample_loss, head_sums, priorities = _UnrollLoss.apply(
@@ -251,6 +390,11 @@ class Trainer:
         b = self._batch_on_device(batch)
         if self._graph_mode:
             return self._step_graphed(b)
+        if self._fc is not None:
+            report, priorities = self._fc_step(b)
+            self.training_step += 1
+            report = report.tolist()
+            return (priorities.cpu().numpy(), report[0], report[1], report[2], report[3])
         steps = self._unroll(b["observations"], b["actions"])
         if b["values"].is_cuda and self.native_loss:
             return self._step_native(b, steps)
@@ -322,6 +466,8 @@ class Trainer:
 
     def _capture(self, b):
         """Warm the step up on a side stream and capture it on static copies of the batch `b` (not executed)."""
+        if self._fc is not None:
+            return self._capture_fc(b)
         self._static = {k: (v.clone() if v is not None else None) for k, v in b.items()}
         side = torch.cuda.Stream(device=b["values"].device)
         side.wait_stream(torch.cuda.current_stream(b["values"].device))

@@ -43,6 +43,9 @@ def main():
                     help="file finished games into the replay store on the device (DeviceSelfPlay.file_to)")
     ap.add_argument("--reanalyse", type=int, default=0,
                     help="games per iteration whose value targets are refreshed by a batched Reanalyse pass (0: none)")
+    ap.add_argument("--fc-step", action="store_true",
+                    help="forward, loss, backward and weight gradients of the training step as four HIP launches "
+                         "(Trainer(fc_step=True))")
     args = ap.parse_args()
     sp = importlib.import_module("muzero-hypermodel_amd.self_play")
     rb_mod = importlib.import_module("muzero-hypermodel_amd.replay_buffer")
@@ -58,7 +61,8 @@ def main():
     replay = rb_mod.ReplayBuffer({"num_played_games": 0, "num_played_steps": 0}, {}, config,
                                  device_sampling=args.device_sampling)
     trainer = tr_mod.Trainer({"weights": weights, "training_step": 0, "optimizer_state": None}, config, device="cuda",
-                                graph=not args.eager_trainer)   # the step as one hipGraph replay
+                                graph=not args.eager_trainer,   # the step as one hipGraph replay
+                                **({"fc_step": True} if args.fc_step else {}))
     flat = actor.engine._fc_flat                     # the buffer the actor's network (and the fused kernel) alias
     reanalyse = rb_mod.Reanalyse({"weights": weights}, config, flat=flat) if args.reanalyse > 0 else None
     finished = []
