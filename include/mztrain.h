@@ -8,8 +8,8 @@
  * with respect to every logit (each unrolled step's share divided by its gradient scale, trainer.py:176-198).
  * It replaces the ~25 element-wise launches per unrolled step between the network's forward and backward.  For
  * fully-connected networks the forward and the backward are HIP launches too (mztrain_fc_*, below); residual networks
- * keep both with PyTorch-ROCm, and the optimizer stays there for every network.  Raw device pointers, fp32, contiguous;
- * no torch types.
+ * keep both with PyTorch-ROCm; the optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
+ * flat buffers of a fully-connected network.  Raw device pointers, fp32, contiguous; no torch types.
  *
  * Domain.  Value and reward logits of loss-bearing positions are finite; a `-inf` entry outside the two target entries
  * does not contribute (the two-hot cross-entropy reads the logits at the two target entries only, where the reference's
@@ -100,6 +100,38 @@ int mztrain_fc_step(mztrain_fc *handle, const mztrain_fc_args *args, void *strea
  * [K1][B][A], with the B and K1 of that step. */
 int mztrain_fc_logits(const mztrain_fc *handle, const float **value_logits, const float **reward_logits,
                       const float **policy_logits);
+
+/* ---- the optimizer's step on the flat buffers (csrc/fc_optimizer.hip, csrc/fc_optimizer.h) ------------------------------
+ * Adam (torch's non-AMSGrad, coupled weight decay) or SGD (dampening 0, no Nesterov) on one flat float32 weight buffer and
+ * one flat gradient buffer: the rule of csrc/fc_optimizer.h, every fused multiply-add spelled out, the per-step scalars in
+ * float64 with glibc's pow, so that the device and mztrain_opt_reference on the host give the same bits.  No handle: the
+ * caller owns every buffer. */
+#define MZTRAIN_OPT_ADAM 0
+#define MZTRAIN_OPT_SGD 1
+
+typedef struct mztrain_opt_args {
+    int32_t kind;            /* MZTRAIN_OPT_ADAM / MZTRAIN_OPT_SGD */
+    int64_t n;               /* floats in each flat buffer */
+    float *weights;          /* dev f32[n], updated in place */
+    const float *grads;      /* dev f32[n] */
+    float *moment1;          /* dev f32[n]: Adam exp_avg / SGD momentum buffer (may be NULL for SGD with momentum 0) */
+    float *moment2;          /* dev f32[n]: Adam exp_avg_sq (NULL for SGD) */
+    const double *lr;        /* dev f64[1]: this step's learning rate, filled by the caller */
+    int64_t *steps_done;     /* dev i64[1]: Adam's t - 1; advanced by one per call, on the device */
+    double beta1, beta2, eps, weight_decay, momentum;
+} mztrain_opt_args;
+
+/* Queues two launches on `stream` (the update, then a one-thread launch that advances steps_done: every element of a step
+ * sees the same count), no allocation, no host decision, no synchronisation (capturable).  Writes exactly [0, n) of
+ * `weights` and of the moments the kind uses; reads `grads`.  MZMCTS_ERR_INVALID with a message through
+ * mzmcts_last_error(NULL) before anything touches a device: null `args`; a null weights, grads, lr or steps_done; a null
+ * moment1 or moment2 for Adam, a null moment1 for SGD with momentum != 0; n <= 0; an unknown kind; beta1 or beta2 outside
+ * [0, 1) and eps <= 0 (Adam); a negative or non-finite weight_decay or momentum. */
+int mztrain_opt_step(const mztrain_opt_args *args, void *stream);
+/* The same rule, and the same refusals, with every pointer a HOST array: what the tests hold the kernel to. */
+int mztrain_opt_reference(const mztrain_opt_args *args);
+/* Adam's per-step scalars {bc1, bc2, step_size, bc2s} of step t >= 1 as the kernel forms them (float64), into out[4]. */
+int mztrain_opt_scalars(double lr, double beta1, double beta2, int64_t t, double *out);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,16 @@ class MzTrainFcArgs(ctypes.Structure):
                [(name, ctypes.c_void_p) for name in ("sample_loss", "head_sums", "priorities")]
 
 
+class MzTrainOptArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_opt_args: one optimizer step on the flat weight / gradient buffers."""
+    _fields_ = [("kind", ctypes.c_int32), ("n", ctypes.c_int64)] + \
+               [(name, ctypes.c_void_p) for name in ("weights", "grads", "moment1", "moment2", "lr", "steps_done")] + \
+               [(name, ctypes.c_double) for name in ("beta1", "beta2", "eps", "weight_decay", "momentum")]
+
+
+OPT_ADAM, OPT_SGD = 0, 1
+
+
 class MzFcDesc(ctypes.Structure):
     _fields_ = [("observation_floats", ctypes.c_int32), ("encoding_size", ctypes.c_int32),
                 ("n_hidden", ctypes.c_int32 * 5), ("hidden", (ctypes.c_int32 * 3) * 5)]
@@ -181,6 +191,10 @@ PROTOTYPES = {
     "mztrain_fc_workspace_bytes": (ctypes.c_int64, [c_void]),
     "mztrain_fc_step": (ctypes.c_int, [c_void, ctypes.POINTER(MzTrainFcArgs), c_void]),
     "mztrain_fc_logits": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), ctypes.POINTER(c_void), ctypes.POINTER(c_void)]),
+    "mztrain_opt_step": (ctypes.c_int, [ctypes.POINTER(MzTrainOptArgs), c_void]),
+    "mztrain_opt_reference": (ctypes.c_int, [ctypes.POINTER(MzTrainOptArgs)]),
+    "mztrain_opt_scalars": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+                                           ctypes.POINTER(ctypes.c_double)]),
     "mzhist_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
     "mzhist_destroy": (None, [c_void]),
     "mzhist_last_error": (ctypes.c_char_p, [c_void]),

@@ -2,7 +2,8 @@
 turns a replay batch into a gradient step, and the producer side of the weight hand-over to the actors.
 
 The arithmetic is PyTorch-ROCm (fp32, the reference's operation order) -- or, for fully-connected networks with
-Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_*); what changes is the plumbing around it:
+Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_*), with fc_optimizer=True the optimizer as
+a HIP launch too (mztrain_opt_step); what changes is the plumbing around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -71,10 +72,129 @@ class _UnrollLoss(torch.autograd.Function):
         return gv * g, gr * g, gp * g, None, None, None, None
 
 
+class FlatOptimizer:
+    """Adam or SGD on a fully-connected network's flat weight and gradient buffers as HIP launches (include/mztrain.h
+    mztrain_opt_step, csrc/fc_optimizer.h): what Trainer(fc_step=True, fc_optimizer=True) holds in place of a torch.optim
+    object.  Owns two flat moment tensors (Adam's exp_avg / SGD's momentum buffer, and Adam's exp_avg_sq), the learning
+    rate as a device float64 and the count of steps done as a device int64 the launches advance.  state_dict() and
+    load_state_dict() speak the format of torch.optim.Adam / torch.optim.SGD of the same configuration."""
+
+    def __init__(self, lib, model, flat_weights, flat_grad, kind, lr, weight_decay, momentum=0.0):
+        from . import _native
+        self._lib, self._native = lib, _native
+        self.kind = kind
+        names = [name for name, _ in model.named_parameters()]
+        if names != list(flat_weights.float_keys):
+            raise NotImplementedError("Trainer(fc_optimizer=True): the flat buffer must hold the parameters and nothing else "
+                                      "(a network with batch-norm statistics keeps torch's optimizer)")
+        self._slices = [(flat_weights.offsets[name], parameter.numel(), tuple(parameter.shape))
+                        for name, parameter in model.named_parameters()]
+        self._weights, self._grads = flat_weights.flat, flat_grad
+        device = self._weights.device
+        self.n = int(flat_weights.numel)
+        self.moment1 = torch.zeros(self.n, dtype=torch.float32, device=device)
+        self.moment2 = torch.zeros(self.n if kind == "Adam" else 0, dtype=torch.float32, device=device)
+        self.lr = torch.full((1,), float(lr), dtype=torch.float64, device=device)
+        self.steps_done = torch.zeros(1, dtype=torch.int64, device=device)
+        self._lr_filled = float(lr)
+        # torch's own param-group keys for this configuration (nothing is allocated before a step)
+        if kind == "Adam":
+            template = torch.optim.Adam(model.parameters(), lr=float(lr), weight_decay=weight_decay)
+        else:
+            template = torch.optim.SGD(model.parameters(), lr=float(lr), momentum=momentum, weight_decay=weight_decay)
+        group = dict(template.state_dict()["param_groups"][0])
+        group["lr"] = float(lr)
+        self.param_groups = [group]
+
+    def zero_grad(self, set_to_none=True):
+        """Nothing to do: the gradient buffer is overwritten whole by every step's launches."""
+
+    def set_lr(self, lr):
+        self.param_groups[0]["lr"] = float(lr)
+        self.lr.fill_(float(lr))
+        self._lr_filled = float(lr)
+
+    def step(self):
+        group = self.param_groups[0]
+        if float(group["lr"]) != self._lr_filled:
+            self.set_lr(group["lr"])
+        adam = self.kind == "Adam"
+        beta1, beta2 = group["betas"] if adam else (0.0, 0.0)
+        momentum = 0.0 if adam else float(group["momentum"])
+        args = self._native.MzTrainOptArgs(
+            kind=self._native.OPT_ADAM if adam else self._native.OPT_SGD, n=self.n, weights=self._weights.data_ptr(),
+            grads=self._grads.data_ptr(), moment1=self.moment1.data_ptr() if adam or momentum != 0.0 else None,
+            moment2=self.moment2.data_ptr() if adam else None, lr=self.lr.data_ptr(), steps_done=self.steps_done.data_ptr(),
+            beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]) if adam else 0.0,
+            weight_decay=float(group["weight_decay"]), momentum=momentum)
+        rc = self._lib.mztrain_opt_step(ctypes.byref(args), torch.cuda.current_stream(self._weights.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mztrain_opt_step failed ({rc}): {(self._lib.mzmcts_last_error(None) or b'').decode()}")
+
+    # ---- what a capture's warm-up puts back ---------------------------------------------------------------
+    def snapshot(self):
+        return self.moment1.clone(), self.moment2.clone(), self.steps_done.clone()
+
+    def restore(self, saved):
+        self.moment1.copy_(saved[0])
+        self.moment2.copy_(saved[1])
+        self.steps_done.copy_(saved[2])
+
+    # ---- torch's state-dict format ------------------------------------------------------------------------
+    def state_dict(self):
+        done = int(self.steps_done.item())
+        group = dict(self.param_groups[0])
+        group["params"] = list(range(len(self._slices)))
+        state = {}
+        with_buffer = self.kind == "SGD" and float(group["momentum"]) != 0.0
+        if done > 0 and (self.kind == "Adam" or with_buffer):
+            for index, (at, count, shape) in enumerate(self._slices):
+                first = self.moment1[at: at + count].view(shape).clone()
+                if self.kind == "Adam":
+                    state[index] = {"step": torch.tensor(float(done), dtype=torch.float32), "exp_avg": first,
+                                    "exp_avg_sq": self.moment2[at: at + count].view(shape).clone()}
+                else:
+                    state[index] = {"momentum_buffer": first}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict, steps_hint=0):
+        """Takes torch's state dict, one without state and an SGD one without momentum buffers included.  SGD's state holds
+        no step count: where it holds momentum buffers, the count becomes `steps_hint` (at least 1)."""
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self._slices):
+            raise ValueError("FlatOptimizer.load_state_dict: one parameter group over the model's parameters is expected")
+        saved = groups[0]
+        if saved.get("amsgrad") or saved.get("maximize") or saved.get("nesterov") or saved.get("dampening") \
+                or saved.get("decoupled_weight_decay"):
+            raise ValueError("FlatOptimizer.load_state_dict: amsgrad, maximize, nesterov, dampening and decoupled weight "
+                             "decay are not what mztrain_opt_step computes")
+        group = self.param_groups[0]
+        for key in ("lr", "betas", "eps", "weight_decay", "momentum"):
+            if key in group and key in saved:
+                value = saved[key]
+                group[key] = tuple(float(v) for v in value) if key == "betas" else float(value)
+        self.set_lr(group["lr"])
+        self.moment1.zero_()
+        self.moment2.zero_()
+        done = 0
+        for index, entry in state_dict["state"].items():
+            at, count, shape = self._slices[saved["params"].index(index)]
+            names = ("exp_avg", "exp_avg_sq") if self.kind == "Adam" else ("momentum_buffer",)
+            for name, flat in zip(names, (self.moment1, self.moment2)):
+                value = entry.get(name)
+                if value is not None:
+                    flat[at: at + count].copy_(torch.as_tensor(value).reshape(-1))
+            if "step" in entry:
+                done = max(done, int(float(entry["step"])))
+            elif self.kind == "SGD" and entry.get("momentum_buffer") is not None:
+                done = max(done, int(steps_hint), 1)
+        self.steps_done.fill_(done)
+
+
 class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
-    def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False):
+    def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False):
         """graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
         hipGraph at the first update_weights and replayed afterwards (the step is launch-bound: ~1 500 launches of
         microsecond kernels for the CartPole network); batches are copied into the capture's static buffers.
@@ -82,7 +202,14 @@ class Trainer:
         fc_step=True (GPU, fully-connected networks): forward, loss, backward and weight gradients are four HIP launches
         (include/mztrain.h mztrain_fc_step) that differentiate the arithmetic the search evaluates; the parameters are
         views of one flat buffer (weights.FlatWeights, `self.flat_weights`), every p.grad a view of one flat gradient buffer
-        the launches overwrite whole, and the optimizer stays torch's.  Combines with graph=True."""
+        the launches overwrite whole, and the optimizer stays torch's.  Combines with graph=True.
+
+        fc_optimizer=True (with fc_step=True): the optimizer is a HIP launch on the two flat buffers too (FlatOptimizer,
+        include/mztrain.h mztrain_opt_step), Adam or SGD; the step is HIP launches only, eager and captured steps give the
+        same bits, graph=True takes SGD as well, and checkpoints keep torch's optimizer format."""
+        if fc_optimizer and not fc_step:
+            raise NotImplementedError("Trainer(fc_optimizer=True) updates the flat buffers of Trainer(fc_step=True): pass "
+                                      "fc_step=True as well")
         self.config = config
         self._fc = None
         self._graph_mode = bool(graph)
@@ -98,7 +225,12 @@ class Trainer:
         if fc_step:
             self._fc_setup(torch.device(device))      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]
-        if self.config.optimizer == "SGD":
+        self._fc_opt = bool(fc_optimizer)
+        if self._fc_opt and self.config.optimizer in ("SGD", "Adam"):
+            self.optimizer = FlatOptimizer(self._fc_lib, self.model, self.flat_weights, self._flat_grad, self.config.optimizer,
+                                           self.config.lr_init, self.config.weight_decay,
+                                           momentum=self.config.momentum if self.config.optimizer == "SGD" else 0.0)
+        elif self.config.optimizer == "SGD":
             self.optimizer = torch.optim.SGD(self.model.parameters(), lr=self.config.lr_init,
                                              momentum=self.config.momentum, weight_decay=self.config.weight_decay)
         elif self.config.optimizer == "Adam":
@@ -112,14 +244,18 @@ class Trainer:
         else:
             raise NotImplementedError(
                 f"{self.config.optimizer} is not implemented. You can change the optimizer manually in trainer.py.")
-        if self._graph_mode and (self.config.optimizer != "Adam" or torch.device(device).type != "cuda"):
+        if self._graph_mode and not self._fc_opt and (self.config.optimizer != "Adam" or torch.device(device).type != "cuda"):
             raise NotImplementedError("Trainer(graph=True) captures an Adam step on the GPU")
         self._lr_host = float(self.config.lr_init)
         if initial_checkpoint.get("optimizer_state") is not None:
-            self.optimizer.load_state_dict(copy.deepcopy(self._portable_optimizer_state(initial_checkpoint["optimizer_state"])))
+            portable = copy.deepcopy(self._portable_optimizer_state(initial_checkpoint["optimizer_state"]))
+            if self._fc_opt:
+                self.optimizer.load_state_dict(portable, steps_hint=self.training_step)
+            else:
+                self.optimizer.load_state_dict(portable)
             saved_lr = self.optimizer.param_groups[0]["lr"]
             self._lr_host = float(saved_lr)
-            if self._graph_mode:
+            if self._graph_mode and not self._fc_opt:
                 # load_state_dict replaced every param group's settings with the checkpoint's: put the device-resident
                 # learning rate and the capturable flag back (an eager checkpoint carries a float lr, capturable False and
                 # CPU step counters; a graphed one a tensor lr), or update_lr() would fill an orphaned tensor and the
@@ -243,18 +379,22 @@ class Trainer:
         dev = b["values"].device
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        state = (copy.deepcopy(self.model.state_dict()), copy.deepcopy(self.optimizer.state_dict()))
+        state = (copy.deepcopy(self.model.state_dict()),
+                 self.optimizer.snapshot() if self._fc_opt else copy.deepcopy(self.optimizer.state_dict()))
         with torch.cuda.stream(side):
             for _ in range(3):                       # warm-up steps, undone below
                 self._fc_step(self._static)
         torch.cuda.current_stream(dev).wait_stream(side)
         self.model.load_state_dict(state[0])         # in place: the parameters stay views of the flat buffer
-        live = self.optimizer.state_dict()["state"]
-        for index, entry in live.items():
-            saved = state[1]["state"].get(index)
-            for name, value in entry.items():
-                if torch.is_tensor(value):
-                    value.copy_(saved[name]) if saved is not None else value.zero_()
+        if self._fc_opt:
+            self.optimizer.restore(state[1])         # the moments and the count of steps done, as they were
+        else:
+            live = self.optimizer.state_dict()["state"]
+            for index, entry in live.items():
+                saved = state[1]["state"].get(index)
+                for name, value in entry.items():
+                    if torch.is_tensor(value):
+                        value.copy_(saved[name]) if saved is not None else value.zero_()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self._graph_out = self._fc_step(self._static)
@@ -500,6 +640,9 @@ class Trainer:
     def update_lr(self):
         lr = self.config.lr_init * self.config.lr_decay_rate ** (self.training_step / self.config.lr_decay_steps)
         self._lr_host = float(lr)              # what set_info publishes: a Python float, as in the reference
+        if self._fc_opt:
+            self.optimizer.set_lr(lr)
+            return
         if self._graph_mode:
             self._lr.fill_(lr)
             return

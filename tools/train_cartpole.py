@@ -5,7 +5,7 @@ weights.  Not a benchmark: it shows that the pieces learn together (the referenc
 ~420 reward after ~2000 training steps with one worker).
 
     python tools/train_cartpole.py [--envs 64] [--iterations 30] [--moves 8] [--train-steps 100] [--device-sampling]
-                                   [--device-filing] [--reanalyse N]
+                                   [--device-filing] [--reanalyse N] [--fc-step] [--fc-optimizer]
 
 --device-sampling: replay batches are drawn on the device and an iteration's training steps are queued without a host
 round trip (Trainer.train_steps); the log is the host-sampling run's, line for line, except the seconds.
@@ -46,7 +46,11 @@ def main():
     ap.add_argument("--fc-step", action="store_true",
                     help="forward, loss, backward and weight gradients of the training step as four HIP launches "
                          "(Trainer(fc_step=True))")
+    ap.add_argument("--fc-optimizer", action="store_true",
+                    help="the optimizer as a HIP launch on the flat buffers too (Trainer(fc_step=True, fc_optimizer=True)); "
+                         "implies --fc-step")
     args = ap.parse_args()
+    args.fc_step = args.fc_step or args.fc_optimizer
     sp = importlib.import_module("muzero-hypermodel_amd.self_play")
     rb_mod = importlib.import_module("muzero-hypermodel_amd.replay_buffer")
     tr_mod = importlib.import_module("muzero-hypermodel_amd.trainer")
@@ -62,7 +66,8 @@ def main():
                                  device_sampling=args.device_sampling)
     trainer = tr_mod.Trainer({"weights": weights, "training_step": 0, "optimizer_state": None}, config, device="cuda",
                                 graph=not args.eager_trainer,   # the step as one hipGraph replay
-                                **({"fc_step": True} if args.fc_step else {}))
+                                **({"fc_step": True} if args.fc_step else {}),
+                                **({"fc_optimizer": True} if args.fc_optimizer else {}))
     flat = actor.engine._fc_flat                     # the buffer the actor's network (and the fused kernel) alias
     reanalyse = rb_mod.Reanalyse({"weights": weights}, config, flat=flat) if args.reanalyse > 0 else None
     finished = []
