@@ -8,7 +8,8 @@
  * with respect to every logit (each unrolled step's share divided by its gradient scale, trainer.py:176-198).
  * It replaces the ~25 element-wise launches per unrolled step between the network's forward and backward.  For
  * fully-connected networks the forward and the backward are HIP launches too (mztrain_fc_*, below); residual networks
- * keep both with PyTorch-ROCm; the optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
+ * keep both with PyTorch-ROCm but for the convolution epilogue in training (mztrain_epilogue_*, below, on request); the
+ * optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
  * flat buffers of a fully-connected network.  Raw device pointers, fp32, contiguous; no torch types.
  *
  * Domain.  Value and reward logits of loss-bearing positions are finite; a `-inf` entry outside the two target entries
@@ -132,6 +133,56 @@ int mztrain_opt_step(const mztrain_opt_args *args, void *stream);
 int mztrain_opt_reference(const mztrain_opt_args *args);
 /* Adam's per-step scalars {bc1, bc2, step_size, bc2s} of step t >= 1 as the kernel forms them (float64), into out[4]. */
 int mztrain_opt_scalars(double lr, double beta1, double beta2, int64_t t, double *out);
+
+/* ---- the convolution epilogue of a residual network in training (csrc/bn_epilogue.hip, csrc/bn_epilogue.h) --------------
+ * out = relu(batch_norm(x) [+ residual]) with the batch's own statistics, and its backward, one launch each: a workgroup
+ * per channel, every sum over a channel in float64 in the one fixed order the header states, no atomics, the same bits from
+ * run to run and as the host entries below.  x, residual, out, dy, dx, dresidual are NCHW float32, contiguous, hw = H * W;
+ * a channel has M = batch * hw values.  No alignment beyond a float's is assumed. */
+typedef struct mztrain_epilogue_forward_args {
+    const float *x;          /* [batch][channels][hw] */
+    const float *residual;   /* [batch][channels][hw], or NULL */
+    const float *gamma;      /* [channels] batch norm's weight */
+    const float *beta;       /* [channels] batch norm's bias */
+    float *running_mean;     /* [channels] updated in place: (1 - momentum) * running + momentum * mean */
+    float *running_var;      /* [channels] updated in place with the unbiased variance (sum of squares / (M - 1)) */
+    float *out;              /* out [batch][channels][hw]; must not overlap x */
+    float *save_mean;        /* out [channels] what the backward reads */
+    float *save_invstd;      /* out [channels] 1 / sqrt(biased variance + eps) */
+    int64_t batch;
+    int32_t channels;
+    int32_t hw;
+    double eps;
+    double momentum;
+} mztrain_epilogue_forward_args;
+
+typedef struct mztrain_epilogue_backward_args {
+    const float *dy;          /* [batch][channels][hw] gradient of `out` */
+    const float *x;           /* the forward's x */
+    const float *out;         /* the forward's out: the ReLU mask is out > 0 */
+    const float *gamma;
+    const float *save_mean;
+    const float *save_invstd;
+    float *dx;                /* out [batch][channels][hw] */
+    float *dresidual;         /* out [batch][channels][hw] (dy where out > 0, else 0), or NULL */
+    float *dgamma;            /* out [channels] */
+    float *dbeta;             /* out [channels] */
+    int64_t batch;
+    int32_t channels;
+    int32_t hw;
+} mztrain_epilogue_backward_args;
+
+/* Each queues one launch on `stream`, no allocation, no host decision beyond the choice of the kernel's form by M, no
+ * synchronisation (capturable).  MZMCTS_ERR_INVALID with a message through mzmcts_last_error(NULL) before anything touches
+ * a device: null `args`; a null member (`residual` / `dresidual` alone may be null); channels < 1; batch or hw < 1;
+ * M = batch * hw < 2; hw > 2^30 or M > 2^40; forward: a negative eps, a momentum outside [0, 1]. */
+int mztrain_epilogue_forward(const mztrain_epilogue_forward_args *args, void *stream);
+int mztrain_epilogue_backward(const mztrain_epilogue_backward_args *args, void *stream);
+/* The same rule, and the same refusals, with every pointer a HOST array: what the tests hold the kernels to. */
+int mztrain_epilogue_reference_forward(const mztrain_epilogue_forward_args *args);
+int mztrain_epilogue_reference_backward(const mztrain_epilogue_backward_args *args);
+/* M up to which a channel stays in LDS between the kernels' passes (the one switch of form). */
+#define MZTRAIN_EPILOGUE_KEEP_VALUES 4096
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,24 @@ class MzTrainOptArgs(ctypes.Structure):
 OPT_ADAM, OPT_SGD = 0, 1
 
 
+class MzTrainEpilogueForwardArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_epilogue_forward_args: relu(batch_norm(x) [+ residual]) in training."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("x", "residual", "gamma", "beta", "running_mean", "running_var", "out",
+                                                     "save_mean", "save_invstd")] + \
+               [("batch", ctypes.c_int64), ("channels", ctypes.c_int32), ("hw", ctypes.c_int32), ("eps", ctypes.c_double),
+                ("momentum", ctypes.c_double)]
+
+
+class MzTrainEpilogueBackwardArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_epilogue_backward_args."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("dy", "x", "out", "gamma", "save_mean", "save_invstd", "dx", "dresidual",
+                                                     "dgamma", "dbeta")] + \
+               [("batch", ctypes.c_int64), ("channels", ctypes.c_int32), ("hw", ctypes.c_int32)]
+
+
+EPILOGUE_KEEP_VALUES = 4096     # include/mztrain.h MZTRAIN_EPILOGUE_KEEP_VALUES
+
+
 class MzFcDesc(ctypes.Structure):
     _fields_ = [("observation_floats", ctypes.c_int32), ("encoding_size", ctypes.c_int32),
                 ("n_hidden", ctypes.c_int32 * 5), ("hidden", (ctypes.c_int32 * 3) * 5)]
@@ -195,6 +213,10 @@ PROTOTYPES = {
     "mztrain_opt_reference": (ctypes.c_int, [ctypes.POINTER(MzTrainOptArgs)]),
     "mztrain_opt_scalars": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
                                            ctypes.POINTER(ctypes.c_double)]),
+    "mztrain_epilogue_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueForwardArgs), c_void]),
+    "mztrain_epilogue_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueBackwardArgs), c_void]),
+    "mztrain_epilogue_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueForwardArgs)]),
+    "mztrain_epilogue_reference_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueBackwardArgs)]),
     "mzhist_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
     "mzhist_destroy": (None, [c_void]),
     "mzhist_last_error": (ctypes.c_char_p, [c_void]),

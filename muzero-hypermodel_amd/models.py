@@ -255,10 +255,83 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
         return torch.addcmul(shift.view(1, -1, 1, 1), x, scale.view(1, -1, 1, 1))
 
 
+class _TrainingEpilogue(torch.autograd.Function):
+    """relu(batch_norm(x) [+ residual]) with the batch's statistics as ONE HIP launch forward and one backward
+    (include/mztrain.h mztrain_epilogue_*, csrc/bn_epilogue.h): every sum over a channel in float64 in one fixed order, no
+    atomics, the same bits eager and captured.  The forward updates running_mean / running_var in place through raw
+    pointers (their version counters do not move, so the caller drops the batch norm's folded eval-mode constants) and
+    saves x, out, the weight and the per-channel mean and 1 / sqrt(var + eps) for the backward."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, eps, momentum):
+        lib = _native.load()
+        x = x.contiguous()
+        if residual is not None:
+            residual = residual.contiguous()
+        n, c, h, w = x.shape
+        out = torch.empty_like(x)
+        stats = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        args = _native.MzTrainEpilogueForwardArgs(
+            x=x.data_ptr(), residual=residual.data_ptr() if residual is not None else None, gamma=weight.data_ptr(),
+            beta=bias.data_ptr(), running_mean=running_mean.data_ptr(), running_var=running_var.data_ptr(),
+            out=out.data_ptr(), save_mean=stats[0].data_ptr(), save_invstd=stats[1].data_ptr(), batch=n, channels=c,
+            hw=h * w, eps=float(eps), momentum=float(momentum))
+        with torch.cuda.device(x.device):
+            rc = lib.mztrain_epilogue_forward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mztrain_epilogue_forward failed ({rc}) on a tensor of shape {tuple(x.shape)}: "
+                               f"{(lib.mzmcts_last_error(None) or b'').decode()}")
+        ctx.save_for_backward(x, out, weight, stats)
+        ctx.with_residual = residual is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _native.load()
+        x, out, weight, stats = ctx.saved_tensors
+        dy = grad_out.contiguous()
+        n, c, h, w = x.shape
+        dx = torch.empty_like(x)
+        dresidual = torch.empty_like(x) if ctx.with_residual and ctx.needs_input_grad[1] else None
+        dparams = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        args = _native.MzTrainEpilogueBackwardArgs(
+            dy=dy.data_ptr(), x=x.data_ptr(), out=out.data_ptr(), gamma=weight.data_ptr(), save_mean=stats[0].data_ptr(),
+            save_invstd=stats[1].data_ptr(), dx=dx.data_ptr(),
+            dresidual=dresidual.data_ptr() if dresidual is not None else None, dgamma=dparams[0].data_ptr(),
+            dbeta=dparams[1].data_ptr(), batch=n, channels=c, hw=h * w)
+        with torch.cuda.device(x.device):
+            rc = lib.mztrain_epilogue_backward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mztrain_epilogue_backward failed ({rc}) on a tensor of shape {tuple(x.shape)}: "
+                               f"{(lib.mzmcts_last_error(None) or b'').decode()}")
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, dresidual, dparams[0] if need[2] else None, dparams[1] if need[3] else None,
+                None, None, None, None)
+
+
+def _native_training(x, bn):
+    """Whether conv_epilogue takes the HIP training path: switched on (MuZeroResidualNetwork.native_training_epilogue), in
+    training mode, an affine batch norm that tracks running statistics with a float momentum, a float32 CUDA tensor of 4
+    dimensions."""
+    return (getattr(bn, "native_training", False) and bn.training and bn.affine and bn.track_running_stats
+            and isinstance(bn.momentum, float) and bn.running_mean is not None and x.is_cuda and x.dtype == torch.float32
+            and x.dim() == 4)
+
+
 def conv_epilogue(x, bn, residual=None):
     """relu(bn(x) [+ residual]) after a convolution (reference models.py:215-237).  Inference on the GPU: one HIP
     launch (include/mzmcts.h mzmcts_affine_act) instead of torch's three element-wise ones, same operations in
-    the same order; training, autograd and CPU tensors take the torch expression."""
+    the same order; training, autograd and CPU tensors take the torch expression -- unless the batch norm has been
+    switched to the HIP training path (_TrainingEpilogue), one launch forward and one backward."""
+    if _native_training(x, bn):
+        if x.numel() // x.shape[1] == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
+        if x.shape[1] != bn.num_features:
+            raise ValueError(f"conv_epilogue: {x.shape[1]} channels into a batch norm of {bn.num_features}")
+        bn._folded = None                       # the launch writes the running statistics behind their version counters
+        bn.num_batches_tracked.add_(1)
+        return _TrainingEpilogue.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
     native = (x.is_cuda and not bn.training and x.dtype == torch.float32 and x.dim() == 4
               and not (torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad))))
     if native:
@@ -820,6 +893,15 @@ class MuZeroResidualNetwork(AbstractNetwork):
 
     def prediction(self, encoded_state):
         return self.prediction_network(encoded_state)
+
+    def native_training_epilogue(self, on=True):
+        """Switch every BatchNorm2d of the network to (or back from) the HIP training epilogue: in train() mode
+        conv_epilogue then runs relu(batch_norm(x) [+ residual]) as one launch forward and one backward
+        (_TrainingEpilogue) instead of torch's expression.  eval() mode and CPU tensors are not affected."""
+        for module in self.modules():
+            if isinstance(module, BatchNorm2d):
+                module.native_training = bool(on)
+        return self
 
     # ---- 128-channel layers on 11 x 11 boards (include/mzmcts.h mzmcts_board_conv_wide) -------------------------------
     def _share_wide_counter(self):

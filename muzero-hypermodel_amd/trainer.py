@@ -3,7 +3,8 @@ turns a replay batch into a gradient step, and the producer side of the weight h
 
 The arithmetic is PyTorch-ROCm (fp32, the reference's operation order) -- or, for fully-connected networks with
 Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_*), with fc_optimizer=True the optimizer as
-a HIP launch too (mztrain_opt_step); what changes is the plumbing around it:
+a HIP launch too (mztrain_opt_step), and for residual networks with Trainer(native_epilogue=True) every
+relu(batch_norm(x) [+ residual]) as one HIP launch each way (mztrain_epilogue_*); what changes is the plumbing around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -194,7 +195,8 @@ class FlatOptimizer:
 class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
-    def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False):
+    def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False,
+                 native_epilogue=False):
         """graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
         hipGraph at the first update_weights and replayed afterwards (the step is launch-bound: ~1 500 launches of
         microsecond kernels for the CartPole network); batches are copied into the capture's static buffers.
@@ -206,7 +208,12 @@ class Trainer:
 
         fc_optimizer=True (with fc_step=True): the optimizer is a HIP launch on the two flat buffers too (FlatOptimizer,
         include/mztrain.h mztrain_opt_step), Adam or SGD; the step is HIP launches only, eager and captured steps give the
-        same bits, graph=True takes SGD as well, and checkpoints keep torch's optimizer format."""
+        same bits, graph=True takes SGD as well, and checkpoints keep torch's optimizer format.
+
+        native_epilogue=True (GPU, residual networks): every relu(batch_norm(x) [+ residual]) of the network in training is
+        one HIP launch forward and one backward (include/mztrain.h mztrain_epilogue_*, models._TrainingEpilogue) instead of
+        torch's batch norm, add and ReLU with their autograd nodes; convolutions, heads and the optimizer stay torch's.
+        Combines with graph=True; checkpoints, publish and update_lr are untouched."""
         if fc_optimizer and not fc_step:
             raise NotImplementedError("Trainer(fc_optimizer=True) updates the flat buffers of Trainer(fc_step=True): pass "
                                       "fc_step=True as well")
@@ -222,6 +229,15 @@ class Trainer:
             device = torch.device("cuda" if self.config.train_on_gpu else "cpu")
         self.model.to(torch.device(device))
         self.model.train()
+        if native_epilogue:
+            if self.config.network != "resnet":
+                raise NotImplementedError(f"Trainer(native_epilogue=True) fuses the batch norms of residual networks; "
+                                          f"config.network is {self.config.network!r}")
+            if torch.device(device).type != "cuda":
+                raise NotImplementedError(f"Trainer(native_epilogue=True) runs HIP kernels: the model must be on the GPU, "
+                                          f"not on {torch.device(device)}")
+            self.model.native_training_epilogue(True)
+        self._native_norms = [m for m in self.model.modules() if isinstance(m, models.BatchNorm2d)] if native_epilogue else []
         if fc_step:
             self._fc_setup(torch.device(device))      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]
@@ -472,7 +488,7 @@ class Trainer:
                     for key, value in b.items():
                         if value is not None:
                             self._static[key].copy_(value)
-                self._graph.replay()
+                self._replay()
                 report, priorities = self._graph_out
             elif self._fc is not None:
                 report, priorities = self._fc_step(b)
@@ -599,10 +615,15 @@ class Trainer:
         for key, value in b.items():
             if value is not None:
                 self._static[key].copy_(value)
-        self._graph.replay()
+        self._replay()
         self.training_step += 1
         report = self._graph_out[0].tolist()
         return (self._graph_out[1].cpu().numpy(), report[0], report[1], report[2], report[3])
+
+    def _replay(self):
+        self._graph.replay()
+        for norm in self._native_norms:      # a replay runs no Python: drop the eval-mode constants the launches outdated
+            norm._folded = None
 
     def _capture(self, b):
         """Warm the step up on a side stream and capture it on static copies of the batch `b` (not executed)."""

@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """Time of Trainer.update_weights on the MI355X with the loss as one HIP launch (csrc/trainer_kernels.hip) and as the
 torch expression: CartPole FC config and TicTacToe residual network, synthetic replay batches resident on the GPU.
-One JSON line per (config, loss path)."""
-import importlib, json, os, sys, time
+One JSON line per (config, loss path).
+
+--native-epilogue times the residual configs of --games (default tictactoe,connect4) instead, each eager and as a hipGraph,
+each without and with Trainer(native_epilogue=True) (relu(batch_norm(x) [+ residual]) in training as one HIP launch each
+way, csrc/bn_epilogue.hip): the ways are alternated, the unflagged first, --windows windows of at least --seconds each,
+every window closed by a synchronise; one JSON line per (config, way) with the windows, their median and max - min, and for
+the flagged ways whether a window overlaps one of the unflagged way of the same form.  --one-step WAY runs --steps steps of
+one way and nothing else (for a kernel trace of that way alone: two traces with different --steps differ by whole steps).
+--kernel-alone times the two launches at --shape (default Gomoku's layer, 512,128,11,11) against torch's expression."""
+import argparse, importlib, json, os, statistics, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 pkg = lambda m: importlib.import_module("muzero-hypermodel_amd." + m)
 
-for game in ("cartpole", "tictactoe"):
-    config = pkg("games." + game).MuZeroConfig()
-    config.train_on_gpu = True
+
+def synthetic(config):
     model = pkg("models").MuZeroNetwork(config)
     ckpt = {"weights": model.get_weights(), "training_step": 0, "optimizer_state": None}
     B, K1, A = config.batch_size, config.num_unroll_steps + 1, len(config.action_space)
@@ -21,16 +28,135 @@ for game in ("cartpole", "tictactoe"):
              torch.softmax(torch.randn(B, K1, A, generator=g, device="cuda"), dim=2),
              torch.rand(B, generator=g, device="cuda") + 0.5,
              torch.randint(1, K1 + 1, (B, K1), generator=g, device="cuda").float())
-    for native, graph in ((True, True), (True, False), (False, False)):
-        trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", graph=graph)
-        trainer.native_loss = native
+    return ckpt, batch, B, K1
+
+
+def loss_paths():
+    for game in ("cartpole", "tictactoe"):
+        config = pkg("games." + game).MuZeroConfig()
+        config.train_on_gpu = True
+        ckpt, batch, B, K1 = synthetic(config)
+        for native, graph in ((True, True), (True, False), (False, False)):
+            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", graph=graph)
+            trainer.native_loss = native
+            for _ in range(10):
+                trainer.update_weights(batch)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = 100
+            for _ in range(n):
+                trainer.update_weights(batch)
+            torch.cuda.synchronize()
+            print(json.dumps({"config": game, "batch": B, "unrolled_positions": K1, "loss": "one HIP launch" if native else "torch expression", "hipgraph": graph,
+                              "ms_per_training_step": round((time.perf_counter() - t0) / n * 1e3, 3)}), flush=True)
+
+
+def window(trainer, batch, seconds):
+    """Steps until `seconds` have passed, in blocks of 10, closed by a synchronise: ms per step."""
+    torch.cuda.synchronize()
+    t0, n = time.perf_counter(), 0
+    while True:
         for _ in range(10):
             trainer.update_weights(batch)
+        n += 10
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        n = 100
-        for _ in range(n):
-            trainer.update_weights(batch)
+        elapsed = time.perf_counter() - t0
+        if elapsed >= seconds:
+            return elapsed / n * 1e3
+
+
+WAYS = [("library, eager", dict(graph=False)), ("native_epilogue, eager", dict(graph=False, native_epilogue=True)),
+        ("library, hipgraph", dict(graph=True)), ("native_epilogue, hipgraph", dict(graph=True, native_epilogue=True))]
+
+
+def epilogue_ways(args):
+    for game in args.games.split(","):
+        config = pkg("games." + game).MuZeroConfig()
+        config.train_on_gpu = True
+        torch.manual_seed(0)
+        ckpt, batch, B, K1 = synthetic(config)
+        if args.one_step is not None:
+            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **dict(WAYS)[args.one_step])
+            for _ in range(args.steps):
+                trainer.update_weights(batch)
+            torch.cuda.synchronize()
+            print(json.dumps({"config": game, "way": args.one_step, "steps": args.steps}), flush=True)
+            continue
+        trainers = []
+        for name, how in WAYS:
+            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **how)
+            for _ in range(5):
+                trainer.update_weights(batch)
+            trainers.append((name, trainer, []))
+        for _ in range(args.windows):
+            for name, trainer, times in trainers:
+                times.append(window(trainer, batch, args.seconds))
+        spans = {name: (min(times), max(times)) for name, trainer, times in trainers}
+        for name, trainer, times in trainers:
+            line = {"config": game, "batch": B, "unrolled_positions": K1, "way": name,
+                    "ms_per_training_step_windows": [round(t, 4) for t in times],
+                    "median_ms": round(statistics.median(times), 4), "max_minus_min_ms": round(max(times) - min(times), 4)}
+            if name.startswith("native_epilogue"):
+                lo, hi = spans[name.replace("native_epilogue", "library")]
+                line["windows_overlap_library"] = not (max(times) < lo or min(times) > hi)
+            print(json.dumps(line), flush=True)
+
+
+def kernel_alone(args):
+    """Forward + backward of the epilogue at one shape, with a residual: the two HIP launches against torch's expression,
+    both through autograd; the bytes the shape needs are x, residual and dy read once, out, dx and dresidual written once."""
+    models = pkg("models")
+    shape = tuple(int(v) for v in args.shape.split(","))
+    n, c, h, w = shape
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randn(shape, generator=g, device="cuda").requires_grad_()
+    residual = torch.randn(shape, generator=g, device="cuda").requires_grad_()
+    dy = torch.randn(shape, generator=g, device="cuda")
+    needed = 6 * x.numel() * 4
+    times = {}
+    for name, on in (("torch expression", False), ("native_epilogue", True)) * args.windows:
+        bn = models.BatchNorm2d(c).cuda().train()
+        bn.native_training = on
+
+        def once():
+            x.grad = residual.grad = None
+            models.conv_epilogue(x, bn, residual).backward(dy)
+
+        for _ in range(5):
+            once()
         torch.cuda.synchronize()
-        print(json.dumps({"config": game, "batch": B, "unrolled_positions": K1, "loss": "one HIP launch" if native else "torch expression", "hipgraph": graph,
-                          "ms_per_training_step": round((time.perf_counter() - t0) / n * 1e3, 3)}), flush=True)
+        t0, count = time.perf_counter(), 0
+        while time.perf_counter() - t0 < args.seconds:
+            for _ in range(20):
+                once()
+            count += 20
+            torch.cuda.synchronize()
+        times.setdefault(name, []).append((time.perf_counter() - t0) / count * 1e3)
+    for name, values in times.items():
+        median = statistics.median(values)
+        print(json.dumps({"shape": list(shape), "way": name, "forward_plus_backward_ms_windows": [round(v, 4) for v in values],
+                          "median_ms": round(median, 4), "max_minus_min_ms": round(max(values) - min(values), 4),
+                          "bytes_needed": needed, "achieved_GB_per_s": round(needed / (median * 1e-3) / 1e9, 1)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--native-epilogue", action="store_true")
+    ap.add_argument("--kernel-alone", action="store_true")
+    ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(name for name, _ in WAYS))
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--games", default="tictactoe,connect4")
+    ap.add_argument("--shape", default="512,128,11,11")
+    args = ap.parse_args()
+    if args.kernel_alone:
+        kernel_alone(args)
+    elif args.native_epilogue or args.one_step is not None:
+        epilogue_ways(args)
+    else:
+        loss_paths()
+
+
+if __name__ == "__main__":
+    main()
