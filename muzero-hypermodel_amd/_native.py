@@ -366,6 +366,18 @@ def check(lib, engine, rc):
     raise RuntimeError(msg)
 
 
+def check_train(lib, rc, what, where="", reason=True, refusal=None):
+    """Translate the status of a mztrain_* call (include/mztrain.h): RuntimeError "<what> failed (<rc>)<where>: <the
+    library's last error>" (`reason=False`: the call leaves no error string, the text ends at <where>).  With `refusal`,
+    status -1 -- a shape the library does not cover -- is NotImplementedError "<refusal>: <last error>"."""
+    if rc == 0:
+        return
+    message = (lib.mzmcts_last_error(None) or b"").decode() if reason else ""
+    if rc == -1 and refusal is not None:
+        raise NotImplementedError(f"{refusal}: {message}")
+    raise RuntimeError(f"{what} failed ({rc}){where}" + (f": {message}" if reason else ""))
+
+
 class MzHeadDesc(ctypes.Structure):
     """mzmcts_head_desc (include/mzmcts.h): one reward / value / policy head of the residual networks."""
     _fields_ = [("conv_w", c_void), ("conv_b", c_void), ("fc1_w", c_void), ("fc1_b", c_void), ("fc2_w", c_void),

@@ -278,9 +278,7 @@ class _TrainingEpilogue(torch.autograd.Function):
             hw=h * w, eps=float(eps), momentum=float(momentum))
         with torch.cuda.device(x.device):
             rc = lib.mztrain_epilogue_forward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mztrain_epilogue_forward failed ({rc}) on a tensor of shape {tuple(x.shape)}: "
-                               f"{(lib.mzmcts_last_error(None) or b'').decode()}")
+        _native.check_train(lib, rc, "mztrain_epilogue_forward", where=f" on a tensor of shape {tuple(x.shape)}")
         ctx.save_for_backward(x, out, weight, stats)
         ctx.with_residual = residual is not None
         return out
@@ -302,9 +300,7 @@ class _TrainingEpilogue(torch.autograd.Function):
             dbeta=dparams[1].data_ptr(), batch=n, channels=c, hw=h * w)
         with torch.cuda.device(x.device):
             rc = lib.mztrain_epilogue_backward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mztrain_epilogue_backward failed ({rc}) on a tensor of shape {tuple(x.shape)}: "
-                               f"{(lib.mzmcts_last_error(None) or b'').decode()}")
+        _native.check_train(lib, rc, "mztrain_epilogue_backward", where=f" on a tensor of shape {tuple(x.shape)}")
         need = ctx.needs_input_grad
         return (dx if need[0] else None, dresidual, dparams[0] if need[2] else None, dparams[1] if need[3] else None,
                 None, None, None, None)

@@ -9,6 +9,12 @@ batches arrive as CUDA tensors from the device replay store (replay_buffer.Repla
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
 instead of a state_dict through shared storage.
+
+There is one training step, Trainer._queue_step: produce the gradients, step the optimizer, build the report of the four
+losses.  Three things produce gradients -- the four fc_step launches (_fc_queue), autograd under the loss launch
+(_loss_native) and autograd under the torch expression (_loss_torch: on the CPU, or with native_loss = False) -- and
+update_weights, train_steps and graph mode's warm-up and capture (_capture) all run that one body; _step replays a
+captured one.  A non-zero status of a mztrain_* call is raised by _native.check_train.
 """
 import copy
 import ctypes
@@ -18,7 +24,7 @@ import weakref
 import numpy
 import torch
 
-from . import models
+from . import _native, models
 
 
 def _scale_gradient(tensor, divisor):
@@ -27,6 +33,12 @@ def _scale_gradient(tensor, divisor):
     shared parameters accumulate their gradients -- stays the reference's, which one-step Adam parity needs."""
     tensor.register_hook(lambda grad: grad / divisor)
     return tensor
+
+
+def _loss_outputs(size, steps, device):
+    """What a loss launch fills: per-sample loss [B], per-sample head sums [3, B], priorities [B, K+1]."""
+    return (torch.empty(size, device=device), torch.empty((3, size), device=device),
+            torch.empty((size, steps), device=device))
 
 
 class _UnrollLoss(torch.autograd.Function):
@@ -39,7 +51,6 @@ class _UnrollLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, value_logits, reward_logits, policy_logits, batch, support_size, value_loss_weight, per_alpha):
-        from . import _native
         lib = _native.load()      # raises when the HIP library is missing: no silent fallback on a GPU box
         steps, size, full = value_logits.shape
         actions = policy_logits.shape[2]
@@ -47,10 +58,7 @@ class _UnrollLoss(torch.autograd.Function):
         v, r, p = (t.detach().contiguous().float() for t in (value_logits, reward_logits, policy_logits))
         tv, tr, tp, gs = (batch[key].contiguous() for key in ("values", "rewards", "policies", "gradient_scales"))
         weight = batch["weights"].contiguous() if batch["weights"] is not None else None
-        dev = v.device
-        sample_loss = torch.empty(size, device=dev)
-        head_sums = torch.empty((3, size), device=dev)
-        priorities = torch.empty((size, steps), device=dev)
+        sample_loss, head_sums, priorities = _loss_outputs(size, steps, v.device)
         grads = (torch.empty_like(v), torch.empty_like(r), torch.empty_like(p))
         args = _native.MzTrainLossArgs(
             value_logits=v.data_ptr(), reward_logits=r.data_ptr(), policy_logits=p.data_ptr(), target_value=tv.data_ptr(),
@@ -59,9 +67,8 @@ class _UnrollLoss(torch.autograd.Function):
             actions=actions, value_loss_weight=float(value_loss_weight), per_alpha=float(per_alpha),
             sample_loss=sample_loss.data_ptr(), head_sums=head_sums.data_ptr(), priorities=priorities.data_ptr(),
             grad_value=grads[0].data_ptr(), grad_reward=grads[1].data_ptr(), grad_policy=grads[2].data_ptr())
-        rc = lib.mztrain_unroll_loss(ctypes.byref(args), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mztrain_unroll_loss failed ({rc})")
+        rc = lib.mztrain_unroll_loss(ctypes.byref(args), torch.cuda.current_stream(v.device).cuda_stream)
+        _native.check_train(lib, rc, "mztrain_unroll_loss", reason=False)
         ctx.save_for_backward(*grads)
         ctx.mark_non_differentiable(head_sums, priorities)
         return sample_loss, head_sums, priorities
@@ -81,8 +88,7 @@ class FlatOptimizer:
     load_state_dict() speak the format of torch.optim.Adam / torch.optim.SGD of the same configuration."""
 
     def __init__(self, lib, model, flat_weights, flat_grad, kind, lr, weight_decay, momentum=0.0):
-        from . import _native
-        self._lib, self._native = lib, _native
+        self._lib = lib
         self.kind = kind
         names = [name for name, _ in model.named_parameters()]
         if names != list(flat_weights.float_keys):
@@ -122,15 +128,14 @@ class FlatOptimizer:
         adam = self.kind == "Adam"
         beta1, beta2 = group["betas"] if adam else (0.0, 0.0)
         momentum = 0.0 if adam else float(group["momentum"])
-        args = self._native.MzTrainOptArgs(
-            kind=self._native.OPT_ADAM if adam else self._native.OPT_SGD, n=self.n, weights=self._weights.data_ptr(),
+        args = _native.MzTrainOptArgs(
+            kind=_native.OPT_ADAM if adam else _native.OPT_SGD, n=self.n, weights=self._weights.data_ptr(),
             grads=self._grads.data_ptr(), moment1=self.moment1.data_ptr() if adam or momentum != 0.0 else None,
             moment2=self.moment2.data_ptr() if adam else None, lr=self.lr.data_ptr(), steps_done=self.steps_done.data_ptr(),
             beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]) if adam else 0.0,
             weight_decay=float(group["weight_decay"]), momentum=momentum)
         rc = self._lib.mztrain_opt_step(ctypes.byref(args), torch.cuda.current_stream(self._weights.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mztrain_opt_step failed ({rc}): {(self._lib.mzmcts_last_error(None) or b'').decode()}")
+        _native.check_train(self._lib, rc, "mztrain_opt_step")
 
     # ---- what a capture's warm-up puts back ---------------------------------------------------------------
     def snapshot(self):
@@ -197,7 +202,9 @@ class Trainer:
 
     def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False,
                  native_epilogue=False):
-        """graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
+        """The flags choose what produces a step's gradients and what applies them; the step itself is one (_queue_step).
+
+        graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
         hipGraph at the first update_weights and replayed afterwards (the step is launch-bound: ~1 500 launches of
         microsecond kernels for the CartPole network); batches are copied into the capture's static buffers.
 
@@ -225,68 +232,72 @@ class Trainer:
         torch.manual_seed(self.config.seed)
         self.model = models.MuZeroNetwork(self.config)
         self.model.set_weights(copy.deepcopy(initial_checkpoint["weights"]))
-        if device is None:
-            device = torch.device("cuda" if self.config.train_on_gpu else "cpu")
-        self.model.to(torch.device(device))
+        device = torch.device(device if device is not None else "cuda" if self.config.train_on_gpu else "cpu")
+        self.model.to(device)
         self.model.train()
+        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, fc_step
+        # (_fc_setup), then the optimizer's and graph's (_make_optimizer)
         if native_epilogue:
             if self.config.network != "resnet":
                 raise NotImplementedError(f"Trainer(native_epilogue=True) fuses the batch norms of residual networks; "
                                           f"config.network is {self.config.network!r}")
-            if torch.device(device).type != "cuda":
+            if device.type != "cuda":
                 raise NotImplementedError(f"Trainer(native_epilogue=True) runs HIP kernels: the model must be on the GPU, "
-                                          f"not on {torch.device(device)}")
+                                          f"not on {device}")
             self.model.native_training_epilogue(True)
         self._native_norms = [m for m in self.model.modules() if isinstance(m, models.BatchNorm2d)] if native_epilogue else []
         if fc_step:
-            self._fc_setup(torch.device(device))      # before the optimizer: it must hold the re-pointed parameters
+            self._fc_setup(device)      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]
         self._fc_opt = bool(fc_optimizer)
-        if self._fc_opt and self.config.optimizer in ("SGD", "Adam"):
-            self.optimizer = FlatOptimizer(self._fc_lib, self.model, self.flat_weights, self._flat_grad, self.config.optimizer,
-                                           self.config.lr_init, self.config.weight_decay,
-                                           momentum=self.config.momentum if self.config.optimizer == "SGD" else 0.0)
-        elif self.config.optimizer == "SGD":
-            self.optimizer = torch.optim.SGD(self.model.parameters(), lr=self.config.lr_init,
-                                             momentum=self.config.momentum, weight_decay=self.config.weight_decay)
-        elif self.config.optimizer == "Adam":
-            if self._graph_mode:        # step counter and learning rate live on the device, so a replay can move them
-                self._lr = torch.tensor(float(self.config.lr_init), device=torch.device(device))
-                self.optimizer = torch.optim.Adam(self.model.parameters(), lr=self._lr, capturable=True,
-                                                  weight_decay=self.config.weight_decay)
-            else:
-                self.optimizer = torch.optim.Adam(self.model.parameters(), lr=self.config.lr_init,
-                                                  weight_decay=self.config.weight_decay)
-        else:
-            raise NotImplementedError(
-                f"{self.config.optimizer} is not implemented. You can change the optimizer manually in trainer.py.")
-        if self._graph_mode and not self._fc_opt and (self.config.optimizer != "Adam" or torch.device(device).type != "cuda"):
-            raise NotImplementedError("Trainer(graph=True) captures an Adam step on the GPU")
+        self.optimizer = self._make_optimizer(device)
         self._lr_host = float(self.config.lr_init)
         if initial_checkpoint.get("optimizer_state") is not None:
-            portable = copy.deepcopy(self._portable_optimizer_state(initial_checkpoint["optimizer_state"]))
-            if self._fc_opt:
-                self.optimizer.load_state_dict(portable, steps_hint=self.training_step)
-            else:
-                self.optimizer.load_state_dict(portable)
-            saved_lr = self.optimizer.param_groups[0]["lr"]
-            self._lr_host = float(saved_lr)
-            if self._graph_mode and not self._fc_opt:
-                # load_state_dict replaced every param group's settings with the checkpoint's: put the device-resident
-                # learning rate and the capturable flag back (an eager checkpoint carries a float lr, capturable False and
-                # CPU step counters; a graphed one a tensor lr), or update_lr() would fill an orphaned tensor and the
-                # capture of optimizer.step() would break / bake the learning rate in
-                self._lr.fill_(self._lr_host)
-                dev = self._lr.device
-                for group in self.optimizer.param_groups:
-                    group["lr"], group["capturable"] = self._lr, True
-                for state in self.optimizer.state.values():
-                    if "step" in state:
-                        state["step"] = torch.as_tensor(state["step"], dtype=torch.float32).to(dev).reshape(())
+            self._load_optimizer_state(initial_checkpoint["optimizer_state"])
+
+    def _make_optimizer(self, device):
+        """FlatOptimizer (fc_optimizer=True), or torch's SGD / Adam -- in graph mode the capturable Adam."""
+        cfg = self.config
+        if cfg.optimizer not in ("SGD", "Adam"):
+            raise NotImplementedError(
+                f"{cfg.optimizer} is not implemented. You can change the optimizer manually in trainer.py.")
+        if self._graph_mode and not self._fc_opt and (cfg.optimizer != "Adam" or device.type != "cuda"):
+            raise NotImplementedError("Trainer(graph=True) captures an Adam step on the GPU")
+        if self._fc_opt:
+            return FlatOptimizer(self._fc_lib, self.model, self.flat_weights, self._flat_grad, cfg.optimizer, cfg.lr_init,
+                                 cfg.weight_decay, momentum=cfg.momentum if cfg.optimizer == "SGD" else 0.0)
+        if cfg.optimizer == "SGD":
+            return torch.optim.SGD(self.model.parameters(), lr=cfg.lr_init, momentum=cfg.momentum,
+                                   weight_decay=cfg.weight_decay)
+        if not self._graph_mode:
+            return torch.optim.Adam(self.model.parameters(), lr=cfg.lr_init, weight_decay=cfg.weight_decay)
+        # step counter and learning rate live on the device, so a replay can move them
+        self._lr = torch.tensor(float(cfg.lr_init), device=device)
+        return torch.optim.Adam(self.model.parameters(), lr=self._lr, capturable=True, weight_decay=cfg.weight_decay)
+
+    def _load_optimizer_state(self, state):
+        """A checkpoint's optimizer state, eager or graphed, torch's or FlatOptimizer's (they share a format)."""
+        portable = copy.deepcopy(self._portable_optimizer_state(state))
+        if self._fc_opt:
+            self.optimizer.load_state_dict(portable, steps_hint=self.training_step)
+        else:
+            self.optimizer.load_state_dict(portable)
+        self._lr_host = float(self.optimizer.param_groups[0]["lr"])
+        if self._graph_mode and not self._fc_opt:
+            # load_state_dict replaced every param group's settings with the checkpoint's: put the device-resident
+            # learning rate and the capturable flag back (an eager checkpoint carries a float lr, capturable False and
+            # CPU step counters; a graphed one a tensor lr), or update_lr() would fill an orphaned tensor and the
+            # capture of optimizer.step() would break / bake the learning rate in
+            self._lr.fill_(self._lr_host)
+            for group in self.optimizer.param_groups:
+                group["lr"], group["capturable"] = self._lr, True
+            for entry in self.optimizer.state.values():
+                if "step" in entry:
+                    entry["step"] = torch.as_tensor(entry["step"], dtype=torch.float32).to(self._lr.device).reshape(())
 
     # ---- the fully-connected step as HIP launches (include/mztrain.h mztrain_fc_*) -------------------------
     def _fc_setup(self, device):
-        from . import _native, weights
+        from . import weights
         cfg = self.config
         if cfg.network != "fullyconnected":
             raise NotImplementedError(f"Trainer(fc_step=True) differentiates fully-connected networks; config.network is "
@@ -332,11 +343,7 @@ class Trainer:
                 ctypes.byref(self._fc_desc), len(self.config.action_space), int(self.config.support_size),
                 self.flat_weights.flat.data_ptr(), self.flat_weights.numel, self._flat_grad.data_ptr(), batch, steps,
                 self._fc_device.index, ctypes.byref(handle))
-        if rc != 0:
-            message = (self._fc_lib.mzmcts_last_error(None) or b"").decode()
-            if rc == -1:
-                raise NotImplementedError(f"Trainer(fc_step=True): {message}")
-            raise RuntimeError(f"mztrain_fc_create failed ({rc}): {message}")
+        _native.check_train(self._fc_lib, rc, "mztrain_fc_create", refusal="Trainer(fc_step=True)")
         self._fc_release()
         self._fc, self._fc_max = handle, (batch, steps)
         self._fc_live[0] = handle
@@ -358,7 +365,6 @@ class Trainer:
     def _fc_queue(self, b):
         """Queue forward, loss, backward and weight gradients of batch `b` on the current stream: the flat gradient buffer
         is overwritten whole.  Returns (per-sample loss [B], head sums [3, B], priorities [B, K+1]) as device tensors."""
-        from . import _native
         values = b["values"]
         size, steps = values.shape
         handle = self._fc_handle(size, steps)
@@ -368,9 +374,7 @@ class Trainer:
         assert actions.dtype == torch.int64 and obs.shape[1] == self._fc_desc.observation_floats
         tv, tr, tp, gs = (b[key].contiguous() for key in ("values", "rewards", "policies", "gradient_scales"))
         weight = b["weights"].contiguous() if b["weights"] is not None else None
-        sample_loss = torch.empty(size, device=dev)
-        head_sums = torch.empty((3, size), device=dev)
-        priorities = torch.empty((size, steps), device=dev)
+        sample_loss, head_sums, priorities = _loss_outputs(size, steps, dev)
         args = _native.MzTrainFcArgs(
             observations=obs.data_ptr(), actions=actions.data_ptr(), target_value=tv.data_ptr(), target_reward=tr.data_ptr(),
             target_policy=tp.data_ptr(), gradient_scale=gs.data_ptr(),
@@ -378,42 +382,8 @@ class Trainer:
             value_loss_weight=float(self.config.value_loss_weight), per_alpha=float(self.config.PER_alpha),
             sample_loss=sample_loss.data_ptr(), head_sums=head_sums.data_ptr(), priorities=priorities.data_ptr())
         rc = self._fc_lib.mztrain_fc_step(handle, ctypes.byref(args), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mztrain_fc_step failed ({rc}): {(self._fc_lib.mzmcts_last_error(None) or b'').decode()}")
+        _native.check_train(self._fc_lib, rc, "mztrain_fc_step")
         return sample_loss, head_sums, priorities
-
-    def _fc_step(self, b):
-        """One eager step: the four launches, then the optimizer; the report tensor and the priorities stay on the device."""
-        sample_loss, head_sums, priorities = self._fc_queue(b)
-        self.optimizer.step()
-        return torch.cat([sample_loss.mean().reshape(1), head_sums.mean(dim=1)]), priorities
-
-    def _capture_fc(self, b):
-        """_capture for the fc_step path: the gradient buffer is overwritten by every step, so nothing is zeroed."""
-        self._fc_handle(*b["values"].shape)
-        self._static = {k: (v.clone() if v is not None else None) for k, v in b.items()}
-        dev = b["values"].device
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        state = (copy.deepcopy(self.model.state_dict()),
-                 self.optimizer.snapshot() if self._fc_opt else copy.deepcopy(self.optimizer.state_dict()))
-        with torch.cuda.stream(side):
-            for _ in range(3):                       # warm-up steps, undone below
-                self._fc_step(self._static)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.model.load_state_dict(state[0])         # in place: the parameters stay views of the flat buffer
-        if self._fc_opt:
-            self.optimizer.restore(state[1])         # the moments and the count of steps done, as they were
-        else:
-            live = self.optimizer.state_dict()["state"]
-            for index, entry in live.items():
-                saved = state[1]["state"].get(index)
-                for name, value in entry.items():
-                    if torch.is_tensor(value):
-                        value.copy_(saved[name]) if saved is not None else value.zero_()
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self._graph_out = self._fc_step(self._static)
 
     @staticmethod
     def _portable_optimizer_state(state):
@@ -465,8 +435,9 @@ class Trainer:
     def train_steps(self, replay_buffer, n):
         """`n` training steps on a device-sampling replay buffer (ReplayBuffer(device_sampling=True)): get_batch ->
         update_lr -> step -> update_priorities, queued back to back on the current stream with no synchronisation in
-        between; in graph mode the batch is written straight into the capture's static buffers.  Returns the last step's
-        (total, value, reward, policy) losses, read back with one synchronisation at the end."""
+        between; in graph mode the batch is written straight into the capture's static buffers.  The step is
+        update_weights' (_queue_step), so an eager trainer with native_loss = False takes the torch expression here too.
+        Returns the last step's (total, value, reward, policy) losses, read back with one synchronisation at the end."""
         if not getattr(replay_buffer, "device_sampling", False):
             raise ValueError("train_steps needs a ReplayBuffer(device_sampling=True)")
         device = next(self.model.parameters()).device
@@ -476,33 +447,13 @@ class Trainer:
         for _ in range(int(n)):
             if self._graph_mode and self._graph is not None:
                 index_batch, _batch = replay_buffer.get_batch(out=self._static)
-                b = None
+                b = None                                 # already where the capture reads it: nothing to copy
             else:
                 index_batch, (obs, act, val, rew, pol, weights, scales) = replay_buffer.get_batch()
                 b = {"observations": obs, "actions": act.unsqueeze(-1), "values": val, "rewards": rew, "policies": pol,
                      "weights": weights if self.config.PER else None, "gradient_scales": scales}
             self.update_lr()
-            if self._graph_mode:
-                if self._graph is None:
-                    self._capture(b)
-                    for key, value in b.items():
-                        if value is not None:
-                            self._static[key].copy_(value)
-                self._replay()
-                report, priorities = self._graph_out
-            elif self._fc is not None:
-                report, priorities = self._fc_step(b)
-            else:
-                steps = self._unroll(b["observations"], b["actions"])
-                sample_loss, head_sums, priorities = _UnrollLoss.apply(
-                    torch.stack([s[0] for s in steps]), torch.stack([s[1] for s in steps]),
-                    torch.stack([s[2] for s in steps]), b, self.config.support_size, self.config.value_loss_weight,
-                    self.config.PER_alpha)
-                loss = sample_loss.mean()
-                self.optimizer.zero_grad()
-                loss.backward()
-                self.optimizer.step()
-                report = torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)])
+            report, priorities = self._step(b)
             self.training_step += 1
             if self.config.PER:
                 replay_buffer.update_priorities(priorities, index_batch)
@@ -542,18 +493,61 @@ class Trainer:
         return steps
 
     def update_weights(self, batch):
-        cfg = self.config
-        b = self._batch_on_device(batch)
-        if self._graph_mode:
-            return self._step_graphed(b)
+        report, new_priorities = self._step(self._batch_on_device(batch))
+        self.training_step += 1
+        total_loss, value_loss, reward_loss, policy_loss = report.tolist()       # the step's one device-to-host report
+        return new_priorities.cpu().numpy(), total_loss, value_loss, reward_loss, policy_loss
+
+    def _step(self, b):
+        """One step on the batch dict `b`, eager or (graph mode) as a hipGraph replay: (report, priorities) as device
+        tensors, report = the (total, value, reward, policy) losses.  `b` None: the batch is in the static buffers."""
+        if not self._graph_mode:
+            return self._queue_step(b)
+        if self._graph is None:
+            self._capture(b)
+        if b is not None:
+            self._to_static(b)
+        self._replay()
+        return self._graph_out
+
+    def _queue_step(self, b):
+        """Queue one whole training step on the current stream -- what update_weights, train_steps, a capture's warm-up and
+        the capture itself run.  The ways differ in what produces the gradients, nothing else."""
         if self._fc is not None:
-            report, priorities = self._fc_step(b)
-            self.training_step += 1
-            report = report.tolist()
-            return (priorities.cpu().numpy(), report[0], report[1], report[2], report[3])
+            # four HIP launches overwrite the flat gradient buffer whole.  No zero_grad here, ever: with torch's optimizer
+            # set_to_none would drop the p.grad views into that buffer
+            sample_loss, head_sums, priorities = self._fc_queue(b)
+            loss = sample_loss.mean()
+        else:
+            # autograd through the unroll, under the loss as one HIP launch or, on the CPU and with native_loss = False,
+            # as the torch expression (a capture always takes the launch).  The gradients are None from here to backward,
+            # so a capture's backward allocates them from the graph's pool
+            if b["values"].is_cuda and (self.native_loss or self._graph_mode):
+                sample_loss, head_sums, priorities = self._loss_native(b)
+            else:
+                sample_loss, head_sums, priorities = self._loss_torch(b)
+            loss = sample_loss.mean()
+            self.optimizer.zero_grad(set_to_none=True)
+            loss.backward()
+        self.optimizer.step()
+        return torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)]), priorities
+
+    def _loss_native(self, b):
+        """Everything between the network's outputs and `loss.mean()` in one HIP launch (_UnrollLoss): the logits of all
+        unrolled positions are stacked step-major, the kernel returns the per-sample loss and keeps its gradient for
+        backward."""
         steps = self._unroll(b["observations"], b["actions"])
-        if b["values"].is_cuda and self.native_loss:
-            return self._step_native(b, steps)
+        cfg = self.config
+        return _UnrollLoss.apply(torch.stack([s[0] for s in steps]), torch.stack([s[1] for s in steps]),
+                                 torch.stack([s[2] for s in steps]), b, cfg.support_size, cfg.value_loss_weight,
+                                 cfg.PER_alpha)
+
+    def _loss_torch(self, b):
+        """The reference's loss as a torch expression, in _loss_native's form: (per-sample loss [B], head sums, priorities
+        [B, K+1]).  The head sums come back already averaged over the batch, as [3, 1], each by the reference's own
+        `.mean()` of a [B] vector: the mean over that last axis of one entry is exact."""
+        cfg = self.config
+        steps = self._unroll(b["observations"], b["actions"])
         value_targets = models.scalar_to_support(b["values"], cfg.support_size)
         reward_targets = models.scalar_to_support(b["rewards"], cfg.support_size)
         priorities = torch.zeros_like(b["values"])
@@ -575,50 +569,14 @@ class Trainer:
         loss = sums["value"] * cfg.value_loss_weight + sums["reward"] + sums["policy"]
         if cfg.PER:
             loss = loss * b["weights"]           # importance-sampling correction of the prioritised replay
-        loss = loss.mean()
-        self.optimizer.zero_grad()
-        loss.backward()
-        self.optimizer.step()
-        self.training_step += 1
-        return (priorities.detach().cpu().numpy(), loss.item(), sums["value"].mean().item(),
-                sums["reward"].mean().item(), sums["policy"].mean().item())
+        head_means = torch.stack([sums[head].mean().detach() for head in ("value", "reward", "policy")])
+        return loss, head_means.unsqueeze(1), priorities
 
-    def _step_native(self, b, steps):
-        """The same step with everything between the network's outputs and `loss.mean()` in one HIP launch
-        (_UnrollLoss): the logits of all unrolled positions are stacked step-major, the kernel returns the
-        per-sample loss and keeps its gradient for backward."""
-        cfg = self.config
-        sample_loss, head_sums, priorities = _UnrollLoss.apply(
-            torch.stack([s[0] for s in steps]), torch.stack([s[1] for s in steps]), torch.stack([s[2] for s in steps]), b,
-            cfg.support_size, cfg.value_loss_weight, cfg.PER_alpha)
-        loss = sample_loss.mean()
-        self.optimizer.zero_grad()
-        loss.backward()
-        self.optimizer.step()
-        self.training_step += 1
-        report = torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)]).tolist()     # one device-to-host copy
-        return (priorities.cpu().numpy(), report[0], report[1], report[2], report[3])
-
-    def _loss_native(self, b):
-        steps = self._unroll(b["observations"], b["actions"])
-        cfg = self.config
-        return _UnrollLoss.apply(torch.stack([s[0] for s in steps]), torch.stack([s[1] for s in steps]),
-                                 torch.stack([s[2] for s in steps]), b, cfg.support_size, cfg.value_loss_weight,
-                                 cfg.PER_alpha)
-
-    def _step_graphed(self, b):
-        """update_weights as one hipGraph replay: the first call warms the step up eagerly on a side stream (what
-        stream capture requires), captures it on static copies of the batch, and every call copies its batch in,
-        replays, and reads loss / head sums / priorities out of the capture's output tensors."""
-        if self._graph is None:
-            self._capture(b)
+    # ---- graph mode: the step captured once, then replayed ----------------------------------------------
+    def _to_static(self, b):
         for key, value in b.items():
             if value is not None:
                 self._static[key].copy_(value)
-        self._replay()
-        self.training_step += 1
-        report = self._graph_out[0].tolist()
-        return (self._graph_out[1].cpu().numpy(), report[0], report[1], report[2], report[3])
 
     def _replay(self):
         self._graph.replay()
@@ -626,37 +584,44 @@ class Trainer:
             norm._folded = None
 
     def _capture(self, b):
-        """Warm the step up on a side stream and capture it on static copies of the batch `b` (not executed)."""
-        if self._fc is not None:
-            return self._capture_fc(b)
+        """Warm _queue_step up on a side stream (what stream capture requires) and capture it into a hipGraph on static
+        copies of the batch `b`; the capture itself does not execute the step.  Every later step copies its batch in,
+        replays, and reads report and priorities out of the capture's output tensors (_graph_out).  On the fc_step way
+        the warm-up sizes the handle for this batch; a larger one after the capture is refused (_fc_handle)."""
         self._static = {k: (v.clone() if v is not None else None) for k, v in b.items()}
-        side = torch.cuda.Stream(device=b["values"].device)
-        side.wait_stream(torch.cuda.current_stream(b["values"].device))
-        state = (copy.deepcopy(self.model.state_dict()), copy.deepcopy(self.optimizer.state_dict()))
+        dev = b["values"].device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        weights, optimizer = copy.deepcopy(self.model.state_dict()), self._optimizer_snapshot()
         with torch.cuda.stream(side):
             for _ in range(3):                       # warm-up steps, undone below
-                self.optimizer.zero_grad(set_to_none=True)
-                self._loss_native(self._static)[0].mean().backward()
-                self.optimizer.step()
-        torch.cuda.current_stream(b["values"].device).wait_stream(side)
-        self.model.load_state_dict(state[0])
-        # the optimizer's moments and step counters must exist BEFORE the capture (created inside it they would be
-        # re-initialised by every replay): keep the tensors the warm-up made, put the saved values back in place
-        live = self.optimizer.state_dict()["state"]
-        for index, entry in live.items():
-            saved = state[1]["state"].get(index)
-            for name, value in entry.items():
-                if torch.is_tensor(value):
-                    value.copy_(saved[name]) if saved is not None else value.zero_()
-        self.optimizer.zero_grad(set_to_none=True)
+                self._queue_step(self._static)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.model.load_state_dict(weights)          # in place: fc_step's parameters stay views of the flat buffer
+        self._optimizer_restore(optimizer)
+        if self._fc is None:
+            # the warm-up's gradients go before the capture begins, not at the zero_grad inside it: the capture's
+            # backward allocates them anew from the graph's pool either way (same bits), but the allocator then enters
+            # the capture with nothing of the warm-up alive, which the step times of the residual networks prefer
+            self.optimizer.zero_grad(set_to_none=True)
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
-            sample_loss, head_sums, priorities = self._loss_native(self._static)
-            loss = sample_loss.mean()
-            loss.backward()
-            self.optimizer.step()
-            self._graph_out = (torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)]), priorities)
-        # (the capture itself does not execute the step)
+            self._graph_out = self._queue_step(self._static)
+
+    def _optimizer_snapshot(self):
+        return self.optimizer.snapshot() if self._fc_opt else copy.deepcopy(self.optimizer.state_dict())
+
+    def _optimizer_restore(self, saved):
+        """Undo a capture's warm-up steps on the optimizer, in place."""
+        if self._fc_opt:
+            return self.optimizer.restore(saved)     # the moments and the count of steps done, as they were
+        # the optimizer's moments and step counters must exist BEFORE the capture (created inside it they would be
+        # re-initialised by every replay): keep the tensors the warm-up made, put the saved values back in place
+        for index, entry in self.optimizer.state_dict()["state"].items():
+            before = saved["state"].get(index)
+            for name, value in entry.items():
+                if torch.is_tensor(value):
+                    value.copy_(before[name]) if before is not None else value.zero_()
 
     def update_lr(self):
         lr = self.config.lr_init * self.config.lr_decay_rate ** (self.training_step / self.config.lr_decay_steps)
