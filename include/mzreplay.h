@@ -140,11 +140,18 @@ int mzreplay_read_games(mzreplay *store, int32_t n, const int32_t *slots, int32_
                         void *stream);
 
 /* ---- finished self-play games filed on the device ---------------------------------------------------------------------
- * The producer side of the store without the host: a filer is owned by a store (one per store) and bound to one actor of
- * E envs.  It keeps, in device memory, one running row per env in the store's own slot layout and the store-wide counters
- * (next game id, games stored, total_samples, steps played), and turns a whole move batch -- read where the search engine
- * and the environment kernels left it -- into stored games in three launches with no host decision in between
- * (csrc/replay_filer.h holds the index arithmetic):
+ * The producer side of the store without the host: a filer is owned by a store and bound to one actor of E envs; a store
+ * may have any number of filers, each with a stream of its own.  A filer keeps, in device memory, one running row per env
+ * in the store's own slot layout, its list of filed games and its error word.  The store-wide counters (next game id,
+ * games stored, total_samples, steps played) live in one device block of the STORE, which every filer's kernels read and
+ * move.  The store numbers games in the order of the mzreplay_filer_file calls made on it, whatever stream each call runs
+ * on: a call makes its stream wait for the store's "last filing" event before its first launch and records that event
+ * behind its last one, so the calls of all filers run one after the other on the device, in the order the host made them
+ * (no host wait, no allocation and no extra launch; one filer on one stream runs as it would without the event; the
+ * calls are made from one host thread, or serialised by the caller).  A call may evict games another filer stored.
+ * A filer turns a whole move batch -- read where the search engine and the environment kernels left it -- into stored
+ * games in three launches with no host decision in between (csrc/replay_filer.h holds the index arithmetic; DESIGN.md
+ * sections 7.9 and 7.9.1):
  *   1. per env and move what mzhist_file does: child_visits[len][legal[i]] = double(visits[i]) / S over a zeroed row,
  *      root_values[len] = root_value_sum / S (IEEE fp64 divisions), actions / rewards / observations / to_play[len + 1];
  *      on `done` the row is a finished game of len moves and the next one starts with obs_next, action 0, reward 0 and the
@@ -163,6 +170,9 @@ int mzreplay_read_games(mzreplay *store, int32_t n, const int32_t *slots, int32_
  * mzreplay_filer_file leaves it alone).  The games of the calls BEFORE the refused one are not lost: the failing sync keeps
  * them, the following sync hands them out, and the store and the counters are those of a filer that was given only those
  * calls (tests/test_gpu_replay_filer_forms.py).
+ * A refusal stays with its filer: the error word refuses that filer's later unsynced calls and no other filer's, and a
+ * refused call moves no shared counter, so the other filers' ids stay contiguous around it
+ * (tests/test_gpu_replay_filer_shared.py).
  * Errors of these calls are read with mzreplay_last_error(store). */
 typedef struct mzreplay_filer mzreplay_filer;
 
@@ -201,13 +211,21 @@ void mzreplay_filer_destroy(mzreplay_filer *filer);
 int mzreplay_filer_begin(mzreplay_filer *filer, const float *first_observations, const int32_t *first_to_play,
                          void *stream);
 /* The store-wide counters as the host knows them: counters[4] = next game id, games stored, total_samples, steps played.
- * At the start, and after every mzreplay_add_games into a store that has a filer.  Asynchronous (the values are copied). */
+ * At the start, and after every mzreplay_add_games into a store that has a filer; through any of the store's filers (the
+ * block is the store's).  Waits for the filings queued so far; the values are copied. */
 int mzreplay_filer_set_counters(mzreplay_filer *filer, const int64_t *counters, void *stream);
-/* File a move batch.  Asynchronous on `stream`: queue it behind the batch's last environment kernel. */
+/* File a move batch.  Asynchronous on `stream`: queue it behind the batch's last environment kernel.  The call's games
+ * take the ids that follow those of the call made before it on this store, through whichever filer and stream. */
 int mzreplay_filer_file(mzreplay_filer *filer, const mzreplay_file_moves *moves, void *stream);
-/* The games filed since the last sync, as host arrays of 4 bytes per game (valid until the next call on this filer), the
- * id of the first of them (they are consecutive), the counters (counters[4] as above, may be NULL), and the device error
- * word turned into a message.  The only data that comes back.  Blocking. */
+/* The games this filer filed since its last sync, as host arrays (valid until the next call on this filer): 4 bytes per
+ * game each for the env and the length, the id the store gave every game (ascending; consecutive only while no other
+ * filer's call came in between), the store's counters once every filing queued so far has run (counters[4] as above, may
+ * be NULL), and the filer's device error word turned into a message.  The only data that comes back.  Blocking; `stream`
+ * waits for the store's last filing, so it need not be the filer's own. */
+int mzreplay_filer_sync_ids(mzreplay_filer *filer, int32_t *n_new, const int32_t **env_index, const int32_t **lengths,
+                            const int64_t **game_ids, int64_t *counters, void *stream);
+/* mzreplay_filer_sync_ids for a store with one filer, whose games are consecutive: the id of the first of them instead
+ * of the list.  Fails on a store with more than one filer (use mzreplay_filer_sync_ids). */
 int mzreplay_filer_sync(mzreplay_filer *filer, int32_t *n_new, const int32_t **env_index, const int32_t **lengths,
                         int64_t *first_game_id, int64_t *counters, void *stream);
 /* Moves played so far in every env's running game: host i32[E] (what mzhist_lengths gives for the host filer).  Blocking. */

@@ -254,6 +254,8 @@ PROTOTYPES = {
     "mzreplay_filer_file": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzreplay_filer_sync": (ctypes.c_int, [c_void, c_i32_p, ctypes.POINTER(c_void), ctypes.POINTER(c_void), c_i64_p, c_i64_p,
                                            c_void]),
+    "mzreplay_filer_sync_ids": (ctypes.c_int, [c_void, c_i32_p, ctypes.POINTER(c_void), ctypes.POINTER(c_void),
+                                               ctypes.POINTER(c_void), c_i64_p, c_void]),
     "mzreplay_filer_lengths": (ctypes.c_int, [c_void, c_i32_p, c_void]),
     "mzreplay_filer_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_f32_p, c_f32_p, c_void]),
     "mzreplay_reanalyse_enable": (ctypes.c_int, [c_void, ctypes.c_uint32]),

@@ -794,8 +794,9 @@ __global__ __launch_bounds__(kReanalyseThreads) void reanalyse_fc_kernel(StorePa
 //                             observation floats; a finished game's row goes to its slot in coalesced copies
 //   filer_priorities_kernel   a fixed grid strides over the call's surviving games: priorities_kernel's arithmetic into the
 //                             priority arrays (the sampler's when it is on, with the game id)
-struct FilerState {                  // one block of device memory, read back whole by mzreplay_filer_sync
-    mz::filer::Counters counters;
+// The store-wide counters are one device block of the store (FilerParams::shared), which the calls of every filer move in
+// the order the host made them (mzreplay_filer_file chains the calls with the store's "last filing" event).
+struct FilerState {                  // a filer's own block of device memory, read back whole by mzreplay_filer_sync
     int32_t pending;                 // games in the list since the last sync
     int32_t error;                   // mz::filer::kErr* bits
 };
@@ -813,9 +814,11 @@ struct FilerParams {
     int32_t* count;
     int32_t* offset;
     FilerState* state;
+    mz::filer::Counters* shared;     // the store's counters: one block for all its filers
     mz::filer::Call* call;
     int32_t* list_env;               // [list_cap] games filed since the last sync
     int32_t* list_len;
+    int64_t* list_id;                // (another filer's calls may lie between two of this one's: ids are not consecutive)
     int32_t list_cap;
     float* priorities;               // [G][L], [G]: the sampler's arrays when it is on, else the filer's own
     float* game_priority;
@@ -876,7 +879,7 @@ __global__ __launch_bounds__(kScanThreads) void filer_scan_kernel(StoreParams p,
         carry += scan[cur][kScanThreads - 1];
         __syncthreads();
     }
-    const mz::filer::Counters before = f.state->counters;
+    const mz::filer::Counters before = *f.shared;
     const bool refused = f.state->error != 0;
     const int64_t list_room = static_cast<int64_t>(f.list_cap) - f.state->pending;
     // (the host sized the list for E x M games per unsynced call: a call that does not fit is refused whole)
@@ -896,7 +899,7 @@ __global__ __launch_bounds__(kScanThreads) void filer_scan_kernel(StoreParams p,
     if (t == 0) {
         if (no_room) atomicOr(&f.state->error, mz::filer::kErrList);
         // (the new games' own lengths are added by the wavefronts that file them)
-        f.state->counters = mz::filer::counters_after(before, call.n_new, p.G, 0, 0, evicted_s[0]);
+        *f.shared = mz::filer::counters_after(before, call.n_new, p.G, 0, 0, evicted_s[0]);
         f.state->pending += call.n_new;
         *f.call = call;
     }
@@ -975,9 +978,10 @@ __global__ __launch_bounds__(kFilerWave) void filer_append_kernel(StoreParams p,
             if (lane == 0) {
                 f.list_env[call.list_base + j] = e;
                 f.list_len[call.list_base + j] = len;
-                atomicAdd(reinterpret_cast<unsigned long long*>(&f.state->counters.steps_played), static_cast<unsigned long long>(len));
+                f.list_id[call.list_base + j] = mz::filer::game_id(call, j);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&f.shared->steps_played), static_cast<unsigned long long>(len));
                 if (mz::filer::survives(call, j))
-                    atomicAdd(reinterpret_cast<unsigned long long*>(&f.state->counters.total_samples), static_cast<unsigned long long>(len));
+                    atomicAdd(reinterpret_cast<unsigned long long*>(&f.shared->total_samples), static_cast<unsigned long long>(len));
             }
             __syncthreads();   // the copies have read the row before the next game starts in it
             len = 0;
@@ -1066,7 +1070,11 @@ struct mzreplay {
     SamplerParams sp{};
     int64_t next_game_id = 0;        // id of the next game mzreplay_add_games stores (sampler on)
     size_t sampler_batch = 0;        // samples the per-batch scratch holds
-    mzreplay_filer* filer = nullptr; // the device filer bound to this store (at most one)
+    std::vector<mzreplay_filer*> filers;         // the device filers bound to this store, one per filing actor
+    mz::filer::Counters* filer_counters = nullptr;   // the store-wide counters every filer's kernels move (device)
+    hipEvent_t last_filing = nullptr;            // recorded behind every mzreplay_filer_file: the next one waits for it
+    float* filer_priorities = nullptr;           // [G][L], [G]: what the filers write while the sampler is off
+    float* filer_game_priority = nullptr;
     bool reanalyse_on = false;       // mzreplay_reanalyse_enable: the pass's stream and scratch exist
     ReanalyseParams rp{};
     bool re_fc_ready = false;        // mzreplay_reanalyse_fc_configure
@@ -1084,9 +1092,10 @@ struct mzreplay_filer {
     int32_t* d_gather_slots = nullptr;   // mzreplay_filer_priorities' staging
     float* d_gather = nullptr;
     size_t gather_games = 0;
-    bool own_priorities = false;     // f.priorities / f.game_priority are the filer's own arrays (sampler off)
     std::vector<int32_t> h_env, h_len;   // games drained from the device list since the last sync
+    std::vector<int64_t> h_id;
     std::vector<int32_t> out_env, out_len;   // what the last mzreplay_filer_sync handed out
+    std::vector<int64_t> out_id;
 };
 
 namespace {
@@ -1174,7 +1183,8 @@ int mzreplay_create(const mzreplay_config* c, mzreplay** out) {
 
 void mzreplay_destroy(mzreplay* s) {
     if (!s) return;
-    if (s->filer) mzreplay_filer_destroy(s->filer);
+    while (!s->filers.empty()) mzreplay_filer_destroy(s->filers.back());
+    if (s->last_filing) (void)hipEventDestroy(s->last_filing);
     for (void* ptr : s->allocs) (void)hipFree(ptr);
     delete s;
 }
@@ -1518,18 +1528,25 @@ int filer_alloc(mzreplay_filer* fl, T** out, size_t count) {
 }
 
 // the games of the unsynced calls, moved from the device list to the host arrays mzreplay_filer_sync hands out
-int filer_drain(mzreplay_filer* fl, FilerState* state_out, hipStream_t stream) {
+// (`stream` need not be the filer's own: it waits for the store's last filing, behind which every earlier one has run;
+// the counters it reads are then those after every filing queued so far)
+int filer_drain(mzreplay_filer* fl, FilerState* state_out, mz::filer::Counters* counters_out, hipStream_t stream) {
     mzreplay* s = fl->store;
     FilerState st{};
+    mz::filer::Counters counters{};
+    RP_HIP(s, hipStreamWaitEvent(stream, s->last_filing, 0));
     RP_HIP(s, hipMemcpyAsync(&st, fl->f.state, sizeof(st), hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipMemcpyAsync(&counters, fl->f.shared, sizeof(counters), hipMemcpyDeviceToHost, stream));
     RP_HIP(s, hipStreamSynchronize(stream));
     if (st.pending < 0 || st.pending > fl->f.list_cap) return fail(s, "mzreplay_filer_sync: the device list is corrupt");
     if (st.pending > 0) {
         const size_t have = fl->h_env.size(), more = static_cast<size_t>(st.pending);
         fl->h_env.resize(have + more);
         fl->h_len.resize(have + more);
+        fl->h_id.resize(have + more);
         RP_HIP(s, hipMemcpyAsync(fl->h_env.data() + have, fl->f.list_env, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
         RP_HIP(s, hipMemcpyAsync(fl->h_len.data() + have, fl->f.list_len, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
+        RP_HIP(s, hipMemcpyAsync(fl->h_id.data() + have, fl->f.list_id, sizeof(int64_t) * more, hipMemcpyDeviceToHost, stream));
     }
     // pending starts again at zero; the error word (adjacent) only for the sync, which reports it: a drain between two
     // unsynced calls leaves it standing, so the device goes on refusing and the next sync still sees it
@@ -1537,6 +1554,7 @@ int filer_drain(mzreplay_filer* fl, FilerState* state_out, hipStream_t stream) {
     RP_HIP(s, hipStreamSynchronize(stream));
     fl->pending_bound = 0;
     if (state_out) *state_out = st;
+    if (counters_out) *counters_out = counters;
     return 0;
 }
 }  // namespace
@@ -1547,10 +1565,12 @@ int mzreplay_filer_create(mzreplay* s, int32_t num_envs, mzreplay_filer** out) {
     if (!s || !out) return fail(s, "mzreplay_filer_create: null store or output");
     *out = nullptr;
     if (num_envs <= 0) return fail(s, "mzreplay_filer_create: num_envs must be positive");
-    if (s->filer) return fail(s, "mzreplay_filer_create: the store already has a filer (one actor files into one store)");
     // (a store with stacked_observations > 0 is filed like any other: the rows hold the plain observations the env
     // kernels produced, and stacked_element stacks them when a batch is built; the actor's frame stack feeds the searches)
     RP_HIP(s, hipSetDevice(s->cfg.device));
+    // what the store's filers share exists from the first of them on: the counters' block and the event that orders the calls
+    if (!s->filer_counters && dev_alloc(s, &s->filer_counters, 1)) return -1;
+    if (!s->last_filing) RP_HIP(s, hipEventCreateWithFlags(&s->last_filing, hipEventDisableTiming));
     mzreplay_filer* fl = new mzreplay_filer();
     fl->store = s;
     FilerParams& f = fl->f;
@@ -1575,7 +1595,8 @@ int mzreplay_filer_create(mzreplay* s, int32_t num_envs, mzreplay_filer** out) {
         mzreplay_filer_destroy(fl);
         return fail(s, msg.empty() ? "mzreplay_filer_create: device allocation failed" : msg);
     }
-    s->filer = fl;
+    f.shared = s->filer_counters;
+    s->filers.push_back(fl);
     *out = fl;
     return 0;
 }
@@ -1584,7 +1605,10 @@ void mzreplay_filer_destroy(mzreplay_filer* fl) {
     if (!fl) return;
     (void)hipDeviceSynchronize();
     for (void* ptr : fl->allocs) (void)hipFree(ptr);
-    if (fl->store && fl->store->filer == fl) fl->store->filer = nullptr;
+    if (fl->store) {
+        std::vector<mzreplay_filer*>& all = fl->store->filers;
+        all.erase(std::remove(all.begin(), all.end(), fl), all.end());
+    }
     delete fl;
 }
 
@@ -1604,7 +1628,8 @@ int mzreplay_filer_set_counters(mzreplay_filer* fl, const int64_t* counters, voi
         return fail(s, "mzreplay_filer_set_counters: counters out of range");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     mz::filer::Counters c{counters[0], counters[1], counters[2], counters[3]};
-    RP_HIP(s, hipMemcpyAsync(&fl->f.state->counters, &c, sizeof(c), hipMemcpyHostToDevice, stream));
+    RP_HIP(s, hipStreamWaitEvent(stream, s->last_filing, 0));   // (behind the filings queued so far, on whichever stream)
+    RP_HIP(s, hipMemcpyAsync(fl->f.shared, &c, sizeof(c), hipMemcpyHostToDevice, stream));
     RP_HIP(s, hipStreamSynchronize(stream));   // (c is a local)
     s->next_game_id = counters[0];
     return 0;
@@ -1627,12 +1652,16 @@ int mzreplay_filer_file(mzreplay_filer* fl, const mzreplay_file_moves* mv, void*
     if (fl->pending_bound + most > f.list_cap) {
         // the list grows: what it holds goes to the host first (blocking, like any allocation; a warmed-up actor that
         // syncs after every batch does not come here again)
-        if (filer_drain(fl, nullptr, stream)) return -1;
+        if (filer_drain(fl, nullptr, nullptr, stream)) return -1;
         if (most > f.list_cap) {
             int32_t *env = nullptr, *len = nullptr;
-            if (filer_alloc(fl, &env, static_cast<size_t>(most)) || filer_alloc(fl, &len, static_cast<size_t>(most))) return -1;
+            int64_t* id = nullptr;
+            if (filer_alloc(fl, &env, static_cast<size_t>(most)) || filer_alloc(fl, &len, static_cast<size_t>(most)) ||
+                filer_alloc(fl, &id, static_cast<size_t>(most)))
+                return -1;
             f.list_env = env;
             f.list_len = len;
+            f.list_id = id;
             f.list_cap = static_cast<int32_t>(most);
         }
     }
@@ -1640,13 +1669,19 @@ int mzreplay_filer_file(mzreplay_filer* fl, const mzreplay_file_moves* mv, void*
         f.priorities = s->sp.priorities;
         f.game_priority = s->sp.game_priority;
         f.game_id = s->sp.game_id;
-    } else if (!fl->own_priorities) {
-        if (filer_alloc(fl, &f.priorities, static_cast<size_t>(p.G) * p.L) || filer_alloc(fl, &f.game_priority, static_cast<size_t>(p.G)))
+    } else {
+        // (the store's, not the filer's: mzreplay_filer_priorities reads a slot whichever filer wrote it)
+        if (!s->filer_priorities &&
+            (dev_alloc(s, &s->filer_priorities, static_cast<size_t>(p.G) * p.L) || dev_alloc(s, &s->filer_game_priority, static_cast<size_t>(p.G))))
             return -1;
+        f.priorities = s->filer_priorities;
+        f.game_priority = s->filer_game_priority;
         f.game_id = nullptr;
-        fl->own_priorities = true;
     }
     fl->pending_bound += most;
+    // the store numbers games in the order of these calls: this one's launches run behind the last launch of the call
+    // made before it, on whichever stream that was queued
+    RP_HIP(s, hipStreamWaitEvent(stream, s->last_filing, 0));
     filer_count_kernel<<<dim3((f.E + 255) / 256), dim3(256), 0, stream>>>(p, f, *mv);
     RP_HIP(s, hipGetLastError());
     filer_scan_kernel<<<dim3(1), dim3(kScanThreads), 0, stream>>>(p, f);
@@ -1662,21 +1697,23 @@ int mzreplay_filer_file(mzreplay_filer* fl, const mzreplay_file_moves* mv, void*
     const int64_t grid = std::min<int64_t>(std::min<int64_t>(most, p.G), 2048);
     filer_priorities_kernel<<<dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream>>>(p, f);
     RP_HIP(s, hipGetLastError());
+    RP_HIP(s, hipEventRecord(s->last_filing, stream));
     return 0;
 }
 
-int mzreplay_filer_sync(mzreplay_filer* fl, int32_t* n_new, const int32_t** env_index, const int32_t** lengths,
-                        int64_t* first_game_id, int64_t* counters, void* stream_) {
+int mzreplay_filer_sync_ids(mzreplay_filer* fl, int32_t* n_new, const int32_t** env_index, const int32_t** lengths,
+                            const int64_t** game_ids, int64_t* counters, void* stream_) {
     if (!fl || !n_new) return fail(fl ? fl->store : nullptr, "mzreplay_filer_sync: null argument");
     mzreplay* s = fl->store;
     FilerState st{};
-    if (filer_drain(fl, &st, static_cast<hipStream_t>(stream_))) return -1;
-    s->next_game_id = st.counters.next_game_id;
+    mz::filer::Counters now{};
+    if (filer_drain(fl, &st, &now, static_cast<hipStream_t>(stream_))) return -1;
+    s->next_game_id = now.next_game_id;
     if (counters) {
-        counters[0] = st.counters.next_game_id;
-        counters[1] = st.counters.games_stored;
-        counters[2] = st.counters.total_samples;
-        counters[3] = st.counters.steps_played;
+        counters[0] = now.next_game_id;
+        counters[1] = now.games_stored;
+        counters[2] = now.total_samples;
+        counters[3] = now.steps_played;
     }
     if (st.error) {
         // (the batch that raised it filed nothing; games of earlier, unsynced batches stay for the next sync)
@@ -1688,12 +1725,29 @@ int mzreplay_filer_sync(mzreplay_filer* fl, int32_t* n_new, const int32_t** env_
     }
     fl->out_env.swap(fl->h_env);
     fl->out_len.swap(fl->h_len);
+    fl->out_id.swap(fl->h_id);
     fl->h_env.clear();
     fl->h_len.clear();
+    fl->h_id.clear();
     *n_new = static_cast<int32_t>(fl->out_env.size());
     if (env_index) *env_index = fl->out_env.data();
     if (lengths) *lengths = fl->out_len.data();
-    if (first_game_id) *first_game_id = st.counters.next_game_id - static_cast<int64_t>(fl->out_env.size());
+    if (game_ids) *game_ids = fl->out_id.data();
+    return 0;
+}
+
+int mzreplay_filer_sync(mzreplay_filer* fl, int32_t* n_new, const int32_t** env_index, const int32_t** lengths,
+                        int64_t* first_game_id, int64_t* counters, void* stream_) {
+    if (!fl || !n_new) return fail(fl ? fl->store : nullptr, "mzreplay_filer_sync: null argument");
+    mzreplay* s = fl->store;
+    if (s->filers.size() > 1)
+        return fail(s, "mzreplay_filer_sync: the store has more than one filer, whose games are not consecutive: use "
+                       "mzreplay_filer_sync_ids");
+    int64_t now[4] = {0, 0, 0, 0};
+    const int rc = mzreplay_filer_sync_ids(fl, n_new, env_index, lengths, nullptr, now, stream_);
+    if (counters) std::memcpy(counters, now, sizeof(now));
+    if (rc) return rc;
+    if (first_game_id) *first_game_id = now[0] - static_cast<int64_t>(*n_new);
     return 0;
 }
 
@@ -1711,7 +1765,11 @@ int mzreplay_filer_priorities(mzreplay_filer* fl, int32_t n, const int32_t* slot
     if (!fl || !slots || !priorities || !game_priority) return fail(fl ? fl->store : nullptr, "mzreplay_filer_priorities: null argument");
     mzreplay* s = fl->store;
     if (n <= 0) return 0;
-    if (!fl->f.priorities) return fail(s, "mzreplay_filer_priorities: nothing has been filed yet");
+    // (the arrays the store's filers write, whichever of them filed: this one may not have filed yet)
+    FilerParams from = fl->f;
+    from.priorities = s->sampler_on ? s->sp.priorities : s->filer_priorities;
+    from.game_priority = s->sampler_on ? s->sp.game_priority : s->filer_game_priority;
+    if (!from.priorities) return fail(s, "mzreplay_filer_priorities: nothing has been filed yet");
     const StoreParams& p = s->p;
     for (int g = 0; g < n; ++g)
         if (slots[g] < 0 || slots[g] >= p.G) return fail(s, "mzreplay_filer_priorities: slot out of range");
@@ -1724,7 +1782,7 @@ int mzreplay_filer_priorities(mzreplay_filer* fl, int32_t n, const int32_t* slot
     float* d_pri = fl->d_gather;
     float* d_game = fl->d_gather + count * L;
     RP_HIP(s, hipMemcpyAsync(fl->d_gather_slots, slots, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
-    gather_priorities_kernel<<<dim3(n), dim3(256), 0, stream>>>(p, fl->f, fl->d_gather_slots, d_pri, d_game);
+    gather_priorities_kernel<<<dim3(n), dim3(256), 0, stream>>>(p, from, fl->d_gather_slots, d_pri, d_game);
     RP_HIP(s, hipGetLastError());
     RP_HIP(s, hipMemcpyAsync(priorities, d_pri, sizeof(float) * count * L, hipMemcpyDeviceToHost, stream));
     RP_HIP(s, hipMemcpyAsync(game_priority, d_game, sizeof(float) * count, hipMemcpyDeviceToHost, stream));

@@ -15,7 +15,9 @@ tensor -- draw for draw what the host path returns.
 With `DeviceSelfPlay.file_to(replay_buffer)` the producer side is on the device too (include/mzreplay.h mzreplay_filer_*,
 csrc/replay_filer.h): the actor's finished games go from the search engine's and the environment kernels' device rings
 straight into the store's slots, and only their lengths (4 bytes per game) and the counters come back, once per move
-batch (`sync_filing`).  Such games have no host copy: `download_games` reads them back when someone asks.
+batch (`sync_filing`).  Such games have no host copy: `download_games` reads them back when someone asks.  Several actors
+(the groups of a `PipelinedDeviceSelfPlay`, or separate `DeviceSelfPlay`s that ask for it with `shared=True`) may file into one store, each through a
+`DeviceFiler` and a stream of its own: the store numbers games in the order the filings are queued, whatever the streams do.
 
 Reanalyse refreshes the stored games' value targets with the current network, one game per call
 (`Reanalyse.reanalyse_game`, the reference's loop body) or N games per pass queued on one stream
@@ -94,6 +96,38 @@ class _DeviceEntry(dict):
             super().__setitem__(key, value)
 
 
+class DeviceFiler:
+    """One actor's filer on a ReplayBuffer's store (ReplayBuffer.attach_filer): the running rows of its `num_envs` envs,
+    its list of filed games and its error word.  `begin` / `file` / `lengths` address it; `take_filed` hands its owner the
+    games the syncs have fetched for it (ReplayBuffer.sync_filing syncs every filer of the store at once)."""
+
+    def __init__(self, buffer, handle, num_envs):
+        self.buffer, self.handle, self.num_envs = buffer, handle, int(num_envs)
+        self.pending = False                              # a move batch was filed and not synced yet
+        self.refused = False                              # its last sync failed: the next one asks it again
+        self._filed = []                                  # (env_index, length, game_id) per sync, not yet taken
+
+    def begin(self, first_observations, first_to_play=None):
+        self.buffer.filer_begin(first_observations, first_to_play, filer=self)
+
+    def file(self, moves):
+        self.buffer.filer_file(moves, filer=self)
+
+    def lengths(self):
+        return self.buffer.filer_lengths(filer=self)
+
+    def take_filed(self):
+        """This filer's games since it last took them: (env_index, length, game_id) host arrays, ids ascending; syncs the
+        store's filers first when this one has a filing pending."""
+        if self.pending:
+            self.buffer._sync_filers()
+        taken, self._filed = self._filed, []
+        if len(taken) == 1:
+            return taken[0]
+        dtypes = (numpy.int32, numpy.int32, numpy.int64)
+        return tuple(numpy.concatenate([t[i] for t in taken]) if taken else numpy.zeros(0, dtype=dtypes[i]) for i in range(3))
+
+
 class ReplayBuffer:
     def __init__(self, initial_checkpoint, initial_buffer, config, device=None, device_sampling=False):
         """device_sampling=True: get_batch / update_priorities run on the device (see the module docstring).  Batch
@@ -131,8 +165,8 @@ class ReplayBuffer:
                 raise NotImplementedError("device sampling draws absorbing actions as indices: action_space must be range(A)")
             self._check(self._lib.mzreplay_sampler_enable(self._h, int(config.seed) & 0xFFFFFFFF, int(self.num_played_games)))
         self.buffer = {}                                  # game_id -> dict(length, priorities, game_priority[, history])
-        self._filer = None                                # device filer handle (attach_filer)
-        self._filing_pending = False                      # a move batch was filed on the device and not synced yet
+        self._filers = []                                 # DeviceFiler per filing actor (attach_filer)
+        self._unbooked = []                               # (filer, games) synced while another filer's sync failed
         self._reanalyse_plans = {}                        # n_games -> ReanalysePlan (the pass's device arrays, kept)
         # the batched Reanalyse pass draws from a stream of its own, seeded like the reference's Reanalyse worker
         # (numpy.random.seed(config.seed), replay_buffer.py:309); the buffer's and the batch sampler's never move for it
@@ -149,9 +183,9 @@ class ReplayBuffer:
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def close(self):
-        if getattr(self, "_filer", None):
-            self._lib.mzreplay_filer_destroy(self._filer)
-            self._filer = None
+        for filer in getattr(self, "_filers", []):
+            self._lib.mzreplay_filer_destroy(filer.handle)
+        self._filers = []
         if getattr(self, "_h", None):
             self._lib.mzreplay_destroy(self._h)
             self._h = None
@@ -234,7 +268,7 @@ class ReplayBuffer:
                 del_id = self.num_played_games - len(self.buffer)
                 self.total_samples -= self.buffer[del_id]["length"]
                 del self.buffer[del_id]
-        if self._filer is not None:
+        if self._filers:
             self._push_counters()
         if shared_storage:
             shared_storage.set_info("num_played_games", self.num_played_games)
@@ -250,81 +284,131 @@ class ReplayBuffer:
 
     # ---- games filed on the device (include/mzreplay.h mzreplay_filer_*) ---------------------------------
     def attach_filer(self, num_envs):
-        """Bind the store's device filer to an actor of `num_envs` envs (DeviceSelfPlay.file_to calls this).  One actor
-        files into one store: ids are handed out in the order of the filings on one stream."""
-        if self._filer is not None:
-            raise NotImplementedError("this replay buffer already receives the games of an actor that called file_to(): "
-                                      "several actors filing into one store are not supported (game ids would depend on "
-                                      "the order of their streams); use on_games -> save_games for the others")
+        """A device filer on this store for an actor of `num_envs` envs (DeviceSelfPlay.file_to calls this): a DeviceFiler.
+        Several actors may file into one store, each through a filer and a stream of its own: the store numbers games in
+        the order of the filer_file calls made on it, whatever stream each runs on (include/mzreplay.h)."""
+        self._sync_if_pending()                              # (the counters pushed below are the host's)
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             self._check(self._lib.mzreplay_filer_create(self._h, int(num_envs), ctypes.byref(handle)))
-        self._filer, self._filer_envs = handle, int(num_envs)
+        filer = DeviceFiler(self, handle, num_envs)
+        self._filers.append(filer)
         self._push_counters()
+        return filer
+
+    @property
+    def filers(self):
+        """The DeviceFilers attached so far, in the order they were attached."""
+        return tuple(self._filers)
+
+    def _the_filer(self, filer):
+        """The filer a call addresses: the one given, or the store's only one."""
+        if filer is not None:
+            return filer
+        if len(self._filers) != 1:
+            raise RuntimeError("no actor files into this buffer (DeviceSelfPlay.file_to)" if not self._filers else
+                               "several actors file into this buffer: name the filer (what attach_filer returned)")
+        return self._filers[0]
 
     def _push_counters(self):
         counters = numpy.array([self.num_played_games, len(self.buffer), self.total_samples, self.num_played_steps],
                                dtype=numpy.int64)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.mzreplay_filer_set_counters(self._filer, ptr(counters, _native.c_i64_p), self._stream()))
+        with torch.cuda.device(self.device):    # (the counters are the store's: any of its filers reaches them)
+            self._check(self._lib.mzreplay_filer_set_counters(self._filers[0].handle, ptr(counters, _native.c_i64_p),
+                                                              self._stream()))
 
-    def filer_begin(self, first_observations, first_to_play=None):
+    def filer_begin(self, first_observations, first_to_play=None, filer=None):
         """Every env of the filing actor starts a game: device tensors f32 [E, ...] and int32 [E] (None: player 0)."""
+        filer = self._the_filer(filer)
         assert first_observations.is_cuda and first_observations.dtype == torch.float32 and first_observations.is_contiguous()
-        assert first_observations.numel() == self._filer_envs * self.C * self.H * self.W
+        assert first_observations.numel() == filer.num_envs * self.C * self.H * self.W
         assert first_to_play is None or (first_to_play.is_cuda and first_to_play.dtype == torch.int32
-                                         and first_to_play.numel() == self._filer_envs)
+                                         and first_to_play.numel() == filer.num_envs)
         with torch.cuda.device(self.device):
-            self._check(self._lib.mzreplay_filer_begin(self._filer, first_observations.data_ptr(),
+            self._check(self._lib.mzreplay_filer_begin(filer.handle, first_observations.data_ptr(),
                                                        None if first_to_play is None else first_to_play.data_ptr(),
                                                        self._stream()))
 
-    def filer_file(self, moves):
-        """Queue the filing of a move batch (a _native.MzReplayFileMoves of device pointers) on the current stream."""
+    def filer_file(self, moves, filer=None):
+        """Queue the filing of a move batch (a _native.MzReplayFileMoves of device pointers) on the current stream.  The
+        batch's games take the ids behind those of the filer_file call made before this one, through whichever filer."""
+        filer = self._the_filer(filer)
         with torch.cuda.device(self.device):
-            self._check(self._lib.mzreplay_filer_file(self._filer, ctypes.byref(moves), self._stream()))
-        self._filing_pending = True
+            self._check(self._lib.mzreplay_filer_file(filer.handle, ctypes.byref(moves), self._stream()))
+        filer.pending = True
 
     @property
     def filing_pending(self):
         """A move batch was filed on the device (filer_file) and sync_filing has not fetched its games yet."""
-        return self._filing_pending
+        return any(f.pending for f in self._filers) or bool(self._unbooked)
 
-    def filer_lengths(self):
+    def filer_lengths(self, filer=None):
         """Moves played so far in every env's running game (int32 [E]; waits for the device)."""
-        out = numpy.zeros(self._filer_envs, dtype=numpy.int32)
+        filer = self._the_filer(filer)
+        out = numpy.zeros(filer.num_envs, dtype=numpy.int32)
         with torch.cuda.device(self.device):
-            self._check(self._lib.mzreplay_filer_lengths(self._filer, ptr(out, c_i32_p), self._stream()))
+            self._check(self._lib.mzreplay_filer_lengths(filer.handle, ptr(out, c_i32_p), self._stream()))
         return out
 
     def _sync_if_pending(self):
-        if self._filing_pending:
+        if self.filing_pending:
             self.sync_filing()
+
+    def _sync_filer(self, filer, counters):
+        """mzreplay_filer_sync_ids of one filer: its new games as host arrays, the store's counters into `counters`."""
+        n = ctypes.c_int32()
+        env_p, len_p, id_p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        filer.pending = False
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_filer_sync_ids(filer.handle, ctypes.byref(n), ctypes.byref(env_p), ctypes.byref(len_p),
+                                                          ctypes.byref(id_p), ptr(counters, _native.c_i64_p), self._stream()))
+        count = n.value
+
+        def arr(p, ctype, dtype):
+            if count == 0:
+                return numpy.zeros(0, dtype=dtype)
+            return numpy.ctypeslib.as_array(ctypes.cast(p, ctype), shape=(count,)).copy()
+        return arr(env_p, c_i32_p, numpy.int32), arr(len_p, c_i32_p, numpy.int32), arr(id_p, _native.c_i64_p, numpy.int64)
 
     def sync_filing(self, shared_storage=None):
         """The games filed on the device since the last sync join the host bookkeeping: `buffer` entries (length,
         history=None), num_played_games / num_played_steps / total_samples from the device counters and, for host-side
-        prioritised sampling, the new games' initial priorities.  Returns (env_index, length, game_id) host arrays.
-        Small and blocking: 4 bytes per game come back."""
-        if self._filer is None:
-            raise RuntimeError("sync_filing: no actor files into this buffer (DeviceSelfPlay.file_to)")
-        n, first = ctypes.c_int32(), ctypes.c_int64()
-        env_p, len_p = ctypes.c_void_p(), ctypes.c_void_p()
-        counters = numpy.zeros(4, dtype=numpy.int64)
-        self._filing_pending = False
-        with torch.cuda.device(self.device):
-            self._check(self._lib.mzreplay_filer_sync(self._filer, ctypes.byref(n), ctypes.byref(env_p), ctypes.byref(len_p),
-                                                      ctypes.byref(first), ptr(counters, _native.c_i64_p), self._stream()))
-        count = n.value
+        prioritised sampling, the new games' initial priorities.  Every filer with a filing pending is synced, the new
+        games of all of them are merged by ascending id and booked once, in id order, against the counters read after the
+        last sync; each filer's (env_index, length, game_id) wait in it for its owner (DeviceFiler.take_filed).  With one
+        filer on the store, returns that filer's (env_index, length, game_id) host arrays; with several, None.
+        Small and blocking: 16 bytes per game come back.
+        A filer whose device error word is set fails its sync with the word's message, which is raised here: nothing is
+        booked then (the counters already count the games that filer keeps for its next sync), what the other filers
+        handed over waits, and the following sync_filing books it all."""
+        self._sync_filers(shared_storage)
+        return self._filers[0].take_filed() if len(self._filers) == 1 else None
 
-        def arr(p):
-            if count == 0:
-                return numpy.zeros(0, dtype=numpy.int32)
-            return numpy.ctypeslib.as_array(ctypes.cast(p, c_i32_p), shape=(count,)).copy()
-        env_index, lengths = arr(env_p), arr(len_p)
-        ids = first.value + numpy.arange(count, dtype=numpy.int64)
+    def _sync_filers(self, shared_storage=None):
+        if not self._filers:
+            raise RuntimeError("sync_filing: no actor files into this buffer (DeviceSelfPlay.file_to)")
+        counters = numpy.zeros(4, dtype=numpy.int64)
+        synced, failure = self._unbooked, None
+        self._unbooked = []
+        for filer in [f for f in self._filers if f.pending or f.refused] or self._filers[:1]:
+            try:
+                filer.refused = False
+                synced.append((filer, self._sync_filer(filer, counters)))
+            except RuntimeError as error:
+                filer.refused = True
+                failure = failure or error
+        if failure is not None:
+            self._unbooked = synced
+            raise failure
+        for filer, filed in synced:
+            filer._filed.append(filed)
+        lengths = numpy.concatenate([filed[1] for _, filed in synced]) if synced else numpy.zeros(0, dtype=numpy.int32)
+        ids = numpy.concatenate([filed[2] for _, filed in synced]) if synced else numpy.zeros(0, dtype=numpy.int64)
+        order = numpy.argsort(ids, kind="stable")
+        lengths, ids = lengths[order], ids[order]
+        count = len(ids)
         if count:
-            keep_from = max(0, count - self.capacity)            # a call can finish more games than there are slots
+            keep_from = max(0, count - self.capacity)            # the calls can finish more games than there are slots
             kept_ids, kept_len = ids[keep_from:].tolist(), lengths[keep_from:].tolist()
             if self.device_sampling:
                 entries = [_DeviceEntry(self, gid, length=n_moves, history=None) for gid, n_moves in zip(kept_ids, kept_len)]
@@ -335,9 +419,9 @@ class ReplayBuffer:
                     pri = numpy.zeros((len(kept_ids), self.L), dtype=numpy.float32)
                     game_pri = numpy.zeros(len(kept_ids), dtype=numpy.float32)
                     with torch.cuda.device(self.device):
-                        self._check(self._lib.mzreplay_filer_priorities(self._filer, len(kept_ids), ptr(slots, c_i32_p),
-                                                                        ptr(pri, c_f32_p), ptr(game_pri, c_f32_p),
-                                                                        self._stream()))
+                        self._check(self._lib.mzreplay_filer_priorities(self._filers[0].handle, len(kept_ids),
+                                                                        ptr(slots, c_i32_p), ptr(pri, c_f32_p),
+                                                                        ptr(game_pri, c_f32_p), self._stream()))
                     for g, entry in enumerate(entries):
                         entry["priorities"] = pri[g, : kept_len[g]].copy()
                         entry["game_priority"] = game_pri[g]
@@ -350,7 +434,6 @@ class ReplayBuffer:
         if shared_storage:
             shared_storage.set_info("num_played_games", self.num_played_games)
             shared_storage.set_info("num_played_steps", self.num_played_steps)
-        return env_index, lengths, ids
 
     def download_games(self, game_ids):
         """Stored games read back from the device as a self_play.PackedGames (rows max_moves wide; rewards float64 as the

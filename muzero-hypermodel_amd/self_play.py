@@ -891,7 +891,7 @@ class FiledGames(typing.NamedTuple):
     PackedGames would have had (env-major, then in move order)."""
     env_index: numpy.ndarray     # int32 [n]
     length: numpy.ndarray        # int32 [n] moves
-    game_id: numpy.ndarray       # int64 [n] consecutive
+    game_id: numpy.ndarray       # int64 [n] ascending (consecutive while one actor files into the store)
 
     def __len__(self):
         return len(self.env_index)
@@ -1044,14 +1044,14 @@ class StoreRows:
 
     def __init__(self, replay_buffer, engine, envs, config):
         self.replay_buffer, self.engine, self.envs, self.config = replay_buffer, engine, envs, config
-        replay_buffer.attach_filer(envs.E)
+        self.filer = replay_buffer.attach_filer(envs.E)      # this actor's own: other actors may file into the same store
         obs, _, _, to_play = envs.observe()
-        replay_buffer.filer_begin(obs, to_play)
+        self.filer.begin(obs, to_play)
         self.pending = None                     # (MzReplayFileMoves, ring): described, not queued yet (the ring stays alive with it)
 
     @property
     def lengths(self):
-        return self.replay_buffer.filer_lengths()           # (a small download)
+        return self.filer.lengths()                          # (a small download)
 
     def admit(self, step=False, on_game=None, opponent="self", batched_pass=True):
         """Evaluation games are never saved to a replay buffer, and the device filer takes whole move batches."""
@@ -1083,7 +1083,7 @@ class StoreRows:
 
     def queue(self):
         if self.pending is not None:
-            self.replay_buffer.filer_file(self.pending[0])
+            self.filer.file(self.pending[0])
             self.pending = None
 
     def flush(self):
@@ -1094,10 +1094,10 @@ class StoreRows:
         return None
 
     def games_after_collect(self):
-        """The games of the filing queued last: their lengths and ids join the host bookkeeping (one small sync)."""
-        if not self.replay_buffer.filing_pending:
-            return None
-        filed = FiledGames(*self.replay_buffer.sync_filing())
+        """The games of the filing queued last: their lengths and ids join the host bookkeeping (one small sync of every
+        filer of the store that has a filing pending; what a sync another actor asked for fetched for this one waits in
+        the filer)."""
+        filed = FiledGames(*self.filer.take_filed())
         return filed if len(filed) else None
 
     def keep_predrawn(self, out, ring, n_moves, cur):
@@ -1131,6 +1131,14 @@ class StoreRows:
         mv.rewards, mv.done = ring["reward"].data_ptr(), ring["done"].data_ptr()
         mv.obs_after, mv.obs_next = ring["obs_after"].data_ptr(), ring["obs_next"].data_ptr()
         self.pending = (mv, ring)
+
+
+def _device_store(replay_buffer):
+    """file_to()'s sink is the device store of a replay_buffer.ReplayBuffer: nothing else can be filed into."""
+    from .replay_buffer import ReplayBuffer
+    if not isinstance(replay_buffer, ReplayBuffer):
+        raise NotImplementedError(f"file_to() files into the device store of a replay_buffer.ReplayBuffer; a "
+                                  f"{type(replay_buffer).__name__} is not one (hand other sinks the games through on_games)")
 
 
 class DeviceSelfPlay(ManyEnvLoop):
@@ -1195,16 +1203,25 @@ class DeviceSelfPlay(ManyEnvLoop):
         """Moves played in every env's running game: the host filer's counters, or the device filer's (a small download)."""
         return self._rows.lengths
 
-    def file_to(self, replay_buffer):
+    def file_to(self, replay_buffer, shared=False):
         """From now on finished games go into `replay_buffer`'s store on the device (include/mzreplay.h
         mzreplay_filer_file): play_moves queues the filing behind the batch's last environment kernel, no observation,
         policy row or value of a game visits the host, and `on_games` receives a FiledGames (env_index, length, game_id)
         instead of a PackedGames.  Before the first move only, same device only; step(), on_game and opponent modes are
-        not available afterwards (evaluation games are never saved to a replay buffer)."""
+        not available afterwards (evaluation games are never saved to a replay buffer).
+        shared=True: the buffer may already receive another actor's games.  The store then numbers games in the order of
+        the actors' play_moves / flush calls, and what the first actor's owner sees changes with it -- its ids are no
+        longer consecutive, sync_filing() returns None and the buffer's filer_* calls want the filer named -- which is
+        why joining a store is asked for and never happens by default."""
         if isinstance(self._rows, StoreRows):
             raise ValueError("file_to was called before")
         if self.moves_played or self._batch_ready or self._dev_batch is not None or self._rows.pending is not None:
             raise ValueError("file_to comes before the first move: the running games live in the host filer by now")
+        _device_store(replay_buffer)
+        if replay_buffer.filers and not shared:
+            raise NotImplementedError("this replay buffer already receives the games of an actor that called file_to(); "
+                                      "sharing a store is not the default: pass file_to(replay_buffer, shared=True) to join "
+                                      "it (ids then follow the order of the actors' calls), or use on_games -> save_games")
         store_device = torch.device(replay_buffer.device)
         mine = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         if store_device != mine:
@@ -1569,7 +1586,8 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
     of a move (step_begin / step_end): while the host samples, steps, observes and files one group's move, the GPU
     searches the other group's positions.  Env e keeps seed `seed + e`, so the groups together play the games one
     DeviceSelfPlay of num_envs envs plays (tests/test_gpu_envs.py).  Callbacks see global env indices.  Carries the
-    reference's continuous_self_play loop (ManyEnvLoop): a weight pull reaches every group's network replica."""
+    reference's continuous_self_play loop (ManyEnvLoop): a weight pull reaches every group's network replica.
+    file_to(replay_buffer) files every group's games into one store on the device, ids in the host path's order."""
 
     def __init__(self, initial_checkpoint, game_name, config, seed, num_envs, groups=2, device=None, use_graph=True):
         assert num_envs % groups == 0
@@ -1585,12 +1603,27 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             self.streams.append(stream)
         self._started = [False] * groups         # group g's next search is queued (step)
         self._batch_queued = [False] * groups    # group g's next move batch is queued (play_moves)
+        self._filing = False                     # file_to(): every group files into one store on the device
         self.device, self.model = self.actors[0].device, self.actors[0].model   # (what ManyEnvLoop's weight pull addresses)
 
-    def file_to(self, replay_buffer):
-        raise NotImplementedError("PipelinedDeviceSelfPlay cannot file_to() a replay buffer: its groups run on streams of "
-                                  "their own, and game ids would depend on the order the streams happen to run in; use "
-                                  "one DeviceSelfPlay, or on_games -> save_games")
+    def file_to(self, replay_buffer, shared=False):
+        """DeviceSelfPlay.file_to for every group: each group's actor files into the one store through a filer of its own,
+        on the group's stream (shared=True: the store may already receive another actor's games).  The store numbers games in the order the filings are queued, whatever the streams do
+        (include/mzreplay.h), and play_moves queues them in the order the host path hands the games out: per batch, group
+        0, then group 1, and so on -- with and without prefetch.  `on_games` receives a FiledGames per group with global
+        env indices.  What StoreRows.admit refuses holds for every group: no step(), no on_game, no opponent."""
+        _device_store(replay_buffer)
+        if self._filing:
+            raise ValueError("file_to was called before")
+        if any(self._started) or any(self._batch_queued):
+            raise ValueError("file_to comes before the first move")
+        for g, (actor, stream) in enumerate(zip(self.actors, self.streams)):
+            with torch.cuda.stream(stream):
+                actor.file_to(replay_buffer, shared=shared or g > 0)     # (the groups share the store among themselves)
+        self._filing = True
+
+    def _filed_counters(self):
+        return self.actors[0]._filed_counters() if self._filing else None    # (one store: every group's rows count it)
 
     def _pull_weights(self, shared_storage, version):
         self._no_batch_queued("weight pull")
@@ -1642,7 +1675,10 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         one = None if on_game is None else (lambda e, gh: on_game(base + e, gh))
 
         def many(batch):
-            batch.env_index = batch.env_index + base
+            if isinstance(batch, FiledGames):                # (after file_to(): a tuple of host arrays)
+                batch = FiledGames(batch.env_index + base, batch.length, batch.game_id)
+            else:
+                batch.env_index = batch.env_index + base
             on_games(batch)
         return one, (None if on_games is None else many)
 
@@ -1702,6 +1738,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                 raise RuntimeError("play_moves: a step() is half done; call step(..., prefetch=False) before batches")
             one, many = self._callbacks(g, on_game, on_games)
             with torch.cuda.stream(self.streams[g]):
+                self._queue_filing(actor, one, mode)
                 actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold, *mode)
         for m in range(n_moves):
             for g in fresh:
@@ -1716,12 +1753,21 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                 played.append(actor._device_batch_end(one, many))
                 queued[g] = False
                 if prefetch:
+                    self._queue_filing(actor, one, mode)
                     actor._device_batch_begin(n_moves, temperature, one, many, temperature_threshold, *mode)
                     for m in range(n_moves):
                         actor._device_batch_move(m)
                     queued[g] = True
                     actor.flush(one, many)                   # the collected batch's games, while the GPU runs the next
         return numpy.concatenate(played)
+
+    @staticmethod
+    def _queue_filing(actor, on_game, mode):
+        """What DeviceSelfPlay.play_moves does ahead of a batch: after file_to() the group's collected batch is filed on
+        its stream, ahead of anything the next batch rewrites -- the groups in turn, so the store's ids follow the order
+        the host path hands the games out.  (Host rows: nothing to do.)"""
+        actor._rows.admit(on_game=on_game, opponent=mode[0])
+        actor._rows.queue()
 
     def _no_batch_queued(self, what):
         if any(self._batch_queued):
@@ -1733,7 +1779,8 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         groups' halves alternating -- the last move of a pass queues nothing behind it either."""
         finished = []
         if self.actors[0]._batchable(temperature, temperature_threshold, moves_per_pass, device_inputs=True):
-            collect = lambda e, gh: finished.append((e, gh))
+            # (after file_to() the games are in the store: none is rebuilt on the host)
+            collect = None if self._filing else (lambda e, gh: finished.append((e, gh)))
             self.play_moves(moves_per_pass, temperature, on_game=collect, temperature_threshold=temperature_threshold or 0)
             self.flush(on_game=collect)
             return finished

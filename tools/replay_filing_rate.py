@@ -5,8 +5,12 @@
     host     on_games -> ReplayBuffer.save_games: env outputs downloaded, filed by host threads, padded, copied game by game
     device   file_to(replay_buffer): filed where the batch lies, 4 bytes per game come back (include/mzreplay.h)
 
-    python tools/replay_filing_rate.py --config cartpole|tictactoe_fc|connect4|gomoku [--envs E] [--moves M]
-                                       [--seconds 1.0] [--rounds 3] [--out profiles/NAME.jsonl]
+    python tools/replay_filing_rate.py --config cartpole|tictactoe|tictactoe_fc|connect4|gomoku [--envs E] [--moves M]
+                                       [--seconds 1.0] [--rounds 3] [--groups N] [--out profiles/NAME.jsonl]
+
+--groups N adds a pipelined leg for each sink (PipelinedDeviceSelfPlay with N groups on streams of their own, batches
+prefetched: pipelined_none, pipelined_host, pipelined_device -- every group files into the one store through a filer of
+its own) and runs them beside the one-actor `device` leg unless --legs says otherwise.
 
 Every leg has an actor (and a store) of its own with the same weights and seeds; a round runs each leg for at least
 --seconds after two warm-up batches; the clock is the host's, closed by a device synchronise.  One JSON line per leg with
@@ -27,7 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-DEFAULTS = {"cartpole": (4096, 50), "tictactoe_fc": (32768, 8), "connect4": (1024, 8), "gomoku": (256, 8)}
+DEFAULTS = {"cartpole": (4096, 50), "tictactoe": (65536, 9), "tictactoe_fc": (32768, 8), "connect4": (1024, 8),
+            "gomoku": (256, 8)}
 
 
 def setup(name):
@@ -65,7 +70,8 @@ def main():
     ap.add_argument("--moves", type=int)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--legs", default="none,host,device")
+    ap.add_argument("--groups", type=int, default=1, help="N > 1: pipelined legs with N groups")
+    ap.add_argument("--legs", help="default none,host,device; with --groups: pipelined_none,pipelined_host,pipelined_device,device")
     ap.add_argument("--out")
     args = ap.parse_args()
     sp = importlib.import_module("muzero-hypermodel_amd.self_play")
@@ -75,15 +81,22 @@ def main():
     M = args.moves or DEFAULTS[args.config][1]
     config.replay_buffer_size = max(int(config.replay_buffer_size), 4 * E)
     legs = {}
-    for leg in args.legs.split(","):
-        actor = sp.DeviceSelfPlay({"weights": weights}, game, config, 0, E)
-        store = None if leg == "none" else rb_mod.ReplayBuffer({"num_played_games": 0, "num_played_steps": 0}, {}, config)
+    names = args.legs or ("none,host,device" if args.groups < 2 else "pipelined_none,pipelined_host,pipelined_device,device")
+    for leg in names.split(","):
+        pipelined, sink = leg.startswith("pipelined_"), leg.split("_")[-1]
+        if pipelined:
+            if args.groups < 2:
+                ap.error(f"leg {leg} needs --groups N with N > 1")
+            actor = sp.PipelinedDeviceSelfPlay({"weights": weights}, game, config, 0, E, groups=args.groups)
+        else:
+            actor = sp.DeviceSelfPlay({"weights": weights}, game, config, 0, E)
+        store = None if sink == "none" else rb_mod.ReplayBuffer({"num_played_games": 0, "num_played_steps": 0}, {}, config)
         on_games = None
-        if leg == "host":
+        if sink == "host":
             on_games = store.save_games
-        elif leg == "device":
+        elif sink == "device":
             actor.file_to(store)
-        legs[leg] = dict(actor=actor, store=store, on_games=on_games, rates=[], games=0, plies=0)
+        legs[leg] = dict(actor=actor, store=store, on_games=on_games, rates=[], games=0, plies=0, pipelined=pipelined)
     dev = next(iter(legs.values()))["actor"].device
 
     def run(state, seconds):
@@ -91,6 +104,14 @@ def main():
         torch.cuda.synchronize(dev)
         games0, plies0, t0 = actor.games_finished, actor.moves_played, time.perf_counter()
         while True:
+            if state["pipelined"]:
+                # the next batch of every group is queued before this one's games are filed; the window's last call
+                # leaves nothing queued behind it, so every move the window counts was played inside it
+                last = time.perf_counter() - t0 >= seconds
+                actor.play_moves(M, 1.0, on_games=state["on_games"], prefetch=not last)
+                if last:
+                    break
+                continue
             actor.play_moves(M, 1.0, on_games=state["on_games"])
             if time.perf_counter() - t0 >= seconds:
                 break
@@ -111,12 +132,12 @@ def main():
     lines = []
     for leg, state in legs.items():
         rates = state["rates"]
-        row = dict(config=args.config, leg=leg, envs=E, moves_per_batch=M, rounds=args.rounds, seconds_per_round=args.seconds,
+        row = dict(config=args.config, leg=leg, groups=args.groups if state["pipelined"] else 1, envs=E, moves_per_batch=M, rounds=args.rounds, seconds_per_round=args.seconds,
                    moves_per_s=[round(r) for r in rates], median_moves_per_s=round(statistics.median(rates)),
                    spread=round((max(rates) - min(rates)) / statistics.median(rates), 4),
                    games=state["games"], mean_game_length=round(state["plies"] / max(1, state["games"]), 2),
                    measured="host clock closed by a device synchronise, legs alternated in one process")
-        if leg == "device":
+        if leg.split("_")[-1] == "device":
             row["filing_bytes_per_env_move"] = round(filing_bytes(config, E, M, state["games"], state["plies"]) / max(1, state["plies"]), 1)
         lines.append(json.dumps(row))
         print(lines[-1], flush=True)
