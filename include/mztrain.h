@@ -8,7 +8,8 @@
  * with respect to every logit (each unrolled step's share divided by its gradient scale, trainer.py:176-198).
  * It replaces the ~25 element-wise launches per unrolled step between the network's forward and backward.  For
  * fully-connected networks the forward and the backward are HIP launches too (mztrain_fc_*, below); residual networks
- * keep both with PyTorch-ROCm but for the convolution epilogue in training (mztrain_epilogue_*, below, on request); the
+ * keep both with PyTorch-ROCm but for the convolution epilogue in training (mztrain_epilogue_*, below, on request) and the
+ * 3 x 3 convolutions with their two gradients (mztrain_conv_*, below, on request); the
  * optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
  * flat buffers of a fully-connected network.  Raw device pointers, fp32, contiguous; no torch types.
  *
@@ -183,6 +184,102 @@ int mztrain_epilogue_reference_forward(const mztrain_epilogue_forward_args *args
 int mztrain_epilogue_reference_backward(const mztrain_epilogue_backward_args *args);
 /* M up to which a channel stays in LDS between the kernels' passes (the one switch of form). */
 #define MZTRAIN_EPILOGUE_KEEP_VALUES 4096
+
+/* ---- the 3 x 3 convolutions of a residual network in training (csrc/conv_train.hip, csrc/conv_train.h) ------------------
+ * The padded, stride-1, bias-free 3 x 3 convolution on the boards of mzmcts_board_conv_supported (3 x 3, 6 x 6, 6 x 7; cout
+ * 16 or 64; 1 <= cin <= 80), its data gradient and its weight gradient, exact float32 on v_mfma_f32_16x16x4_f32.  Forward and
+ * data gradient run mzmcts_board_conv3x3 on two packings of the weight; the weight gradient is a kernel of its own.  The
+ * order of every sum is csrc/conv_train.h's; the device entries and the reference entries give the same bits.
+ *   forward   y = conv3x3(x, w), raw.  The launch path is the inference one with a ones / zeros scale / shift pair and no
+ *             ReLU: y = acc * 1 + 0, so a sum of -0 comes out as +0, on the device and in the reference entry alike.
+ *   dgrad     dx [batch][dx_planes][hw] = the gradient of x's FIRST dx_planes planes: conv3x3(dy, w') with
+ *             w'[ci][co][ky][kx] = w[co][ci][2 - ky][2 - kx], ci < dx_planes (cin' = cout, cout' = dx_planes), the same -0 rule.
+ *   wgrad     dw[co][ci][ky][kx] = sum over k = b * hw + p, ascending, of dy[b][co][p] * xpad[b][ci][p + (ky - 1, kx - 1)]:
+ *             float32 fmaf chains from zero over slices of MZTRAIN_CONV_SLICE indices (the last one padded with 0 * 0
+ *             terms), the slice sums added in ascending order in float64, one rounding.  No atomics; every entry of dw is
+ *             written by every call; the same bits from run to run, eager and captured.
+ * A border tap multiplies a float32 zero (a NaN dy or weight there gives NaN).  All tensors float32, contiguous. */
+#define MZTRAIN_CONV_SLICE 64
+#define MZTRAIN_CONV_AFFINE 64      /* floats of each half of `affine`: ones, then zeros */
+
+typedef struct mztrain_conv_pack_args {
+    const float *weight;     /* [cout][cin][3][3] */
+    float *packed;           /* out f32[mzmcts_board_conv_packed_floats(cin, cout)]: the layout of mzmcts_board_conv_pack */
+    float *packed_dx;        /* out f32[mzmcts_board_conv_packed_floats(cout, dx_planes)]: that layout for w'; NULL with
+                                dx_planes == 0 */
+    float *affine;           /* out f32[2 * MZTRAIN_CONV_AFFINE]: the ones | zeros pair the two convolutions read */
+    int32_t cin;
+    int32_t cout;
+    int32_t dx_planes;       /* 0 (no data gradient wanted), 16 or 64, at most cin */
+} mztrain_conv_pack_args;
+
+typedef struct mztrain_conv_forward_args {
+    const float *x;          /* [batch][cin][hw] */
+    const float *packed;     /* what mztrain_conv_pack wrote (the launch reads these two) */
+    const float *affine;
+    const float *weight;     /* [cout][cin][3][3] (the reference entry reads this one instead) */
+    float *y;                /* out [batch][cout][hw]; must not be x */
+    int64_t batch;
+    int32_t cin;
+    int32_t cout;
+    int32_t height;
+    int32_t width;
+} mztrain_conv_forward_args;
+
+typedef struct mztrain_conv_dgrad_args {
+    const float *dy;         /* [batch][cout][hw] */
+    const float *packed_dx;  /* what mztrain_conv_pack wrote (the launch reads these two) */
+    const float *affine;
+    const float *weight;     /* [cout][cin][3][3] (the reference entry reads this one instead) */
+    float *dx;               /* out [batch][dx_planes][hw]; must not be dy */
+    int64_t batch;
+    int32_t cin;
+    int32_t cout;
+    int32_t height;
+    int32_t width;
+    int32_t dx_planes;       /* 16 or 64, at most cin */
+} mztrain_conv_dgrad_args;
+
+typedef struct mztrain_conv_wgrad_args {
+    const float *x;          /* [batch][cin][hw] */
+    const float *dy;         /* [batch][cout][hw] */
+    float *dw;               /* out [cout][cin][3][3] */
+    int64_t batch;
+    int32_t cin;
+    int32_t cout;
+    int32_t height;
+    int32_t width;
+} mztrain_conv_wgrad_args;
+
+/* 1 where the three launches take the shape: the forward shapes of mzmcts_board_conv_supported that mzmcts_board_conv3x3
+ * launches (with cout 16 its workgroup's planes fit 160 KB of LDS up to cin 48 on 3 x 3 boards, 32 on 6 x 6, 64 on 6 x 7), and
+ * for need_dx_planes > 0 a data gradient of exactly 16 or 64 planes, at most cin, whose convolution cout -> need_dx_planes is
+ * such a shape too (need_dx_planes == 0: no data gradient is asked for). */
+int mztrain_conv_supported(int32_t cin, int32_t cout, int32_t height, int32_t width, int32_t need_dx_planes);
+int32_t mztrain_conv_slice(void);                                  /* MZTRAIN_CONV_SLICE as the library was built */
+/* the largest batch the entries take (batch * hw * max(cin, cout) + MZTRAIN_CONV_SLICE within int32); -1: unsupported shape */
+int64_t mztrain_conv_max_batch(int32_t cin, int32_t cout, int32_t height, int32_t width);
+/* the weight gradient's launch plan into out[5] = {grid, block, LDS bytes, slices per block, rounds}; MZMCTS_ERR_INVALID
+ * (and zeros) for an unsupported shape or a batch outside [1, mztrain_conv_max_batch] */
+int mztrain_conv_wgrad_plan(int64_t batch, int32_t cin, int32_t cout, int32_t height, int32_t width, int64_t *out);
+
+/* Each queues one launch on `stream`, no allocation, no host decision beyond the choice of the launch's form, no
+ * synchronisation (capturable); pack writes both packings and `affine` in its one launch, into buffers the caller keeps
+ * (a captured step repacks on replay).  MZMCTS_ERR_INVALID with a message through mzmcts_last_error(NULL) before anything
+ * touches a device: null `args`; a null member a launch reads or writes (`weight` may be null for the launches, `packed`,
+ * `packed_dx` and `affine` for the reference entries, `packed_dx` for a pack with dx_planes == 0); an unsupported shape;
+ * batch < 1 or above mztrain_conv_max_batch; dx_planes not 16 or 64 (pack: or 0), or above cin; y == x or dx == dy; x, y,
+ * dy, dx, packed or packed_dx not 16-byte aligned (forward and dgrad launches: they move 16 bytes per lane). */
+int mztrain_conv_pack(const mztrain_conv_pack_args *args, void *stream);
+int mztrain_conv_forward(const mztrain_conv_forward_args *args, void *stream);
+int mztrain_conv_dgrad(const mztrain_conv_dgrad_args *args, void *stream);
+int mztrain_conv_wgrad(const mztrain_conv_wgrad_args *args, void *stream);
+/* The same rule, and the same refusals but for alignment, with every pointer a HOST array: what the tests hold the
+ * kernels to. */
+int mztrain_conv_reference_pack(const mztrain_conv_pack_args *args);
+int mztrain_conv_reference_forward(const mztrain_conv_forward_args *args);
+int mztrain_conv_reference_dgrad(const mztrain_conv_dgrad_args *args);
+int mztrain_conv_reference_wgrad(const mztrain_conv_wgrad_args *args);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,37 @@ class MzTrainEpilogueBackwardArgs(ctypes.Structure):
 EPILOGUE_KEEP_VALUES = 4096     # include/mztrain.h MZTRAIN_EPILOGUE_KEEP_VALUES
 
 
+class MzTrainConvPackArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_conv_pack_args: both packings of a 3 x 3 weight and the ones | zeros pair."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("weight", "packed", "packed_dx", "affine")] + \
+               [("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("dx_planes", ctypes.c_int32)]
+
+
+class MzTrainConvForwardArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_conv_forward_args."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("x", "packed", "affine", "weight", "y")] + \
+               [("batch", ctypes.c_int64), ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("width", ctypes.c_int32)]
+
+
+class MzTrainConvDgradArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_conv_dgrad_args."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("dy", "packed_dx", "affine", "weight", "dx")] + \
+               [("batch", ctypes.c_int64), ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("dx_planes", ctypes.c_int32)]
+
+
+class MzTrainConvWgradArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_conv_wgrad_args."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("x", "dy", "dw")] + \
+               [("batch", ctypes.c_int64), ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("width", ctypes.c_int32)]
+
+
+CONV_SLICE = 64                 # include/mztrain.h MZTRAIN_CONV_SLICE
+CONV_AFFINE = 64                # include/mztrain.h MZTRAIN_CONV_AFFINE
+
+
 class MzFcDesc(ctypes.Structure):
     _fields_ = [("observation_floats", ctypes.c_int32), ("encoding_size", ctypes.c_int32),
                 ("n_hidden", ctypes.c_int32 * 5), ("hidden", (ctypes.c_int32 * 3) * 5)]
@@ -217,6 +248,18 @@ PROTOTYPES = {
     "mztrain_epilogue_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueBackwardArgs), c_void]),
     "mztrain_epilogue_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueForwardArgs)]),
     "mztrain_epilogue_reference_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueBackwardArgs)]),
+    "mztrain_conv_supported": (ctypes.c_int, [ctypes.c_int32] * 5),
+    "mztrain_conv_slice": (ctypes.c_int32, []),
+    "mztrain_conv_max_batch": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "mztrain_conv_wgrad_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int64)]),
+    "mztrain_conv_pack": (ctypes.c_int, [ctypes.POINTER(MzTrainConvPackArgs), c_void]),
+    "mztrain_conv_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainConvForwardArgs), c_void]),
+    "mztrain_conv_dgrad": (ctypes.c_int, [ctypes.POINTER(MzTrainConvDgradArgs), c_void]),
+    "mztrain_conv_wgrad": (ctypes.c_int, [ctypes.POINTER(MzTrainConvWgradArgs), c_void]),
+    "mztrain_conv_reference_pack": (ctypes.c_int, [ctypes.POINTER(MzTrainConvPackArgs)]),
+    "mztrain_conv_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainConvForwardArgs)]),
+    "mztrain_conv_reference_dgrad": (ctypes.c_int, [ctypes.POINTER(MzTrainConvDgradArgs)]),
+    "mztrain_conv_reference_wgrad": (ctypes.c_int, [ctypes.POINTER(MzTrainConvWgradArgs)]),
     "mzhist_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
     "mzhist_destroy": (None, [c_void]),
     "mzhist_last_error": (ctypes.c_char_p, [c_void]),

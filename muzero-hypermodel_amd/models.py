@@ -353,6 +353,70 @@ def conv_epilogue(x, bn, residual=None):
     return out
 
 
+def _aligned16(t):
+    """A contiguous tensor whose first byte is 16-byte aligned (the convolution kernel moves 16 bytes per lane): fresh
+    torch allocations are, contiguous views at an odd offset need not be."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _TrainingConv3x3(torch.autograd.Function):
+    """The padded, stride-1 3 x 3 convolution of a BoardConv2d in training as HIP launches (include/mztrain.h
+    mztrain_conv_*, csrc/conv_train.h): the forward on the module's forward packing, in the backward the data gradient on
+    its transposed, flipped packing (where the input needs one) and the weight gradient (float32 chains over slices of the
+    batch, folded in float64 in one fixed order; no atomics, the same bits eager and captured).  The packings are the
+    module's own buffers, filled by BoardConv2d.pack_training() -- once per training step, not here.
+
+    `plane` (or None) is one more input plane [B, 1, H, W] that takes no gradient -- the action plane of the dynamics
+    input: the gradient covers x's planes only, exactly the planes the launch computed, and `plane` gets None."""
+
+    @staticmethod
+    def forward(ctx, x, plane, weight, conv):
+        lib = _native.load()
+        if plane is not None:
+            x = torch.cat((x, plane), dim=1)
+        x = _aligned16(x)
+        b, cin, h, w = x.shape
+        packed, _, affine = conv.training_buffers()
+        y = torch.empty((b, conv.out_channels, h, w), dtype=torch.float32, device=x.device)
+        args = _native.MzTrainConvForwardArgs(x=x.data_ptr(), packed=packed.data_ptr(), affine=affine.data_ptr(), weight=None,
+                                              y=y.data_ptr(), batch=b, cin=cin, cout=conv.out_channels, height=h, width=w)
+        with torch.cuda.device(x.device):
+            rc = lib.mztrain_conv_forward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
+        _native.check_train(lib, rc, "mztrain_conv_forward", where=f" on a tensor of shape {tuple(x.shape)}")
+        ctx.save_for_backward(x)
+        ctx.conv = conv
+        ctx.dx_planes = cin - (1 if plane is not None else 0)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _native.load()
+        x, = ctx.saved_tensors
+        conv = ctx.conv
+        dy = _aligned16(grad_out)
+        b, cin, h, w = x.shape
+        _, packed_dx, affine = conv.training_buffers()
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        dx = dw = None
+        with torch.cuda.device(x.device):
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty((b, ctx.dx_planes, h, w), dtype=torch.float32, device=x.device)
+                args = _native.MzTrainConvDgradArgs(dy=dy.data_ptr(), packed_dx=packed_dx.data_ptr(), affine=affine.data_ptr(),
+                                                    weight=None, dx=dx.data_ptr(), batch=b, cin=cin, cout=conv.out_channels,
+                                                    height=h, width=w, dx_planes=ctx.dx_planes)
+                rc = lib.mztrain_conv_dgrad(ctypes.byref(args), stream)
+                _native.check_train(lib, rc, "mztrain_conv_dgrad", where=f" on a tensor of shape {tuple(dy.shape)}")
+            if ctx.needs_input_grad[2]:
+                dw = torch.empty((conv.out_channels, cin, 3, 3), dtype=torch.float32, device=x.device)
+                args = _native.MzTrainConvWgradArgs(x=x.data_ptr(), dy=dy.data_ptr(), dw=dw.data_ptr(), batch=b, cin=cin,
+                                                    cout=conv.out_channels, height=h, width=w)
+                rc = lib.mztrain_conv_wgrad(ctypes.byref(args), stream)
+                _native.check_train(lib, rc, "mztrain_conv_wgrad", where=f" on a tensor of shape {tuple(x.shape)}")
+        return dx, None, dw, None
+
+
 class PointwiseConv2d(torch.nn.Conv2d):
     """1x1 convolution (same parameters / state-dict keys as torch.nn.Conv2d(c_in, c_out, 1)) evaluated as
     ONE GEMM over all (sample, position) rows.  MIOpen lowers these tiny-board 1x1 convolutions to a
@@ -677,7 +741,87 @@ class BoardConv2d(torch.nn.Conv2d):
                 and self.in_channels * self.out_channels * (h * w) ** 2 <= self.DENSE_MAX_ELEMENTS
                 and self.stride == (1, 1) and not torch.is_grad_enabled())
 
+    # ---- training on the matrix cores (include/mztrain.h mztrain_conv_*) ------------------------------------------
+    def training_dx_planes(self):
+        """Input planes the data-gradient packing covers: all of them (16 or 64), all but the last (the dynamics input's
+        17 or 65, whose last plane is the action), or none."""
+        for planes in (self.in_channels, self.in_channels - 1):
+            if planes in (16, 64):
+                return planes
+        return 0
+
+    def training_covered(self):
+        """Whether the HIP training launches cover the module on some board: float32, stride 1, padding 1, no bias, 16 or 64
+        output channels and at most 80 input channels (the board itself is decided per call)."""
+        return (self.weight.dtype == torch.float32 and self.stride == (1, 1) and self.kernel_size == (3, 3)
+                and self.padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and self.bias is None
+                and any(_native.load().mztrain_conv_supported(self.in_channels, self.out_channels, h, w, self.training_dx_planes())
+                        for h, w in ((3, 3), (6, 6), (6, 7))))
+
+    def native_training(self, on=True):
+        """Switch the module to (or back from) the HIP training path; True when it is then on.  On needs a weight on the
+        GPU, stride 1 and channel counts the launches cover (the board is decided per call).  The two packings and the
+        ones | zeros pair live in buffers of the module's own, allocated here once and never moved (captured graphs), apart
+        from every inference cache."""
+        self.__dict__["_train_on"] = False
+        if not on or not self.weight.is_cuda or not self.training_covered():
+            return False
+        lib = _native.load()
+        buffers = self.__dict__.get("_train_buffers")
+        if buffers is None or buffers[0].device != self.weight.device:
+            dx_planes, device = self.training_dx_planes(), self.weight.device
+            self.__dict__["_train_buffers"] = (
+                torch.empty(lib.mzmcts_board_conv_packed_floats(self.in_channels, self.out_channels), dtype=torch.float32,
+                            device=device),
+                torch.empty(lib.mzmcts_board_conv_packed_floats(self.out_channels, dx_planes), dtype=torch.float32,
+                            device=device) if dx_planes else None,
+                torch.empty(2 * _native.CONV_AFFINE, dtype=torch.float32, device=device))
+        self.__dict__["_train_on"] = True
+        self.pack_training()
+        return True
+
+    def training_buffers(self):
+        """(forward packing, data-gradient packing or None, ones | zeros pair) of the training path."""
+        return self.__dict__["_train_buffers"]
+
+    def pack_training(self):
+        """Queue the ONE launch that refills both training packings from the current weight.  Whoever moves the weight
+        calls it before the next training forward (Trainer: at the start of every step, so a captured step repacks on
+        replay); no version counter is consulted."""
+        packed, packed_dx, affine = self.training_buffers()
+        weight = self.weight.detach()
+        args = _native.MzTrainConvPackArgs(weight=weight.data_ptr(), packed=packed.data_ptr(),
+                                           packed_dx=packed_dx.data_ptr() if packed_dx is not None else None,
+                                           affine=affine.data_ptr(), cin=self.in_channels, cout=self.out_channels,
+                                           dx_planes=self.training_dx_planes())
+        lib = _native.load()
+        with torch.cuda.device(packed.device):
+            rc = lib.mztrain_conv_pack(ctypes.byref(args), torch.cuda.current_stream(packed.device).cuda_stream)
+        _native.check_train(lib, rc, "mztrain_conv_pack", where=f" on a weight of shape {tuple(weight.shape)}")
+
+    def takes_training_path(self, x, extra_plane=False):
+        """Whether this call runs the HIP training launches: switched on (MuZeroResidualNetwork.native_training_conv),
+        gradients enabled, a float32 CUDA tensor of 4 dimensions, and a shape the launches cover -- with a data gradient for
+        exactly x's planes when x needs one.  `extra_plane`: x is the input without its last plane, which arrives separately
+        and takes no gradient (the dynamics input).  An input that needs a gradient on all of 17 or 65 planes says no."""
+        if not self.__dict__.get("_train_on") or not torch.is_grad_enabled() or not torch.is_tensor(x) or not x.is_cuda \
+                or x.dtype != torch.float32 or x.dim() != 4 or x.device != self.weight.device \
+                or self.training_buffers()[0].device != x.device \
+                or x.shape[1] + (1 if extra_plane else 0) != self.in_channels:
+            return False
+        need = x.shape[1] if x.requires_grad else 0
+        if need and need != self.training_dx_planes():
+            return False
+        return bool(_native.load().mztrain_conv_supported(self.in_channels, self.out_channels, x.shape[2], x.shape[3], need))
+
+    def training_forward(self, x, plane=None):
+        """conv(x) -- conv(cat(x, plane)) with `plane` [B, 1, H, W] -- on the HIP training path (takes_training_path said
+        yes); `plane` gets no gradient."""
+        return _TrainingConv3x3.apply(x, plane, self.weight, self)
+
     def forward(self, x):
+        if self.takes_training_path(x):
+            return self.training_forward(x)
         if not self.takes_dense_path(x):
             return super().forward(x)
         b, _, h, w = x.shape
@@ -835,8 +979,13 @@ class DynamicsNetwork(torch.nn.Module):
         self.block_output_size_reward = block_output_size_reward
         self.fc = mlp(block_output_size_reward, fc_reward_layers, full_support_size)
 
-    def forward(self, x):
-        x = conv_bn_relu(self.conv, self.bn, x)
+    def forward(self, x, plane=None):
+        """`plane`: the action plane [B, 1, H, W] handed over apart from the state planes x, for the HIP training
+        convolution (BoardConv2d.training_forward), which returns a gradient for the state planes alone."""
+        if plane is not None:
+            x = conv_epilogue(self.conv.training_forward(x, plane), self.bn)
+        else:
+            x = conv_bn_relu(self.conv, self.bn, x)
         for block in self.resblocks:
             x = block(x)
         reward = conv_head(x, self.conv1x1_reward, self.fc, self.block_output_size_reward)
@@ -898,6 +1047,20 @@ class MuZeroResidualNetwork(AbstractNetwork):
             if isinstance(module, BatchNorm2d):
                 module.native_training = bool(on)
         return self
+
+    def native_training_conv(self, on=True):
+        """Switch every 3 x 3 convolution the HIP training launches cover to (or back from) them (BoardConv2d.native_training,
+        _TrainingConv3x3): with gradients enabled such a module then runs its forward, data gradient and weight gradient as
+        HIP launches instead of the convolution library's.  Returns how many modules are switched on; every other module
+        (strides, 128 channels, weights off the GPU) keeps torch's convolution, and so does any call on a board the launches
+        do not cover.  Inference paths and their caches are not affected."""
+        return sum(1 for m in self.modules() if isinstance(m, BoardConv2d) and m.native_training(on))
+
+    def pack_training_convs(self):
+        """One pack launch per switched convolution: what a training step queues before its first forward."""
+        for module in self.modules():
+            if isinstance(module, BoardConv2d) and module.__dict__.get("_train_on"):
+                module.pack_training()
 
     # ---- 128-channel layers on 11 x 11 boards (include/mzmcts.h mzmcts_board_conv_wide) -------------------------------
     def _share_wide_counter(self):
@@ -1140,6 +1303,14 @@ class MuZeroResidualNetwork(AbstractNetwork):
         return board_rescale(self.representation_network(observation))
 
     def dynamics(self, encoded_state, action, out_state=None):
+        conv = self.dynamics_network.module.conv
+        if not action.is_floating_point() and action.dim() == 2 and conv.takes_training_path(encoded_state, extra_plane=True):
+            # the HIP training convolution takes the state planes and the action plane apart: its data gradient is the
+            # state planes', and the plane (an integer action scaled: nothing to differentiate) gets none
+            b, _, h, w = encoded_state.shape
+            plane = (action.to(encoded_state.dtype) / self.action_space_size)[:, :, None, None].expand(b, 1, h, w)
+            raw, reward = self.dynamics_network(encoded_state, plane)
+            return board_rescale(raw, out=out_state), reward
         return self.dynamics_from_planes(state_action_planes(encoded_state, action, self.action_space_size), out_state)
 
     def dynamics_from_planes(self, x, out_state=None):

@@ -4,7 +4,8 @@ turns a replay batch into a gradient step, and the producer side of the weight h
 The arithmetic is PyTorch-ROCm (fp32, the reference's operation order) -- or, for fully-connected networks with
 Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_*), with fc_optimizer=True the optimizer as
 a HIP launch too (mztrain_opt_step), and for residual networks with Trainer(native_epilogue=True) every
-relu(batch_norm(x) [+ residual]) as one HIP launch each way (mztrain_epilogue_*); what changes is the plumbing around it:
+relu(batch_norm(x) [+ residual]) as one HIP launch each way (mztrain_epilogue_*), with Trainer(native_conv=True) their 3 x 3
+convolutions and both gradients as HIP launches (mztrain_conv_*); what changes is the plumbing around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -201,7 +202,7 @@ class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
     def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False,
-                 native_epilogue=False):
+                 native_epilogue=False, native_conv=False):
         """The flags choose what produces a step's gradients and what applies them; the step itself is one (_queue_step).
 
         graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
@@ -220,7 +221,13 @@ class Trainer:
         native_epilogue=True (GPU, residual networks): every relu(batch_norm(x) [+ residual]) of the network in training is
         one HIP launch forward and one backward (include/mztrain.h mztrain_epilogue_*, models._TrainingEpilogue) instead of
         torch's batch norm, add and ReLU with their autograd nodes; convolutions, heads and the optimizer stay torch's.
-        Combines with graph=True; checkpoints, publish and update_lr are untouched."""
+        Combines with graph=True; checkpoints, publish and update_lr are untouched.
+
+        native_conv=True (GPU, residual networks): every 3 x 3 convolution the launches cover (boards 3 x 3, 6 x 6, 6 x 7; 16
+        or 64 output channels; stride 1) runs its forward, data gradient and weight gradient as HIP launches (include/mztrain.h
+        mztrain_conv_*, models._TrainingConv3x3) instead of the convolution library's; every step first queues one pack
+        launch per such module, so a captured step repacks on replay.  Other convolutions stay torch's.  Combines with
+        native_epilogue, graph=True and train_steps."""
         if fc_optimizer and not fc_step:
             raise NotImplementedError("Trainer(fc_optimizer=True) updates the flat buffers of Trainer(fc_step=True): pass "
                                       "fc_step=True as well")
@@ -235,7 +242,7 @@ class Trainer:
         device = torch.device(device if device is not None else "cuda" if self.config.train_on_gpu else "cpu")
         self.model.to(device)
         self.model.train()
-        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, fc_step
+        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, native_conv, fc_step
         # (_fc_setup), then the optimizer's and graph's (_make_optimizer)
         if native_epilogue:
             if self.config.network != "resnet":
@@ -246,6 +253,18 @@ class Trainer:
                                           f"not on {device}")
             self.model.native_training_epilogue(True)
         self._native_norms = [m for m in self.model.modules() if isinstance(m, models.BatchNorm2d)] if native_epilogue else []
+        self._native_conv = bool(native_conv)
+        if native_conv:
+            if self.config.network != "resnet":
+                raise NotImplementedError(f"Trainer(native_conv=True) runs the 3 x 3 convolutions of residual networks; "
+                                          f"config.network is {self.config.network!r}")
+            if not any(isinstance(m, models.BoardConv2d) and m.training_covered() for m in self.model.modules()):
+                raise NotImplementedError("Trainer(native_conv=True) found no 3 x 3 convolution its launches cover (16 or 64 "
+                                          "output channels, at most 80 input channels, stride 1) in this network")
+            if device.type != "cuda":
+                raise NotImplementedError(f"Trainer(native_conv=True) runs HIP kernels: the model must be on the GPU, "
+                                          f"not on {device}")
+            self.model.native_training_conv(True)
         if fc_step:
             self._fc_setup(device)      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]
@@ -484,6 +503,8 @@ class Trainer:
     def _unroll(self, observations, actions):
         """(value logits, reward logits, policy logits) per unroll step; the hidden state handed from step to step
         passes half of its gradient on (paper appendix "Training", trainer.py:171-173)."""
+        if getattr(self, "_native_conv", False):     # (getattr: the tests unroll float64 twins through a bare namespace)
+            self.model.pack_training_convs()         # once per step and module, queued with the step: a replay repacks
         out = self.model.initial_inference(observations)
         steps, hidden = [out[:3]], out[3]
         for k in range(1, actions.shape[1]):

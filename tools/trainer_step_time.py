@@ -9,7 +9,11 @@ way, csrc/bn_epilogue.hip): the ways are alternated, the unflagged first, --wind
 every window closed by a synchronise; one JSON line per (config, way) with the windows, their median and max - min, and for
 the flagged ways whether a window overlaps one of the unflagged way of the same form.  --one-step WAY runs --steps steps of
 one way and nothing else (for a kernel trace of that way alone: two traces with different --steps differ by whole steps).
---kernel-alone times the two launches at --shape (default Gomoku's layer, 512,128,11,11) against torch's expression."""
+--kernel-alone times the two launches at --shape (default Gomoku's layer, 512,128,11,11) against torch's expression.
+
+--native-conv is the same protocol over four ways per form -- library, native_conv (the 3 x 3 convolutions and both gradients
+as HIP launches, csrc/conv_train.hip), native_epilogue, both -- eager and as a hipGraph, all alternated in one process with
+the unflagged way first; --one-step takes the names of these ways too."""
 import argparse, importlib, json, os, statistics, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -67,23 +71,27 @@ def window(trainer, batch, seconds):
 
 WAYS = [("library, eager", dict(graph=False)), ("native_epilogue, eager", dict(graph=False, native_epilogue=True)),
         ("library, hipgraph", dict(graph=True)), ("native_epilogue, hipgraph", dict(graph=True, native_epilogue=True))]
+FLAGS = [("library", {}), ("native_conv", dict(native_conv=True)), ("native_epilogue", dict(native_epilogue=True)),
+         ("native_conv + native_epilogue", dict(native_conv=True, native_epilogue=True))]
+CONV_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
+             for name, flags in FLAGS]
 
 
-def epilogue_ways(args):
+def epilogue_ways(args, ways=WAYS):
     for game in args.games.split(","):
         config = pkg("games." + game).MuZeroConfig()
         config.train_on_gpu = True
         torch.manual_seed(0)
         ckpt, batch, B, K1 = synthetic(config)
         if args.one_step is not None:
-            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **dict(WAYS)[args.one_step])
+            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **dict(CONV_WAYS)[args.one_step])
             for _ in range(args.steps):
                 trainer.update_weights(batch)
             torch.cuda.synchronize()
             print(json.dumps({"config": game, "way": args.one_step, "steps": args.steps}), flush=True)
             continue
         trainers = []
-        for name, how in WAYS:
+        for name, how in ways:
             trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **how)
             for _ in range(5):
                 trainer.update_weights(batch)
@@ -96,8 +104,8 @@ def epilogue_ways(args):
             line = {"config": game, "batch": B, "unrolled_positions": K1, "way": name,
                     "ms_per_training_step_windows": [round(t, 4) for t in times],
                     "median_ms": round(statistics.median(times), 4), "max_minus_min_ms": round(max(times) - min(times), 4)}
-            if name.startswith("native_epilogue"):
-                lo, hi = spans[name.replace("native_epilogue", "library")]
+            if not name.startswith("library"):
+                lo, hi = spans["library, " + name.rsplit(", ", 1)[1]]
                 line["windows_overlap_library"] = not (max(times) < lo or min(times) > hi)
             print(json.dumps(line), flush=True)
 
@@ -142,8 +150,9 @@ def kernel_alone(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--native-epilogue", action="store_true")
+    ap.add_argument("--native-conv", action="store_true")
     ap.add_argument("--kernel-alone", action="store_true")
-    ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(name for name, _ in WAYS))
+    ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(name for name, _ in CONV_WAYS))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=1.0)
@@ -152,6 +161,8 @@ def main():
     args = ap.parse_args()
     if args.kernel_alone:
         kernel_alone(args)
+    elif args.native_conv:
+        epilogue_ways(args, CONV_WAYS)
     elif args.native_epilogue or args.one_step is not None:
         epilogue_ways(args)
     else:
