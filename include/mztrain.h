@@ -9,7 +9,8 @@
  * It replaces the ~25 element-wise launches per unrolled step between the network's forward and backward.  For
  * fully-connected networks the forward and the backward are HIP launches too (mztrain_fc_*, below); residual networks
  * keep both with PyTorch-ROCm but for the convolution epilogue in training (mztrain_epilogue_*, below, on request) and the
- * 3 x 3 convolutions with their two gradients (mztrain_conv_*, below, on request); the
+ * 3 x 3 convolutions with their two gradients (mztrain_conv_*, below, on request) and the three heads (mztrain_heads_*,
+ * below, on request); the
  * optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
  * flat buffers of a fully-connected network.  Raw device pointers, fp32, contiguous; no torch types.
  *
@@ -280,6 +281,69 @@ int mztrain_conv_reference_pack(const mztrain_conv_pack_args *args);
 int mztrain_conv_reference_forward(const mztrain_conv_forward_args *args);
 int mztrain_conv_reference_dgrad(const mztrain_conv_dgrad_args *args);
 int mztrain_conv_reference_wgrad(const mztrain_conv_wgrad_args *args);
+
+/* ---- the reward / value / policy heads of a residual network in training (csrc/head_train.hip, csrc/head_train.h) -------
+ * One call of models.conv_heads: n_heads (1 or 2) heads in the layout of mzmcts_head_desc -- 1 x 1 convolution with bias,
+ * flatten (i = r * plane + p), Linear, ELU with alpha 1, Linear -- read ONE x [batch][channels][plane]; all heads of a call
+ * share channels and plane.  The order of every sum is csrc/head_train.h's.
+ *   forward   one launch, a workgroup per sample: the logits of every head, and what the backward does not recompute: the
+ *             flattened convolution output `flat` and the fc1 pre-activation `pre`, into buffers of the caller's.
+ *   backward  two launches.  Per sample: dlogits -> dh -> dpre = dh * elu'(pre) -> dflat -> dx; dx is one chain over all
+ *             heads of the call, written once (not accumulated into), and skipped with dx == NULL; dpre and dflat go to
+ *             caller-owned buffers that the second launch reads.  Reduction: the six parameter gradients of each head, every
+ *             entry 16 float64 partial sums over interleaved samples (for the convolution: samples and positions) folded in
+ *             ascending order and rounded once.  A NULL gradient pointer: that gradient is not computed.  No atomics, nothing
+ *             that has to be zeroed; every entry of every wanted output is written by every call; the same bits from run to
+ *             run, eager and captured.
+ * Host and device: bit for bit the same where no fc1 pre-activation is negative; with negative ones ELU goes through expm1f
+ * (its derivative through expf), whose bits differ between a host libm and the device's: each ELU output and each derivative
+ * agrees within MZTRAIN_HEADS_ELU_ULPS float32 ulps, and what follows them within what that perturbation propagates to
+ * (csrc/head_train.h).  No alignment beyond a float's is assumed. */
+#define MZTRAIN_HEADS_MAX 2
+#define MZTRAIN_HEADS_ELU_ULPS 4
+#define MZTRAIN_HEADS_MAX_BATCH 65536
+
+typedef struct mztrain_heads_forward_args {
+    const float *x;                              /* [batch][channels][plane] */
+    mzmcts_head_desc heads[MZTRAIN_HEADS_MAX];   /* the first n_heads are read */
+    float *logits[MZTRAIN_HEADS_MAX];            /* out [batch][outputs] */
+    float *flat[MZTRAIN_HEADS_MAX];              /* out [batch][reduced * plane] */
+    float *pre[MZTRAIN_HEADS_MAX];               /* out [batch][hidden] */
+    int64_t batch;
+    int32_t n_heads;
+} mztrain_heads_forward_args;
+
+typedef struct mztrain_heads_grads {             /* one head's parameter gradients, in the shapes of the parameters */
+    float *conv_w, *conv_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;    /* out; each may be NULL */
+} mztrain_heads_grads;
+
+typedef struct mztrain_heads_backward_args {
+    const float *x;                              /* the forward's x */
+    mzmcts_head_desc heads[MZTRAIN_HEADS_MAX];
+    const float *dlogits[MZTRAIN_HEADS_MAX];     /* [batch][outputs] */
+    const float *flat[MZTRAIN_HEADS_MAX];        /* what the forward wrote */
+    const float *pre[MZTRAIN_HEADS_MAX];
+    float *dpre[MZTRAIN_HEADS_MAX];              /* out [batch][hidden]: the per-sample launch writes, the reduction reads */
+    float *dflat[MZTRAIN_HEADS_MAX];             /* out [batch][reduced * plane] */
+    float *dx;                                   /* out [batch][channels][plane], or NULL */
+    mztrain_heads_grads grads[MZTRAIN_HEADS_MAX];
+    int64_t batch;
+    int32_t n_heads;
+} mztrain_heads_backward_args;
+
+/* 1 where the launches take the shape (per head; all heads of a call must pass): n_heads 1 or 2, channels in [1, 256], plane
+ * in [1, 128], reduced in [1, 16], hidden in [1, 128], outputs in [1, 256]; batches up to MZTRAIN_HEADS_MAX_BATCH.  0
+ * otherwise, with the reason through mzmcts_last_error(NULL). */
+int mztrain_heads_supported(int32_t channels, int32_t plane, int32_t reduced, int32_t hidden, int32_t outputs, int32_t n_heads);
+/* Forward queues one launch, backward two, on `stream`; no allocation, no host decision beyond the grid sizes, no
+ * synchronisation (capturable).  MZMCTS_ERR_INVALID with a message through mzmcts_last_error(NULL) before anything touches a
+ * device: null `args`; a null member of a head in use (`dx` and the members of `grads` alone may be null); heads of
+ * different channels or plane; a shape mztrain_heads_supported refuses; batch outside [1, MZTRAIN_HEADS_MAX_BATCH]. */
+int mztrain_heads_forward(const mztrain_heads_forward_args *args, void *stream);
+int mztrain_heads_backward(const mztrain_heads_backward_args *args, void *stream);
+/* The same rule, and the same refusals, with every pointer a HOST array: what the tests hold the kernels to. */
+int mztrain_heads_reference_forward(const mztrain_heads_forward_args *args);
+int mztrain_heads_reference_backward(const mztrain_heads_backward_args *args);
 
 #ifdef __cplusplus
 }

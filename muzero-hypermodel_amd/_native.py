@@ -133,6 +133,36 @@ CONV_SLICE = 64                 # include/mztrain.h MZTRAIN_CONV_SLICE
 CONV_AFFINE = 64                # include/mztrain.h MZTRAIN_CONV_AFFINE
 
 
+class MzHeadDesc(ctypes.Structure):
+    """mzmcts_head_desc (include/mzmcts.h): one reward / value / policy head of the residual networks."""
+    _fields_ = [("conv_w", c_void), ("conv_b", c_void), ("fc1_w", c_void), ("fc1_b", c_void), ("fc2_w", c_void),
+                ("fc2_b", c_void), ("channels", ctypes.c_int32), ("plane", ctypes.c_int32), ("reduced", ctypes.c_int32),
+                ("hidden", ctypes.c_int32), ("outputs", ctypes.c_int32)]
+
+
+HEADS_MAX = 2                   # include/mztrain.h MZTRAIN_HEADS_MAX
+HEADS_ELU_ULPS = 4              # include/mztrain.h MZTRAIN_HEADS_ELU_ULPS
+HEADS_MAX_BATCH = 65536         # include/mztrain.h MZTRAIN_HEADS_MAX_BATCH
+
+
+class MzTrainHeadsForwardArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_heads_forward_args: one or two heads reading one tensor."""
+    _fields_ = [("x", c_void), ("heads", MzHeadDesc * HEADS_MAX), ("logits", c_void * HEADS_MAX), ("flat", c_void * HEADS_MAX),
+                ("pre", c_void * HEADS_MAX), ("batch", ctypes.c_int64), ("n_heads", ctypes.c_int32)]
+
+
+class MzTrainHeadsGrads(ctypes.Structure):
+    """include/mztrain.h mztrain_heads_grads: one head's parameter gradients (None: not computed)."""
+    _fields_ = [(name, c_void) for name in ("conv_w", "conv_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+class MzTrainHeadsBackwardArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_heads_backward_args."""
+    _fields_ = [("x", c_void), ("heads", MzHeadDesc * HEADS_MAX)] + \
+               [(name, c_void * HEADS_MAX) for name in ("dlogits", "flat", "pre", "dpre", "dflat")] + \
+               [("dx", c_void), ("grads", MzTrainHeadsGrads * HEADS_MAX), ("batch", ctypes.c_int64), ("n_heads", ctypes.c_int32)]
+
+
 class MzFcDesc(ctypes.Structure):
     _fields_ = [("observation_floats", ctypes.c_int32), ("encoding_size", ctypes.c_int32),
                 ("n_hidden", ctypes.c_int32 * 5), ("hidden", (ctypes.c_int32 * 3) * 5)]
@@ -260,6 +290,11 @@ PROTOTYPES = {
     "mztrain_conv_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainConvForwardArgs)]),
     "mztrain_conv_reference_dgrad": (ctypes.c_int, [ctypes.POINTER(MzTrainConvDgradArgs)]),
     "mztrain_conv_reference_wgrad": (ctypes.c_int, [ctypes.POINTER(MzTrainConvWgradArgs)]),
+    "mztrain_heads_supported": (ctypes.c_int, [ctypes.c_int32] * 6),
+    "mztrain_heads_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsForwardArgs), c_void]),
+    "mztrain_heads_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsBackwardArgs), c_void]),
+    "mztrain_heads_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsForwardArgs)]),
+    "mztrain_heads_reference_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsBackwardArgs)]),
     "mzhist_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
     "mzhist_destroy": (None, [c_void]),
     "mzhist_last_error": (ctypes.c_char_p, [c_void]),
@@ -421,13 +456,6 @@ def check_train(lib, rc, what, where="", reason=True, refusal=None):
     if rc == -1 and refusal is not None:
         raise NotImplementedError(f"{refusal}: {message}")
     raise RuntimeError(f"{what} failed ({rc}){where}" + (f": {message}" if reason else ""))
-
-
-class MzHeadDesc(ctypes.Structure):
-    """mzmcts_head_desc (include/mzmcts.h): one reward / value / policy head of the residual networks."""
-    _fields_ = [("conv_w", c_void), ("conv_b", c_void), ("fc1_w", c_void), ("fc1_b", c_void), ("fc2_w", c_void),
-                ("fc2_b", c_void), ("channels", ctypes.c_int32), ("plane", ctypes.c_int32), ("reduced", ctypes.c_int32),
-                ("hidden", ctypes.c_int32), ("outputs", ctypes.c_int32)]
 
 
 class MzTowerHead(ctypes.Structure):

@@ -423,6 +423,8 @@ class PointwiseConv2d(torch.nn.Conv2d):
     per-image im2col + GEMM loop (4096 launches per call at 4096 envs), which dominated a TicTacToe
     simulation step."""
 
+    native_training = False     # True: conv_heads may run the head of this convolution as HIP training launches
+
     def __init__(self, in_channels, out_channels):
         super().__init__(in_channels, out_channels, 1)
 
@@ -440,14 +442,123 @@ def _head_is_native(x, conv, fc):
             and conv.bias is not None)
 
 
+_HEAD_PARAMETERS = ("conv_w", "conv_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")     # include/mztrain.h mztrain_heads_grads
+
+
+def _head_shape(conv, fc):
+    """(channels, plane, reduced, hidden, outputs) of a head the HIP training launches may cover -- one hidden layer, ELU
+    with alpha 1, a convolution bias, float32: what _head_is_native asks of the modules -- or None."""
+    if not (len(fc) == 4 and isinstance(fc[0], torch.nn.Linear) and isinstance(fc[1], torch.nn.ELU) and fc[1].alpha == 1.0
+            and isinstance(fc[2], torch.nn.Linear) and isinstance(fc[3], torch.nn.Identity) and conv.bias is not None
+            and fc[0].bias is not None and fc[2].bias is not None and conv.weight.dtype == torch.float32
+            and conv.kernel_size == (1, 1) and fc[0].in_features % conv.out_channels == 0
+            and fc[2].in_features == fc[0].out_features):
+        return None
+    return (conv.in_channels, fc[0].in_features // conv.out_channels, conv.out_channels, fc[0].out_features,
+            fc[2].out_features)
+
+
+def _head_covered(conv, fc):
+    """Whether the HIP training launches cover the head (include/mztrain.h mztrain_heads_supported), wherever it lives."""
+    shape = _head_shape(conv, fc)
+    return shape is not None and bool(_native.load().mztrain_heads_supported(*shape, 1))
+
+
+def _heads_take_training_path(x, heads):
+    """Whether this call of conv_heads runs the HIP training launches: every head switched on
+    (MuZeroResidualNetwork.native_training_heads), gradients enabled, a float32 CUDA tensor of 4 dimensions, and shapes the
+    launches cover together."""
+    if not (1 <= len(heads) <= _native.HEADS_MAX) or not torch.is_grad_enabled() \
+            or not all(getattr(conv, "native_training", False) for conv, _, _ in heads):
+        return False
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        return False
+    lib = _native.load()
+    for conv, fc, _ in heads:
+        shape = _head_shape(conv, fc)
+        if shape is None or shape[0] != x.shape[1] or shape[1] != x.shape[2] * x.shape[3] or conv.weight.device != x.device \
+                or not lib.mztrain_heads_supported(*shape, len(heads)):
+            return False
+    return x.shape[0] <= _native.HEADS_MAX_BATCH
+
+
+class _TrainingHeads(torch.autograd.Function):
+    """One call of conv_heads in training as HIP launches (include/mztrain.h mztrain_heads_*, csrc/head_train.h): one launch
+    forward for the one or two heads that read x -- it also saves each head's flattened convolution output and fc1
+    pre-activation --, two backward: per sample down to dx, which sums the heads and is written once, then the six parameter
+    gradients of each head as float64 sums in one fixed order.  No atomics, the same bits eager and captured.
+
+    apply(x, n_heads, conv weight, conv bias, fc1 weight, fc1 bias, fc2 weight, fc2 bias [, the second head's six])
+    returns a tuple of n_heads logits; the backward returns None for every gradient nobody needs and computes no dx then."""
+
+    @staticmethod
+    def forward(ctx, x, n_heads, *params):
+        lib = _native.load()
+        x = _aligned16(x)
+        params = tuple(_aligned16(p) for p in params)
+        b, c, h, w = x.shape
+        args = _native.MzTrainHeadsForwardArgs(x=x.data_ptr(), batch=b, n_heads=n_heads)
+        outs, flats, pres = [], [], []
+        for k in range(n_heads):
+            head = params[6 * k:6 * k + 6]
+            reduced, hidden, outputs = head[0].shape[0], head[2].shape[0], head[4].shape[0]
+            args.heads[k] = _native.MzHeadDesc(*[p.data_ptr() for p in head], c, h * w, reduced, hidden, outputs)
+            outs.append(torch.empty((b, outputs), dtype=torch.float32, device=x.device))
+            flats.append(torch.empty((b, reduced * h * w), dtype=torch.float32, device=x.device))
+            pres.append(torch.empty((b, hidden), dtype=torch.float32, device=x.device))
+            args.logits[k], args.flat[k], args.pre[k] = outs[k].data_ptr(), flats[k].data_ptr(), pres[k].data_ptr()
+        with torch.cuda.device(x.device):
+            rc = lib.mztrain_heads_forward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
+        _native.check_train(lib, rc, "mztrain_heads_forward", where=f" on a tensor of shape {tuple(x.shape)}")
+        ctx.save_for_backward(x, *params, *flats, *pres)
+        ctx.n_heads = n_heads
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grad_outs):
+        lib = _native.load()
+        n_heads = ctx.n_heads
+        x, *rest = ctx.saved_tensors
+        params, flats, pres = rest[:6 * n_heads], rest[6 * n_heads:7 * n_heads], rest[7 * n_heads:]
+        need = ctx.needs_input_grad                      # x, n_heads, then six per head
+        b, c, h, w = x.shape
+        dx = torch.empty_like(x) if need[0] else None
+        args = _native.MzTrainHeadsBackwardArgs(x=x.data_ptr(), dx=dx.data_ptr() if dx is not None else None, batch=b,
+                                                n_heads=n_heads)
+        grads, keep = [None] * (6 * n_heads), []
+        for k in range(n_heads):
+            head = params[6 * k:6 * k + 6]
+            reduced, hidden, outputs = head[0].shape[0], head[2].shape[0], head[4].shape[0]
+            args.heads[k] = _native.MzHeadDesc(*[p.data_ptr() for p in head], c, h * w, reduced, hidden, outputs)
+            dlogits = _aligned16(grad_outs[k])
+            dpre = torch.empty((b, hidden), dtype=torch.float32, device=x.device)
+            dflat = torch.empty((b, reduced * h * w), dtype=torch.float32, device=x.device)
+            keep += [dlogits, dpre, dflat]
+            args.dlogits[k], args.flat[k], args.pre[k] = dlogits.data_ptr(), flats[k].data_ptr(), pres[k].data_ptr()
+            args.dpre[k], args.dflat[k] = dpre.data_ptr(), dflat.data_ptr()
+            for i, name in enumerate(_HEAD_PARAMETERS):
+                if need[2 + 6 * k + i]:
+                    grads[6 * k + i] = torch.empty(head[i].shape, dtype=torch.float32, device=x.device)
+                    setattr(args.grads[k], name, grads[6 * k + i].data_ptr())
+        with torch.cuda.device(x.device):
+            rc = lib.mztrain_heads_backward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
+        _native.check_train(lib, rc, "mztrain_heads_backward", where=f" on a tensor of shape {tuple(x.shape)}")
+        return (dx, None, *grads)
+
+
 def conv_heads(x, heads):
     """[fc(conv(x).reshape(-1, flat_size)) for (conv, fc, flat_size) in heads]: reward / value / policy heads that
     read the same tensor (reference models.py:467-480, 500-522).  Inference on the GPU with the usual
     one-hidden-layer MLPs: ONE HIP launch for up to two heads (include/mzmcts.h mzmcts_conv_heads) reading the
     modules' own parameters; anything else (training, autograd, CPU, deeper MLPs, heads too large for LDS)
-    evaluates the torch modules.  The entry takes three heads; this wrapper stays at two because no network has
+    evaluates the torch modules -- unless the heads have been switched to the HIP training path (_TrainingHeads), one launch
+    forward and two backward per call.  The entry takes three heads; this wrapper stays at two because no network has
     three heads on ONE tensor (value and policy share the prediction features, the reward head reads the dynamics
     output): three heads go through conv_heads_multi, which admits them."""
+    if _heads_take_training_path(x, heads):
+        return list(_TrainingHeads.apply(x, len(heads), *[p for conv, fc, _ in heads for p in (
+            conv.weight, conv.bias, fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias)]))
     if 1 <= len(heads) <= 2 and all(_head_is_native(x, conv, fc) for conv, fc, _ in heads):
         x = x.contiguous()
         b, c, h, w = x.shape
@@ -1055,6 +1166,24 @@ class MuZeroResidualNetwork(AbstractNetwork):
         (strides, 128 channels, weights off the GPU) keeps torch's convolution, and so does any call on a board the launches
         do not cover.  Inference paths and their caches are not affected."""
         return sum(1 for m in self.modules() if isinstance(m, BoardConv2d) and m.native_training(on))
+
+    def training_heads(self):
+        """(conv, fc) of the reward, value and policy heads."""
+        dynamics, prediction = self.dynamics_network.module, self.prediction_network.module
+        return [(dynamics.conv1x1_reward, dynamics.fc), (prediction.conv1x1_value, prediction.fc_value),
+                (prediction.conv1x1_policy, prediction.fc_policy)]
+
+    def native_training_heads(self, on=True):
+        """Switch every head the HIP training launches cover (one hidden layer, ELU with alpha 1, a convolution bias, a shape
+        of mztrain_heads_supported) to (or back from) them: with gradients enabled conv_heads then runs a call's heads as
+        one launch forward and two backward (_TrainingHeads) instead of the torch modules with their autograd nodes.
+        Returns how many heads are switched on; the others, CPU tensors and every call with gradients off keep their
+        paths.  Inference paths and their caches are not affected."""
+        count = 0
+        for conv, fc in self.training_heads():
+            conv.native_training = bool(on) and _head_covered(conv, fc)
+            count += conv.native_training
+        return count
 
     def pack_training_convs(self):
         """One pack launch per switched convolution: what a training step queues before its first forward."""

@@ -5,7 +5,8 @@ The arithmetic is PyTorch-ROCm (fp32, the reference's operation order) -- or, fo
 Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_*), with fc_optimizer=True the optimizer as
 a HIP launch too (mztrain_opt_step), and for residual networks with Trainer(native_epilogue=True) every
 relu(batch_norm(x) [+ residual]) as one HIP launch each way (mztrain_epilogue_*), with Trainer(native_conv=True) their 3 x 3
-convolutions and both gradients as HIP launches (mztrain_conv_*); what changes is the plumbing around it:
+convolutions and both gradients as HIP launches (mztrain_conv_*), with Trainer(native_heads=True) their reward, value and
+policy heads as HIP launches (mztrain_heads_*); what changes is the plumbing around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -202,7 +203,7 @@ class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
     def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False,
-                 native_epilogue=False, native_conv=False):
+                 native_epilogue=False, native_conv=False, native_heads=False):
         """The flags choose what produces a step's gradients and what applies them; the step itself is one (_queue_step).
 
         graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
@@ -227,7 +228,13 @@ class Trainer:
         or 64 output channels; stride 1) runs its forward, data gradient and weight gradient as HIP launches (include/mztrain.h
         mztrain_conv_*, models._TrainingConv3x3) instead of the convolution library's; every step first queues one pack
         launch per such module, so a captured step repacks on replay.  Other convolutions stay torch's.  Combines with
-        native_epilogue, graph=True and train_steps."""
+        native_epilogue, graph=True and train_steps.
+
+        native_heads=True (GPU, residual networks): every reward, value and policy head the launches cover (one hidden
+        layer, ELU with alpha 1, a convolution bias) runs as one HIP launch forward per call and two backward
+        (include/mztrain.h mztrain_heads_*, models._TrainingHeads) instead of the torch modules with their autograd nodes;
+        value and policy share a call.  Other heads stay torch's.  Combines with native_epilogue, native_conv, graph=True and
+        train_steps."""
         if fc_optimizer and not fc_step:
             raise NotImplementedError("Trainer(fc_optimizer=True) updates the flat buffers of Trainer(fc_step=True): pass "
                                       "fc_step=True as well")
@@ -242,7 +249,7 @@ class Trainer:
         device = torch.device(device if device is not None else "cuda" if self.config.train_on_gpu else "cpu")
         self.model.to(device)
         self.model.train()
-        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, native_conv, fc_step
+        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, native_conv, native_heads, fc_step
         # (_fc_setup), then the optimizer's and graph's (_make_optimizer)
         if native_epilogue:
             if self.config.network != "resnet":
@@ -265,6 +272,18 @@ class Trainer:
                 raise NotImplementedError(f"Trainer(native_conv=True) runs HIP kernels: the model must be on the GPU, "
                                           f"not on {device}")
             self.model.native_training_conv(True)
+        if native_heads:
+            if self.config.network != "resnet":
+                raise NotImplementedError(f"Trainer(native_heads=True) runs the heads of residual networks; "
+                                          f"config.network is {self.config.network!r}")
+            if not any(models._head_covered(conv, fc) for conv, fc in self.model.training_heads()):
+                raise NotImplementedError("Trainer(native_heads=True) found no head its launches cover (one hidden layer, "
+                                          "ELU with alpha 1, a convolution bias, at most 256 channels, 128 positions, 16 "
+                                          "reduced channels, 128 hidden units and 256 outputs) in this network")
+            if device.type != "cuda":
+                raise NotImplementedError(f"Trainer(native_heads=True) runs HIP kernels: the model must be on the GPU, "
+                                          f"not on {device}")
+            self.model.native_training_heads(True)
         if fc_step:
             self._fc_setup(device)      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]

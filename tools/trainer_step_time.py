@@ -13,7 +13,11 @@ one way and nothing else (for a kernel trace of that way alone: two traces with 
 
 --native-conv is the same protocol over four ways per form -- library, native_conv (the 3 x 3 convolutions and both gradients
 as HIP launches, csrc/conv_train.hip), native_epilogue, both -- eager and as a hipGraph, all alternated in one process with
-the unflagged way first; --one-step takes the names of these ways too."""
+the unflagged way first; --one-step takes the names of these ways too.
+
+--native-heads is that protocol over library, native_heads (the reward, value and policy heads as HIP launches,
+csrc/head_train.hip), native_conv + native_epilogue, and all three flags; a line of the last way also says whether its windows
+overlap those of native_conv + native_epilogue of the same form.  --one-step takes these names as well."""
 import argparse, importlib, json, os, statistics, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,6 +79,11 @@ FLAGS = [("library", {}), ("native_conv", dict(native_conv=True)), ("native_epil
          ("native_conv + native_epilogue", dict(native_conv=True, native_epilogue=True))]
 CONV_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
              for name, flags in FLAGS]
+HEADS_FLAGS = [FLAGS[0], ("native_heads", dict(native_heads=True)), FLAGS[3],
+               ("native_conv + native_epilogue + native_heads", dict(native_conv=True, native_epilogue=True, native_heads=True))]
+HEADS_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
+              for name, flags in HEADS_FLAGS]
+ONE_STEP_WAYS = dict(CONV_WAYS + HEADS_WAYS)
 
 
 def epilogue_ways(args, ways=WAYS):
@@ -84,7 +93,7 @@ def epilogue_ways(args, ways=WAYS):
         torch.manual_seed(0)
         ckpt, batch, B, K1 = synthetic(config)
         if args.one_step is not None:
-            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **dict(CONV_WAYS)[args.one_step])
+            trainer = pkg("trainer").Trainer(ckpt, config, device="cuda", **ONE_STEP_WAYS[args.one_step])
             for _ in range(args.steps):
                 trainer.update_weights(batch)
             torch.cuda.synchronize()
@@ -107,6 +116,9 @@ def epilogue_ways(args, ways=WAYS):
             if not name.startswith("library"):
                 lo, hi = spans["library, " + name.rsplit(", ", 1)[1]]
                 line["windows_overlap_library"] = not (max(times) < lo or min(times) > hi)
+            if name.startswith("native_conv + native_epilogue + native_heads"):
+                lo, hi = spans["native_conv + native_epilogue, " + name.rsplit(", ", 1)[1]]
+                line["windows_overlap_conv_and_epilogue"] = not (max(times) < lo or min(times) > hi)
             print(json.dumps(line), flush=True)
 
 
@@ -151,8 +163,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--native-epilogue", action="store_true")
     ap.add_argument("--native-conv", action="store_true")
+    ap.add_argument("--native-heads", action="store_true")
     ap.add_argument("--kernel-alone", action="store_true")
-    ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(name for name, _ in CONV_WAYS))
+    ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(ONE_STEP_WAYS))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=1.0)
@@ -163,6 +176,8 @@ def main():
         kernel_alone(args)
     elif args.native_conv:
         epilogue_ways(args, CONV_WAYS)
+    elif args.native_heads:
+        epilogue_ways(args, HEADS_WAYS)
     elif args.native_epilogue or args.one_step is not None:
         epilogue_ways(args)
     else:
