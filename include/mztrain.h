@@ -10,7 +10,7 @@
  * fully-connected networks the forward and the backward are HIP launches too (mztrain_fc_*, below); residual networks
  * keep both with PyTorch-ROCm but for the convolution epilogue in training (mztrain_epilogue_*, below, on request) and the
  * 3 x 3 convolutions with their two gradients (mztrain_conv_*, below, on request) and the three heads (mztrain_heads_*,
- * below, on request); the
+ * below, on request) and the backward of the hidden state's min-max rescale (mztrain_rescale_*, below, on request); the
  * optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
  * flat buffers of a fully-connected network.  Raw device pointers, fp32, contiguous; no torch types.
  *
@@ -344,6 +344,35 @@ int mztrain_heads_backward(const mztrain_heads_backward_args *args, void *stream
 /* The same rule, and the same refusals, with every pointer a HOST array: what the tests hold the kernels to. */
 int mztrain_heads_reference_forward(const mztrain_heads_forward_args *args);
 int mztrain_heads_reference_backward(const mztrain_heads_backward_args *args);
+
+/* ---- the hidden state's min-max rescale of a residual network in training (csrc/rescale_train.hip, csrc/rescale_train.h) -----
+ * The backward of mzmcts_unit_rescale (include/mzmcts.h), which stays the forward: a row is one (sample, channel) plane of
+ * row_len = H * W floats, y = (x - min) / s with s = max - min, + 1e-5 where that is below 1e-5.  One launch: lo, hi, s and y
+ * are formed again from x by the forward's float32 operations (nothing but x is saved), the two sums over a row -- of g and
+ * of g * y -- run in float64 in ascending order, ties at an extreme share its gradient evenly (torch's amin / amax), and
+ * every grad_x entry is rounded to float32 once.  No atomics, nothing that has to be zeroed; every entry of grad_x is written
+ * by every call; the same bits from run to run, eager and captured, and as the host entry.  A NaN in a row makes that row's
+ * grad_x NaN and no other's.  grad_x may be grad_out.  No alignment beyond a float's is assumed. */
+typedef struct mztrain_rescale_backward_args {
+    const float *x;          /* [rows][row_len] the forward's input */
+    const float *grad_out;   /* [rows][row_len] gradient of the forward's output */
+    float *grad_x;           /* out [rows][row_len] */
+    int64_t rows;            /* batch * channels */
+    int32_t row_len;         /* H * W */
+} mztrain_rescale_backward_args;
+
+/* 1 where the launch takes the shape: row_len in [1, 128] (the bound of mzmcts_unit_rescale), rows >= 1, rows * row_len below
+ * 2^31.  0 otherwise, with the reason through mzmcts_last_error(NULL). */
+int mztrain_rescale_supported(int64_t rows, int32_t row_len);
+/* Queues one launch on `stream`, no allocation, no host decision beyond the plan below, no synchronisation (capturable).
+ * MZMCTS_ERR_INVALID with a message through mzmcts_last_error(NULL) before anything touches a device: null `args`; a null
+ * member; a shape mztrain_rescale_supported refuses. */
+int mztrain_rescale_backward(const mztrain_rescale_backward_args *args, void *stream);
+/* The same rule, and the same refusals, with every pointer a HOST array: what the tests hold the kernel to. */
+int mztrain_rescale_reference_backward(const mztrain_rescale_backward_args *args);
+/* The launch's plan into out[5] = {grid, block, rows per workgroup, floats between two rows in LDS (odd), LDS bytes};
+ * MZMCTS_ERR_INVALID (and zeros) for a null `out` or a shape mztrain_rescale_supported refuses. */
+int mztrain_rescale_backward_plan(int64_t rows, int32_t row_len, int64_t *out);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,11 @@ class MzTrainHeadsBackwardArgs(ctypes.Structure):
                [("dx", c_void), ("grads", MzTrainHeadsGrads * HEADS_MAX), ("batch", ctypes.c_int64), ("n_heads", ctypes.c_int32)]
 
 
+class MzTrainRescaleBackwardArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_rescale_backward_args: rows of row_len floats."""
+    _fields_ = [("x", c_void), ("grad_out", c_void), ("grad_x", c_void), ("rows", ctypes.c_int64), ("row_len", ctypes.c_int32)]
+
+
 class MzFcDesc(ctypes.Structure):
     _fields_ = [("observation_floats", ctypes.c_int32), ("encoding_size", ctypes.c_int32),
                 ("n_hidden", ctypes.c_int32 * 5), ("hidden", (ctypes.c_int32 * 3) * 5)]
@@ -295,6 +300,10 @@ PROTOTYPES = {
     "mztrain_heads_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsBackwardArgs), c_void]),
     "mztrain_heads_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsForwardArgs)]),
     "mztrain_heads_reference_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainHeadsBackwardArgs)]),
+    "mztrain_rescale_supported": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32]),
+    "mztrain_rescale_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainRescaleBackwardArgs), c_void]),
+    "mztrain_rescale_reference_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainRescaleBackwardArgs)]),
+    "mztrain_rescale_backward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
     "mzhist_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void)]),
     "mzhist_destroy": (None, [c_void]),
     "mzhist_last_error": (ctypes.c_char_p, [c_void]),

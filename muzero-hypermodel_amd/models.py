@@ -90,11 +90,60 @@ def _unit_rescale(x, dims):
     return x - low, span
 
 
-def board_rescale(raw, out=None):
+class _TrainingRescale(torch.autograd.Function):
+    """The per-plane min-max rescale of an NCHW tensor in training as ONE HIP launch each way: the forward is the inference
+    launch (include/mzmcts.h mzmcts_unit_rescale, the torch expression's bits), the backward one launch of its own
+    (include/mztrain.h mztrain_rescale_backward, csrc/rescale_train.h) that forms minimum, maximum and span again from the
+    saved input, sums in float64 in one fixed order and lets ties share an extreme's gradient evenly, as torch's amin and
+    amax do.  No atomics, the same bits eager and captured."""
+
+    @staticmethod
+    def forward(ctx, raw):
+        raw = raw.contiguous()
+        out = torch.empty_like(raw)
+        with torch.cuda.device(raw.device):
+            rc = _native.load().mzmcts_unit_rescale(raw.data_ptr(), out.data_ptr(), raw.shape[0] * raw.shape[1],
+                                                    raw.shape[2] * raw.shape[3],
+                                                    torch.cuda.current_stream(raw.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mzmcts_unit_rescale failed ({rc}) on a tensor of shape {tuple(raw.shape)}")
+        ctx.save_for_backward(raw)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None
+        lib = _native.load()
+        raw, = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        grad_raw = torch.empty_like(raw)
+        args = _native.MzTrainRescaleBackwardArgs(x=raw.data_ptr(), grad_out=grad_out.data_ptr(), grad_x=grad_raw.data_ptr(),
+                                                  rows=raw.shape[0] * raw.shape[1], row_len=raw.shape[2] * raw.shape[3])
+        with torch.cuda.device(raw.device):
+            rc = lib.mztrain_rescale_backward(ctypes.byref(args), torch.cuda.current_stream(raw.device).cuda_stream)
+        _native.check_train(lib, rc, "mztrain_rescale_backward", where=f" on a tensor of shape {tuple(raw.shape)}")
+        return grad_raw
+
+
+def _rescale_takes_training_path(raw, out, native_training):
+    """Whether this call of board_rescale runs _TrainingRescale: switched on (MuZeroResidualNetwork.native_training_rescale),
+    gradients enabled and wanted, a float32 CUDA tensor of 4 dimensions, no `out`, and a shape the launch covers (an empty
+    tensor is none)."""
+    return (native_training and out is None and torch.is_grad_enabled() and torch.is_tensor(raw) and raw.requires_grad
+            and raw.is_cuda and raw.dtype == torch.float32 and raw.dim() == 4
+            and bool(_native.load().mztrain_rescale_supported(raw.shape[0] * raw.shape[1], raw.shape[2] * raw.shape[3])))
+
+
+def board_rescale(raw, out=None, native_training=False):
     """Min-max rescale of every (sample, channel) board plane of an NCHW tensor to [0, 1] (reference
     models.py:525-549, 586-602), into `out` if given.  Inference on the GPU: one HIP launch
     (include/mzmcts.h mzmcts_unit_rescale), bit-identical to the torch expression below, which training, autograd
-    and CPU tensors take."""
+    and CPU tensors take -- unless `native_training` switches the call to the HIP training path (_TrainingRescale), that
+    launch forward and one backward."""
+    if _rescale_takes_training_path(raw, out, native_training):
+        return _TrainingRescale.apply(raw)
     plane = raw.shape[2] * raw.shape[3]
     native = (raw.is_cuda and raw.dtype == torch.float32 and plane <= 128 and not (torch.is_grad_enabled() and raw.requires_grad)
               and (out is None or (out.is_contiguous() and out.dtype == torch.float32 and out.shape == raw.shape)))
@@ -1125,6 +1174,8 @@ class PredictionNetwork(torch.nn.Module):
 
 
 class MuZeroResidualNetwork(AbstractNetwork):
+    native_rescale = False      # True: board_rescale may run the hidden state's rescale as HIP training launches
+
     def __init__(self, observation_shape, stacked_observations, action_space_size, num_blocks,
                  num_channels, reduced_channels_reward, reduced_channels_value,
                  reduced_channels_policy, fc_reward_layers, fc_value_layers, fc_policy_layers,
@@ -1136,6 +1187,7 @@ class MuZeroResidualNetwork(AbstractNetwork):
             plane = math.ceil(observation_shape[1] / 16) * math.ceil(observation_shape[2] / 16)
         else:
             plane = observation_shape[1] * observation_shape[2]
+        self.hidden_plane = plane           # positions of a hidden-state plane
         self.representation_network = _Replica(RepresentationNetwork(
             observation_shape, stacked_observations, num_blocks, num_channels, downsample))
         self.dynamics_network = _Replica(DynamicsNetwork(
@@ -1184,6 +1236,15 @@ class MuZeroResidualNetwork(AbstractNetwork):
             conv.native_training = bool(on) and _head_covered(conv, fc)
             count += conv.native_training
         return count
+
+    def native_training_rescale(self, on=True):
+        """Switch the hidden state's min-max rescale -- after the representation network and after every dynamics step -- to
+        (or back from) the HIP training path: with gradients enabled board_rescale then runs the inference launch forward and
+        one launch backward (_TrainingRescale) instead of torch's eight launches with their autograd nodes.  Decided per
+        call: CPU tensors, calls with gradients off, calls that write into `out_state` and planes of more than 128
+        positions keep their paths.  Inference is not affected."""
+        self.native_rescale = bool(on)
+        return self
 
     def pack_training_convs(self):
         """One pack launch per switched convolution: what a training step queues before its first forward."""
@@ -1429,7 +1490,7 @@ class MuZeroResidualNetwork(AbstractNetwork):
         return value, reward, policy_logits, next_state
 
     def representation(self, observation):
-        return board_rescale(self.representation_network(observation))
+        return board_rescale(self.representation_network(observation), native_training=self.native_rescale)
 
     def dynamics(self, encoded_state, action, out_state=None):
         conv = self.dynamics_network.module.conv
@@ -1439,13 +1500,13 @@ class MuZeroResidualNetwork(AbstractNetwork):
             b, _, h, w = encoded_state.shape
             plane = (action.to(encoded_state.dtype) / self.action_space_size)[:, :, None, None].expand(b, 1, h, w)
             raw, reward = self.dynamics_network(encoded_state, plane)
-            return board_rescale(raw, out=out_state), reward
+            return board_rescale(raw, out=out_state, native_training=self.native_rescale), reward
         return self.dynamics_from_planes(state_action_planes(encoded_state, action, self.action_space_size), out_state)
 
     def dynamics_from_planes(self, x, out_state=None):
         """dynamics on its ready-made input [B, channels + 1, h, w] (state planes + action / A plane)."""
         raw, reward = self.dynamics_network(x)
-        return board_rescale(raw, out=out_state), reward
+        return board_rescale(raw, out=out_state, native_training=self.native_rescale), reward
 
     def _root_tower(self, observation):
         """representation (stem or down-sampler + residual blocks) + rescale + prediction blocks of initial_inference

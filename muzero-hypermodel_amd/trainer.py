@@ -6,7 +6,8 @@ Trainer(fc_step=True), four HIP launches per step (include/mztrain.h mztrain_fc_
 a HIP launch too (mztrain_opt_step), and for residual networks with Trainer(native_epilogue=True) every
 relu(batch_norm(x) [+ residual]) as one HIP launch each way (mztrain_epilogue_*), with Trainer(native_conv=True) their 3 x 3
 convolutions and both gradients as HIP launches (mztrain_conv_*), with Trainer(native_heads=True) their reward, value and
-policy heads as HIP launches (mztrain_heads_*); what changes is the plumbing around it:
+policy heads as HIP launches (mztrain_heads_*), with Trainer(native_rescale=True) the hidden state's min-max rescale as one
+HIP launch each way (mzmcts_unit_rescale, mztrain_rescale_backward); what changes is the plumbing around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -203,7 +204,7 @@ class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
     def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False,
-                 native_epilogue=False, native_conv=False, native_heads=False):
+                 native_epilogue=False, native_conv=False, native_heads=False, native_rescale=False):
         """The flags choose what produces a step's gradients and what applies them; the step itself is one (_queue_step).
 
         graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
@@ -234,6 +235,13 @@ class Trainer:
         layer, ELU with alpha 1, a convolution bias) runs as one HIP launch forward per call and two backward
         (include/mztrain.h mztrain_heads_*, models._TrainingHeads) instead of the torch modules with their autograd nodes;
         value and policy share a call.  Other heads stay torch's.  Combines with native_epilogue, native_conv, graph=True and
+        train_steps.
+
+        native_rescale=True (GPU, residual networks, hidden-state planes of at most 128 positions): the per-plane min-max
+        rescale of the hidden state, after the representation network and after every dynamics step, runs the inference
+        launch forward and one HIP launch backward (include/mztrain.h mztrain_rescale_backward, models._TrainingRescale)
+        instead of torch's eight launches with their autograd nodes; ties at a plane's minimum or maximum share the gradient
+        evenly, as torch's amin and amax do.  Combines with native_epilogue, native_conv, native_heads, graph=True and
         train_steps."""
         if fc_optimizer and not fc_step:
             raise NotImplementedError("Trainer(fc_optimizer=True) updates the flat buffers of Trainer(fc_step=True): pass "
@@ -249,7 +257,8 @@ class Trainer:
         device = torch.device(device if device is not None else "cuda" if self.config.train_on_gpu else "cpu")
         self.model.to(device)
         self.model.train()
-        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, native_conv, native_heads, fc_step
+        # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, native_conv, native_heads,
+        # native_rescale, fc_step
         # (_fc_setup), then the optimizer's and graph's (_make_optimizer)
         if native_epilogue:
             if self.config.network != "resnet":
@@ -284,6 +293,17 @@ class Trainer:
                 raise NotImplementedError(f"Trainer(native_heads=True) runs HIP kernels: the model must be on the GPU, "
                                           f"not on {device}")
             self.model.native_training_heads(True)
+        if native_rescale:
+            if self.config.network != "resnet":
+                raise NotImplementedError(f"Trainer(native_rescale=True) runs the hidden-state rescale of residual networks; "
+                                          f"config.network is {self.config.network!r}")
+            if self.model.hidden_plane > 128:
+                raise NotImplementedError(f"Trainer(native_rescale=True) covers hidden-state planes of at most 128 positions; "
+                                          f"this network's have {self.model.hidden_plane}")
+            if device.type != "cuda":
+                raise NotImplementedError(f"Trainer(native_rescale=True) runs HIP kernels: the model must be on the GPU, "
+                                          f"not on {device}")
+            self.model.native_training_rescale(True)
         if fc_step:
             self._fc_setup(device)      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]

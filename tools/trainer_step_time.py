@@ -17,7 +17,11 @@ the unflagged way first; --one-step takes the names of these ways too.
 
 --native-heads is that protocol over library, native_heads (the reward, value and policy heads as HIP launches,
 csrc/head_train.hip), native_conv + native_epilogue, and all three flags; a line of the last way also says whether its windows
-overlap those of native_conv + native_epilogue of the same form.  --one-step takes these names as well."""
+overlap those of native_conv + native_epilogue of the same form.  --one-step takes these names as well.
+
+--native-rescale is that protocol over library, native_rescale (the backward of the hidden state's min-max rescale as one HIP
+launch, csrc/rescale_train.hip, under the inference launch as the forward), the three earlier flags, and all four; a line of
+the last way also says whether its windows overlap those of the three earlier flags.  --one-step takes these names too."""
 import argparse, importlib, json, os, statistics, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,7 +87,16 @@ HEADS_FLAGS = [FLAGS[0], ("native_heads", dict(native_heads=True)), FLAGS[3],
                ("native_conv + native_epilogue + native_heads", dict(native_conv=True, native_epilogue=True, native_heads=True))]
 HEADS_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
               for name, flags in HEADS_FLAGS]
-ONE_STEP_WAYS = dict(CONV_WAYS + HEADS_WAYS)
+RESCALE_FLAGS = [FLAGS[0], ("native_rescale", dict(native_rescale=True)), HEADS_FLAGS[3],
+                 ("native_conv + native_epilogue + native_heads + native_rescale",
+                  dict(native_conv=True, native_epilogue=True, native_heads=True, native_rescale=True))]
+RESCALE_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
+                for name, flags in RESCALE_FLAGS]
+ONE_STEP_WAYS = dict(CONV_WAYS + HEADS_WAYS + RESCALE_WAYS)
+# the way whose windows a line of the all-flags way is also compared with: {prefix of the way: (prefix of the other, key)}
+COMPARED = {"native_conv + native_epilogue + native_heads + native_rescale, ":
+            ("native_conv + native_epilogue + native_heads, ", "windows_overlap_three_flags"),
+            "native_conv + native_epilogue + native_heads, ": ("native_conv + native_epilogue, ", "windows_overlap_conv_and_epilogue")}
 
 
 def epilogue_ways(args, ways=WAYS):
@@ -116,9 +129,10 @@ def epilogue_ways(args, ways=WAYS):
             if not name.startswith("library"):
                 lo, hi = spans["library, " + name.rsplit(", ", 1)[1]]
                 line["windows_overlap_library"] = not (max(times) < lo or min(times) > hi)
-            if name.startswith("native_conv + native_epilogue + native_heads"):
-                lo, hi = spans["native_conv + native_epilogue, " + name.rsplit(", ", 1)[1]]
-                line["windows_overlap_conv_and_epilogue"] = not (max(times) < lo or min(times) > hi)
+            for prefix, (other, key) in COMPARED.items():
+                if name.startswith(prefix) and other + name.rsplit(", ", 1)[1] in spans:
+                    lo, hi = spans[other + name.rsplit(", ", 1)[1]]
+                    line[key] = not (max(times) < lo or min(times) > hi)
             print(json.dumps(line), flush=True)
 
 
@@ -164,6 +178,7 @@ def main():
     ap.add_argument("--native-epilogue", action="store_true")
     ap.add_argument("--native-conv", action="store_true")
     ap.add_argument("--native-heads", action="store_true")
+    ap.add_argument("--native-rescale", action="store_true")
     ap.add_argument("--kernel-alone", action="store_true")
     ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(ONE_STEP_WAYS))
     ap.add_argument("--steps", type=int, default=20)
@@ -178,6 +193,8 @@ def main():
         epilogue_ways(args, CONV_WAYS)
     elif args.native_heads:
         epilogue_ways(args, HEADS_WAYS)
+    elif args.native_rescale:
+        epilogue_ways(args, RESCALE_WAYS)
     elif args.native_epilogue or args.one_step is not None:
         epilogue_ways(args)
     else:
