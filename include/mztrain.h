@@ -12,7 +12,8 @@
  * 3 x 3 convolutions with their two gradients (mztrain_conv_*, below, on request) and the three heads (mztrain_heads_*,
  * below, on request) and the backward of the hidden state's min-max rescale (mztrain_rescale_*, below, on request); the
  * optimizer stays there too unless the caller asks for mztrain_opt_step (below) on the
- * flat buffers of a fully-connected network.  Raw device pointers, fp32, contiguous; no torch types.
+ * flat buffers of a fully-connected network, or for mztrain_fold_step (below), which folds a residual network's weight
+ * gradients and applies the same rule in one launch.  Raw device pointers, fp32, contiguous; no torch types.
  *
  * Domain.  Value and reward logits of loss-bearing positions are finite; a `-inf` entry outside the two target entries
  * does not contribute (the two-hot cross-entropy reads the logits at the two target entries only, where the reference's
@@ -135,6 +136,58 @@ int mztrain_opt_step(const mztrain_opt_args *args, void *stream);
 int mztrain_opt_reference(const mztrain_opt_args *args);
 /* Adam's per-step scalars {bc1, bc2, step_size, bc2s} of step t >= 1 as the kernel forms them (float64), into out[4]. */
 int mztrain_opt_scalars(double lr, double beta1, double beta2, int64_t t, double *out);
+
+/* ---- weight gradients folded and the optimizer applied in one launch (csrc/grad_fold.hip, csrc/grad_fold.h) ---------------
+ * For networks whose parameters are used several times in a step (a residual network's dynamics and prediction networks,
+ * once per unrolled position): every use writes its weight gradient into a SLOT of one staging buffer, and one launch per
+ * step folds each parameter's slots in ascending order -- plain float32 additions, the order in which autograd's
+ * AccumulateGrad would have summed them --, writes the sum into the flat gradient buffer and applies the rule of
+ * mztrain_opt_step to the parameter.  A segment is one parameter tensor.  A segment with uses == 0 is left alone (weights,
+ * moments, gradient); slots at index uses or above are never read; floats of the flat buffers outside every segment (batch
+ * norm statistics, padding) are never written, so weight decay does not reach them. */
+typedef struct mztrain_fold_segment {
+    int64_t offset;          /* first float of the tensor in the flat weight / moment / gradient buffers */
+    int64_t count;           /* floats of the tensor */
+    int64_t slot_base;       /* first float of slot 0 in the staging buffer */
+    int64_t slot_stride;     /* floats between two slots: >= count, a multiple of 4 */
+    int32_t capacity;        /* slots the staging buffer holds for the tensor */
+    int32_t reserved;
+} mztrain_fold_segment;
+
+typedef struct mztrain_fold_args {
+    mztrain_opt_args opt;    /* as mztrain_opt_step reads it, n = floats of each flat buffer -- but `grads` is WRITTEN here:
+                                the folded gradient of every segment with uses >= 1 */
+    const float *staging;    /* dev f32[staging_floats]: the slots */
+    int64_t staging_floats;
+} mztrain_fold_args;
+
+typedef struct mztrain_fold mztrain_fold;
+
+/* The handle keeps the segment list, the chunk table of the launch and the per-segment uses on `device`.  Refused with
+ * MZMCTS_ERR_INVALID and a message through mzmcts_last_error(NULL) before anything touches a device: a null `segments` or
+ * `out`; n_segments <= 0; n or staging_floats <= 0; a count <= 0; a segment outside [0, n) or one that overlaps another; a
+ * slot_stride below count or not a multiple of 4; a capacity < 1; slots [0, capacity) outside [0, staging_floats). */
+int mztrain_fold_create(const mztrain_fold_segment *segments, int32_t n_segments, int64_t n, int64_t staging_floats,
+                        int32_t device, mztrain_fold **out);
+void mztrain_fold_destroy(mztrain_fold *handle);
+/* The slots written per segment from now on.  Synchronous (waits for the device before and after the upload): not for a
+ * stream capture.  Refused: a null handle or `uses`, another n_segments than the handle's, a uses[k] outside [0, capacity]. */
+int mztrain_fold_set_uses(mztrain_fold *handle, const int32_t *uses, int32_t n_segments);
+/* Queues two launches on `stream` (the fold and update, then the one-thread launch of mztrain_opt_step that advances
+ * steps_done); no allocation, no host decision beyond the alignment of the base pointers, no synchronisation (capturable).
+ * 16 bytes per lane where a segment's offset and slot_base are multiples of 4 and every base pointer is 16-byte aligned,
+ * scalar accesses otherwise.  Refused before anything touches a device: a null handle, `args` or staging; the refusals of
+ * mztrain_opt_step on `opt`; an opt.n that is not the handle's n; staging_floats below the handle's; uses never set. */
+int mztrain_fold_step(mztrain_fold *handle, const mztrain_fold_args *args, void *stream);
+/* The same rule, and the refusals of create, set_uses and step, with every pointer a HOST array: what the tests hold the
+ * launch to. */
+int mztrain_fold_reference(const mztrain_fold_segment *segments, const int32_t *uses, int32_t n_segments,
+                           const mztrain_fold_args *args);
+/* The launch's plan into out[4] = {chunks, grid, block, floats of a full chunk}, and with `chunks` non-null (room for
+ * max_chunks entries) every chunk as {segment, first element within it, count, 1 where it may move 16 bytes per lane}.
+ * create's refusals; MZMCTS_ERR_INVALID (and zeros) for a null `out` or max_chunks below the plan's. */
+int mztrain_fold_plan(const mztrain_fold_segment *segments, int32_t n_segments, int64_t n, int64_t staging_floats,
+                      int64_t *out, int64_t *chunks, int64_t max_chunks);
 
 /* ---- the convolution epilogue of a residual network in training (csrc/bn_epilogue.hip, csrc/bn_epilogue.h) --------------
  * out = relu(batch_norm(x) [+ residual]) with the batch's own statistics, and its backward, one launch each: a workgroup

@@ -84,6 +84,22 @@ class MzTrainOptArgs(ctypes.Structure):
 OPT_ADAM, OPT_SGD = 0, 1
 
 
+class MzTrainFoldSegment(ctypes.Structure):
+    """include/mztrain.h mztrain_fold_segment: one parameter tensor in the flat buffers and its slots in the staging buffer."""
+    _fields_ = [(name, ctypes.c_int64) for name in ("offset", "count", "slot_base", "slot_stride")] + \
+               [("capacity", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MzTrainFoldArgs(ctypes.Structure):
+    """include/mztrain.h mztrain_fold_args: one fold-and-update step."""
+    _fields_ = [("opt", MzTrainOptArgs), ("staging", ctypes.c_void_p), ("staging_floats", ctypes.c_int64)]
+
+
+FOLD_SLOT_ALIGN = 128     # floats: the trainer rounds a segment's slot_stride up to this (512 bytes)
+FOLD_CHUNK = 1024         # floats of a full chunk of the launch (csrc/grad_fold.h kChunk)
+FOLD_MAX_BLOCKS = 1024
+
+
 class MzTrainEpilogueForwardArgs(ctypes.Structure):
     """include/mztrain.h mztrain_epilogue_forward_args: relu(batch_norm(x) [+ residual]) in training."""
     _fields_ = [(name, ctypes.c_void_p) for name in ("x", "residual", "gamma", "beta", "running_mean", "running_var", "out",
@@ -279,6 +295,15 @@ PROTOTYPES = {
     "mztrain_opt_reference": (ctypes.c_int, [ctypes.POINTER(MzTrainOptArgs)]),
     "mztrain_opt_scalars": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
                                            ctypes.POINTER(ctypes.c_double)]),
+    "mztrain_fold_create": (ctypes.c_int, [ctypes.POINTER(MzTrainFoldSegment), ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int32, ctypes.POINTER(c_void)]),
+    "mztrain_fold_destroy": (None, [c_void]),
+    "mztrain_fold_set_uses": (ctypes.c_int, [c_void, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    "mztrain_fold_step": (ctypes.c_int, [c_void, ctypes.POINTER(MzTrainFoldArgs), c_void]),
+    "mztrain_fold_reference": (ctypes.c_int, [ctypes.POINTER(MzTrainFoldSegment), ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.c_int32, ctypes.POINTER(MzTrainFoldArgs)]),
+    "mztrain_fold_plan": (ctypes.c_int, [ctypes.POINTER(MzTrainFoldSegment), ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64]),
     "mztrain_epilogue_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueForwardArgs), c_void]),
     "mztrain_epilogue_backward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueBackwardArgs), c_void]),
     "mztrain_epilogue_reference_forward": (ctypes.c_int, [ctypes.POINTER(MzTrainEpilogueForwardArgs)]),

@@ -132,6 +132,21 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 
 }  // namespace
 
+// what grad_fold.hip shares with the entries below: their refusals and the launch that advances the count
+namespace mz {
+namespace fco {
+
+int check_opt_args(const char* entry, const mztrain_opt_args* a) { return check(entry, a); }
+
+int queue_advance(int64_t* steps_done, void* stream) {
+    fc_optimizer_advance<<<dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream)>>>(steps_done);
+    MZ_HIP(nullptr, hipGetLastError());
+    return MZMCTS_OK;
+}
+
+}  // namespace fco
+}  // namespace mz
+
 extern "C" {
 
 int mztrain_opt_step(const mztrain_opt_args* a, void* stream_) {

@@ -304,6 +304,42 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
         return torch.addcmul(shift.view(1, -1, 1, 1), x, scale.view(1, -1, 1, 1))
 
 
+class GradientSink:
+    """Where the HIP training Functions put their weight gradients when a trainer installed one
+    (MuZeroResidualNetwork.install_gradient_sink, Trainer(native_optimizer=True)): `views[i][s]` is slot s of parameter i, a
+    view into one staging buffer in the parameter's shape.  The first gradient of a step to arrive for a parameter takes slot
+    0, the next slot 1, ...: ascending slots are the order in which autograd's AccumulateGrad would have summed them
+    (include/mztrain.h mztrain_fold_*).  One arrival more than a parameter has slots raises."""
+
+    def __init__(self, names, views):
+        self.names, self.views = list(names), views
+        self.arrivals = [0] * len(views)
+
+    def reset(self):
+        """A step begins: every parameter's next gradient goes to slot 0."""
+        self.arrivals = [0] * len(self.views)
+
+    def next_slot(self, index):
+        taken = self.arrivals[index]
+        if taken >= len(self.views[index]):
+            raise RuntimeError(f"gradient sink: {self.names[index]} received gradient number {taken + 1} of this step, its "
+                               f"staging buffer holds {len(self.views[index])} (config.num_unroll_steps + 1)")
+        self.arrivals[index] = taken + 1
+        return self.views[index][taken]
+
+
+def _sink_slot(parameter):
+    """(sink, index) of a parameter a gradient sink owns, else None -- and then the Functions' paths are what they were."""
+    return getattr(parameter, "_gradient_sink", None)
+
+
+def _sink_or_new(owner, shape, device):
+    """The tensor a weight-gradient launch writes: the parameter's next slot, or a fresh tensor for autograd."""
+    if owner is not None:
+        return owner[0].next_slot(owner[1])
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
 class _TrainingEpilogue(torch.autograd.Function):
     """relu(batch_norm(x) [+ residual]) with the batch's statistics as ONE HIP launch forward and one backward
     (include/mztrain.h mztrain_epilogue_*, csrc/bn_epilogue.h): every sum over a channel in float64 in one fixed order, no
@@ -330,6 +366,7 @@ class _TrainingEpilogue(torch.autograd.Function):
         _native.check_train(lib, rc, "mztrain_epilogue_forward", where=f" on a tensor of shape {tuple(x.shape)}")
         ctx.save_for_backward(x, out, weight, stats)
         ctx.with_residual = residual is not None
+        ctx.sinks = (_sink_slot(weight), _sink_slot(bias))
         return out
 
     @staticmethod
@@ -341,7 +378,12 @@ class _TrainingEpilogue(torch.autograd.Function):
         n, c, h, w = x.shape
         dx = torch.empty_like(x)
         dresidual = torch.empty_like(x) if ctx.with_residual and ctx.needs_input_grad[1] else None
-        dparams = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        need = ctx.needs_input_grad
+        sinks = tuple(owner if wanted else None for owner, wanted in zip(ctx.sinks, need[2:4]))
+        if sinks == (None, None):
+            dparams = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        else:       # a gradient sink owns the parameter: the launch writes its next slot, autograd gets None
+            dparams = [_sink_or_new(owner, (c,), x.device) for owner in sinks]
         args = _native.MzTrainEpilogueBackwardArgs(
             dy=dy.data_ptr(), x=x.data_ptr(), out=out.data_ptr(), gamma=weight.data_ptr(), save_mean=stats[0].data_ptr(),
             save_invstd=stats[1].data_ptr(), dx=dx.data_ptr(),
@@ -350,9 +392,8 @@ class _TrainingEpilogue(torch.autograd.Function):
         with torch.cuda.device(x.device):
             rc = lib.mztrain_epilogue_backward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
         _native.check_train(lib, rc, "mztrain_epilogue_backward", where=f" on a tensor of shape {tuple(x.shape)}")
-        need = ctx.needs_input_grad
-        return (dx if need[0] else None, dresidual, dparams[0] if need[2] else None, dparams[1] if need[3] else None,
-                None, None, None, None)
+        return (dx if need[0] else None, dresidual, dparams[0] if need[2] and sinks[0] is None else None,
+                dparams[1] if need[3] and sinks[1] is None else None, None, None, None, None)
 
 
 def _native_training(x, bn):
@@ -436,6 +477,7 @@ class _TrainingConv3x3(torch.autograd.Function):
         ctx.save_for_backward(x)
         ctx.conv = conv
         ctx.dx_planes = cin - (1 if plane is not None else 0)
+        ctx.sink = _sink_slot(weight)
         return y
 
     @staticmethod
@@ -458,12 +500,12 @@ class _TrainingConv3x3(torch.autograd.Function):
                 rc = lib.mztrain_conv_dgrad(ctypes.byref(args), stream)
                 _native.check_train(lib, rc, "mztrain_conv_dgrad", where=f" on a tensor of shape {tuple(dy.shape)}")
             if ctx.needs_input_grad[2]:
-                dw = torch.empty((conv.out_channels, cin, 3, 3), dtype=torch.float32, device=x.device)
+                dw = _sink_or_new(ctx.sink, (conv.out_channels, cin, 3, 3), x.device)
                 args = _native.MzTrainConvWgradArgs(x=x.data_ptr(), dy=dy.data_ptr(), dw=dw.data_ptr(), batch=b, cin=cin,
                                                     cout=conv.out_channels, height=h, width=w)
                 rc = lib.mztrain_conv_wgrad(ctypes.byref(args), stream)
                 _native.check_train(lib, rc, "mztrain_conv_wgrad", where=f" on a tensor of shape {tuple(x.shape)}")
-        return dx, None, dw, None
+        return dx, None, dw if ctx.sink is None else None, None
 
 
 class PointwiseConv2d(torch.nn.Conv2d):
@@ -544,7 +586,9 @@ class _TrainingHeads(torch.autograd.Function):
     def forward(ctx, x, n_heads, *params):
         lib = _native.load()
         x = _aligned16(x)
-        params = tuple(_aligned16(p) for p in params)
+        ctx.sinks = tuple(_sink_slot(p) for p in params)
+        # (the launches assume no alignment of the parameters beyond a float's: views into a flat weight buffer go as they are)
+        params = tuple(p.contiguous() for p in params)
         b, c, h, w = x.shape
         args = _native.MzTrainHeadsForwardArgs(x=x.data_ptr(), batch=b, n_heads=n_heads)
         outs, flats, pres = [], [], []
@@ -588,12 +632,13 @@ class _TrainingHeads(torch.autograd.Function):
             args.dpre[k], args.dflat[k] = dpre.data_ptr(), dflat.data_ptr()
             for i, name in enumerate(_HEAD_PARAMETERS):
                 if need[2 + 6 * k + i]:
-                    grads[6 * k + i] = torch.empty(head[i].shape, dtype=torch.float32, device=x.device)
+                    grads[6 * k + i] = _sink_or_new(ctx.sinks[6 * k + i], head[i].shape, x.device)
                     setattr(args.grads[k], name, grads[6 * k + i].data_ptr())
         with torch.cuda.device(x.device):
             rc = lib.mztrain_heads_backward(ctypes.byref(args), torch.cuda.current_stream(x.device).cuda_stream)
         _native.check_train(lib, rc, "mztrain_heads_backward", where=f" on a tensor of shape {tuple(x.shape)}")
-        return (dx, None, *grads)
+        # a gradient a sink took goes to autograd as None
+        return (dx, None, *[g if owner is None else None for g, owner in zip(grads, ctx.sinks)])
 
 
 def conv_heads(x, heads):
@@ -1244,6 +1289,34 @@ class MuZeroResidualNetwork(AbstractNetwork):
         call: CPU tensors, calls with gradients off, calls that write into `out_state` and planes of more than 128
         positions keep their paths.  Inference is not affected."""
         self.native_rescale = bool(on)
+        return self
+
+    def training_owned_parameters(self):
+        """Names of the parameters whose gradients the switched-on HIP training Functions produce: the weight of every
+        switched 3 x 3 convolution, weight and bias of every BatchNorm2d under the training epilogue, the six parameters of
+        every switched head.  Decided on the modules, not per call."""
+        owned = set()
+        for module in self.modules():
+            if isinstance(module, BoardConv2d) and module.__dict__.get("_train_on"):
+                owned.add(id(module.weight))
+            elif isinstance(module, BatchNorm2d) and getattr(module, "native_training", False) and module.affine:
+                owned.update((id(module.weight), id(module.bias)))
+        for conv, fc in self.training_heads():
+            if getattr(conv, "native_training", False):
+                owned.update(id(p) for p in (conv.weight, conv.bias, fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias))
+        return [name for name, parameter in self.named_parameters() if id(parameter) in owned]
+
+    def install_gradient_sink(self, sink):
+        """Hand the weight gradients of the parameters `sink.names` to `sink` (a GradientSink; None takes it away): the
+        backward of _TrainingConv3x3, _TrainingEpilogue and _TrainingHeads then writes each of them into the parameter's
+        next slot and returns None to autograd, so p.grad stays None.  Without a sink every path is what it was."""
+        for parameter in self.parameters():
+            parameter.__dict__.pop("_gradient_sink", None)
+        self.__dict__["_gradient_sink"] = sink
+        if sink is not None:
+            parameters = dict(self.named_parameters())
+            for index, name in enumerate(sink.names):
+                parameters[name]._gradient_sink = (sink, index)
         return self
 
     def pack_training_convs(self):

@@ -7,7 +7,9 @@ a HIP launch too (mztrain_opt_step), and for residual networks with Trainer(nati
 relu(batch_norm(x) [+ residual]) as one HIP launch each way (mztrain_epilogue_*), with Trainer(native_conv=True) their 3 x 3
 convolutions and both gradients as HIP launches (mztrain_conv_*), with Trainer(native_heads=True) their reward, value and
 policy heads as HIP launches (mztrain_heads_*), with Trainer(native_rescale=True) the hidden state's min-max rescale as one
-HIP launch each way (mzmcts_unit_rescale, mztrain_rescale_backward); what changes is the plumbing around it:
+HIP launch each way (mzmcts_unit_rescale, mztrain_rescale_backward), with Trainer(native_optimizer=True) the weight gradients
+of all uses of a parameter folded and Adam or SGD applied in one HIP launch (mztrain_fold_step); what changes is the plumbing
+around it:
 batches arrive as CUDA tensors from the device replay store (replay_buffer.ReplayBuffer.get_batch) and never
 visit the host, the new priorities are computed on the device and copied back once per step, and fresh weights
 leave through `publish` into the flat buffer the actors alias (weights.FlatWeights) -- one RCCL broadcast
@@ -90,11 +92,11 @@ class FlatOptimizer:
     rate as a device float64 and the count of steps done as a device int64 the launches advance.  state_dict() and
     load_state_dict() speak the format of torch.optim.Adam / torch.optim.SGD of the same configuration."""
 
-    def __init__(self, lib, model, flat_weights, flat_grad, kind, lr, weight_decay, momentum=0.0):
+    def __init__(self, lib, model, flat_weights, flat_grad, kind, lr, weight_decay, momentum=0.0, parameters_only=True):
         self._lib = lib
         self.kind = kind
         names = [name for name, _ in model.named_parameters()]
-        if names != list(flat_weights.float_keys):
+        if parameters_only and names != list(flat_weights.float_keys):
             raise NotImplementedError("Trainer(fc_optimizer=True): the flat buffer must hold the parameters and nothing else "
                                       "(a network with batch-norm statistics keeps torch's optimizer)")
         self._slices = [(flat_weights.offsets[name], parameter.numel(), tuple(parameter.shape))
@@ -117,26 +119,30 @@ class FlatOptimizer:
         self.param_groups = [group]
 
     def zero_grad(self, set_to_none=True):
-        """Nothing to do: the gradient buffer is overwritten whole by every step's launches."""
+        """Nothing to do: the gradient buffer is overwritten by every step's launches."""
 
     def set_lr(self, lr):
         self.param_groups[0]["lr"] = float(lr)
         self.lr.fill_(float(lr))
         self._lr_filled = float(lr)
 
-    def step(self):
+    def _opt_args(self):
+        """mztrain_opt_args of this step (the learning rate is brought up to the param group's first)."""
         group = self.param_groups[0]
         if float(group["lr"]) != self._lr_filled:
             self.set_lr(group["lr"])
         adam = self.kind == "Adam"
         beta1, beta2 = group["betas"] if adam else (0.0, 0.0)
         momentum = 0.0 if adam else float(group["momentum"])
-        args = _native.MzTrainOptArgs(
+        return _native.MzTrainOptArgs(
             kind=_native.OPT_ADAM if adam else _native.OPT_SGD, n=self.n, weights=self._weights.data_ptr(),
             grads=self._grads.data_ptr(), moment1=self.moment1.data_ptr() if adam or momentum != 0.0 else None,
             moment2=self.moment2.data_ptr() if adam else None, lr=self.lr.data_ptr(), steps_done=self.steps_done.data_ptr(),
             beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]) if adam else 0.0,
             weight_decay=float(group["weight_decay"]), momentum=momentum)
+
+    def step(self):
+        args = self._opt_args()
         rc = self._lib.mztrain_opt_step(ctypes.byref(args), torch.cuda.current_stream(self._weights.device).cuda_stream)
         _native.check_train(self._lib, rc, "mztrain_opt_step")
 
@@ -200,11 +206,67 @@ class FlatOptimizer:
         self.steps_done.fill_(done)
 
 
+class FoldOptimizer(FlatOptimizer):
+    """FlatOptimizer for a residual network under Trainer(native_optimizer=True): the flat buffers hold the batch-norm
+    statistics beside the parameters, the HIP training Functions write every use's weight gradient into a slot of one staging
+    buffer (models.GradientSink), and step() queues ONE launch that folds each parameter's slots in autograd's order into the
+    flat gradient buffer and applies Adam or SGD to exactly the parameters (include/mztrain.h mztrain_fold_step,
+    csrc/grad_fold.h).  Moments, learning rate, step count and torch's state-dict format are the base class's."""
+
+    def __init__(self, lib, model, flat_weights, flat_grad, kind, lr, weight_decay, momentum, capacity):
+        super().__init__(lib, model, flat_weights, flat_grad, kind, lr, weight_decay, momentum=momentum, parameters_only=False)
+        device = self._weights.device
+        self._device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        names = [name for name, _ in model.named_parameters()]
+        segments = (_native.MzTrainFoldSegment * len(names))()
+        total = 0
+        for index, (at, count, _) in enumerate(self._slices):
+            stride = -(-count // _native.FOLD_SLOT_ALIGN) * _native.FOLD_SLOT_ALIGN
+            segments[index] = _native.MzTrainFoldSegment(offset=at, count=count, slot_base=total, slot_stride=stride,
+                                                         capacity=capacity)
+            total += stride * capacity
+        self.segments = segments
+        self.staging = torch.zeros(total, dtype=torch.float32, device=device)
+        views = [[self.staging[s.slot_base + k * s.slot_stride: s.slot_base + k * s.slot_stride + s.count].view(shape)
+                  for k in range(capacity)] for s, (_, _, shape) in zip(segments, self._slices)]
+        self.sink = models.GradientSink(names, views)
+        self.uploaded_uses = None
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self._device):
+            rc = lib.mztrain_fold_create(segments, len(names), self.n, total, self._device.index, ctypes.byref(handle))
+        _native.check_train(lib, rc, "mztrain_fold_create", refusal="Trainer(native_optimizer=True)")
+        self._live = [handle]
+        weakref.finalize(self, self._destroy, lib, self._live, self._device)
+
+    @staticmethod
+    def _destroy(lib, live, device):
+        if live[0] is not None:
+            torch.cuda.synchronize(device)
+            lib.mztrain_fold_destroy(live[0])
+            live[0] = None
+
+    def set_uses(self, uses):
+        """Upload the slots written per parameter; synchronous, not for a capture."""
+        uses = [int(u) for u in uses]
+        with torch.cuda.device(self._device):
+            rc = self._lib.mztrain_fold_set_uses(self._live[0], (ctypes.c_int32 * len(uses))(*uses), len(uses))
+        _native.check_train(self._lib, rc, "mztrain_fold_set_uses")
+        self.uploaded_uses = uses
+
+    def step(self):
+        args = _native.MzTrainFoldArgs(opt=self._opt_args(), staging=self.staging.data_ptr(),
+                                       staging_floats=self.staging.numel())
+        with torch.cuda.device(self._device):
+            rc = self._lib.mztrain_fold_step(self._live[0], ctypes.byref(args),
+                                             torch.cuda.current_stream(self._device).cuda_stream)
+        _native.check_train(self._lib, rc, "mztrain_fold_step")
+
+
 class Trainer:
     native_loss = True      # on the GPU: the loss of a step as one HIP launch (False: the torch expression, for timing)
 
     def __init__(self, initial_checkpoint, config, device=None, graph=False, fc_step=False, fc_optimizer=False,
-                 native_epilogue=False, native_conv=False, native_heads=False, native_rescale=False):
+                 native_epilogue=False, native_conv=False, native_heads=False, native_rescale=False, native_optimizer=False):
         """The flags choose what produces a step's gradients and what applies them; the step itself is one (_queue_step).
 
         graph=True (GPU, Adam): the whole step -- unroll, loss launch, backward, optimizer -- is captured into a
@@ -242,7 +304,15 @@ class Trainer:
         launch forward and one HIP launch backward (include/mztrain.h mztrain_rescale_backward, models._TrainingRescale)
         instead of torch's eight launches with their autograd nodes; ties at a plane's minimum or maximum share the gradient
         evenly, as torch's amin and amax do.  Combines with native_epilogue, native_conv, native_heads, graph=True and
-        train_steps."""
+        train_steps.
+
+        native_optimizer=True (with native_epilogue, native_conv and native_heads; every parameter must belong to a module
+        they cover): the parameters and batch-norm statistics live in one flat buffer (`self.flat_weights`), every use's weight
+        gradient is written into a slot of one staging buffer instead of being summed into p.grad by one launch per
+        parameter and use, and ONE HIP launch per step folds the slots in autograd's order and applies Adam or SGD
+        (FoldOptimizer, include/mztrain.h mztrain_fold_step).  The folded gradients are bit for bit the four-flag trainer's
+        (`gradients()`), eager and captured steps give the same bits, graph=True takes SGD as well, and checkpoints keep
+        torch's optimizer format.  p.grad stays None; a call that falls back to torch's path raises after the backward."""
         if fc_optimizer and not fc_step:
             raise NotImplementedError("Trainer(fc_optimizer=True) updates the flat buffers of Trainer(fc_step=True): pass "
                                       "fc_step=True as well")
@@ -257,6 +327,22 @@ class Trainer:
         device = torch.device(device if device is not None else "cuda" if self.config.train_on_gpu else "cpu")
         self.model.to(device)
         self.model.train()
+        self._fold = None
+        if native_optimizer:
+            missing = [name for name, on in (("native_epilogue", native_epilogue), ("native_conv", native_conv),
+                                             ("native_heads", native_heads)) if not on]
+            if missing:
+                raise NotImplementedError(f"Trainer(native_optimizer=True) folds the gradients the HIP training launches "
+                                          f"write: pass {', '.join(name + '=True' for name in missing)} as well")
+            if self.config.network != "resnet":
+                raise NotImplementedError(f"Trainer(native_optimizer=True) folds the gradients of residual networks; "
+                                          f"config.network is {self.config.network!r}")
+            if device.type != "cuda":
+                raise NotImplementedError(f"Trainer(native_optimizer=True) runs HIP kernels: the model must be on the GPU, "
+                                          f"not on {device}")
+            if fc_step:
+                raise NotImplementedError("Trainer(native_optimizer=True) is the residual networks' way; fc_step=True has "
+                                          "fc_optimizer=True")
         # each flag's refusals stand at the head of what sets it up, in this order: native_epilogue, native_conv, native_heads,
         # native_rescale, fc_step
         # (_fc_setup), then the optimizer's and graph's (_make_optimizer)
@@ -304,10 +390,17 @@ class Trainer:
                 raise NotImplementedError(f"Trainer(native_rescale=True) runs HIP kernels: the model must be on the GPU, "
                                           f"not on {device}")
             self.model.native_training_rescale(True)
+        if native_optimizer:
+            owned = set(self.model.training_owned_parameters())
+            for name, _ in self.model.named_parameters():
+                if name not in owned:
+                    raise NotImplementedError(f"Trainer(native_optimizer=True): no HIP training launch covers the module of "
+                                              f"parameter {name}, its gradient would stay with autograd")
+            self._fold_setup(device)    # before the optimizer, like fc_step
         if fc_step:
             self._fc_setup(device)      # before the optimizer: it must hold the re-pointed parameters
         self.training_step = initial_checkpoint["training_step"]
-        self._fc_opt = bool(fc_optimizer)
+        self._fc_opt = bool(fc_optimizer) or bool(native_optimizer)      # the optimizer is a FlatOptimizer
         self.optimizer = self._make_optimizer(device)
         self._lr_host = float(self.config.lr_init)
         if initial_checkpoint.get("optimizer_state") is not None:
@@ -321,6 +414,12 @@ class Trainer:
                 f"{cfg.optimizer} is not implemented. You can change the optimizer manually in trainer.py.")
         if self._graph_mode and not self._fc_opt and (cfg.optimizer != "Adam" or device.type != "cuda"):
             raise NotImplementedError("Trainer(graph=True) captures an Adam step on the GPU")
+        if self._fold:
+            optimizer = FoldOptimizer(self._fc_lib, self.model, self.flat_weights, self._flat_grad, cfg.optimizer, cfg.lr_init,
+                                      cfg.weight_decay, cfg.momentum if cfg.optimizer == "SGD" else 0.0,
+                                      capacity=int(cfg.num_unroll_steps) + 1)
+            self.model.install_gradient_sink(optimizer.sink)
+            return optimizer
         if self._fc_opt:
             return FlatOptimizer(self._fc_lib, self.model, self.flat_weights, self._flat_grad, cfg.optimizer, cfg.lr_init,
                                  cfg.weight_decay, momentum=cfg.momentum if cfg.optimizer == "SGD" else 0.0)
@@ -352,6 +451,45 @@ class Trainer:
             for entry in self.optimizer.state.values():
                 if "step" in entry:
                     entry["step"] = torch.as_tensor(entry["step"], dtype=torch.float32).to(self._lr.device).reshape(())
+
+    # ---- gradients folded and the optimizer applied in one launch (include/mztrain.h mztrain_fold_*) -------
+    def _fold_setup(self, device):
+        """Parameters and batch-norm statistics into one flat buffer, and a flat gradient buffer indexed like it."""
+        from . import weights
+        self._fc_lib = _native.load()
+        self.flat_weights = weights.FlatWeights(self.model)
+        self._flat_grad = torch.zeros(self.flat_weights.numel, dtype=torch.float32, device=device)
+        self._fold = True
+
+    def _fold_after_backward(self):
+        """What the host checks after every backward Python runs (eager, warm-up, capture): no gradient went to autograd,
+        and the slots written are the ones the launch will read."""
+        for name, parameter in self.model.named_parameters():
+            if parameter.grad is not None:
+                raise NotImplementedError(f"Trainer(native_optimizer=True): the gradient of {name} came through autograd -- a "
+                                          f"call of its module fell back to torch's path; the fold launch would lose it")
+        uses = list(self.optimizer.sink.arrivals)
+        if uses != self.optimizer.uploaded_uses:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Trainer(native_optimizer=True): the uses of the parameters changed while a capture is "
+                                   f"open ({self.optimizer.uploaded_uses} -> {uses})")
+            if self._graph is not None:
+                raise RuntimeError("Trainer(native_optimizer=True): the captured step was recorded with other uses")
+            self.optimizer.set_uses(uses)
+
+    def _fold_mark_moved(self):
+        """The fold launch writes the parameters through raw pointers: move their version counters on the host (no launch),
+        so that every inference cache keyed by them (folded batch norms, packed and expanded convolutions) is rebuilt on its
+        next use, as after a step of torch's optimizer."""
+        for parameter in self.model.parameters():
+            torch.autograd.graph.increment_version(parameter)
+
+    def gradients(self):
+        """{name: view into the flat gradient buffer}: the folded gradients of the last step (native_optimizer=True)."""
+        if not self._fold:
+            raise NotImplementedError("Trainer.gradients() reads the flat gradient buffer of Trainer(native_optimizer=True)")
+        return {name: self._flat_grad[self.flat_weights.offsets[name]: self.flat_weights.offsets[name] + p.numel()].view(p.shape)
+                for name, p in self.model.named_parameters()}
 
     # ---- the fully-connected step as HIP launches (include/mztrain.h mztrain_fc_*) -------------------------
     def _fc_setup(self, device):
@@ -544,6 +682,8 @@ class Trainer:
         passes half of its gradient on (paper appendix "Training", trainer.py:171-173)."""
         if getattr(self, "_native_conv", False):     # (getattr: the tests unroll float64 twins through a bare namespace)
             self.model.pack_training_convs()         # once per step and module, queued with the step: a replay repacks
+        if getattr(self, "_fold", None):
+            self.optimizer.sink.reset()              # this step's first gradient of every parameter goes to slot 0
         out = self.model.initial_inference(observations)
         steps, hidden = [out[:3]], out[3]
         for k in range(1, actions.shape[1]):
@@ -587,9 +727,16 @@ class Trainer:
             else:
                 sample_loss, head_sums, priorities = self._loss_torch(b)
             loss = sample_loss.mean()
-            self.optimizer.zero_grad(set_to_none=True)
-            loss.backward()
+            if self._fold:
+                # p.grad is None and stays None: the Functions write every weight gradient into its slot
+                loss.backward()
+                self._fold_after_backward()
+            else:
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
         self.optimizer.step()
+        if self._fold:
+            self._fold_mark_moved()
         return torch.cat([loss.detach().reshape(1), head_sums.mean(dim=1)]), priorities
 
     def _loss_native(self, b):
@@ -642,6 +789,8 @@ class Trainer:
         self._graph.replay()
         for norm in self._native_norms:      # a replay runs no Python: drop the eval-mode constants the launches outdated
             norm._folded = None
+        if self._fold:
+            self._fold_mark_moved()
 
     def _capture(self, b):
         """Warm _queue_step up on a side stream (what stream capture requires) and capture it into a hipGraph on static

@@ -21,7 +21,12 @@ overlap those of native_conv + native_epilogue of the same form.  --one-step tak
 
 --native-rescale is that protocol over library, native_rescale (the backward of the hidden state's min-max rescale as one HIP
 launch, csrc/rescale_train.hip, under the inference launch as the forward), the three earlier flags, and all four; a line of
-the last way also says whether its windows overlap those of the three earlier flags.  --one-step takes these names too."""
+the last way also says whether its windows overlap those of the three earlier flags.  --one-step takes these names too.
+
+--native-optimizer is that protocol over two ways per form: the four flags with torch's optimizer ("four flags", the unflagged
+way here, first) and the same with Trainer(native_optimizer=True) (the weight gradients folded and Adam applied in one HIP
+launch, csrc/grad_fold.hip); a line of the second way says whether its windows overlap those of the first.  --one-step takes
+these names too."""
 import argparse, importlib, json, os, statistics, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,9 +97,13 @@ RESCALE_FLAGS = [FLAGS[0], ("native_rescale", dict(native_rescale=True)), HEADS_
                   dict(native_conv=True, native_epilogue=True, native_heads=True, native_rescale=True))]
 RESCALE_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
                 for name, flags in RESCALE_FLAGS]
-ONE_STEP_WAYS = dict(CONV_WAYS + HEADS_WAYS + RESCALE_WAYS)
+OPTIMIZER_FLAGS = [("four flags", RESCALE_FLAGS[3][1]), ("four flags + native_optimizer", dict(native_optimizer=True, **RESCALE_FLAGS[3][1]))]
+OPTIMIZER_WAYS = [(f"{name}, {form}", dict(graph=graph, **flags)) for form, graph in (("eager", False), ("hipgraph", True))
+                  for name, flags in OPTIMIZER_FLAGS]
+ONE_STEP_WAYS = dict(CONV_WAYS + HEADS_WAYS + RESCALE_WAYS + OPTIMIZER_WAYS)
 # the way whose windows a line of the all-flags way is also compared with: {prefix of the way: (prefix of the other, key)}
-COMPARED = {"native_conv + native_epilogue + native_heads + native_rescale, ":
+COMPARED = {"four flags + native_optimizer, ": ("four flags, ", "windows_overlap_four_flags"),
+            "native_conv + native_epilogue + native_heads + native_rescale, ":
             ("native_conv + native_epilogue + native_heads, ", "windows_overlap_three_flags"),
             "native_conv + native_epilogue + native_heads, ": ("native_conv + native_epilogue, ", "windows_overlap_conv_and_epilogue")}
 
@@ -126,7 +135,7 @@ def epilogue_ways(args, ways=WAYS):
             line = {"config": game, "batch": B, "unrolled_positions": K1, "way": name,
                     "ms_per_training_step_windows": [round(t, 4) for t in times],
                     "median_ms": round(statistics.median(times), 4), "max_minus_min_ms": round(max(times) - min(times), 4)}
-            if not name.startswith("library"):
+            if not name.startswith("library") and "library, " + name.rsplit(", ", 1)[1] in spans:
                 lo, hi = spans["library, " + name.rsplit(", ", 1)[1]]
                 line["windows_overlap_library"] = not (max(times) < lo or min(times) > hi)
             for prefix, (other, key) in COMPARED.items():
@@ -179,6 +188,7 @@ def main():
     ap.add_argument("--native-conv", action="store_true")
     ap.add_argument("--native-heads", action="store_true")
     ap.add_argument("--native-rescale", action="store_true")
+    ap.add_argument("--native-optimizer", action="store_true")
     ap.add_argument("--kernel-alone", action="store_true")
     ap.add_argument("--one-step", default=None, metavar="WAY", help="one of: " + "; ".join(ONE_STEP_WAYS))
     ap.add_argument("--steps", type=int, default=20)
@@ -195,6 +205,8 @@ def main():
         epilogue_ways(args, HEADS_WAYS)
     elif args.native_rescale:
         epilogue_ways(args, RESCALE_WAYS)
+    elif args.native_optimizer:
+        epilogue_ways(args, OPTIMIZER_WAYS)
     elif args.native_epilogue or args.one_step is not None:
         epilogue_ways(args)
     else:
