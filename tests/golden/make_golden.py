@@ -1084,6 +1084,189 @@ def g12_reference_speed(ctx):
          games=len(games), positions=positions)
 
 
+def save_exact(name, **arrays):
+    """An .npz whose bytes depend on the arrays alone (numpy's savez stamps every member with the time of day)."""
+    import zipfile
+    path = os.path.join(HERE, name + ".npz")
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for key, value in arrays.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with zf.open(info, "w") as fid:
+                numpy.lib.format.write_array(fid, numpy.ascontiguousarray(value), allow_pickle=False)
+    print(f"  wrote {name}.npz  ({os.path.getsize(path)/1024:.1f} KiB)")
+
+
+def g24_board_rules(ctx):
+    """The rules of the two board games line by line.  TicTacToe whole: every reachable non-terminal position, every
+    ply from it, the expert's move in it.  Connect4 as a selection from seeded random legal playouts: plies chosen so
+    that every winning line is completed and blocked by one (and the draws, last-ply wins and double wins are there),
+    expert positions chosen so that the windows' findings are covered.  The positions are chosen with the line tables
+    of tests/board_rules_reference.py; every recorded verdict is the reference's own (Game.step, legal_actions,
+    expert_agent), the env put into the position by assigning env.board and env.player."""
+    import games.connect4 as c4
+    import games.tictactoe as ttt
+    tests_dir = os.path.dirname(HERE)
+    if tests_dir not in sys.path:
+        sys.path.insert(0, tests_dir)
+    import board_rules_reference as model
+
+    # ---- TicTacToe, all of it
+    game = ttt.Game()
+    game.reset()
+
+    def put(board, player):
+        game.env.board = numpy.array(board, dtype="int32").reshape(3, 3)
+        game.env.player = player
+
+    start = tuple(int(v) for v in game.env.board.reshape(-1))
+    index, boards, players = {start: 0}, [start], [int(game.env.player)]
+    ply = dict(position=[], action=[], reward=[], done=[])
+    i = 0
+    while i < len(boards):
+        put(boards[i], players[i])
+        for a in list(game.legal_actions()):
+            put(boards[i], players[i])
+            _, reward, done = game.step(a)
+            ply["position"].append(i); ply["action"].append(a); ply["reward"].append(reward); ply["done"].append(done)
+            key = tuple(int(v) for v in game.env.board.reshape(-1))
+            if not done and key not in index:
+                index[key] = len(boards)
+                boards.append(key)
+                players.append(int(game.env.player))
+        i += 1
+    experts = []
+    for i in range(len(boards)):
+        put(boards[i], players[i])
+        numpy.random.seed(7000 + i)
+        experts.append(int(game.expert_agent()))
+    print(f"   tictactoe: {len(boards)} non-terminal positions, {len(ply['action'])} plies, "
+          f"{sum(ply['done'])} of them ending the game, {sum(r != 0 for r in ply['reward'])} won")
+    save_exact("g24_tictactoe_rules", board=numpy.array(boards, dtype="int8"), player=numpy.array(players, dtype="int8"),
+               expert=numpy.array(experts, dtype="int32"), seed=7000 + numpy.arange(len(boards), dtype="int64"),
+               ply_position=numpy.array(ply["position"], dtype="int32"), ply_action=numpy.array(ply["action"], dtype="int32"),
+               ply_reward=numpy.array(ply["reward"], dtype="int32"), ply_done=numpy.array(ply["done"], dtype="bool"))
+
+    # ---- Connect4: choose
+    rs = numpy.random.RandomState(2424)
+    cases = set((line, colour, last) for line, last in model.c4_last_stone_cases() for colour in (1, -1))
+    seen_last, seen_win, seen_block = set(), set(), set()
+    counts = dict(draw42=0, win42=0, double=0, quiet=0, busy=0)
+    seen_effective, seen_failed = set(), set()
+    expert_counts = dict(override=0, nothing=0, single=0)
+    plies, positions = [], []
+    CAP = dict(draw42=30, win42=30, double=40, override=260, nothing=70, single=70)
+    games_played = plies_seen = 0
+    expert_games = 0
+
+    def plies_complete():
+        return (len(seen_last) >= 424 and len(seen_win) == 138 and len(seen_block) == 138 and counts["draw42"] >= 24
+                and counts["win42"] >= 24 and counts["double"] >= 24)
+
+    def experts_complete():
+        return (len(seen_effective) >= 540 and len(seen_failed) >= 510 and expert_counts["override"] >= 220
+                and expert_counts["nothing"] >= 60 and expert_counts["single"] >= 60)
+
+    while games_played < 400000 and not (plies_complete() and experts_complete()):
+        board, player = [0] * 42, 1
+        draws = rs.random_sample(42)
+        scan_experts = not experts_complete()
+        expert_games += scan_experts
+        for t in range(42):
+            legal = model.c4_legal(board)
+            action = legal[int(draws[t] * len(legal))]
+            plies_seen += 1
+            if scan_experts:
+                move, findings = model.c4_expert(board, player, None)
+                effective = set(f[:6] for f in findings if f[6])
+                failed = set(f[:6] for f in findings if not f[6])
+                first = model.first_effective(findings)
+                keep = bool(effective - seen_effective) or bool(failed - seen_failed)
+                override = first is not None and move != model.c4_finding_column(first)
+                if override and expert_counts["override"] < CAP["override"]:
+                    keep = True
+                nothing = not findings and t == (7 * expert_counts["nothing"]) % 40
+                if nothing and expert_counts["nothing"] < CAP["nothing"]:
+                    keep = True
+                if len(legal) == 1 and expert_counts["single"] < CAP["single"]:
+                    keep = True
+                if keep:
+                    seen_effective |= effective
+                    seen_failed |= failed
+                    expert_counts["override"] += override
+                    expert_counts["nothing"] += not findings
+                    expert_counts["single"] += len(legal) == 1
+                    positions.append((tuple(board), player))
+            completed, blocked = model.c4_ply_events(board, player, action)
+            new_last = set((line, player, last) for line, last in completed) - seen_last
+            new_block = set((line, -player) for line in blocked) - seen_block
+            keep = bool(new_last) or bool(new_block)
+            last_ply = t == 41
+            if last_ply and not completed and counts["draw42"] < CAP["draw42"]:
+                keep = True
+            if last_ply and completed and counts["win42"] < CAP["win42"]:
+                keep = True
+            if len(completed) >= 2 and counts["double"] < CAP["double"]:
+                keep = True
+            quiet = not completed and not blocked and not last_ply
+            if quiet and counts["quiet"] < counts["busy"] and t == (5 * counts["quiet"]) % 41:
+                keep = True
+            if keep:
+                seen_last |= new_last
+                seen_win |= set((line, player) for line, _ in completed)
+                seen_block |= new_block
+                counts["draw42"] += last_ply and not completed
+                counts["win42"] += last_ply and bool(completed)
+                counts["double"] += len(completed) >= 2
+                counts["quiet"] += quiet
+                counts["busy"] += not quiet
+                plies.append((tuple(board), player, action))
+            board[model.c4_landing(board, action)] = player
+            player = -player
+            if completed:
+                break
+        games_played += 1
+    assert seen_last <= cases
+    print(f"   connect4: {games_played} games, {plies_seen} plies looked at ({expert_games} games for the expert rows)")
+    print(f"   connect4 plies kept: {len(plies)}: wins {len(seen_win)}/138 (line, colour), {len(seen_last)}/426 (line, colour, "
+          f"last stone), blocks {len(seen_block)}/138, draws on ply 42: {counts['draw42']}, wins on ply 42: {counts['win42']}, "
+          f"double wins: {counts['double']}, quiet plies: {counts['quiet']}")
+    print(f"   connect4 expert rows kept: {len(positions)}: effective findings {len(seen_effective)}, failed height tests "
+          f"{len(seen_failed)}, overridden first findings {expert_counts['override']}, no finding {expert_counts['nothing']}, "
+          f"single legal column {expert_counts['single']}")
+
+    # ---- Connect4: record the reference's verdicts
+    game = c4.Game()
+    game.reset()
+
+    def put4(board, player):
+        game.env.board = numpy.array(board, dtype="int32").reshape(6, 7)
+        game.env.player = player
+
+    rows = dict(reward=[], done=[], legal=[], n_legal=[])
+    for board, player, action in plies:
+        put4(board, player)
+        assert action in game.legal_actions()
+        _, reward, done = game.step(action)
+        legal = list(game.legal_actions())
+        rows["reward"].append(reward); rows["done"].append(done); rows["n_legal"].append(len(legal))
+        rows["legal"].append(legal + [-1] * (7 - len(legal)))
+    moves = []
+    for r, (board, player) in enumerate(positions):
+        put4(board, player)
+        numpy.random.seed(9000 + r)
+        moves.append(int(game.expert_agent()))
+    save_exact("g24_connect4_rules",
+               ply_board=numpy.array([p[0] for p in plies], dtype="int8"), ply_player=numpy.array([p[1] for p in plies], dtype="int8"),
+               ply_action=numpy.array([p[2] for p in plies], dtype="int32"), ply_reward=numpy.array(rows["reward"], dtype="int32"),
+               ply_done=numpy.array(rows["done"], dtype="bool"), ply_legal=numpy.array(rows["legal"], dtype="int32"),
+               ply_n_legal=numpy.array(rows["n_legal"], dtype="int32"),
+               expert_board=numpy.array([p[0] for p in positions], dtype="int8"),
+               expert_player=numpy.array([p[1] for p in positions], dtype="int8"),
+               expert_seed=9000 + numpy.arange(len(positions), dtype="int64"), expert_move=numpy.array(moves, dtype="int32"))
+
+
 def make_configs():
     import games.tictactoe as ttt
     import games.connect4 as c4
@@ -1105,7 +1288,7 @@ def make_configs():
 ALL = [g0_weights, g1_support_to_scalar, g2_fc_inference, g3_resnet_inference, g4_cartpole,
        g5_tictactoe, g5_connect4, g5_atari84, g5_degenerate, g6_play_game, g6_connect4_opponents, g7_rng, g8_select_action,
        g9_stacked, g10_reference_speed, g11_envs, g12_replay_targets, g12_reference_speed, g13_reanalyse, g14_trainer, g15_self_play_loop, g16_trainer_resnet,
-       g17_replay_edges]
+       g17_replay_edges, g24_board_rules]
 
 
 def main():
