@@ -235,6 +235,42 @@ int mzreplay_filer_lengths(mzreplay_filer *filer, int32_t *lengths, void *stream
 int mzreplay_filer_priorities(mzreplay_filer *filer, int32_t n, const int32_t *slots, float *priorities,
                               float *game_priority, void *stream);
 
+/* ---- what a finished game reports (csrc/game_outcomes.h) ----------------------------------------
+ * The numbers the reference's self-play loop logs per game (self_play.py:65-90), computed where the game lies: the total
+ * reward (Python's sum over the reward history, fp64, ascending), the reward earned on each player's moves
+ * (reward_of_player[p] = sum of rewards[i], i = 1 .. n, where to_play[i - 1] == p; [1] stays +0.0 in one-player games),
+ * and the count and numpy's pairwise fp64 sum of the non-zero root values (a NaN counts, both zeros do not), from which
+ * the host takes mean_value = value_sum / value_count = numpy.mean([v for v in root_values if v]), bit for bit.
+ * 40 bytes per game. */
+typedef struct mzreplay_game_outcome {
+    double total_reward;
+    double reward_of_player[2];
+    double value_sum;
+    int32_t value_count;
+    int32_t reserved;
+} mzreplay_game_outcome;
+
+/* The rule on host arrays, for a game of n >= 1 moves in the store's row layout: rewards f64[n + 1], to_play i8[n + 1],
+ * root_values f64[n].  Touches no device (the CPU tests hold it to Python's sum and numpy.mean).  -1 on a null pointer
+ * or n < 1 (mzreplay_last_error(NULL)). */
+int mzreplay_outcomes_reference(int32_t n, const double *rewards, const int8_t *to_play, const double *root_values,
+                                mzreplay_game_outcome *out);
+/* The outcomes of stored games, whichever way they were stored (mzreplay_add_games or a filer): `slots` host i32[n],
+ * `outcomes` host [n].  One launch, a wavefront per game; an empty slot reports zeros.  Blocking, in the manner of
+ * mzreplay_filer_priorities.  Refused on the arguments alone: a null pointer, n < 0, a slot outside the store. */
+int mzreplay_game_outcomes(mzreplay *store, int32_t n, const int32_t *slots, mzreplay_game_outcome *outcomes, void *stream);
+/* The filer reports the outcome of every game it finishes -- those a call drops because it finished more games than the
+ * store has slots included -- in a list parallel to the one mzreplay_filer_sync_ids hands out: filer_append_kernel applies
+ * the rule to the complete row where it finishes the game, before the row is reused.  Accepted only before
+ * mzreplay_filer_begin (the kernel form and the scratch of max_moves doubles per env are chosen once).  Off by default:
+ * the filer's launches then make the memory accesses they made before this switch existed.  A refused batch (rule 5)
+ * reports no outcomes, like it reports no games. */
+int mzreplay_filer_enable_outcomes(mzreplay_filer *filer, int32_t on);
+/* The outcomes of the games the last mzreplay_filer_sync_ids / mzreplay_filer_sync of this filer returned, in that order
+ * (a host array, valid until the next call on this filer): 40 bytes per game on top of the sync's 16.  No device work:
+ * the sync fetched them.  Fails while the switch is off. */
+int mzreplay_filer_sync_outcomes(mzreplay_filer *filer, int32_t *n, const mzreplay_game_outcome **outcomes);
+
 /* ---- Reanalyse in batches (csrc/reanalyse_plan.h) ------------------------------------------------
  * N games per pass, queued on one stream: the games drawn on the device, every position of every drawn game evaluated
  * as one batch, the fresh values written back.  A pass is a PLAN -- device arrays game_ids i64[n], slots i32[n], row_start

@@ -370,6 +370,10 @@ PROTOTYPES = {
                                                ctypes.POINTER(c_void), c_i64_p, c_void]),
     "mzreplay_filer_lengths": (ctypes.c_int, [c_void, c_i32_p, c_void]),
     "mzreplay_filer_priorities": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_f32_p, c_f32_p, c_void]),
+    "mzreplay_outcomes_reference": (ctypes.c_int, [ctypes.c_int32, c_f64_p, ctypes.POINTER(ctypes.c_int8), c_f64_p, c_void]),
+    "mzreplay_game_outcomes": (ctypes.c_int, [c_void, ctypes.c_int32, c_i32_p, c_void, c_void]),
+    "mzreplay_filer_enable_outcomes": (ctypes.c_int, [c_void, ctypes.c_int32]),
+    "mzreplay_filer_sync_outcomes": (ctypes.c_int, [c_void, c_i32_p, ctypes.POINTER(c_void)]),
     "mzreplay_reanalyse_enable": (ctypes.c_int, [c_void, ctypes.c_uint32]),
     "mzreplay_reanalyse_get_rng": (ctypes.c_int, [c_void, c_u32_p, c_i32_p]),
     "mzreplay_reanalyse_set_rng": (ctypes.c_int, [c_void, c_u32_p, ctypes.c_int32]),
@@ -515,6 +519,34 @@ class MzReplayFileMoves(ctypes.Structure):
                 ("num_legal_stride", ctypes.c_int64), ("to_play", c_void), ("to_play_stride", ctypes.c_int64),
                 ("to_play_last", c_void), ("rewards", c_void), ("done", c_void), ("obs_after", c_void),
                 ("obs_next", c_void), ("players", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MzReplayGameOutcome(ctypes.Structure):
+    """mzreplay_game_outcome (include/mzreplay.h): what one finished game reports, 40 bytes."""
+    _fields_ = [("total_reward", ctypes.c_double), ("reward_of_player", ctypes.c_double * 2),
+                ("value_sum", ctypes.c_double), ("value_count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# the same 40 bytes as a numpy record: arrays of outcomes cross the C ABI as this dtype
+GAME_OUTCOME_DTYPE = np.dtype([("total_reward", np.float64), ("reward_of_player", np.float64, (2,)),
+                               ("value_sum", np.float64), ("value_count", np.int32), ("reserved", np.int32)])
+
+
+def outcomes_reference(rewards, to_play, root_values):
+    """mzreplay_outcomes_reference: csrc/game_outcomes.h's rule for one game of n = len(root_values) moves on host arrays
+    (rewards [n + 1], to_play [n + 1]); touches no device.  Returns a GAME_OUTCOME_DTYPE record."""
+    rewards = np.ascontiguousarray(rewards, dtype=np.float64)
+    to_play = np.ascontiguousarray(to_play, dtype=np.int8)
+    root_values = np.ascontiguousarray(root_values, dtype=np.float64)
+    n = len(root_values)
+    if len(rewards) != n + 1 or len(to_play) != n + 1:
+        raise ValueError("outcomes_reference: rewards and to_play hold one entry more than root_values")
+    out = np.zeros(1, dtype=GAME_OUTCOME_DTYPE)
+    lib = load()
+    if lib.mzreplay_outcomes_reference(n, ptr(rewards, c_f64_p), ptr(to_play, ctypes.POINTER(ctypes.c_int8)),
+                                       ptr(root_values, c_f64_p), out.ctypes.data) != 0:
+        raise ValueError(lib.mzreplay_last_error(None).decode())
+    return out[0]
 
 
 class HostRng:

@@ -25,6 +25,10 @@
 //   reanalyse_store_kernel         a workgroup per draw, grid-stride: values into the slots of the carrying draws
 //   reanalyse_fc_kernel            fully-connected networks: a fixed grid, weights and neuron tables staged once per
 //                                  workgroup, a lane group per row from the observation to the stored value
+// What a finished game reports (mzreplay_game_outcomes, mzreplay_filer_enable_outcomes; the rule in game_outcomes.h) is one
+// device function, wave_outcome, a wavefront per game, with two callers:
+//   game_outcomes_kernel           a workgroup of one wavefront per requested slot
+//   filer_append_kernel<., true>   where the filer finishes a game, on the row it is about to copy
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +40,7 @@
 
 #include "../../include/mzreplay.h"
 #include "fc_net_host.h"
+#include "game_outcomes.h"
 #include "reanalyse_plan.h"
 #include "replay_filer.h"
 #include "replay_sampler.h"
@@ -792,6 +797,7 @@ __global__ __launch_bounds__(kReanalyseThreads) void reanalyse_fc_kernel(StorePa
 //                             the counters
 //   filer_append_kernel       a wavefront per env walks its moves in order: lanes spread over the policy entries and the
 //                             observation floats; a finished game's row goes to its slot in coalesced copies
+//                             (with outcomes on, game_outcomes.h's rule on the complete row, same launch)
 //   filer_priorities_kernel   a fixed grid strides over the call's surviving games: priorities_kernel's arithmetic into the
 //                             priority arrays (the sampler's when it is on, with the game id)
 // The store-wide counters are one device block of the store (FilerParams::shared), which the calls of every filer move in
@@ -823,6 +829,8 @@ struct FilerParams {
     float* priorities;               // [G][L], [G]: the sampler's arrays when it is on, else the filer's own
     float* game_priority;
     int64_t* game_id;                // the sampler's [G], or null
+    mz::outcomes::Outcome* list_out; // [list_cap] parallel to the list (mzreplay_filer_enable_outcomes), else null
+    double* packed;                  // [E][L] an env's counted root values, compacted (outcomes on), else null
 };
 
 constexpr int kScanThreads = 1024;
@@ -921,7 +929,72 @@ __device__ __forceinline__ void copy_items(T* __restrict__ dst, const T* __restr
     for (size_t i = lane; i < count; i += kFilerWave) dst[i] = src[i];
 }
 
-template <bool kVec4>
+// ---- what a finished game reports (game_outcomes.h) -----------------------------------------------------------------------
+// One wavefront and one complete row: the counted root values are compacted in order by ballot into `packed` (room for n
+// doubles), every lane sums the leaves of numpy's tree whose turn is its own and leaves each sum in the leaf's first
+// cell (only that lane reads the leaf), and one lane adds the leaves up as the recursion would, its stack in LDS (`walk`:
+// 640 bytes whatever max_moves is; four indexed arrays in registers cost the kernel its occupancy).  The three reward
+// sums are one ascending chain each, on lanes 0..2 in step.  Called by all 64 lanes of a one-wavefront workgroup.
+__device__ __forceinline__ void wave_outcome(const double* __restrict__ rewards, const int8_t* __restrict__ to_play,
+                                             const double* __restrict__ root_values, int n, double* __restrict__ packed,
+                                             mz::outcomes::Outcome* __restrict__ out, mz::outcomes::WalkStack* walk,
+                                             int lane) {
+    int count = 0;
+    for (int base = 0; base < n; base += kFilerWave) {
+        const int i = base + lane;
+        const double v = i < n ? root_values[i] : 0.0;
+        const bool keep = i < n && mz::outcomes::counts(v);
+        const unsigned long long mask = __ballot(keep);
+        if (keep) packed[count + __popcll(mask & ((1ull << lane) - 1ull))] = v;
+        count += __popcll(mask);
+    }
+    __syncthreads();
+    // leaf k of the tree goes to lane k % 64: leaf_of names it from its first value, no stack
+    for (int off = 0, leaf_index = 0; off < count; ++leaf_index) {
+        int leaf_off, leaf_len;
+        mz::outcomes::leaf_of(count, off, &leaf_off, &leaf_len);
+        if (leaf_index % kFilerWave == lane)
+            packed[leaf_off] = mz::outcomes::pairwise_leaf([&](int i) { return packed[i]; }, leaf_off, leaf_len);
+        off = leaf_off + leaf_len;
+    }
+    __syncthreads();
+    double acc = 0.0;
+    if (lane < 3) {
+        // lane 0: every reward from i = 0; lanes 1 and 2: rewards[i], i >= 1, earned on the moves of player lane - 1
+        for (int i = lane == 0 ? 0 : 1; i <= n; ++i) {
+            const bool mine = lane == 0 || to_play[i - 1] == lane - 1;
+            if (mine) acc = acc + rewards[i];
+        }
+    } else if (lane == 3 && count > 0) {
+        acc = mz::outcomes::pairwise_walk(*walk, 0, count, [&](int off, int) { return packed[off]; });
+    }
+    if (lane == 0) out->total_reward = acc;
+    if (lane == 1 || lane == 2) out->reward_of_player[lane - 1] = acc;
+    if (lane == 3) {
+        out->value_sum = acc;
+        out->value_count = count;
+        out->reserved = 0;
+    }
+}
+
+// mzreplay_game_outcomes: a wavefront per stored game
+__global__ __launch_bounds__(kFilerWave) void game_outcomes_kernel(StoreParams p, const int32_t* __restrict__ slots,
+                                                                   double* __restrict__ packed,   // [n][L]
+                                                                   mz::outcomes::Outcome* __restrict__ out) {
+    __shared__ mz::outcomes::WalkStack walk;
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int slot = slots[g];
+    const int n = p.length[slot];
+    if (n < 1 || n > p.L) {   // an empty slot (block-uniform: before any barrier)
+        if (lane == 0) out[g] = mz::outcomes::Outcome{0.0, {0.0, 0.0}, 0.0, 0, 0};
+        return;
+    }
+    const size_t L = p.L;
+    wave_outcome(p.rewards + slot * (L + 1), p.to_play + slot * (L + 1), p.root_values + slot * L, n, packed + g * L,
+                 out + g, &walk, lane);
+}
+
+template <bool kVec4, bool kOutcomes>
 __global__ __launch_bounds__(kFilerWave) void filer_append_kernel(StoreParams p, FilerParams f, mzreplay_file_moves mv) {
     extern __shared__ double policy_row[];   // [A] one move's child_visits row, scattered by action, written out in order
     const int e = blockIdx.x, lane = threadIdx.x;
@@ -962,6 +1035,11 @@ __global__ __launch_bounds__(kFilerWave) void filer_append_kernel(StoreParams p,
         if (mv.done[me]) {
             __syncthreads();   // the row is complete (and visible to every lane) before it is copied
             const int j = rank++;
+            if constexpr (kOutcomes) {   // of every game the call finishes, dropped ones included: the row is whole here only
+                __shared__ mz::outcomes::WalkStack walk;
+                wave_outcome(row_rew, row_tp, row_rv, len, f.packed + static_cast<size_t>(e) * L, f.list_out + call.list_base + j,
+                             &walk, lane);
+            }
             if (mz::filer::survives(call, j)) {
                 const size_t slot = static_cast<size_t>(mz::filer::slot_of(mz::filer::game_id(call, j), p.G));
                 copy_floats<kVec4>(p.obs + slot * L1 * obs, row_obs, static_cast<size_t>(len + 1) * obs, lane);
@@ -1066,6 +1144,10 @@ struct mzreplay {
     float* d_priorities = nullptr;
     float* d_game_priority = nullptr;
     size_t staging_games = 0, staging_batch = 0;
+    int32_t* d_outcome_slots = nullptr;      // mzreplay_game_outcomes' staging (grown on demand)
+    double* d_outcome_packed = nullptr;
+    mz::outcomes::Outcome* d_outcomes = nullptr;
+    size_t outcome_games = 0;
     bool sampler_on = false;
     SamplerParams sp{};
     int64_t next_game_id = 0;        // id of the next game mzreplay_add_games stores (sampler on)
@@ -1096,7 +1178,13 @@ struct mzreplay_filer {
     std::vector<int64_t> h_id;
     std::vector<int32_t> out_env, out_len;   // what the last mzreplay_filer_sync handed out
     std::vector<int64_t> out_id;
+    bool begun = false;                  // mzreplay_filer_begin was called: the outcome switch no longer moves
+    bool outcomes_on = false;            // mzreplay_filer_enable_outcomes
+    std::vector<mz::outcomes::Outcome> h_outcome, out_outcome;   // parallel to h_* / out_* while the switch is on
 };
+
+static_assert(sizeof(mz::outcomes::Outcome) == 40 && sizeof(mzreplay_game_outcome) == 40,
+              "mzreplay_game_outcome is mz::outcomes::Outcome: 40 bytes per game");
 
 namespace {
 std::string g_create_error;
@@ -1547,6 +1635,11 @@ int filer_drain(mzreplay_filer* fl, FilerState* state_out, mz::filer::Counters* 
         RP_HIP(s, hipMemcpyAsync(fl->h_env.data() + have, fl->f.list_env, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
         RP_HIP(s, hipMemcpyAsync(fl->h_len.data() + have, fl->f.list_len, sizeof(int32_t) * more, hipMemcpyDeviceToHost, stream));
         RP_HIP(s, hipMemcpyAsync(fl->h_id.data() + have, fl->f.list_id, sizeof(int64_t) * more, hipMemcpyDeviceToHost, stream));
+        if (fl->outcomes_on) {
+            fl->h_outcome.resize(have + more);
+            RP_HIP(s, hipMemcpyAsync(fl->h_outcome.data() + have, fl->f.list_out, sizeof(mz::outcomes::Outcome) * more,
+                                     hipMemcpyDeviceToHost, stream));
+        }
     }
     // pending starts again at zero; the error word (adjacent) only for the sync, which reports it: a drain between two
     // unsynced calls leaves it standing, so the device goes on refusing and the next sync still sees it
@@ -1615,6 +1708,7 @@ void mzreplay_filer_destroy(mzreplay_filer* fl) {
 int mzreplay_filer_begin(mzreplay_filer* fl, const float* first_observations, const int32_t* first_to_play, void* stream_) {
     if (!fl || !first_observations) return fail(fl ? fl->store : nullptr, "mzreplay_filer_begin: null argument");
     mzreplay* s = fl->store;
+    fl->begun = true;
     filer_begin_kernel<<<dim3(fl->f.E), dim3(256), 0, static_cast<hipStream_t>(stream_)>>>(s->p, fl->f, first_observations,
                                                                                           first_to_play);
     RP_HIP(s, hipGetLastError());
@@ -1662,9 +1756,13 @@ int mzreplay_filer_file(mzreplay_filer* fl, const mzreplay_file_moves* mv, void*
             f.list_env = env;
             f.list_len = len;
             f.list_id = id;
+            if (fl->outcomes_on && filer_alloc(fl, &f.list_out, static_cast<size_t>(most))) return -1;
             f.list_cap = static_cast<int32_t>(most);
         }
     }
+    if (fl->outcomes_on && (!f.list_out || !f.packed))   // (the switch moved after a filing that came before begin)
+        return fail(s, "mzreplay_filer_file: the outcome list does not exist: mzreplay_filer_enable_outcomes comes before "
+                       "mzreplay_filer_begin and before the first filing");
     if (s->sampler_on) {
         f.priorities = s->sp.priorities;
         f.game_priority = s->sp.game_priority;
@@ -1689,10 +1787,16 @@ int mzreplay_filer_file(mzreplay_filer* fl, const mzreplay_file_moves* mv, void*
     auto aligned = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; };
     const bool vec4 = p.obs_floats % 4 == 0 && aligned(mv->obs_after) && aligned(mv->obs_next);
     const size_t lds = sizeof(double) * p.A;
-    if (vec4)
-        filer_append_kernel<true><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
-    else
-        filer_append_kernel<false><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+    if (fl->outcomes_on) {
+        if (vec4)
+            filer_append_kernel<true, true><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+        else
+            filer_append_kernel<false, true><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+    } else if (vec4) {
+        filer_append_kernel<true, false><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+    } else {
+        filer_append_kernel<false, false><<<dim3(f.E), dim3(kFilerWave), lds, stream>>>(p, f, *mv);
+    }
     RP_HIP(s, hipGetLastError());
     const int64_t grid = std::min<int64_t>(std::min<int64_t>(most, p.G), 2048);
     filer_priorities_kernel<<<dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream>>>(p, f);
@@ -1726,9 +1830,11 @@ int mzreplay_filer_sync_ids(mzreplay_filer* fl, int32_t* n_new, const int32_t** 
     fl->out_env.swap(fl->h_env);
     fl->out_len.swap(fl->h_len);
     fl->out_id.swap(fl->h_id);
+    fl->out_outcome.swap(fl->h_outcome);
     fl->h_env.clear();
     fl->h_len.clear();
     fl->h_id.clear();
+    fl->h_outcome.clear();
     *n_new = static_cast<int32_t>(fl->out_env.size());
     if (env_index) *env_index = fl->out_env.data();
     if (lengths) *lengths = fl->out_len.data();
@@ -1757,6 +1863,59 @@ int mzreplay_filer_lengths(mzreplay_filer* fl, int32_t* lengths, void* stream_) 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     RP_HIP(s, hipMemcpyAsync(lengths, fl->f.length, sizeof(int32_t) * fl->f.E, hipMemcpyDeviceToHost, stream));
     RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int mzreplay_outcomes_reference(int32_t n, const double* rewards, const int8_t* to_play, const double* root_values,
+                                mzreplay_game_outcome* out) {
+    if (!rewards || !to_play || !root_values || !out) return fail(nullptr, "mzreplay_outcomes_reference: null argument");
+    if (n < 1) return fail(nullptr, "mzreplay_outcomes_reference: a game has at least one move");
+    std::vector<double> packed(static_cast<size_t>(n));
+    const mz::outcomes::Outcome o = mz::outcomes::game_outcome(rewards, to_play, root_values, n, packed.data());
+    std::memcpy(out, &o, sizeof(o));
+    return 0;
+}
+
+int mzreplay_game_outcomes(mzreplay* s, int32_t n, const int32_t* slots, mzreplay_game_outcome* outcomes, void* stream_) {
+    if (n < 0) return fail(s, "mzreplay_game_outcomes: n must not be negative");   // (before the pointers: no device needed)
+    if (!s || !slots || !outcomes) return fail(s, "mzreplay_game_outcomes: null argument");
+    const StoreParams& p = s->p;
+    for (int g = 0; g < n; ++g)
+        if (slots[g] < 0 || slots[g] >= p.G) return fail(s, "mzreplay_game_outcomes: slot out of range");
+    if (n == 0) return 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t count = static_cast<size_t>(n);
+    if (count > s->outcome_games) {
+        if (dev_alloc(s, &s->d_outcome_slots, count) || dev_alloc(s, &s->d_outcome_packed, count * p.L) ||
+            dev_alloc(s, &s->d_outcomes, count))
+            return -1;
+        s->outcome_games = count;
+    }
+    if (s->last_filing) RP_HIP(s, hipStreamWaitEvent(stream, s->last_filing, 0));   // (behind the filings queued so far)
+    RP_HIP(s, hipMemcpyAsync(s->d_outcome_slots, slots, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
+    game_outcomes_kernel<<<dim3(n), dim3(kFilerWave), 0, stream>>>(p, s->d_outcome_slots, s->d_outcome_packed, s->d_outcomes);
+    RP_HIP(s, hipGetLastError());
+    RP_HIP(s, hipMemcpyAsync(outcomes, s->d_outcomes, sizeof(mz::outcomes::Outcome) * count, hipMemcpyDeviceToHost, stream));
+    RP_HIP(s, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int mzreplay_filer_enable_outcomes(mzreplay_filer* fl, int32_t on) {
+    if (!fl) return fail(nullptr, "mzreplay_filer_enable_outcomes: null filer");
+    mzreplay* s = fl->store;
+    if (fl->begun) return fail(s, "mzreplay_filer_enable_outcomes: the switch is set before mzreplay_filer_begin");
+    if (on && !fl->f.packed && filer_alloc(fl, &fl->f.packed, static_cast<size_t>(fl->f.E) * s->p.L)) return -1;
+    fl->outcomes_on = on != 0;
+    return 0;
+}
+
+int mzreplay_filer_sync_outcomes(mzreplay_filer* fl, int32_t* n, const mzreplay_game_outcome** outcomes) {
+    if (!fl || !n || !outcomes) return fail(fl ? fl->store : nullptr, "mzreplay_filer_sync_outcomes: null argument");
+    if (!fl->outcomes_on)
+        return fail(fl->store, "mzreplay_filer_sync_outcomes: the filer reports no outcomes: call "
+                               "mzreplay_filer_enable_outcomes(filer, 1) before mzreplay_filer_begin");
+    *n = static_cast<int32_t>(fl->out_outcome.size());
+    *outcomes = reinterpret_cast<const mzreplay_game_outcome*>(fl->out_outcome.data());
     return 0;
 }
 

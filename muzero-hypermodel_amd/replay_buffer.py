@@ -101,11 +101,14 @@ class DeviceFiler:
     its list of filed games and its error word.  `begin` / `file` / `lengths` address it; `take_filed` hands its owner the
     games the syncs have fetched for it (ReplayBuffer.sync_filing syncs every filer of the store at once)."""
 
-    def __init__(self, buffer, handle, num_envs):
+    def __init__(self, buffer, handle, num_envs, outcomes=False):
         self.buffer, self.handle, self.num_envs = buffer, handle, int(num_envs)
+        self.outcomes = bool(outcomes)                    # the filer reports every finished game's outcome (attach_filer)
         self.pending = False                              # a move batch was filed and not synced yet
         self.refused = False                              # its last sync failed: the next one asks it again
         self._filed = []                                  # (env_index, length, game_id) per sync, not yet taken
+        self._filed_outcomes = []                         # GAME_OUTCOME_DTYPE records per sync, parallel to _filed
+        self._handed = []                                 # self_play.GameOutcomes of the games take_filed handed out
 
     def begin(self, first_observations, first_to_play=None):
         self.buffer.filer_begin(first_observations, first_to_play, filer=self)
@@ -122,10 +125,25 @@ class DeviceFiler:
         if self.pending:
             self.buffer._sync_filers()
         taken, self._filed = self._filed, []
+        if self.outcomes:
+            from .self_play import GameOutcomes
+            self._handed += [GameOutcomes.from_records(*filed, records) for filed, records in zip(taken, self._filed_outcomes)]
+            self._filed_outcomes = []
         if len(taken) == 1:
             return taken[0]
         dtypes = (numpy.int32, numpy.int32, numpy.int64)
         return tuple(numpy.concatenate([t[i] for t in taken]) if taken else numpy.zeros(0, dtype=dtypes[i]) for i in range(3))
+
+    def take_outcomes(self):
+        """The outcomes of the games take_filed has handed out since the last take_outcomes, in that order: a
+        self_play.GameOutcomes.  The filer computed them where it finished the games (40 bytes per game came back with the
+        sync); a filer attached without outcomes=True has none and raises."""
+        if not self.outcomes:
+            raise RuntimeError("this filer reports no outcomes: turn them on when the actor starts filing, "
+                               "file_to(replay_buffer, outcomes=True) (ReplayBuffer.attach_filer(num_envs, outcomes=True))")
+        from .self_play import GameOutcomes
+        handed, self._handed = self._handed, []
+        return GameOutcomes.concatenate(handed)
 
 
 class ReplayBuffer:
@@ -283,15 +301,19 @@ class ReplayBuffer:
         return {gid: fetched[gid] if gid in fetched else e["history"] for gid, e in self.buffer.items()}
 
     # ---- games filed on the device (include/mzreplay.h mzreplay_filer_*) ---------------------------------
-    def attach_filer(self, num_envs):
+    def attach_filer(self, num_envs, outcomes=False):
         """A device filer on this store for an actor of `num_envs` envs (DeviceSelfPlay.file_to calls this): a DeviceFiler.
         Several actors may file into one store, each through a filer and a stream of its own: the store numbers games in
-        the order of the filer_file calls made on it, whatever stream each runs on (include/mzreplay.h)."""
+        the order of the filer_file calls made on it, whatever stream each runs on (include/mzreplay.h).
+        outcomes=True: the filer also reports every finished game's outcome (mzreplay_filer_enable_outcomes; the owner
+        reads them with DeviceFiler.take_outcomes)."""
         self._sync_if_pending()                              # (the counters pushed below are the host's)
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             self._check(self._lib.mzreplay_filer_create(self._h, int(num_envs), ctypes.byref(handle)))
-        filer = DeviceFiler(self, handle, num_envs)
+            if outcomes:
+                self._check(self._lib.mzreplay_filer_enable_outcomes(handle, 1))
+        filer = DeviceFiler(self, handle, num_envs, outcomes=outcomes)
         self._filers.append(filer)
         self._push_counters()
         return filer
@@ -355,7 +377,8 @@ class ReplayBuffer:
             self.sync_filing()
 
     def _sync_filer(self, filer, counters):
-        """mzreplay_filer_sync_ids of one filer: its new games as host arrays, the store's counters into `counters`."""
+        """mzreplay_filer_sync_ids of one filer: its new games as host arrays, the store's counters into `counters`; with
+        them the games' outcome records (None from a filer that reports none)."""
         n = ctypes.c_int32()
         env_p, len_p, id_p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         filer.pending = False
@@ -368,7 +391,16 @@ class ReplayBuffer:
             if count == 0:
                 return numpy.zeros(0, dtype=dtype)
             return numpy.ctypeslib.as_array(ctypes.cast(p, ctype), shape=(count,)).copy()
-        return arr(env_p, c_i32_p, numpy.int32), arr(len_p, c_i32_p, numpy.int32), arr(id_p, _native.c_i64_p, numpy.int64)
+        filed = arr(env_p, c_i32_p, numpy.int32), arr(len_p, c_i32_p, numpy.int32), arr(id_p, _native.c_i64_p, numpy.int64)
+        records = None
+        if filer.outcomes:
+            n_out, out_p = ctypes.c_int32(), ctypes.c_void_p()
+            self._check(self._lib.mzreplay_filer_sync_outcomes(filer.handle, ctypes.byref(n_out), ctypes.byref(out_p)))
+            assert n_out.value == count, "the filer's outcome list left its game list"
+            records = numpy.zeros(count, dtype=_native.GAME_OUTCOME_DTYPE)
+            if count:
+                ctypes.memmove(records.ctypes.data, out_p.value, records.nbytes)
+        return filed, records
 
     def sync_filing(self, shared_storage=None):
         """The games filed on the device since the last sync join the host bookkeeping: `buffer` entries (length,
@@ -393,17 +425,19 @@ class ReplayBuffer:
         for filer in [f for f in self._filers if f.pending or f.refused] or self._filers[:1]:
             try:
                 filer.refused = False
-                synced.append((filer, self._sync_filer(filer, counters)))
+                synced.append((filer, *self._sync_filer(filer, counters)))
             except RuntimeError as error:
                 filer.refused = True
                 failure = failure or error
         if failure is not None:
             self._unbooked = synced
             raise failure
-        for filer, filed in synced:
+        for filer, filed, records in synced:
             filer._filed.append(filed)
-        lengths = numpy.concatenate([filed[1] for _, filed in synced]) if synced else numpy.zeros(0, dtype=numpy.int32)
-        ids = numpy.concatenate([filed[2] for _, filed in synced]) if synced else numpy.zeros(0, dtype=numpy.int64)
+            if records is not None:
+                filer._filed_outcomes.append(records)
+        lengths = numpy.concatenate([filed[1] for _, filed, _ in synced]) if synced else numpy.zeros(0, dtype=numpy.int32)
+        ids = numpy.concatenate([filed[2] for _, filed, _ in synced]) if synced else numpy.zeros(0, dtype=numpy.int64)
         order = numpy.argsort(ids, kind="stable")
         lengths, ids = lengths[order], ids[order]
         count = len(ids)
@@ -460,6 +494,25 @@ class ReplayBuffer:
                                                           ptr(tp, c_i32_p), ptr(cv, c_f64_p), ptr(rv, c_f64_p), self._stream()))
         return PackedGames(env_index=numpy.full(n, -1, dtype=numpy.int32), length=lengths, observations=obs, actions=act,
                            rewards=rew, to_play=tp, child_visits=cv, root_values=rv)
+
+    def game_outcomes(self, game_ids):
+        """What stored games report (csrc/game_outcomes.h; include/mzreplay.h mzreplay_game_outcomes): a
+        self_play.GameOutcomes for `game_ids`, computed on the device whichever way the games were stored (save_game,
+        save_games, a device filer).  One launch, a wavefront per game, 40 bytes per game back; env_index is -1 (the store
+        does not keep it)."""
+        from .self_play import GameOutcomes
+        self._sync_if_pending()
+        game_ids = [int(g) for g in game_ids]
+        for gid in game_ids:
+            if gid not in self.buffer:
+                raise KeyError(f"game {gid} is not in the buffer")
+        n = len(game_ids)
+        slots = numpy.ascontiguousarray([self._slot(g) for g in game_ids], dtype=numpy.int32)
+        records = numpy.zeros(n, dtype=_native.GAME_OUTCOME_DTYPE)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.mzreplay_game_outcomes(self._h, n, ptr(slots, c_i32_p), records.ctypes.data, self._stream()))
+        lengths = numpy.array([self.buffer[g]["length"] for g in game_ids], dtype=numpy.int32)
+        return GameOutcomes.from_records(numpy.full(n, -1, dtype=numpy.int32), lengths, game_ids, records)
 
     # ---- sampling (replay_buffer.py:135-195) -----------------------------------------------------------
     def sample_game(self, force_uniform=False):

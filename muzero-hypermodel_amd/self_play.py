@@ -897,6 +897,43 @@ class FiledGames(typing.NamedTuple):
         return len(self.env_index)
 
 
+class GameOutcomes(typing.NamedTuple):
+    """What finished games report to a training loop's log (the numbers of reference self_play.py:65-90), computed on the
+    device where the games lie (csrc/game_outcomes.h): DeviceSelfPlay.take_outcomes() after file_to(outcomes=True), or
+    ReplayBuffer.game_outcomes(game_ids) for stored games.  Host arrays, one entry per game."""
+    env_index: numpy.ndarray         # int32 [n] (-1: the store does not keep it)
+    length: numpy.ndarray            # int32 [n] moves
+    game_id: numpy.ndarray           # int64 [n]
+    total_reward: numpy.ndarray      # float64 [n] sum(reward_history)
+    reward_of_player: numpy.ndarray  # float64 [n, 2] rewards earned on player p's moves ([:, 1] is 0 in one-player games)
+    value_sum: numpy.ndarray         # float64 [n] numpy's sum of the non-zero root values
+    value_count: numpy.ndarray       # int32 [n] how many those are
+
+    def __len__(self):
+        return len(self.env_index)
+
+    @property
+    def mean_value(self):
+        """numpy.mean([value for value in root_values if value]) per game, bit for bit; nan where no value counts."""
+        with numpy.errstate(divide="ignore", invalid="ignore"):
+            return self.value_sum / self.value_count
+
+    @classmethod
+    def from_records(cls, env_index, length, game_id, records):
+        """`records`: a _native.GAME_OUTCOME_DTYPE array parallel to the three lists."""
+        return cls(numpy.asarray(env_index, dtype=numpy.int32), numpy.asarray(length, dtype=numpy.int32),
+                   numpy.asarray(game_id, dtype=numpy.int64), records["total_reward"].copy(),
+                   records["reward_of_player"].reshape(-1, 2).copy(), records["value_sum"].copy(),
+                   records["value_count"].copy())
+
+    @classmethod
+    def concatenate(cls, parts):
+        parts = list(parts)
+        if not parts:
+            return cls.from_records([], [], [], numpy.zeros(0, dtype=_native.GAME_OUTCOME_DTYPE))
+        return cls(*(numpy.concatenate(column) for column in zip(*parts)))
+
+
 ENV_OUTPUTS = ("reward", "done", "obs_after", "obs_next")    # what the environment kernels return for a move of a batch
 
 
@@ -1042,9 +1079,10 @@ class StoreRows:
     batch's last environment kernel, ahead of anything that rewrites the rings -- or in flush(), and its few bytes are
     synchronised right behind the current batch's moves_collect; the new batch is described only then."""
 
-    def __init__(self, replay_buffer, engine, envs, config):
+    def __init__(self, replay_buffer, engine, envs, config, outcomes=False):
         self.replay_buffer, self.engine, self.envs, self.config = replay_buffer, engine, envs, config
-        self.filer = replay_buffer.attach_filer(envs.E)      # this actor's own: other actors may file into the same store
+        # this actor's own: other actors may file into the same store
+        self.filer = replay_buffer.attach_filer(envs.E, outcomes=outcomes)
         obs, _, _, to_play = envs.observe()
         self.filer.begin(obs, to_play)
         self.pending = None                     # (MzReplayFileMoves, ring): described, not queued yet (the ring stays alive with it)
@@ -1203,7 +1241,7 @@ class DeviceSelfPlay(ManyEnvLoop):
         """Moves played in every env's running game: the host filer's counters, or the device filer's (a small download)."""
         return self._rows.lengths
 
-    def file_to(self, replay_buffer, shared=False):
+    def file_to(self, replay_buffer, shared=False, outcomes=False):
         """From now on finished games go into `replay_buffer`'s store on the device (include/mzreplay.h
         mzreplay_filer_file): play_moves queues the filing behind the batch's last environment kernel, no observation,
         policy row or value of a game visits the host, and `on_games` receives a FiledGames (env_index, length, game_id)
@@ -1212,7 +1250,10 @@ class DeviceSelfPlay(ManyEnvLoop):
         shared=True: the buffer may already receive another actor's games.  The store then numbers games in the order of
         the actors' play_moves / flush calls, and what the first actor's owner sees changes with it -- its ids are no
         longer consecutive, sync_filing() returns None and the buffer's filer_* calls want the filer named -- which is
-        why joining a store is asked for and never happens by default."""
+        why joining a store is asked for and never happens by default.
+        outcomes=True: the filer also reports what every finished game earned (total reward, reward per player, the sum
+        and count of its non-zero root values: csrc/game_outcomes.h), computed where it finishes the game; take_outcomes()
+        hands them out.  The store's contents and ids are the same either way."""
         if isinstance(self._rows, StoreRows):
             raise ValueError("file_to was called before")
         if self.moves_played or self._batch_ready or self._dev_batch is not None or self._rows.pending is not None:
@@ -1229,7 +1270,15 @@ class DeviceSelfPlay(ManyEnvLoop):
         if (replay_buffer.L != int(self.config.max_moves) or replay_buffer.A != self.envs.A
                 or (replay_buffer.C, replay_buffer.H, replay_buffer.W) != tuple(self.envs.observation_shape)):
             raise ValueError("file_to: the replay buffer was built for another game shape or move limit")
-        self._rows = StoreRows(replay_buffer, self.engine, self.envs, self.config)
+        self._rows = StoreRows(replay_buffer, self.engine, self.envs, self.config, outcomes=outcomes)
+
+    def take_outcomes(self):
+        """The GameOutcomes of the games handed out (on_games) since the last take, in that order.  Needs
+        file_to(replay_buffer, outcomes=True)."""
+        if not isinstance(self._rows, StoreRows) or not self._rows.filer.outcomes:
+            raise RuntimeError("take_outcomes: the actor reports no outcomes: turn them on when it starts filing on the "
+                               "device, file_to(replay_buffer, outcomes=True)")
+        return self._rows.filer.take_outcomes()
 
     def _filed_counters(self):
         return self._rows.counters()
@@ -1606,7 +1655,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         self._filing = False                     # file_to(): every group files into one store on the device
         self.device, self.model = self.actors[0].device, self.actors[0].model   # (what ManyEnvLoop's weight pull addresses)
 
-    def file_to(self, replay_buffer, shared=False):
+    def file_to(self, replay_buffer, shared=False, outcomes=False):
         """DeviceSelfPlay.file_to for every group: each group's actor files into the one store through a filer of its own,
         on the group's stream (shared=True: the store may already receive another actor's games).  The store numbers games in the order the filings are queued, whatever the streams do
         (include/mzreplay.h), and play_moves queues them in the order the host path hands the games out: per batch, group
@@ -1619,8 +1668,24 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
             raise ValueError("file_to comes before the first move")
         for g, (actor, stream) in enumerate(zip(self.actors, self.streams)):
             with torch.cuda.stream(stream):
-                actor.file_to(replay_buffer, shared=shared or g > 0)     # (the groups share the store among themselves)
+                # (the groups share the store among themselves)
+                actor.file_to(replay_buffer, shared=shared or g > 0, outcomes=outcomes)
         self._filing = True
+
+    def take_outcomes(self):
+        """DeviceSelfPlay.take_outcomes of every group as one GameOutcomes with global env indices, merged by ascending
+        game_id (the order the store numbered the games in, which is the order on_games saw them)."""
+        if not self._filing:
+            raise RuntimeError("take_outcomes: the actor reports no outcomes: turn them on when it starts filing on the "
+                               "device, file_to(replay_buffer, outcomes=True)")
+        parts = []
+        for g, actor in enumerate(self.actors):
+            part = actor.take_outcomes()
+            # (built anew: a NamedTuple whose len() counts games cannot _replace)
+            parts.append(GameOutcomes(part.env_index + numpy.int32(g * self.per_group), *part[1:]))
+        merged = GameOutcomes.concatenate(parts)
+        order = numpy.argsort(merged.game_id, kind="stable")
+        return GameOutcomes(*(column[order] for column in merged))
 
     def _filed_counters(self):
         return self.actors[0]._filed_counters() if self._filing else None    # (one store: every group's rows count it)
