@@ -275,8 +275,11 @@ struct mzmcts_engine {
     //   MZMCTS_NARROW_SERIAL_TWIST=1      lane 0 alone draws from the tree's stream and regenerates its block
     //   MZMCTS_NARROW_TABLE_PER_LAUNCH=1  every workgroup of every launch computes the (N, n) table
     //   MZMCTS_NARROW_NO_PREFETCH=1       the per-tree inputs are read where they are needed, after the staging barrier
+    //   MZMCTS_NARROW_GENERIC_SHAPE=1     the run-time-shape form of the kernel even for the flagship network
+    //                                     (tests/test_gpu_fused_shape_forms.py)
     bool narrow_row_rng = true;
     bool narrow_prefetch = true;
+    bool narrow_generic_shape = false;
     double* narrow_table[3] = {nullptr, nullptr, nullptr};   // by pbc2_mode; built at create (S and pb_c never change)
 
     // profiling

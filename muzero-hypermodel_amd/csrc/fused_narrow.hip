@@ -197,7 +197,9 @@ __device__ __forceinline__ void stage_narrow_tables(const TreeParams& p, const N
 // -------------------------------------------------------------------------------------------------
 // one launch per move: root inference + expansion + noise, S simulations, publish
 // -------------------------------------------------------------------------------------------------
-template <int SPAN, int PBC2>
+// Shape: GenericShape (the network's shape read at run time) or FlagshipShape (CartPole's, every value a constant; SPAN 2
+// only) -- see narrow_device.h.  The launcher picks the form; both compute the same.
+template <int SPAN, int PBC2, typename Shape>
 __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_fused_narrow_kernel(
     TreeParams p, FcNet net, NarrowLayout lay, const float* __restrict__ weights,
     const float* __restrict__ observations,  // [E][obs]
@@ -258,9 +260,11 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
     float* hidden_lds = reinterpret_cast<float*>(region + lay.off_hidden);
     int32_t* root_action_lds = reinterpret_cast<int32_t*>(region + lay.off_misc);
     float* root_logit_lds = reinterpret_cast<float*>(region + lay.off_misc) + kRow;
-    const int enc = net.enc;
-    const bool two_player = p.P == 2;
-    const bool wide_support = net.F > kRow;
+    static_assert(!Shape::kFixed || SPAN == 2, "the fixed shape has two actions");
+    const Shape shape(p, net);
+    const int enc = shape.enc(), A = shape.actions(), F = shape.features(), support = shape.support();
+    const bool two_player = shape.two_player();
+    const bool wide_support = F > kRow;
 
     // ---- root: initial inference, root.expand over the legal actions, exploration noise ----------
     float predicted;
@@ -268,9 +272,9 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
         const float obs = prefetch ? in.obs : ((j < net.obs) ? observations[static_cast<size_t>(e) * net.obs + j] : 0.f);
         const NarrowHeads h = narrow_initial(units, bias, enc, wide_support, net.repr.n_layers == 2, obs, j);
         float unused;
-        narrow_support_pair(h.value_a, h.value_b, h.value_a, h.value_b, net.F, net.support, j, predicted, unused);
+        narrow_support_pair(h.value_a, h.value_b, h.value_a, h.value_b, F, support, j, predicted, unused);
         // child slot c of the root is action root_action[c]: fetch its logit across the lanes through LDS
-        const int my_action = (j < n_root) ? (prefetch ? in.root_action : p.root_action[static_cast<size_t>(e) * p.A + j]) : 0;
+        const int my_action = (j < n_root) ? (prefetch ? in.root_action : p.root_action[static_cast<size_t>(e) * A + j]) : 0;
         root_action_lds[j] = my_action;
         root_logit_lds[j] = h.policy;
         if (j < enc) hidden_lds[j] = h.norm;  // slab 0
@@ -278,13 +282,13 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
         const bool valid = j < n_root;
         double prior[1] = {narrow_softmax(valid ? root_logit_lds[my_action] : 0.f, valid)};
         if (prefetch)
-            write_root_children_row(tree, p.A, n_root, prior[0], noise != nullptr, in.noise, p.noise_frac, j);
+            write_root_children_row(tree, A, n_root, prior[0], noise != nullptr, in.noise, p.noise_frac, j);
         else
-            write_root_children<kRow, 1>(tree, p.A, n_root, prior, noise ? noise + static_cast<size_t>(e) * p.A : nullptr,
+            write_root_children<kRow, 1>(tree, A, n_root, prior, noise ? noise + static_cast<size_t>(e) * A : nullptr,
                                          p.noise_frac, j);
         if constexpr (SPAN == 2) {  // the prior moves aside; the block holds table[0][0] * prior (see LdsTreeV)
             if (j == 0) *reinterpret_cast<uint4*>(region + lay.off_desc) = uint4{0u, 0u, 0u, 0u};   // (the root, at position 1 of its own table)
-            if (j < p.A) {
+            if (j < A) {
                 const double pr = tree.stats(0)[j].prior;
                 tree.side(0)[j].prior = pr;
                 tree.stats(0)[j].prior = exploration_factor<PBC2>(pbc, pbc2, p.S, 0, 0) * pr;
@@ -317,7 +321,7 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
             d = descend_window(tree, region + lay.off_desc, root_entry, sim, n_root, mm, exotic, mt_key, mt_pos, words, row_rng, j,
                                group_base, p.error_flag);
         else
-            d = descend_row<SPAN, PBC2>(tree, pbc, pbc2, p.S, p.A, sim, n_root, mm, exotic, mt_key, mt_pos, words, row_rng,
+            d = descend_row<SPAN, PBC2>(tree, pbc, pbc2, p.S, A, sim, n_root, mm, exotic, mt_key, mt_pos, words, row_rng,
                                         j, group_base, p.error_flag MZ_DSTAMP_ARGS);
         state = hidden_lds[d.parent * enc + (j < enc ? j : 0)];
         // the backup's operands (leaf-side round) and the path entries the new node is linked under: asked for here and
@@ -333,17 +337,17 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
             [&]() { backup_fetch_factors<SPAN, PBC2>(round, pbc, pbc2, p.S, sim, j); });
         MZ_STAMP(3);
         float value_f, reward_f;
-        narrow_support_pair<true>(h.value_a, h.value_b, h.reward_a, h.reward_b, net.F, net.support, j, value_f, reward_f,
+        narrow_support_pair<true>(h.value_a, h.value_b, h.reward_a, h.reward_b, F, support, j, value_f, reward_f,
                                   transform_reciprocal);
-        double prior[1] = {narrow_softmax<SPAN, true>(h.policy, j < p.A)};
+        double prior[1] = {narrow_softmax<SPAN, true>(h.policy, j < A)};
         MZ_STAMP(4);
         const int k_new = sim + 1;
         if constexpr (SPAN == 2) {
-            write_pair_children(tree, k_new, p.A, prior[0], leaf_factor, j);
+            write_pair_children(tree, k_new, A, prior[0], leaf_factor, j);
             link_new_node(region + lay.off_desc, link_entry, d.depth, k_new, j);
             root_entry = window_root_entry(region + lay.off_desc, j);
         } else {
-            write_children<kRow, 1>(tree, k_new, p.A, prior, j);
+            write_children<kRow, 1>(tree, k_new, A, prior, j);
         }
         if (j < enc) hidden_lds[k_new * enc + j] = h.norm;
         MZ_STAMP(5);
@@ -391,22 +395,22 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
         if (ctl.max_depth) ctl.max_depth[e] = max_depth;
         if (ctl.depth_sum) ctl.depth_sum[e] = static_cast<int32_t>(depth_sum);
     }
-    if (ctl.visits && j < p.A) ctl.visits[static_cast<size_t>(e) * p.A + j] = (j < n_root) ? tree.links(0)[j].visits : 0;
+    if (ctl.visits && j < A) ctl.visits[static_cast<size_t>(e) * A + j] = (j < n_root) ? tree.links(0)[j].visits : 0;
     // (in LDS a block is two member arrays with the value sums apart, in HBM an array of 32-byte child records: 16-byte
     // word 2 c / 2 c + 1 of a record block are the stats / links of child c; a child never visited has value_sum 0)
-    const int block_words = 2 * p.A;
+    const int block_words = 2 * A;
     const int n_blocks = publish_tree ? n_sims + 1 : 1;
     for (int t = j; t < n_blocks * block_words; t += kRow) {
         const int k = t / block_words, i = t - k * block_words;
         uint4* dst = reinterpret_cast<uint4*>(p.blocks + (static_cast<size_t>(k) * p.E + e) * p.line_stride);   // own line, half 0
-        if (i < p.A) {
+        if (i < A) {
             ChildStats st = tree.stats(k)[i];
             const SideStats sd = tree.side(k)[i];
             st.value_sum = tree.links(k)[i].visits > 0 ? sd.value_sum : 0.0;
             if constexpr (SPAN == 2) st.prior = sd.prior;
             *reinterpret_cast<ChildStats*>(dst + 2 * i) = st;
         } else {
-            *reinterpret_cast<ChildLinks*>(dst + 2 * (i - p.A) + 1) = tree.links(k)[i - p.A];
+            *reinterpret_cast<ChildLinks*>(dst + 2 * (i - A) + 1) = tree.links(k)[i - A];
         }
     }
     for (int t = j; t < n_blocks * enc; t += kRow) {
@@ -488,9 +492,17 @@ static hipError_t launch_narrow_span(const TreeParams& p, const FcNet& net, cons
                       ctl, n_sims, publish_tree);
         return hipGetLastError();
     };
-    if (lay.pbc2_mode == 2) return go(search_fused_narrow_kernel<SPAN, 2>);
-    if (lay.pbc2_mode == 1) return go(search_fused_narrow_kernel<SPAN, 1>);
-    return go(search_fused_narrow_kernel<SPAN, 0>);
+    // the constant-shape form exists for the two-action kernels with an exploration table (every CartPole search at
+    // S <= 254); any other shape, and lay.generic_shape, take the run-time form
+    if constexpr (SPAN == 2) {
+        if (!lay.generic_shape && FlagshipShape::matches(p, net)) {
+            if (lay.pbc2_mode == 2) return go(search_fused_narrow_kernel<2, 2, FlagshipShape>);
+            if (lay.pbc2_mode == 1) return go(search_fused_narrow_kernel<2, 1, FlagshipShape>);
+        }
+    }
+    if (lay.pbc2_mode == 2) return go(search_fused_narrow_kernel<SPAN, 2, GenericShape>);
+    if (lay.pbc2_mode == 1) return go(search_fused_narrow_kernel<SPAN, 1, GenericShape>);
+    return go(search_fused_narrow_kernel<SPAN, 0, GenericShape>);
 }
 
 hipError_t launch_search_fused_narrow(const TreeParams& p, const FcNet& net, const NarrowLayout& lay, const float* weights,

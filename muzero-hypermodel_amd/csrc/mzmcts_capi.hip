@@ -183,6 +183,8 @@ int mzmcts_create(const mzmcts_config* c, mzmcts_engine** out) {
         eng->narrow_row_rng = !(serial && std::atoi(serial) != 0);
         const char* no_prefetch = std::getenv("MZMCTS_NARROW_NO_PREFETCH");
         eng->narrow_prefetch = !(no_prefetch && std::atoi(no_prefetch) != 0);
+        const char* generic_shape = std::getenv("MZMCTS_NARROW_GENERIC_SHAPE");
+        eng->narrow_generic_shape = generic_shape && std::atoi(generic_shape) != 0;
         const char* per_launch = std::getenv("MZMCTS_NARROW_TABLE_PER_LAUNCH");
         if (!(per_launch && std::atoi(per_launch) != 0)) {
             for (int mode = 1; mode <= 2; ++mode) {
@@ -866,6 +868,7 @@ int mzhost_launch_fused_move(mzmcts_engine* eng, const float* observations, cons
         mz::plan_narrow_layout(eng->p, eng->fc, kLdsPerWorkgroup, &nl);
         nl.row_rng = eng->narrow_row_rng ? 1 : 0;
         nl.prefetch = eng->narrow_prefetch ? 1 : 0;
+        nl.generic_shape = eng->narrow_generic_shape ? 1 : 0;
         nl.pbc2_table = eng->narrow_table[nl.pbc2_mode];
         ProfScope scope(eng, stream, kProfFused);
         MZ_HIP(eng, mz::launch_search_fused_narrow(eng->p, eng->fc, nl, eng->fc_weights, observations, ctl, eng->p.S,

@@ -68,6 +68,42 @@ struct NarrowLayout {
     int32_t row_rng;       // != 0: the tree's row draws from its stream together (mt_regenerate_row); 0: lane 0 alone
     const double* pbc2_table;  // the (N, n) table of pbc2_mode, built once per engine; null: every launch computes it
     int32_t prefetch;      // != 0: the per-tree inputs are asked for ahead of the staging (NarrowInputs)
+    int32_t generic_shape; // != 0: the launcher takes the run-time-shape form even for the flagship network (GenericShape)
+};
+
+// ---- the network's shape as the whole-move kernel sees it --------------------------------------------------
+// The kernel is built in two forms.  GenericShape reads every value from the engine's structs at run time and serves
+// every network narrow_supported admits.  FlagshipShape is CartPole's network (models.py with the game's config: encoding
+// 8, support 10 = 21 logits per head, two actions, one player) with every value a constant: the device functions below are
+// all inlined into the kernel, so a constant handed to them folds their uniform branches away -- the second-half support
+// units are plain loads with nothing zeroed first, the two-player paths and the multiplies by enc / A disappear.
+// Only the kernel's template argument differs: both forms run the same functions on the same operands in the same order.
+struct GenericShape {
+    static constexpr bool kFixed = false;
+    int enc_, features_, support_, actions_;
+    bool two_player_;
+    __device__ __forceinline__ GenericShape(const TreeParams& p, const FcNet& net)
+        : enc_(net.enc), features_(net.F), support_(net.support), actions_(p.A), two_player_(p.P == 2) {}
+    __device__ __forceinline__ int enc() const { return enc_; }
+    __device__ __forceinline__ int features() const { return features_; }
+    __device__ __forceinline__ int support() const { return support_; }
+    __device__ __forceinline__ int actions() const { return actions_; }
+    __device__ __forceinline__ bool two_player() const { return two_player_; }
+};
+struct FlagshipShape {
+    static constexpr bool kFixed = true;
+    static constexpr int kEnc = 8, kFeatures = 21, kSupport = 10, kActions = 2, kPlayers = 1;
+    __device__ __forceinline__ FlagshipShape(const TreeParams&, const FcNet&) {}
+    static constexpr __host__ __device__ int enc() { return kEnc; }
+    static constexpr __host__ __device__ int features() { return kFeatures; }
+    static constexpr __host__ __device__ int support() { return kSupport; }
+    static constexpr __host__ __device__ int actions() { return kActions; }
+    static constexpr __host__ __device__ bool two_player() { return kPlayers == 2; }
+    // exactly this shape, nothing near it (the launcher's test)
+    static bool matches(const TreeParams& p, const FcNet& net) {
+        return net.enc == kEnc && net.F == kFeatures && net.support == kSupport && net.A == kActions && p.A == kActions &&
+               p.P == kPlayers;
+    }
 };
 
 template <int R>
@@ -100,6 +136,57 @@ __device__ __forceinline__ double dmax(double a, double b) {
 __device__ __forceinline__ double dmin(double a, double b) {
     double r;
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// ---- fminf / fmaxf butterfly steps as one instruction each ---------------------------------------------------
+// `v = fmaxf(v, partner<M>(v))` compiles to v_mov_b32_dpp, a canonicalising v_max_f32 x, x, x, the v_max_f32 itself and
+// often an s_nop; the sum butterflies next to it are a single v_add_f32_dpp.  The canonicalisation only quiets a
+// signalling NaN, and every operand these steps meet is the result of an arithmetic instruction or the constant
+// +-INFINITY -- never a signalling NaN -- so v_max_f32_dpp / v_min_f32_dpp on the partner's lane pattern give the same
+// bits: the larger / smaller operand, +0.0 above -0.0 in either operand order, a quiet NaN giving way to a number as before.
+// The assembler does not see inside the block that a DPP read of a VGPR needs two wait states after the VALU write of it.
+// Two independent chains are stepped side by side, so a chain's next read has the other chain's instruction and one s_nop
+// behind its write; the first step of a butterfly (FIRST) pads for an operand written right ahead of the block.
+#define MZ_DPP_ROW_STEP2(OP_A, OP_B, CTRL)                                                        \
+    asm volatile("s_nop %2\n\t" OP_A " %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+                 OP_B " %1, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1"              \
+                 : "+v"(a), "+v"(b)                                                               \
+                 : "n"(FIRST ? 1 : 0))
+#define MZ_DPP_ROW_STEP1(OP_A, CTRL)                                                                           \
+    asm volatile("s_nop 1\n\t" OP_A " %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a))
+#define MZ_DPP_BY_STEP(STEP, ...)                                                           \
+    do {                                                                                    \
+        static_assert(M == 1 || M == 2 || M == 4 || M == 8, "a step inside the 16-lane row"); \
+        if constexpr (M == 1) STEP(__VA_ARGS__, "quad_perm:[1,0,3,2]");                     \
+        else if constexpr (M == 2) STEP(__VA_ARGS__, "quad_perm:[2,3,0,1]");                \
+        else if constexpr (M == 4) STEP(__VA_ARGS__, "row_half_mirror");                    \
+        else STEP(__VA_ARGS__, "row_mirror");                                               \
+    } while (0)
+
+// a = fminf(a, partner<M>(a)), b = fmaxf(b, partner<M>(b))
+template <int M, bool FIRST>
+__device__ __forceinline__ void row_min_max_step(float& a, float& b) {
+    MZ_DPP_BY_STEP(MZ_DPP_ROW_STEP2, "v_min_f32_dpp", "v_max_f32_dpp");
+}
+// a = fmaxf(a, partner<M>(a)), b = fmaxf(b, partner<M>(b))
+template <int M, bool FIRST>
+__device__ __forceinline__ void row_max_max_step(float& a, float& b) {
+    MZ_DPP_BY_STEP(MZ_DPP_ROW_STEP2, "v_max_f32_dpp", "v_max_f32_dpp");
+}
+// a = fmaxf(a, partner<M>(a)): one chain alone pays both wait states
+template <int M>
+__device__ __forceinline__ void row_max_step(float& a) {
+    MZ_DPP_BY_STEP(MZ_DPP_ROW_STEP1, "v_max_f32_dpp");
+}
+#undef MZ_DPP_BY_STEP
+#undef MZ_DPP_ROW_STEP1
+#undef MZ_DPP_ROW_STEP2
+
+// fmaxf of two such operands held by the same lane
+__device__ __forceinline__ float fmax_plain(float a, float b) {
+    float r;
+    asm("v_max_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
 
@@ -313,7 +400,7 @@ __device__ __forceinline__ void stage_narrow_units(const FcNet& net, const float
 // Sixteen v_fmac_f32 whose activation operand carries the DPP row rotate, written out because the compiler
 // will not fold a DPP move into the tied-accumulator form (it emits mov_dpp + fmac + hazard nops: 2.4x the
 // issue slots).  Two accumulators halve the dependent chain.  Hazards the assembler cannot see inside the
-// block: a VALU write of x (or of EXEC) immediately before the first DPP read -- covered by the leading nop.
+// block: a VALU write of x immediately before the first DPP read -- covered by the block's first two instructions.
 struct UnitWeights {
     float4 w0, w1, w2, w3;
     float bias;
@@ -326,12 +413,16 @@ __device__ __forceinline__ UnitWeights load_unit(const float4* units, const floa
     return UnitWeights{w[0], w[kRow], w[2 * kRow], w[3 * kRow], bias[U * kRow + j]};
 }
 
+// The frame around the sixteen FMAs: accumulator a starts as fma(x, w0, bias) -- the one fused operation that
+// `a = bias; a = fma(x, w0, a)` performs, so the same bits; accumulator b starts from +0.0 and takes its first product
+// through an FMA as well (a multiply would turn +0.0 + (-0.0) = +0.0 into -0.0).  The two instructions ahead of the first
+// DPP read are the two wait states a VALU write of x needs before a DPP instruction reads it; nothing here pads for a
+// VALU write of EXEC (five states): the compiler for this target writes EXEC through scalar instructions only.
 __device__ __forceinline__ float apply_unit(const UnitWeights& u, float x) {
-    float a = u.bias;
-    float b = 0.f;
+    float a, b;
     asm volatile(
-        "s_nop 4\n\t"
-        "v_fmac_f32_e32 %0, %2, %3\n\t"
+        "v_mov_b32_e32 %1, 0\n\t"
+        "v_fma_f32 %0, %2, %3, %19\n\t"
         "v_fmac_f32_dpp %1, %2, %4 row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f32_dpp %0, %2, %5 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f32_dpp %1, %2, %6 row_ror:3 row_mask:0xf bank_mask:0xf\n\t"
@@ -347,9 +438,9 @@ __device__ __forceinline__ float apply_unit(const UnitWeights& u, float x) {
         "v_fmac_f32_dpp %1, %2, %16 row_ror:13 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f32_dpp %0, %2, %17 row_ror:14 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f32_dpp %1, %2, %18 row_ror:15 row_mask:0xf bank_mask:0xf"
-        : "+v"(a), "+v"(b)
+        : "=&v"(a), "=&v"(b)
         : "v"(x), "v"(u.w0.x), "v"(u.w0.y), "v"(u.w0.z), "v"(u.w0.w), "v"(u.w1.x), "v"(u.w1.y), "v"(u.w1.z), "v"(u.w1.w),
-          "v"(u.w2.x), "v"(u.w2.y), "v"(u.w2.z), "v"(u.w2.w), "v"(u.w3.x), "v"(u.w3.y), "v"(u.w3.z), "v"(u.w3.w));
+          "v"(u.w2.x), "v"(u.w2.y), "v"(u.w2.z), "v"(u.w2.w), "v"(u.w3.x), "v"(u.w3.y), "v"(u.w3.z), "v"(u.w3.w), "v"(u.bias));
     return a + b;
 }
 
@@ -357,7 +448,7 @@ __device__ __forceinline__ float apply_unit(const UnitWeights& u, float x) {
 // Sixteen v_fmac_f32 whose activation operand carries the DPP row rotate, written out because the compiler
 // will not fold a DPP move into the tied-accumulator form (it emits mov_dpp + fmac + hazard nops: 2.4x the
 // issue slots).  Two accumulators halve the dependent chain.  Hazards the assembler cannot see inside the
-// block: a VALU write of x (or of EXEC) immediately before the first DPP read -- covered by the leading nop.
+// block: a VALU write of x immediately before the first DPP read -- covered by the block's first two instructions.
 template <int U>
 __device__ __forceinline__ float narrow_unit(const float4* units, const float* bias, float x, int j) {
     return apply_unit(load_unit<U>(units, bias, j), x);
@@ -400,8 +491,11 @@ __device__ __forceinline__ float narrow_elu(float v) {
 __device__ __forceinline__ float narrow_rescale(float raw, int enc, int j) {
     const bool in = j < enc;
     float mn = in ? raw : INFINITY, mx = in ? raw : -INFINITY;
-    const int span = enc <= 8 ? 8 : kRow;   // steps 1, 2, 4 pair lanes inside the lower half row: enough for 8 elements
-    MZ_BUTTERFLY(kRow, span, (mn = fminf(mn, partner<M>(mn)), mx = fmaxf(mx, partner<M>(mx))));
+    // steps 1, 2, 4 pair lanes inside the lower half row: enough for 8 elements
+    row_min_max_step<1, true>(mn, mx);
+    row_min_max_step<2, false>(mn, mx);
+    row_min_max_step<4, false>(mn, mx);
+    if (enc > 8) row_min_max_step<8, false>(mn, mx);
     float scale = mx - mn;
     if (scale < 1e-5f) scale += 1e-5f;
     return in ? (raw - mn) / scale : 0.f;
@@ -537,8 +631,11 @@ __device__ __forceinline__ void narrow_support_pair(float va, float vb, float ra
     const bool in_a = j < F, in_b = kRow + j < F;
     const float xva = in_a ? va : -INFINITY, xvb = in_b ? vb : -INFINITY;
     const float xra = in_a ? ra : -INFINITY, xrb = in_b ? rb : -INFINITY;
-    float mv = fmaxf(xva, xvb), mr = fmaxf(xra, xrb);
-    MZ_BUTTERFLY(kRow, kRow, (mv = fmaxf(mv, partner<M>(mv)), mr = fmaxf(mr, partner<M>(mr))));
+    float mv = fmax_plain(xva, xvb), mr = fmax_plain(xra, xrb);
+    row_max_max_step<1, true>(mv, mr);
+    row_max_max_step<2, false>(mv, mr);
+    row_max_max_step<4, false>(mv, mr);
+    row_max_max_step<8, false>(mv, mr);
     float tva = exp_nonpositive(xva - mv), tvb = exp_nonpositive(xvb - mv);
     float tra = exp_nonpositive(xra - mr), trb = exp_nonpositive(xrb - mr);
     asm volatile("" : "+v"(tva), "+v"(tvb), "+v"(tra), "+v"(trb));
@@ -566,7 +663,10 @@ __device__ __forceinline__ void narrow_support_pair(float va, float vb, float ra
 template <int SPAN = kRow, bool CUT = false>
 __device__ __forceinline__ double narrow_softmax(float logit, bool valid) {
     float m = valid ? logit : -INFINITY;
-    MZ_BUTTERFLY(SPAN, SPAN, m = fmaxf(m, partner<M>(m)));
+    if constexpr (SPAN >= 2) row_max_step<1>(m);
+    if constexpr (SPAN >= 4) row_max_step<2>(m);
+    if constexpr (SPAN >= 8) row_max_step<4>(m);
+    if constexpr (SPAN >= 16) row_max_step<8>(m);
     float t = exp_nonpositive(logit - m);
     asm volatile("" : "+v"(t));
     const float e = valid ? t : 0.f;
