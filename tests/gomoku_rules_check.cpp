@@ -5,14 +5,17 @@
 // seeded `seed` must play legal[choice(n_legal)] with the words consumed, the stream position and the key block equal
 // to HostStream's for choice(n_legal) (HostStream is pinned to numpy by fixture G7).  A full board has no move: -1,
 // nothing drawn.  The per-stone test is also run on the bordered board the kernels stage in LDS: the stones that start
-// a five are counted and printed, so that the caller can compare them with its own count.
-// Built and run by tests/test_gomoku_cpu.py:   g++ -O2 -std=c++17 -ffp-contract=off gomoku_rules_check.cpp -lm
+// a five are counted and printed, so that the caller can compare them with its own count.  With the argument --picks
+// every row also prints a line "pick <move> <words> <stream position>": what the opponent did, for a caller that holds
+// numpy's own record of the draw.
+// Built and run by tests/test_gomoku_cpu.py and tests/test_gomoku_rules_cpu.py:   g++ -O2 -std=c++17 -ffp-contract=off gomoku_rules_check.cpp -lm
 #include <cstdio>
 #include <cstring>
 
 #include "board_rules.h"
 
-int main() {
+int main(int argc, char** argv) {
+    const bool print_picks = argc > 1 && std::strcmp(argv[1], "--picks") == 0;
     long rows = 0, bad_finished = 0, bad_legal = 0, bad_random = 0, bad_stream = 0, bad_full = 0, full_boards = 0, starts = 0;
     unsigned seed;
     int finished, n_want;
@@ -39,6 +42,7 @@ int main() {
         int32_t pos = host.pos;
         uint32_t words = 0;
         const int got = mz::gmk_opponent_action(board, key, &pos, &words);
+        if (print_picks) std::printf("pick %d %u %d\n", got, words, pos);
         if (n == 0) {
             ++full_boards;
             if (got != -1 || words != 0 || pos != host.pos || std::memcmp(key, host.key, sizeof(key)) != 0) ++bad_full;
