@@ -337,9 +337,14 @@ __global__ __launch_bounds__(kNarrowMaxThreads) __attribute__((amdgpu_waves_per_
             [&]() { backup_fetch_factors<SPAN, PBC2>(round, pbc, pbc2, p.S, sim, j); });
         MZ_STAMP(3);
         float value_f, reward_f;
-        narrow_support_pair<true>(h.value_a, h.value_b, h.reward_a, h.reward_b, F, support, j, value_f, reward_f,
-                                  transform_reciprocal);
-        double prior[1] = {narrow_softmax<SPAN, true>(h.policy, j < A)};
+        double prior[1];
+        if constexpr (Shape::kFixed) {   // the same decode with its short vectors packed (narrow_decode_flagship)
+            narrow_decode_flagship(h, j, transform_reciprocal, value_f, reward_f, prior[0]);
+        } else {
+            narrow_support_pair<true>(h.value_a, h.value_b, h.reward_a, h.reward_b, F, support, j, value_f, reward_f,
+                                      transform_reciprocal);
+            prior[0] = narrow_softmax<SPAN, true>(h.policy, j < A);
+        }
         MZ_STAMP(4);
         const int k_new = sim + 1;
         if constexpr (SPAN == 2) {

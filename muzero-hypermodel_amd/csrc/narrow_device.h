@@ -675,6 +675,74 @@ __device__ __forceinline__ double narrow_softmax(float logit, bool valid) {
     return static_cast<double>(e * (CUT ? reciprocal_of_sum(s) : 1.0f / s));
 }
 
+// ---- the decode of the flagship shape: narrow_support_pair<true> and narrow_softmax<2, true> in one ----------------
+// With F = 21 the second registers of the two support vectors hold five live lanes each (elements 16..20) and the policy
+// two, and the unpacked decode runs a whole exp_nonpositive chain for each of the three; the two expectations are
+// uniform over the row, and it runs inverse_value_transform_narrow once for each.  Both functions are element-wise, so
+// here one register carries
+//     lanes 0..4  value element 16 + lane minus the value maximum
+//     lanes 8..12 reward element 16 + (lane - 8) minus the reward maximum
+//     lanes 14,15 policy logit (lane - 14) minus the policy maximum            (every other lane 0.f)
+// through one chain, and one register carries the value expectation in lanes 0..7 and the reward's in lanes 8..15 through
+// one transform.  Every subtraction happens before the packing, the results are rotated back to where the unpacked form
+// has them, and the maxima, sums, reciprocals and expectations are the unpacked form's instruction for instruction: the
+// same operations on the same operands in every lane whose result is used -- the same bits (GenericShape, which keeps
+// calling the unpacked functions, is the reference: tests/test_gpu_fused_packed_decode.py).
+// The lane moves are __builtin_amdgcn_update_dpp, not asm blocks: the compiler sees the DPP read and pads the two wait
+// states it needs after the VALU write of its operand by itself (row_min_max_step has to pad by hand).
+
+// lanes of the row's 4-lane banks in BANKS (bit b: lanes 4b .. 4b+3) receive row_ror:R of v, the others keep `old`
+template <int R, int BANKS>
+__device__ __forceinline__ float row_ror_into(float old, float v) {
+    constexpr int kCtrl = R == 0 ? 0xE4 : 0x120 + R;   // quad_perm:[0,1,2,3] (every lane its own) / row_ror:R
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
+                                                                 kCtrl, 0xF, BANKS, false));
+}
+
+__device__ __forceinline__ void narrow_decode_flagship(const NarrowHeads& h, int j, float reciprocal, float& value,
+                                                       float& reward, double& prior) {
+    constexpr int F = FlagshipShape::kFeatures, support = FlagshipShape::kSupport, A = FlagshipShape::kActions;
+    static_assert(F > kRow && F - kRow <= 5 && A == 2, "the lane ranges of the packing");
+    const bool in_b = kRow + j < F, in_p = j < A;   // (every lane holds an element of the first registers: kRow <= F)
+    // maxima: narrow_support_pair's and narrow_softmax<2>'s
+    const float xvb = in_b ? h.value_b : -INFINITY, xrb = in_b ? h.reward_b : -INFINITY;
+    float mv = fmax_plain(h.value_a, xvb), mr = fmax_plain(h.reward_a, xrb);
+    row_max_max_step<1, true>(mv, mr);
+    row_max_max_step<2, false>(mv, mr);
+    row_max_max_step<4, false>(mv, mr);
+    row_max_max_step<8, false>(mv, mr);
+    float m = in_p ? h.policy : -INFINITY;
+    row_max_step<1>(m);
+    // the three short vectors, subtracted where they are, then side by side in one register (OR with the 0.f of the others)
+    const float dvb = in_b ? xvb - mv : 0.f, drb = in_b ? xrb - mr : 0.f, dp = in_p ? h.policy - m : 0.f;
+    const float packed = __builtin_bit_cast(float, __builtin_bit_cast(int, dvb) | row_ror_bits<8>(__builtin_bit_cast(int, drb)) |
+                                                       row_ror_bits<14>(__builtin_bit_cast(int, dp)));
+    float tva = exp_nonpositive(h.value_a - mv), tra = exp_nonpositive(h.reward_a - mr), tp = exp_nonpositive(packed);
+    asm volatile("" : "+v"(tva), "+v"(tra), "+v"(tp));
+    const float eva = tva, era = tra;
+    // lanes 8..12 back to 0..4, lanes 14, 15 back to 0, 1 -- by every lane, ahead of the selects: a lane move inside a
+    // select's arm would run with the other lanes switched off, and a DPP read of a switched-off lane gives 0
+    const float trb = row_ror<8>(tp), tpol = row_ror<2>(tp);
+    const float evb = in_b ? tp : 0.f, erb = in_b ? trb : 0.f;
+    const float e = in_p ? tpol : 0.f;
+    // sums, reciprocals and expectations: narrow_support_pair<true>'s
+    float sv = eva + evb, sr = era + erb;
+    MZ_BUTTERFLY(kRow, kRow, (sv = sv + partner<M>(sv), sr = sr + partner<M>(sr)));
+    const float iv = reciprocal_of_sum(sv), ir = reciprocal_of_sum(sr);
+    const float fa = static_cast<float>(j - support), fb = static_cast<float>(kRow + j - support);
+    float av = fa * (eva * iv) + fb * (evb * iv);
+    float ar = fa * (era * ir) + fb * (erb * ir);
+    MZ_BUTTERFLY(kRow, kRow, (av = av + partner<M>(av), ar = ar + partner<M>(ar)));
+    // av and ar are uniform over the row: one transform on [av x 8 | ar x 8], each half then handed to the other
+    const float y = inverse_value_transform_narrow(row_ror_into<0, 0xC>(av, ar), reciprocal);
+    value = row_ror_into<8, 0xC>(y, y);
+    reward = row_ror_into<8, 0x3>(y, y);
+    // narrow_softmax<2, true>'s sum and quotient
+    float s = e;
+    MZ_BUTTERFLY(A, A, s = s + partner<M>(s));
+    prior = static_cast<double>(e * reciprocal_of_sum(s));
+}
+
 // ---- tree in LDS with the per-child value term ---------------------------------------------------------
 // A block keeps, per child c, the pair { vterm, prior } (16 bytes at c * 16: everything a score needs, one
 // ds_read_b128) and ChildLinks (16 bytes at 16 * SPAN + c * 16); SPAN = pow2 >= A is the kernel's template
