@@ -329,7 +329,8 @@ def test_engine_replays_gomoku_traces_bit_exact_in_injected_mode(eng, oracle):
 # (MIOpen convolutions against torch's CPU ones) flips a UCB near-tie; everything else must match simulation for simulation.
 # The 400-simulation search builds chains up to 63 plies deep with these synthetic weights; the logit deviation grows along
 # a chain of recurrent inferences (9e-7 per evaluation, 8e-4 at the deepest leaves of the 30-simulation traces), and
-# on MI355X it flips a near-tie at simulation 71 of 400.  Its root logits, noise, and visit totals are still held.
+# on MI355X it flips a near-tie at simulation 71 of 400.  Its root logits, noise, root priors and visit totals are still
+# held, and so are the logit, categorical-mean and decoded-value bounds of the 71 leaves before that simulation.
 GOMOKU_EXPECTED_DIVERGENT = {"30 simulations": (), "400 simulations": (0,)}
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from native_replay import StreamReader, export_trees
 from parity_helpers import (cartpole_model_and_weights, categorical_mean_rounding, fixture_config, load_golden,
                             make_search_config, random_streams, run_injected_on_engine, run_injected_on_oracle,
                             streams_from_fixture, support_to_scalar64, synthetic_model, value_transform_bound)
@@ -332,13 +333,73 @@ def _write_parity_report():
         json.dump(PARITY_REPORT, f, indent=1, sort_keys=True)
 
 
-def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_tol=1e-5, name=None):
+def _near_tie(oracle, config, fx, i, first, engine_path):
+    """The reference's own search of trace i replayed on the oracle up to simulation `first`, where the engine's path
+    leaves the reference's: the node at which the two paths fork and, in float64 numpy, the UCB scores
+    (self_play.py:381-405) of the child the reference took and of the child the engine took."""
+    streams = streams_from_fixture(fx, [i])
+    legal = streams["legal"][0]
+    rng = oracle.Rng(streams["seeds"][0])
+    tree = oracle.Tree(oracle.config_from_fixture(fx))
+    tree.reset(rng, legal, streams["to_play"][0], float(streams["root_reward"][0]), root_priors=streams["root_priors"][0][:len(legal)])
+    tree.simulate(rng, first=0, n=first, value=streams["value"][0], reward=streams["reward"][0], priors=streams["priors"][0])
+    S = config.num_simulations
+    assert np.array_equal(tree.sim_actions[:first, :S], fx["sim_actions"][i][:first, :S]), "the oracle left the recorded paths"
+    ref_path = [int(a) for a in fx["sim_actions"][i][first, :S] if a >= 0]
+    eng_path = [int(a) for a in engine_path if a >= 0]
+    fork = next(d for d in range(min(len(ref_path), len(eng_path))) if ref_path[d] != eng_path[d])
+    prefix = ref_path[:fork]
+    root = tree.root_stats()
+    low, high = root["mms_min"], root["mms_max"]
+    parent = tree.node_stats(prefix)
+    N = parent["visit"]
+    two_player = len(config.players) == 2
+
+    def coefficient(n):
+        return (np.log((N + config.pb_c_base + 1.0) / config.pb_c_base) + config.pb_c_init) * np.sqrt(float(N)) / (n + 1.0)
+
+    def score(action):
+        child = tree.node_stats(prefix + [action])
+        n = child["visit"]
+        value_score = 0.0
+        if n > 0:
+            q = child["value_sum"] / n
+            value_score = child["reward"] + float(config.discount) * (-q if two_player else q)
+            if high > low:
+                value_score = (value_score - low) / (high - low)
+        return coefficient(n) * child["prior"] + value_score, n
+
+    (score_ref, n_ref), (score_eng, n_eng) = score(ref_path[fork]), score(eng_path[fork])
+    return dict(fork_depth=fork, parent_visits=int(N), gap_ref=float(score_ref - score_eng), span=float(high - low),
+                coefficient_ref=float(coefficient(n_ref)), coefficient_eng=float(coefficient(n_eng)),
+                child_visits_ref=int(n_ref), child_visits_eng=int(n_eng))
+
+
+def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_tol=1e-5, name=None, oracle=None):
     """Native-mode search (PyTorch-ROCm / HIP inference + HIP tree kernels) of recorded reference traces.
 
     Every trace must walk the reference's paths simulation for simulation -- except the traces listed in
     `expected_divergent`, whose fp32 network outputs flip a UCB near-tie on this hardware (measured, MI355X);
     a trace outside that set that diverges is a regression.  On identical paths every integer statistic, the
     policy target and the sampled action are exact.
+
+    With `oracle`, every trace -- the divergent ones included -- is also replayed on the fp64 oracle from the engine's own
+    decoded outputs, read out of the tree after every simulation (native_replay.StreamReader), and must match bit for
+    bit on every key of EXACT_KEYS and in the count of tie-break words: whatever the network path gave, the tree kernels
+    searched it exactly.
+
+    A divergent trace gets the per-leaf checks below on the simulations before the first differing one, where its paths
+    are still the reference's, and its near-tie is held against the REFERENCE (_near_tie): at the node where the paths
+    fork, gap_ref = score(reference's child) - score(engine's child) >= 0 in the reference's own tree, and a flip needs
+    the two scores to move by gap_ref between them.  What the asserted deviations let one child's score
+    c(N, n) prior + normalise(reward + discount q) move by: the prior by at most `logit_tol` (asserted on child_prior),
+    times c(N, n) = (log((N + base + 1) / base) + init) sqrt(N) / (n + 1); every backed-up value by at most
+    B = leaf-value bound + depth x reward bound (the form of step 4's target_bound), hence the numerator v = reward +
+    discount q and the normaliser's minimum and maximum by at most B each, and (v - min) / (max - min) by at most
+    3 B / (span - 2 B) (to first order (1 + (1 - f) + f) B / span = 2 B / span; 3 covers all three moving against each
+    other with the shrunken span).  So gap_ref <= the sum of that over the two children, i.e. twice one child's
+    allowance.  A gap beyond it is no fp32-sized near-tie: the exact replay then says whether the tree kernels or the
+    network path moved.
 
     Floating point, as a chain of derived bounds (north star: logits / targets "within 1e-5"):
       1. a network evaluation on the reference's own input gives value / reward / policy LOGITS within `logit_tol` = 1e-5
@@ -364,9 +425,12 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
     to_play = [int(fx["to_play"][i]) for i in idx]
     S, support = config.num_simulations, int(config.support_size)
     paths = np.full((T, S, S), -1, np.int32)
+    path_depth, path_ties = np.zeros((T, S), np.int32), np.zeros((T, S, S), np.int32)
+    reader = StreamReader(legal, S, len(config.action_space)) if oracle is not None else None
     leaf_logits = []
     with torch.no_grad():
         value, reward, policy, hidden = model.initial_inference(torch.from_numpy(obs).cuda())
+        root_outputs = tuple(x.clone() for x in (value, reward, policy, hidden))
         want_logits = np.stack([fx["root_policy_logits"][i] for i in idx])
         worst_logit = float(np.abs(policy.cpu().numpy() - want_logits).max())
         np.testing.assert_allclose(policy.cpu().numpy(), want_logits, rtol=0, atol=logit_tol)
@@ -379,13 +443,35 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
             value, reward, policy, _ = engine._infer(model)
             leaf_logits.append((value.clone(), reward.clone(), policy.clone()))
             engine.expand_backup(value, reward, policy, None)
-            _, actions, _ = engine.last_paths()
-            paths[:, s] = actions
+            path_depth[:, s], paths[:, s], path_ties[:, s] = engine.last_paths(with_ties=True)
+            if reader is not None:
+                reader.read(export_trees(engine, T), path_depth[:, s], paths[:, s])
     st = engine.readout()
     cv, rv = engine.search_statistics()
     temps = [float(fx["temperature"][i]) for i in idx]
     actions, _ = engine.sample_actions(temps)
     engine.close()
+    if oracle is not None:
+        # the root's priors before the noise: the same engine form, the same logits, no noise
+        plain = eng.BatchedMCTS(config, T, seeds=[int(fx["seed"][i]) for i in idx])
+        plain.begin_search(legal, to_play, False)
+        plain.expand_roots(*root_outputs)
+        root_priors = plain.readout()["child_prior"].copy()
+        plain.close()
+        streams = dict(seeds=[int(fx["seed"][i]) for i in idx], legal=legal, to_play=to_play, root_reward=np.zeros(T),
+                       root_priors=root_priors, value=reader.value, reward=reader.reward, priors=reader.priors)
+        replayed = run_injected_on_oracle(oracle, config, streams, temperature=temps)
+        native = dict(noise=engine.noise, sim_depth=path_depth, sim_actions=paths, sim_ties=path_ties,
+                      child_visits_target=cv, root_value_target=rv, action=actions,
+                      **{k: st[k] for k in ("visits", "child_value_sum", "child_prior", "child_reward", "root_value_sum",
+                                            "root_visits", "max_tree_depth", "min_max")})
+        assert_exact(native, replayed, where=f"{name or 'native search'} vs the oracle fed its own decoded outputs: ")
+        noise_words = np.zeros(T, np.int64)
+        for t in range(T):
+            rng = oracle.Rng(streams["seeds"][t])
+            rng.dirichlet(float(config.root_dirichlet_alpha), len(legal[t]))
+            noise_words[t] = rng.words
+        assert np.array_equal(st["tie_break_words"].astype(np.int64), replayed["rng_words_run"] - noise_words)
     got_v = torch.stack([x[0] for x in leaf_logits], dim=1).cpu()             # [T, S, F]
     got_r = torch.stack([x[1] for x in leaf_logits], dim=1).cpu()
     got_p = torch.stack([x[2] for x in leaf_logits], dim=1).cpu().numpy()     # [T, S, A]
@@ -396,7 +482,7 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
 
     by_depth = {}
     single_step = 0.0          # worst logit deviation of an evaluation with no chain behind it (root, depth-1 leaves)
-    same, divergent = 0, {}
+    same, divergent, near_ties = 0, {}, {}
     worst = dict(target_abs=0.0, target_rel=0.0, target_over_bound=0.0, pred_abs=0.0, pred_over_bound=0.0, leaf_abs=0.0,
                  leaf_over_bound=0.0, leaf_logit=0.0, prior=0.0, bound_at_bar=0.0, bound_at_measured=0.0)
     for t, i in enumerate(idx):
@@ -412,31 +498,39 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
         worst["pred_abs"], worst["pred_over_bound"] = max(worst["pred_abs"], dev), max(worst["pred_over_bound"], dev / bound)
         assert dev <= bound, (i, dev, bound)
         assert np.array_equal(engine.noise[t, :n], fx["noise"][i][:n])          # host RNG: exact
+        first = None
         if not np.array_equal(paths[t], fx["sim_actions"][i][:, :S]):
             first = int(np.nonzero((paths[t] != fx["sim_actions"][i][:, :S]).any(axis=1))[0][0])
             divergent[int(i)] = first
-            continue
-        same += 1
-        assert np.array_equal(st["visits"][t], fx["visits"][i])
-        assert np.array_equal(cv[t], fx["child_visits_target"][i])              # policy target: exact
+            # the root's priors do not depend on the search: within the bar on a divergent trace too
+            np.testing.assert_allclose(st["child_prior"][t, :n], fx["child_prior"][i][:n], rtol=0, atol=logit_tol)
+            if first == 0:
+                continue
+        else:
+            same += 1
+            assert np.array_equal(st["visits"][t], fx["visits"][i])
+            assert np.array_equal(cv[t], fx["child_visits_target"][i])              # policy target: exact
+        upto = S if first is None else first        # the simulations whose paths are the reference's
+        sim_depth = fx["sim_depth"][i][:upto]
         # 1. every leaf's logits
-        dl_v = np.abs(got_v[t].numpy() - fx["sim_value_logits"][i]).max(axis=1)           # [S]
-        dl_r = np.abs(got_r[t].numpy() - fx["sim_reward_logits"][i]).max(axis=1)
-        dl_p = np.abs(got_p[t] - fx["sim_policy_logits"][i]).max(axis=1)
+        dl_v = np.abs(got_v[t].numpy() - fx["sim_value_logits"][i])[:upto].max(axis=1)           # [upto]
+        dl_r = np.abs(got_r[t].numpy() - fx["sim_reward_logits"][i])[:upto].max(axis=1)
+        dl_p = np.abs(got_p[t] - fx["sim_policy_logits"][i])[:upto].max(axis=1)
         leaf_logit = float(max(dl_v.max(), dl_r.max(), dl_p.max()))
         worst["leaf_logit"] = max(worst["leaf_logit"], leaf_logit)
-        shallow = fx["sim_depth"][i] <= 1            # a leaf one step below the root: no chain behind it yet
+        shallow = sim_depth <= 1            # a leaf one step below the root: no chain behind it yet
         if shallow.any():
             single_step = max(single_step, float(max(dl_v[shallow].max(), dl_r[shallow].max(), dl_p[shallow].max())))
             assert single_step <= logit_tol, i
-        for d in range(1, int(fx["sim_depth"][i].max()) + 1):
-            at = fx["sim_depth"][i] == d
+        for d in range(1, int(sim_depth.max()) + 1):
+            at = sim_depth == d
             if at.any():
                 by_depth[d] = max(by_depth.get(d, 0.0), float(max(dl_v[at].max(), dl_r[at].max(), dl_p[at].max())))
         # 2. categorical means, 3. decoded leaves
         leaf_bounds = {}
-        for kind, got, ref_logits, ref_scalar, dl_k in (("value", got_v[t], fx["sim_value_logits"][i], fx["sim_value"][i], dl_v),
-                                                       ("reward", got_r[t], fx["sim_reward_logits"][i], fx["sim_reward"][i], dl_r)):
+        for kind, got, ref_logits, ref_scalar, dl_k in (
+                ("value", got_v[t][:upto], fx["sim_value_logits"][i][:upto], fx["sim_value"][i][:upto], dl_v),
+                ("reward", got_r[t][:upto], fx["sim_reward_logits"][i][:upto], fx["sim_reward"][i][:upto], dl_r)):
             dx = np.abs(categorical_mean(got.numpy(), support) - categorical_mean(ref_logits, support))
             assert (dx <= categorical_mean_bound(dl_k, support) + 1e-12).all()
             bounds = value_transform_bound(ref_scalar, dx)
@@ -446,6 +540,20 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
             if kind == "value":
                 worst["leaf_abs"] = max(worst["leaf_abs"], float(devs.max()))
                 worst["leaf_over_bound"] = max(worst["leaf_over_bound"], float((devs / bounds).max()))
+        if first is not None:
+            # the near-tie, against the reference's own tree (see the docstring)
+            depth = int(fx["sim_depth"][i][:first + 1].max())
+            B = leaf_bounds["value"] + depth * leaf_bounds["reward"]
+            if oracle is not None:
+                tie = _near_tie(oracle, config, fx, i, first, paths[t, first])
+                span = tie["span"]
+                value_part = 3.0 * B / (span - 2.0 * B) if span > 2.0 * B else (B if span <= 0.0 else np.inf)
+                tie["bound"] = float((tie["coefficient_ref"] + tie["coefficient_eng"]) * logit_tol + 2.0 * value_part)
+                tie["first"], tie["backed_up_value_bound"] = first, float(B)
+                near_ties[int(i)] = tie
+                print(f"trace {i}: paths fork at simulation {first}, depth {tie['fork_depth']}: the reference's gap "
+                      f"{tie['gap_ref']:.3e}, what the asserted deviations allow {tie['bound']:.3e}")
+            continue
         # 4. the root value target
         depth = int(fx["sim_depth"][i].max())
         target_bound = leaf_bounds["value"] + depth * leaf_bounds["reward"]
@@ -470,7 +578,8 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
           f"divergent traces (trace: first differing simulation) {divergent}")
     if name:
         PARITY_REPORT[name] = dict(
-            traces=T, identical_paths=same, divergent_first_simulation=divergent, logit_bar=logit_tol,
+            traces=T, identical_paths=same, divergent_first_simulation=divergent, divergent_near_ties=near_ties,
+            replayed_exactly_on_the_oracle=T if oracle is not None else 0, logit_bar=logit_tol,
             worst_root_policy_logit_abs=worst_logit, worst_depth1_leaf_logit_abs=single_step,
             worst_in_search_leaf_logit_abs=worst["leaf_logit"],
             in_search_leaf_logit_abs_by_depth={str(d): v for d, v in sorted(by_depth.items())}, worst_prior_abs=worst["prior"],
@@ -483,6 +592,9 @@ def native_vs_fixture(eng, model, config, fx, idx, expected_divergent=(), logit_
         _write_parity_report()
     unexpected = sorted(set(divergent) - set(expected_divergent))
     assert not unexpected, f"traces {unexpected} left the reference's paths (identical-path rate {same}/{T})"
+    for i, tie in near_ties.items():
+        assert tie["gap_ref"] >= 0.0, (i, tie)        # the reference took the best child of its own tree
+        assert tie["gap_ref"] <= tie["bound"], f"trace {i}: no fp32-sized near-tie: {tie}"
     return same / T
 
 
@@ -499,35 +611,40 @@ def _g6_value_bound():
 
 RESNET_TOL = dict(value_tol=_g6_value_bound(), logit_tol=1e-5)
 # traces whose search leaves the reference's path on MI355X because an fp32-rounding-sized difference of the
-# network outputs flips a UCB near-tie (trace index: see the report); everything else must match move for move
+# network outputs flips a UCB near-tie (trace index: see the report); everything else must match move for move.
+# What a listed trace is still held to (native_vs_fixture): the root prediction, the noise row and the root's priors; the
+# logit, categorical-mean and decoded value / reward bounds of every leaf before its first differing simulation; its whole
+# search replayed bit for bit on the oracle from the engine's own decoded outputs; and the near-tie itself -- in the
+# REFERENCE's tree the child it took leads the child the engine took by no more than the asserted deviations can move
+# the two scores (gap, bound, fork depth and simulation go to parity_report.json: divergent_near_ties)
 # connect4 (default path: the split-precision tower kernel): traces 23 and 29 leave the reference's path at simulation
 # 167 / 183 of 200, 28/30 identical.  Which near-ties flip depends on the fp32 rounding of the network path: MIOpen's
 # convolution flips 21 and 23, the exact-fp32 MFMA kernel 9, 21 and 23 (MZ_BOARD_CONV_PRECISION=fp32).
 EXPECTED_DIVERGENT = {"cartpole": (), "tictactoe": (), "connect4": (23, 29), "atari84": ()}
 
 
-def test_native_cartpole_vs_reference(eng, models_mod):
+def test_native_cartpole_vs_reference(eng, models_mod, oracle):
     config = games("cartpole").MuZeroConfig()
     model, _ = cartpole_model_and_weights(models_mod, config, "cuda")
     fx = load_golden("g4_cartpole_traces")
     native_vs_fixture(eng, model, config, fx, list(range(len(fx["seed"]))), EXPECTED_DIVERGENT["cartpole"],
-                      name="cartpole")
+                      name="cartpole", oracle=oracle)
 
 
-def test_native_tictactoe_vs_reference(eng, models_mod):
+def test_native_tictactoe_vs_reference(eng, models_mod, oracle):
     config = games("tictactoe").MuZeroConfig()
     model, _ = synthetic_model(models_mod, config, "cuda")
     fx = load_golden("g5_tictactoe_traces")
     native_vs_fixture(eng, model, config, fx, list(range(len(fx["seed"]))), EXPECTED_DIVERGENT["tictactoe"],
-                      name="tictactoe", logit_tol=RESNET_TOL["logit_tol"])
+                      name="tictactoe", logit_tol=RESNET_TOL["logit_tol"], oracle=oracle)
 
 
-def test_native_connect4_vs_reference(eng, models_mod):
+def test_native_connect4_vs_reference(eng, models_mod, oracle):
     config = games("connect4").MuZeroConfig()
     model, _ = synthetic_model(models_mod, config, "cuda")
     fx = load_golden("g5_connect4_traces")
     native_vs_fixture(eng, model, config, fx, list(range(len(fx["seed"]))), EXPECTED_DIVERGENT["connect4"],
-                      name="connect4", logit_tol=RESNET_TOL["logit_tol"])
+                      name="connect4", logit_tol=RESNET_TOL["logit_tol"], oracle=oracle)
 
 
 def atari84_traces():
@@ -536,13 +653,13 @@ def atari84_traces():
     return fx
 
 
-def test_native_atari84_vs_reference(eng, models_mod):
+def test_native_atari84_vs_reference(eng, models_mod, oracle):
     """BASELINE config #5 end to end: DownsampleCNN representation of 4 x 84 x 84 frames, A = 4, 50 simulations."""
     config = games("breakout").atari84_config()
     model, _ = synthetic_model(models_mod, config, "cuda")
     fx = atari84_traces()
     native_vs_fixture(eng, model, config, fx, list(range(len(fx["seed"]))), EXPECTED_DIVERGENT["atari84"],
-                      name="atari84", logit_tol=RESNET_TOL["logit_tol"])
+                      name="atari84", logit_tol=RESNET_TOL["logit_tol"], oracle=oracle)
 
 
 def test_gpu_network_outputs_vs_reference_fixtures(models_mod):
