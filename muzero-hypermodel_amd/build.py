@@ -11,7 +11,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libmzmcts.so")
 SOURCES = ["mcts_kernels.hip", "fused_narrow.hip", "mzmcts_capi.hip", "mzmcts_moves.hip", "mzmcts_rng.hip", "mzhist.hip", "env_kernels.hip", "mzenv_capi.hip", "obs_stack.hip", "mzreplay.hip", "net_kernels.hip", "board_conv.hip", "wide_conv.hip", "downsample_cnn.hip", "trainer_kernels.hip", "fc_train.hip", "fc_optimizer.hip", "grad_fold.hip", "bn_epilogue.hip", "conv_train.hip", "head_train.hip", "rescale_train.hip", "device_checks.hip"]
-HEADERS = ["engine_host.h", "board_rules.h", "gomoku_rules.h", "solo_rules.h", "obs_stack.h", "np_legacy_rng.h", "select_action.h", "replay_sampler.h", "replay_filer.h", "game_outcomes.h", "reanalyse_plan.h", "launch_plan.h", "wide_conv.h", "board_launch.h", "fc_net_host.h", "fc_backward.h", "fc_optimizer.h", "grad_fold.h", "bn_epilogue.h", "conv_train.h", "head_train.h", "rescale_train.h", "glibc_libm.h", "glibc_libm_tables.inc", "tree_layout.h", "tree_device.h", "fc_net_device.h", "narrow_device.h", "kernel_common.h", "env_layout.h", os.path.join("..", "..", "include", "mzmcts.h"),
+HEADERS = ["engine_host.h", "staging_layout.h", "board_rules.h", "gomoku_rules.h", "solo_rules.h", "obs_stack.h", "np_legacy_rng.h", "select_action.h", "replay_sampler.h", "replay_filer.h", "game_outcomes.h", "reanalyse_plan.h", "launch_plan.h", "wide_conv.h", "board_launch.h", "fc_net_host.h", "fc_backward.h", "fc_optimizer.h", "grad_fold.h", "bn_epilogue.h", "conv_train.h", "head_train.h", "rescale_train.h", "glibc_libm.h", "glibc_libm_tables.inc", "tree_layout.h", "tree_device.h", "fc_net_device.h", "narrow_device.h", "kernel_common.h", "env_layout.h", os.path.join("..", "..", "include", "mzmcts.h"),
            os.path.join("..", "..", "include", "mzenv.h"), os.path.join("..", "..", "include", "mzreplay.h"), os.path.join("..", "..", "include", "mzhist.h"), os.path.join("..", "..", "include", "mztrain.h")]
 
 # -fno-slp-vectorize: packing adjacent scalar f32 FMAs into v_pk_fma_f32 costs more in register shuffles

@@ -30,6 +30,7 @@
 #include "kernel_common.h"
 #include "narrow_device.h"
 #include "np_legacy_rng.h"
+#include "staging_layout.h"
 #include "tree_layout.h"
 
 
@@ -222,26 +223,9 @@ struct mzmcts_engine {
     bool owns_hidden = false;
     int64_t device_bytes = 0;
 
-    // device staging for the per-move host inputs
-    double* d_noise = nullptr;
-    uint32_t* d_skip = nullptr;
     uint32_t* d_seeds = nullptr;
     bool noise_this_search = false;
-
-    // pinned host staging
-    int32_t* h_legal = nullptr;      // [E][A]
-    int32_t* h_nlegal = nullptr;     // [E]
-    int32_t* h_to_play = nullptr;    // [E]
-    double* h_noise = nullptr;       // [E][A]
-    uint32_t* h_skip = nullptr;      // [E]
-    uint8_t* h_slab0 = nullptr;      // [E][block_stride]
-    double* h_root_value_sum = nullptr;
-    float* h_root_predicted = nullptr;
-    int32_t* h_max_depth = nullptr;
-    int64_t* h_depth_sum = nullptr;
-    uint32_t* h_tie_words = nullptr;
-    mz::MinMax* h_min_max = nullptr;
-    int32_t* h_error_flag = nullptr;
+    uint8_t* h_slab0 = nullptr;      // pinned [E][block_stride]
 
     // host RNG mirrors; lag[e] = words the host stream is ahead of the device copy.  behind[e] = words the device copy
     // consumed that the mirror has not stepped over yet (device-input move batches draw everything on the device: their
@@ -287,7 +271,6 @@ struct mzmcts_engine {
     bool device_noise = false;       // mzmcts_set_device_noise: exploration noise drawn by root_noise_kernel
     bool noise_on_device = false;    // ... and it was, for the search in progress (readout fetches rows + word counts)
     bool device_temperatures = false;  // mzmcts_set_device_temperatures: move batches take any samplable temperature
-    uint32_t* h_noise_words = nullptr;
     int select_queue_trees = 0;      // mzmcts_set_select_queue: 0 = one descent per lane group
     std::vector<EventPair> events;
     size_t events_used = 0;
@@ -296,13 +279,12 @@ struct mzmcts_engine {
     std::vector<void*> device_allocs;
     std::vector<void*> pinned_allocs;
 
-    // packed per-move upload ([legal | num_legal | to_play | rng_skip | noise]) and per-tree download
-    uint8_t* h_upload = nullptr;
-    uint8_t* d_upload = nullptr;
-    size_t upload_bytes = 0, upload_bytes_no_noise = 0;
-    uint8_t* h_download = nullptr;
-    uint8_t* d_download = nullptr;
-    size_t download_bytes = 0;
+    // packed per-move upload and per-tree download (staging_layout.h): pinned host and device copies, and their fields
+    mz::UploadLayout upload;
+    mz::DownloadLayout download;
+    uint8_t *h_upload = nullptr, *d_upload = nullptr, *h_download = nullptr, *d_download = nullptr;
+    mz::UploadBlock h_up{}, d_up{};
+    mz::DownloadBlock h_down{}, d_down{};
     bool tie_words_applied = false;
 
     // batches of moves queued back to back (mzmcts_moves_*)
@@ -317,8 +299,7 @@ struct mzmcts_engine {
         bool add_noise = false;
         bool drawn = false;
         bool speculative = false;                    // drawn on top of a batch that was still in flight
-        uint8_t* h_in = nullptr;                     // pinned [noise M*E*A f64 | skip M*E u32 | temperature E f64 |
-                                                     //         limit E i32 | expected ties E u32]
+        uint8_t* h_in = nullptr;                     // pinned control block (MoveBatch::ctl)
         std::vector<int32_t> legal, nlegal, to_play; // [E][A], [E], [E]
         std::vector<MoveRecord> start;               // [E] mirror state before this batch's first draw
         std::vector<uint32_t> start_lag;             // [E]
@@ -340,9 +321,9 @@ struct mzmcts_engine {
         bool in_flight = false;                      // set[cur] is uploaded (prepare / submit_next) and not collected
         int cur = 0;
         ChainSet set[2];
-        size_t out_stride = 0;                       // bytes of one move's output block
-        size_t o_actions = 0, o_visits = 0, o_rvs = 0, o_pred = 0, o_depth = 0, o_ties = 0, o_sample = 0, o_dsum = 0;
-        size_t in_bytes = 0, o_skip = 0, o_temp = 0, o_limit = 0, o_expect = 0;
+        mz::MoveControlLayout ctl;                   // d_in and every ChainSet::h_in
+        mz::MoveOutputLayout out;                    // [M] blocks of d_out, h_out
+        mz::MoveInputsLayout inputs;                 // [M] blocks of d_inputs, h_inputs (device-input batches)
         uint8_t* d_in = nullptr;
         uint8_t *h_out = nullptr, *d_out = nullptr;  // [M] output blocks (h_out = h_out_set[host_set])
         // Two pinned download sets, alternating per device-input batch: a batch's blocks are downloaded move by move
@@ -361,12 +342,11 @@ struct mzmcts_engine {
         bool device_inputs = false;
         const int32_t *dev_legal = nullptr, *dev_nlegal = nullptr, *dev_to_play = nullptr;
         int inputs_capacity = 0;
-        size_t in2_stride = 0, o2_nlegal = 0, o2_to_play = 0, o2_words = 0, o2_legal = 0;
-        uint8_t *d_inputs = nullptr, *h_inputs = nullptr;   // [M] blocks: nlegal i32[E] | to_play i32[E] | noise words u32[E] | legal i32[E][A]
+        uint8_t *d_inputs = nullptr, *h_inputs = nullptr;
         // play_game's temperature threshold inside a batch (MoveCtl::game_moves): moves of each env's current game, kept
         // on the device over the batch; `finished` = the env kernels' done flags of the move before (one-shot)
         int32_t temperature_threshold = 0;
-        uint8_t* d_game_moves = nullptr;             // i32[E]
+        int32_t* d_game_moves = nullptr;             // [E]
         const uint8_t* finished = nullptr;
         bool lockstep_open = false;                  // between mzmcts_moves_begin_lockstep and mzmcts_moves_end_lockstep
         bool sit_out = false;                        // mzmcts_moves_sit_out: empty legal sets are plies the caller plays
@@ -453,11 +433,12 @@ struct ProfScope {
 };
 
 
+static_assert(sizeof(mz::MinMax) == mz::kMinMaxBytes, "staging_layout.h sizes the download block's min_max with this");
 using ChainSet = mzmcts_engine::ChainSet;
 using MoveRecord = mzmcts_engine::MoveRecord;
 
 // defined in mzmcts_capi.hip, also used by the move batches (not part of the ABI)
 __attribute__((visibility("hidden"))) bool mzhost_use_narrow(const mzmcts_engine* eng);
-__attribute__((visibility("hidden"))) int mzhost_launch_fused_move(mzmcts_engine* eng, const float* observations,
-                                                                     const mz::MoveCtl& ctl, bool hidden_in_lds,
-                                                                     hipStream_t stream);
+__attribute__((visibility("hidden"))) int mzhost_launch_fused_move(mzmcts_engine* eng, const mz::TreeParams& p,
+                                                                     const float* observations, const mz::MoveCtl& ctl,
+                                                                     bool hidden_in_lds, hipStream_t stream);

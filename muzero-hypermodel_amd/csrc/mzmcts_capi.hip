@@ -105,59 +105,18 @@ int mzmcts_create(const mzmcts_config* c, mzmcts_engine** out) {
     if ((rc = dev_alloc(eng, &p.leaf_parent, E))) return cleanup_on(rc);
     if ((rc = dev_alloc(eng, &p.leaf_loc, E))) return cleanup_on(rc);
     if ((rc = dev_alloc(eng, &p.root_reward, E))) return cleanup_on(rc);
-    {
-        // per-move upload block: [legal i32 E*A | num_legal i32 E | to_play i32 E | rng_skip u32 E | noise f64 E*A]
-        auto align8 = [](size_t v) { return (v + 7) / 8 * 8; };
-        const size_t o_legal = 0;
-        const size_t o_nlegal = o_legal + sizeof(int32_t) * static_cast<size_t>(E) * A;
-        const size_t o_to_play = o_nlegal + sizeof(int32_t) * E;
-        const size_t o_skip = o_to_play + sizeof(int32_t) * E;
-        const size_t o_noise = align8(o_skip + sizeof(uint32_t) * E);
-        eng->upload_bytes_no_noise = o_noise;
-        eng->upload_bytes = o_noise + sizeof(double) * static_cast<size_t>(E) * A;
-        if ((rc = dev_alloc(eng, &eng->d_upload, eng->upload_bytes))) return cleanup_on(rc);
-        if ((rc = pinned_alloc(eng, &eng->h_upload, eng->upload_bytes))) return cleanup_on(rc);
-        p.root_action = reinterpret_cast<int32_t*>(eng->d_upload + o_legal);
-        p.root_children = reinterpret_cast<int32_t*>(eng->d_upload + o_nlegal);
-        p.root_to_play = reinterpret_cast<int32_t*>(eng->d_upload + o_to_play);
-        eng->d_skip = reinterpret_cast<uint32_t*>(eng->d_upload + o_skip);
-        eng->d_noise = reinterpret_cast<double*>(eng->d_upload + o_noise);
-        p.noise_rows = eng->d_noise;
-        eng->h_legal = reinterpret_cast<int32_t*>(eng->h_upload + o_legal);
-        eng->h_nlegal = reinterpret_cast<int32_t*>(eng->h_upload + o_nlegal);
-        eng->h_to_play = reinterpret_cast<int32_t*>(eng->h_upload + o_to_play);
-        eng->h_skip = reinterpret_cast<uint32_t*>(eng->h_upload + o_skip);
-        eng->h_noise = reinterpret_cast<double*>(eng->h_upload + o_noise);
-        // per-tree download block: [root_value_sum f64 E | min_max 2xf64 E | depth_sum i64 E |
-        //                           root_predicted f32 E | max_depth i32 E | tie_words u32 E | error_flag i32 x4]
-        const size_t o_rvs = 0;
-        const size_t o_mm = o_rvs + sizeof(double) * E;
-        const size_t o_ds = o_mm + sizeof(mz::MinMax) * E;
-        const size_t o_pred = o_ds + sizeof(int64_t) * E;
-        const size_t o_md = o_pred + sizeof(float) * E;
-        const size_t o_tw = o_md + sizeof(int32_t) * E;
-        const size_t o_nw = o_tw + sizeof(uint32_t) * E;
-        const size_t o_err = o_nw + sizeof(uint32_t) * E;
-        eng->download_bytes = o_err + sizeof(int32_t) * 4;
-        if ((rc = dev_alloc(eng, &eng->d_download, eng->download_bytes))) return cleanup_on(rc);
-        if ((rc = pinned_alloc(eng, &eng->h_download, eng->download_bytes))) return cleanup_on(rc);
-        p.root_value_sum = reinterpret_cast<double*>(eng->d_download + o_rvs);
-        p.min_max = reinterpret_cast<mz::MinMax*>(eng->d_download + o_mm);
-        p.depth_sum = reinterpret_cast<int64_t*>(eng->d_download + o_ds);
-        p.root_predicted = reinterpret_cast<float*>(eng->d_download + o_pred);
-        p.max_depth = reinterpret_cast<int32_t*>(eng->d_download + o_md);
-        p.tie_words = reinterpret_cast<uint32_t*>(eng->d_download + o_tw);
-        p.noise_words = reinterpret_cast<uint32_t*>(eng->d_download + o_nw);
-        p.error_flag = reinterpret_cast<int32_t*>(eng->d_download + o_err);
-        eng->h_root_value_sum = reinterpret_cast<double*>(eng->h_download + o_rvs);
-        eng->h_min_max = reinterpret_cast<mz::MinMax*>(eng->h_download + o_mm);
-        eng->h_depth_sum = reinterpret_cast<int64_t*>(eng->h_download + o_ds);
-        eng->h_root_predicted = reinterpret_cast<float*>(eng->h_download + o_pred);
-        eng->h_max_depth = reinterpret_cast<int32_t*>(eng->h_download + o_md);
-        eng->h_tie_words = reinterpret_cast<uint32_t*>(eng->h_download + o_tw);
-        eng->h_noise_words = reinterpret_cast<uint32_t*>(eng->h_download + o_nw);
-        eng->h_error_flag = reinterpret_cast<int32_t*>(eng->h_download + o_err);
-    }
+    // the per-move upload and per-tree download blocks (staging_layout.h); the kernels read and write the device copies
+    eng->upload = mz::UploadLayout(E, A), eng->download = mz::DownloadLayout(E);
+    if ((rc = dev_alloc(eng, &eng->d_upload, eng->upload.bytes))) return cleanup_on(rc);
+    if ((rc = pinned_alloc(eng, &eng->h_upload, eng->upload.bytes))) return cleanup_on(rc);
+    if ((rc = dev_alloc(eng, &eng->d_download, eng->download.bytes))) return cleanup_on(rc);
+    if ((rc = pinned_alloc(eng, &eng->h_download, eng->download.bytes))) return cleanup_on(rc);
+    eng->h_up = eng->upload.views(eng->h_upload), eng->d_up = eng->upload.views(eng->d_upload);
+    eng->h_down = eng->download.views(eng->h_download), eng->d_down = eng->download.views(eng->d_download);
+    p.root_action = eng->d_up.legal, p.root_children = eng->d_up.num_legal, p.root_to_play = eng->d_up.to_play, p.noise_rows = eng->d_up.noise;
+    p.root_value_sum = eng->d_down.root_value_sum, p.min_max = eng->d_down.min_max, p.depth_sum = eng->d_down.depth_sum;
+    p.root_predicted = eng->d_down.root_predicted, p.max_depth = eng->d_down.max_depth, p.tie_words = eng->d_down.tie_words;
+    p.noise_words = eng->d_down.noise_words, p.error_flag = eng->d_down.error_flag;
     if ((rc = dev_alloc(eng, &p.mt_key, static_cast<size_t>(E) * mz::kMtN))) return cleanup_on(rc);
     if ((rc = dev_alloc(eng, &p.mt_pos, E))) return cleanup_on(rc);
     if ((rc = dev_alloc(eng, &eng->d_seeds, E))) return cleanup_on(rc);
@@ -326,18 +285,18 @@ int mzmcts_begin_search(mzmcts_engine* eng, const int32_t* legal, const int32_t*
     const bool trace = std::getenv("MZMCTS_TRACE") != nullptr;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = trace ? now() : 0.0;
-    std::memcpy(eng->h_legal, legal, sizeof(int32_t) * static_cast<size_t>(E) * A);
-    std::memcpy(eng->h_nlegal, num_legal, sizeof(int32_t) * E);
-    std::memcpy(eng->h_to_play, to_play, sizeof(int32_t) * E);
+    std::memcpy(eng->h_up.legal, legal, sizeof(int32_t) * static_cast<size_t>(E) * A);
+    std::memcpy(eng->h_up.num_legal, num_legal, sizeof(int32_t) * E);
+    std::memcpy(eng->h_up.to_play, to_play, sizeof(int32_t) * E);
     const double alpha = eng->cfg.root_dirichlet_alpha;
     const bool on_device = add_noise && eng->device_noise;   // root_noise_kernel draws the rows, below
     eng->for_each_env([&](int lo, int hi) {
         for (int e = lo; e < hi; ++e) {
-            const int n = eng->h_nlegal[e];
-            double* row = eng->h_noise + static_cast<size_t>(e) * A;
+            const int n = eng->h_up.num_legal[e];
+            double* row = eng->h_up.noise + static_cast<size_t>(e) * A;
             for (int i = 0; i < A; ++i) row[i] = 0.0;
             if (n == 0) {
-                eng->h_skip[e] = 0;  // inactive: the stream is left alone, pending lag is kept
+                eng->h_up.rng_skip[e] = 0;  // inactive: the stream is left alone, pending lag is kept
                 continue;
             }
             if (add_noise && !on_device) {
@@ -346,17 +305,17 @@ int mzmcts_begin_search(mzmcts_engine* eng, const int32_t* legal, const int32_t*
                 s.dirichlet(alpha, n, row);
                 eng->lag[e] += static_cast<uint32_t>(s.words - before);
             }
-            eng->h_skip[e] = eng->lag[e];
+            eng->h_up.rng_skip[e] = eng->lag[e];
             eng->lag[e] = 0;
         }
     });
     const double t_dirichlet = trace ? now() : 0.0;
-    if (noise_out) std::memcpy(noise_out, eng->h_noise, sizeof(double) * static_cast<size_t>(E) * A);
+    if (noise_out) std::memcpy(noise_out, eng->h_up.noise, sizeof(double) * static_cast<size_t>(E) * A);
     eng->noise_this_search = add_noise != 0;
     MZ_HIP(eng, hipMemcpyAsync(eng->d_upload, eng->h_upload,
-                               (add_noise && !on_device) ? eng->upload_bytes : eng->upload_bytes_no_noise,
+                               (add_noise && !on_device) ? eng->upload.bytes : eng->upload.bytes_no_noise(),
                                hipMemcpyHostToDevice, stream));
-    if (on_device) MZ_HIP(eng, mz::launch_root_noise(eng->p, eng->d_skip, stream));
+    if (on_device) MZ_HIP(eng, mz::launch_root_noise(eng->p, eng->d_up.rng_skip, stream));
     eng->noise_on_device = on_device;
     if (trace)
         std::fprintf(stderr, "[mzmcts] begin_search E=%d: host prep+dirichlet %.1f us, memcpy+enqueue %.1f us\n", E,
@@ -377,8 +336,8 @@ static int expand_roots_common(mzmcts_engine* eng, const float* value_logits, co
     {
         ProfScope scope(eng, stream, kProfRoot);
         MZ_HIP(eng, mz::launch_expand_roots(eng->p, value_logits, reward_logits, policy_logits, root_hidden, inj_reward,
-                                            inj_priors, eng->noise_this_search ? eng->d_noise : nullptr,
-                                            eng->skip_applied ? nullptr : eng->d_skip, injected, stream, scope.get()));
+                                            inj_priors, eng->noise_this_search ? eng->d_up.noise : nullptr,
+                                            eng->skip_applied ? nullptr : eng->d_up.rng_skip, injected, stream, scope.get()));
     }
     eng->roots_ready = true;
     eng->tree_published = true;
@@ -541,9 +500,9 @@ int mzmcts_set_simulations_done(mzmcts_engine* eng, int32_t n) {
 static int enqueue_readout_copies(mzmcts_engine* eng, hipStream_t stream) {
     const mz::TreeParams& p = eng->p;
     MZ_HIP(eng, hipMemcpyAsync(eng->h_slab0, p.blocks, static_cast<size_t>(p.E) * p.line_stride, hipMemcpyDeviceToHost, stream));
-    MZ_HIP(eng, hipMemcpyAsync(eng->h_download, eng->d_download, eng->download_bytes, hipMemcpyDeviceToHost, stream));
+    MZ_HIP(eng, hipMemcpyAsync(eng->h_download, eng->d_download, eng->download.bytes, hipMemcpyDeviceToHost, stream));
     if (eng->noise_on_device)   // the rows the device drew (what mzmcts_begin_search's noise_out holds for a host draw)
-        MZ_HIP(eng, hipMemcpyAsync(eng->h_noise, eng->d_noise, sizeof(double) * static_cast<size_t>(p.E) * p.A,
+        MZ_HIP(eng, hipMemcpyAsync(eng->h_up.noise, eng->d_up.noise, sizeof(double) * static_cast<size_t>(p.E) * p.A,
                                    hipMemcpyDeviceToHost, stream));
     return MZMCTS_OK;
 }
@@ -574,9 +533,9 @@ int mzmcts_readout(mzmcts_engine* eng, const mzmcts_root_stats* out, void* strea
         if (rc) return rc;
         MZ_HIP(eng, hipStreamSynchronize(stream));
     }
-    if (eng->h_error_flag[0] != 0)
+    if (eng->h_down.error_flag[0] != 0)
         return fail(eng, MZMCTS_ERR_INVALID,
-                    (eng->h_error_flag[0] & 2) ? "device error flag set: tree links are inconsistent (descent ran past the "
+                    (eng->h_down.error_flag[0] & 2) ? "device error flag set: tree links are inconsistent (descent ran past the "
                                                  "number of expanded nodes)"
                                                : "device error flag set: a UCB score was NaN (no maximum to select)");
 
@@ -588,7 +547,7 @@ int mzmcts_readout(mzmcts_engine* eng, const mzmcts_root_stats* out, void* strea
         for (int e = lo; e < hi; ++e) {
             const uint8_t* blk = eng->h_slab0 + static_cast<size_t>(e) * p.line_stride;   // the root's block: half 0 of line (0, e)
             const mz::HbmChild* rec = reinterpret_cast<const mz::HbmChild*>(blk);
-            const int n = eng->h_nlegal[e];
+            const int n = eng->h_up.num_legal[e];
             const bool is_active = n > 0;
             for (int i = 0; i < A; ++i) {
                 const size_t o = static_cast<size_t>(e) * A + i;
@@ -602,26 +561,26 @@ int mzmcts_readout(mzmcts_engine* eng, const mzmcts_root_stats* out, void* strea
                     if (out->child_expanded) out->child_expanded[o] = (live && rec[i].links.child_node >= 0) ? 1 : 0;
                 }
             }
-            eng->last_root_value_sum[e] = is_active ? eng->h_root_value_sum[e] : 0.0;
+            eng->last_root_value_sum[e] = is_active ? eng->h_down.root_value_sum[e] : 0.0;
             eng->last_root_visits[e] = is_active ? sims : 0;
             if (is_active) {
                 // the tie-breaks ran on the device copy of the stream: bring the host mirror level (once)
                 // (and, when the device drew this search's exploration noise, the Dirichlet draw before them)
-                if (first) eng->mirror(e).skip((eng->noise_on_device ? eng->h_noise_words[e] : 0u) + eng->h_tie_words[e]);
-                local_depth += eng->h_depth_sum[e];
+                if (first) eng->mirror(e).skip((eng->noise_on_device ? eng->h_down.noise_words[e] : 0u) + eng->h_down.tie_words[e]);
+                local_depth += eng->h_down.depth_sum[e];
                 ++local_active;
             }
             if (out) {
                 if (out->root_value_sum) out->root_value_sum[e] = eng->last_root_value_sum[e];
                 if (out->root_visits) out->root_visits[e] = eng->last_root_visits[e];
-                if (out->max_tree_depth) out->max_tree_depth[e] = is_active ? eng->h_max_depth[e] : 0;
-                if (out->root_predicted_value) out->root_predicted_value[e] = static_cast<double>(eng->h_root_predicted[e]);
+                if (out->max_tree_depth) out->max_tree_depth[e] = is_active ? eng->h_down.max_depth[e] : 0;
+                if (out->root_predicted_value) out->root_predicted_value[e] = static_cast<double>(eng->h_down.root_predicted[e]);
                 if (out->min_max) {
-                    out->min_max[2 * e] = eng->h_min_max[e].minimum;
-                    out->min_max[2 * e + 1] = eng->h_min_max[e].maximum;
+                    out->min_max[2 * e] = eng->h_down.min_max[e].minimum;
+                    out->min_max[2 * e + 1] = eng->h_down.min_max[e].maximum;
                 }
-                if (out->depth_sum) out->depth_sum[e] = is_active ? eng->h_depth_sum[e] : 0;
-                if (out->tie_break_words) out->tie_break_words[e] = is_active ? eng->h_tie_words[e] : 0u;
+                if (out->depth_sum) out->depth_sum[e] = is_active ? eng->h_down.depth_sum[e] : 0;
+                if (out->tie_break_words) out->tie_break_words[e] = is_active ? eng->h_down.tie_words[e] : 0u;
             }
         }
         depth_total.fetch_add(local_depth, std::memory_order_relaxed);
@@ -643,7 +602,7 @@ int mzmcts_sample_actions(mzmcts_engine* eng, const double* temperature, int32_t
     const int E = eng->p.E, A = eng->p.A;
     eng->for_each_env([&](int lo, int hi) {
         for (int e = lo; e < hi; ++e) {
-            const int n = eng->h_nlegal[e];
+            const int n = eng->h_up.num_legal[e];
             if (n == 0) {
                 action_out[e] = -1;
                 if (slot_out) slot_out[e] = -1;
@@ -653,7 +612,7 @@ int mzmcts_sample_actions(mzmcts_engine* eng, const double* temperature, int32_t
             const uint64_t before = s.words;
             const int slot = s.select_action(eng->last_visits.data() + static_cast<size_t>(e) * A, n, temperature[e]);
             eng->lag[e] += static_cast<uint32_t>(s.words - before);
-            action_out[e] = eng->h_legal[static_cast<size_t>(e) * A + slot];
+            action_out[e] = eng->h_up.legal[static_cast<size_t>(e) * A + slot];
             if (slot_out) slot_out[e] = slot;
         }
     });
@@ -668,11 +627,11 @@ int mzmcts_search_statistics(mzmcts_engine* eng, double* child_visits, double* r
     for (int e = 0; e < E; ++e) {
         double* row = child_visits + static_cast<size_t>(e) * A;
         for (int a = 0; a < A; ++a) row[a] = 0.0;
-        const int n = eng->h_nlegal[e];
+        const int n = eng->h_up.num_legal[e];
         int total = 0;
         for (int i = 0; i < n; ++i) total += eng->last_visits[static_cast<size_t>(e) * A + i];
         for (int i = 0; i < n; ++i)
-            row[eng->h_legal[static_cast<size_t>(e) * A + i]] =
+            row[eng->h_up.legal[static_cast<size_t>(e) * A + i]] =
                 static_cast<double>(eng->last_visits[static_cast<size_t>(e) * A + i]) / total;
         const int rv = eng->last_root_visits[e];
         root_values[e] = rv == 0 ? 0.0 : eng->last_root_value_sum[e] / rv;
@@ -707,7 +666,7 @@ int mzmcts_last_paths(mzmcts_engine* eng, int32_t* depth, int32_t* actions, int3
             const size_t o = static_cast<size_t>(e) * S + d;
             if (d < depth[e]) {
                 const int slot = path[static_cast<size_t>(d) * E + e] & 0xff;
-                if (actions) actions[o] = (d == 0) ? eng->h_legal[static_cast<size_t>(e) * A + slot] : slot;
+                if (actions) actions[o] = (d == 0) ? eng->h_up.legal[static_cast<size_t>(e) * A + slot] : slot;
                 if (tie_counts) tie_counts[o] = ties.empty() ? -1 : ties[static_cast<size_t>(d) * E + e];
             } else {
                 if (actions) actions[o] = -1;
@@ -733,7 +692,7 @@ int mzmcts_export_tree(mzmcts_engine* eng, int32_t env, int32_t* visits, double*
                                  static_cast<size_t>(p.E) * p.line_stride, p.line_stride, K, hipMemcpyDeviceToHost,
                                  stream));
     MZ_HIP(eng, hipStreamSynchronize(stream));
-    const int n_root = eng->h_nlegal[env];
+    const int n_root = eng->h_up.num_legal[env];
     std::vector<int32_t> loc_of(static_cast<size_t>(K), -1);
     loc_of[0] = 0;
     for (int k = 0; k < K; ++k) {
@@ -860,28 +819,28 @@ int64_t mzmcts_fused_lds_bytes(mzmcts_engine* eng, int32_t hidden_in_lds) {
 
 }  // extern "C"
 
-// One whole-move kernel (narrow or generic, see mzhost_use_narrow) with the given per-move control block.
-int mzhost_launch_fused_move(mzmcts_engine* eng, const float* observations, const mz::MoveCtl& ctl, bool hidden_in_lds,
-                             hipStream_t stream) {
+// One whole-move kernel (narrow or generic, see mzhost_use_narrow) with the given per-move control block, on the trees and
+// root inputs of `p` (the engine's own TreeParams, or a copy that reads the caller's device arrays).
+int mzhost_launch_fused_move(mzmcts_engine* eng, const mz::TreeParams& p, const float* observations, const mz::MoveCtl& ctl,
+                             bool hidden_in_lds, hipStream_t stream) {
     if (mzhost_use_narrow(eng)) {
         mz::NarrowLayout nl{};
-        mz::plan_narrow_layout(eng->p, eng->fc, kLdsPerWorkgroup, &nl);
+        mz::plan_narrow_layout(p, eng->fc, kLdsPerWorkgroup, &nl);
         nl.row_rng = eng->narrow_row_rng ? 1 : 0;
         nl.prefetch = eng->narrow_prefetch ? 1 : 0;
         nl.generic_shape = eng->narrow_generic_shape ? 1 : 0;
         nl.pbc2_table = eng->narrow_table[nl.pbc2_mode];
         ProfScope scope(eng, stream, kProfFused);
-        MZ_HIP(eng, mz::launch_search_fused_narrow(eng->p, eng->fc, nl, eng->fc_weights, observations, ctl, eng->p.S,
+        MZ_HIP(eng, mz::launch_search_fused_narrow(p, eng->fc, nl, eng->fc_weights, observations, ctl, p.S,
                                                    eng->publish_tree ? 1 : 0, stream, scope.get()));
         eng->tree_published = eng->publish_tree;
     } else {
         mz::FusedLayout lay{};
-        if (!mz::plan_fused_layout(eng->p, eng->fc, hidden_in_lds, kLdsPerWorkgroup, &lay))
+        if (!mz::plan_fused_layout(p, eng->fc, hidden_in_lds, kLdsPerWorkgroup, &lay))
             return fail(eng, MZMCTS_ERR_INVALID, "fused search: the trees of one workgroup do not fit in 160 KB of LDS (use a "
                                                  "wider group_width or the lock-step path)");
         ProfScope scope(eng, stream, kProfFused);
-        MZ_HIP(eng, mz::launch_search_fused_fc(eng->p, eng->fc, lay, eng->fc_weights, observations, ctl, eng->p.S, stream,
-                                               scope.get()));
+        MZ_HIP(eng, mz::launch_search_fused_fc(p, eng->fc, lay, eng->fc_weights, observations, ctl, p.S, stream, scope.get()));
         eng->tree_published = true;
     }
     return MZMCTS_OK;
@@ -895,9 +854,9 @@ int mzmcts_search_fused_fc(mzmcts_engine* eng, const float* observations, int32_
     if (!eng->search_begun) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_search_fused_fc called before begin_search");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     mz::MoveCtl ctl{};
-    ctl.noise = eng->noise_this_search ? eng->d_noise : nullptr;
-    ctl.rng_skip = eng->d_skip;
-    int rc = mzhost_launch_fused_move(eng, observations, ctl, hidden_in_lds != 0, stream);
+    ctl.noise = eng->noise_this_search ? eng->d_up.noise : nullptr;
+    ctl.rng_skip = eng->d_up.rng_skip;
+    int rc = mzhost_launch_fused_move(eng, eng->p, observations, ctl, hidden_in_lds != 0, stream);
     if (rc) return rc;
     eng->roots_ready = true;
     eng->sim = eng->p.S;
@@ -943,7 +902,7 @@ int mzmcts_get_noise(mzmcts_engine* eng, double* noise_out) {
     if (!eng || !noise_out) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_get_noise: null argument");
     if (eng->noise_on_device && !eng->have_readout)
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_get_noise: device-drawn rows reach the host with mzmcts_readout");
-    std::memcpy(noise_out, eng->h_noise, sizeof(double) * static_cast<size_t>(eng->p.E) * eng->p.A);
+    std::memcpy(noise_out, eng->h_up.noise, sizeof(double) * static_cast<size_t>(eng->p.E) * eng->p.A);
     return MZMCTS_OK;
 }
 

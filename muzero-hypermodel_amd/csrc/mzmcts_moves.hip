@@ -56,33 +56,19 @@ static int ensure_batch_capacity(mzmcts_engine* eng, int n_moves) {
     if (b.in_flight || b.set[0].drawn || b.set[1].drawn)
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves: a larger batch needs new buffers; collect the batches in flight first");
     const size_t E = static_cast<size_t>(eng->p.E), A = static_cast<size_t>(eng->p.A), M = static_cast<size_t>(n_moves);
-    auto align = [](size_t v) { return (v + 255) / 256 * 256; };
-    b.o_skip = align(sizeof(double) * M * E * A);
-    b.o_temp = align(b.o_skip + sizeof(uint32_t) * M * E);
-    b.o_limit = align(b.o_temp + sizeof(double) * E);
-    b.o_expect = align(b.o_limit + sizeof(int32_t) * E);
-    b.in_bytes = align(b.o_expect + sizeof(uint32_t) * E);
-    b.o_actions = 0;
-    b.o_visits = align(sizeof(int32_t) * E);
-    b.o_rvs = align(b.o_visits + sizeof(int32_t) * E * A);
-    b.o_pred = align(b.o_rvs + sizeof(double) * E);
-    b.o_depth = align(b.o_pred + sizeof(float) * E);
-    b.o_ties = align(b.o_depth + sizeof(int32_t) * E);
-    b.o_sample = align(b.o_ties + sizeof(uint32_t) * E);
-    b.o_dsum = align(b.o_sample + sizeof(uint32_t) * E);
-    b.out_stride = align(b.o_dsum + sizeof(int32_t) * E);
+    b.ctl = mz::MoveControlLayout(E, A, M), b.out = mz::MoveOutputLayout(E, A);
     int rc;  // (earlier, smaller buffers stay registered with the engine and are freed with it)
-    if ((rc = dev_alloc(eng, &b.d_in, b.in_bytes))) return rc;
-    if ((rc = dev_alloc(eng, &b.d_out, b.out_stride * M))) return rc;
+    if ((rc = dev_alloc(eng, &b.d_in, b.ctl.bytes))) return rc;
+    if ((rc = dev_alloc(eng, &b.d_out, b.out.stride * M))) return rc;
     for (int q = 0; q < 2; ++q)
-        if ((rc = pinned_alloc(eng, &b.h_out_set[q], b.out_stride * M))) return rc;
+        if ((rc = pinned_alloc(eng, &b.h_out_set[q], b.out.stride * M))) return rc;
     b.h_out = b.h_out_set[b.host_set];
     if (!b.d_stall && (rc = dev_alloc(eng, &b.d_stall, E))) return rc;
     if (!b.done) MZ_HIP(eng, hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
     if (!b.move_done) MZ_HIP(eng, hipEventCreateWithFlags(&b.move_done, hipEventDisableTiming));
     if (!b.copy_stream) MZ_HIP(eng, hipStreamCreateWithFlags(&b.copy_stream, hipStreamNonBlocking));
     for (ChainSet& c : b.set) {
-        if ((rc = pinned_alloc(eng, &c.h_in, b.in_bytes))) return rc;
+        if ((rc = pinned_alloc(eng, &c.h_in, b.ctl.bytes))) return rc;
         c.legal.assign(E * A, 0);
         c.nlegal.assign(E, 0);
         c.to_play.assign(E, 0);
@@ -100,8 +86,8 @@ static int ensure_batch_capacity(mzmcts_engine* eng, int n_moves) {
     b.capacity = n_moves;
     // Run both transfers once at full size: the runtime sets up its large-copy path on first use (tens of
     // milliseconds), which would otherwise land in the first full-size batch.
-    MZ_HIP(eng, hipMemcpy(b.d_in, b.set[0].h_in, b.in_bytes, hipMemcpyHostToDevice));
-    for (int q = 0; q < 2; ++q) MZ_HIP(eng, hipMemcpy(b.h_out_set[q], b.d_out, b.out_stride * M, hipMemcpyDeviceToHost));
+    MZ_HIP(eng, hipMemcpy(b.d_in, b.set[0].h_in, b.ctl.bytes, hipMemcpyHostToDevice));
+    for (int q = 0; q < 2; ++q) MZ_HIP(eng, hipMemcpy(b.h_out_set[q], b.d_out, b.out.stride * M, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -174,21 +160,16 @@ static uint32_t assumed_tie_words(int n) { return n > 1 ? 1u : 0u; }
 // previous batch's last noise row and that batch has not finished -- first step over what its last move is
 // assumed to consume.  Returns false (nothing drawn) when that cannot be known in advance.
 static bool draw_env_rows(mzmcts_engine* eng, ChainSet& c, int e, bool tail, const ChainSet* under) {
-    mzmcts_engine::MoveBatch& b = eng->batch;
     const int E = eng->p.E, A = eng->p.A, n_moves = c.n_moves;
     const size_t EA = static_cast<size_t>(E) * A;
-    double* h_noise = reinterpret_cast<double*>(c.h_in);
-    uint32_t* h_skip = reinterpret_cast<uint32_t*>(c.h_in + b.o_skip);
-    double* h_temp = reinterpret_cast<double*>(c.h_in + b.o_temp);
-    int32_t* h_limit = reinterpret_cast<int32_t*>(c.h_in + b.o_limit);
-    uint32_t* h_expect = reinterpret_cast<uint32_t*>(c.h_in + b.o_expect);
+    const mz::MoveControlBlock h = eng->batch.ctl.views(c.h_in);
     const int n = c.nlegal[e];
     const double t = c.temperature[e];
     const int assumed = assumed_sample_words(t);
     const uint32_t tie_words = assumed_tie_words(n);
-    h_temp[e] = kernel_temperature(eng, t);
-    h_limit[e] = (n == 0) ? 0 : (assumed < 0 ? 1 : n_moves);
-    h_expect[e] = tie_words;
+    h.temperature[e] = kernel_temperature(eng, t);
+    h.move_limit[e] = (n == 0) ? 0 : (assumed < 0 ? 1 : n_moves);
+    h.expected_ties[e] = tie_words;
     c.env_twisted[e] = 0;
     c.deferred[e] = 0;
     mz::HostStream& s = eng->mirror(e);
@@ -198,10 +179,10 @@ static bool draw_env_rows(mzmcts_engine* eng, ChainSet& c, int e, bool tail, con
         const int under_sample = assumed_sample_words(under->temperature[e]);
         if (under_n > 0 && under_sample < 0) {  // the batch underneath samples at T = inf: draw these rows at collect()
             c.deferred[e] = 1;
-            h_limit[e] = 0;
+            h.move_limit[e] = 0;
             for (int m = 0; m < n_moves; ++m) {
-                h_skip[static_cast<size_t>(m) * E + e] = 0;
-                for (int i = 0; i < A; ++i) h_noise[static_cast<size_t>(m) * EA + static_cast<size_t>(e) * A + i] = 0.0;
+                h.rng_skip[static_cast<size_t>(m) * E + e] = 0;
+                for (int i = 0; i < A; ++i) h.noise[static_cast<size_t>(m) * EA + static_cast<size_t>(e) * A + i] = 0.0;
             }
             return false;
         }
@@ -220,16 +201,16 @@ static bool draw_env_rows(mzmcts_engine* eng, ChainSet& c, int e, bool tail, con
     }
     const double alpha = eng->cfg.root_dirichlet_alpha;
     for (int m = 0; m < n_moves; ++m) {
-        double* row = h_noise + static_cast<size_t>(m) * EA + static_cast<size_t>(e) * A;
+        double* row = h.noise + static_cast<size_t>(m) * EA + static_cast<size_t>(e) * A;
         for (int i = 0; i < A; ++i) row[i] = 0.0;
         uint32_t skip = 0;
-        if (n > 0 && m < h_limit[e]) {
+        if (n > 0 && m < h.move_limit[e]) {
             if (m > 0) s.skip(static_cast<uint64_t>(tie_words) + static_cast<uint64_t>(assumed));
             const uint64_t before = s.words;
             if (c.add_noise) s.dirichlet(alpha, n, row);
             skip = static_cast<uint32_t>(s.words - before) + (m == 0 ? lag0 : 0u);
         }
-        h_skip[static_cast<size_t>(m) * E + e] = skip;
+        h.rng_skip[static_cast<size_t>(m) * E + e] = skip;
         c.rec[static_cast<size_t>(m) * E + e] = MoveRecord{s.pos, s.has_gauss, s.gauss, s.words};
     }
     if (n > 0) eng->lag[e] = 0;
@@ -254,11 +235,11 @@ static void fill_set(mzmcts_engine* eng, ChainSet& c, int32_t n_moves, const int
 static int upload_set(mzmcts_engine* eng, ChainSet& c, hipStream_t stream) {
     mzmcts_engine::MoveBatch& b = eng->batch;
     const int E = eng->p.E, A = eng->p.A;
-    std::memcpy(eng->h_legal, c.legal.data(), sizeof(int32_t) * static_cast<size_t>(E) * A);
-    std::memcpy(eng->h_nlegal, c.nlegal.data(), sizeof(int32_t) * E);
-    std::memcpy(eng->h_to_play, c.to_play.data(), sizeof(int32_t) * E);
-    MZ_HIP(eng, hipMemcpyAsync(eng->d_upload, eng->h_upload, eng->upload_bytes_no_noise, hipMemcpyHostToDevice, stream));
-    MZ_HIP(eng, hipMemcpyAsync(b.d_in, c.h_in, b.in_bytes, hipMemcpyHostToDevice, stream));
+    std::memcpy(eng->h_up.legal, c.legal.data(), sizeof(int32_t) * static_cast<size_t>(E) * A);
+    std::memcpy(eng->h_up.num_legal, c.nlegal.data(), sizeof(int32_t) * E);
+    std::memcpy(eng->h_up.to_play, c.to_play.data(), sizeof(int32_t) * E);
+    MZ_HIP(eng, hipMemcpyAsync(eng->d_upload, eng->h_upload, eng->upload.bytes_no_noise(), hipMemcpyHostToDevice, stream));
+    MZ_HIP(eng, hipMemcpyAsync(b.d_in, c.h_in, b.ctl.bytes, hipMemcpyHostToDevice, stream));
     if (c.general) MZ_HIP(eng, hipMemcpyAsync(b.d_general_t, c.h_general_t, sizeof(double) * static_cast<size_t>(E), hipMemcpyHostToDevice, stream));
     MZ_HIP(eng, hipMemsetAsync(b.d_stall, 0, static_cast<size_t>(E), stream));
     b.enqueued = 0;
@@ -295,17 +276,11 @@ int mzmcts_moves_prepare(mzmcts_engine* eng, int32_t n_moves, const int32_t* leg
 static int ensure_inputs_capacity(mzmcts_engine* eng, int n_moves) {
     mzmcts_engine::MoveBatch& b = eng->batch;
     if (n_moves <= b.inputs_capacity) return 0;
-    const size_t E = static_cast<size_t>(eng->p.E), A = static_cast<size_t>(eng->p.A);
-    auto align = [](size_t v) { return (v + 255) / 256 * 256; };
-    b.o2_nlegal = 0;
-    b.o2_to_play = align(sizeof(int32_t) * E);
-    b.o2_words = align(b.o2_to_play + sizeof(int32_t) * E);
-    b.o2_legal = align(b.o2_words + sizeof(uint32_t) * E);
-    b.in2_stride = align(b.o2_legal + sizeof(int32_t) * E * A);
+    b.inputs = mz::MoveInputsLayout(static_cast<size_t>(eng->p.E), static_cast<size_t>(eng->p.A));
     int rc;
-    if ((rc = dev_alloc(eng, &b.d_inputs, b.in2_stride * static_cast<size_t>(n_moves)))) return rc;
+    if ((rc = dev_alloc(eng, &b.d_inputs, b.inputs.stride * static_cast<size_t>(n_moves)))) return rc;
     for (int q = 0; q < 2; ++q)
-        if ((rc = pinned_alloc(eng, &b.h_inputs_set[q], b.in2_stride * static_cast<size_t>(n_moves)))) return rc;
+        if ((rc = pinned_alloc(eng, &b.h_inputs_set[q], b.inputs.stride * static_cast<size_t>(n_moves)))) return rc;
     b.h_inputs = b.h_inputs_set[b.host_set];
     b.inputs_capacity = n_moves;
     return 0;
@@ -348,16 +323,17 @@ int mzmcts_moves_prepare_device(mzmcts_engine* eng, int32_t n_moves, const int32
     if ((rc = stage_general_temperatures(eng, c))) return rc;
     // control block: words the mirrors consumed since the device copies last moved (move 0 steps over them), the
     // temperatures, a move limit of the whole batch; no noise rows, no assumed tie-break counts
-    uint32_t* skip = reinterpret_cast<uint32_t*>(c.h_in + b.o_skip);
-    std::memset(skip, 0, sizeof(uint32_t) * static_cast<size_t>(n_moves) * E);
+    const mz::MoveControlBlock h = b.ctl.views(c.h_in);
+    std::memset(h.rng_skip, 0, sizeof(uint32_t) * static_cast<size_t>(n_moves) * E);
     for (int e = 0; e < E; ++e) {
-        skip[e] = eng->lag[e];
+        h.rng_skip[e] = eng->lag[e];
         eng->lag[e] = 0;
-        reinterpret_cast<int32_t*>(c.h_in + b.o_limit)[e] = n_moves;
-        reinterpret_cast<uint32_t*>(c.h_in + b.o_expect)[e] = 0u;
+        h.move_limit[e] = n_moves;
+        h.expected_ties[e] = 0u;
+        h.temperature[e] = kernel_temperature(eng, temperature[e]);
     }
-    for (int e = 0; e < E; ++e) reinterpret_cast<double*>(c.h_in + b.o_temp)[e] = kernel_temperature(eng, temperature[e]);
-    MZ_HIP(eng, hipMemcpyAsync(b.d_in + b.o_skip, c.h_in + b.o_skip, b.in_bytes - b.o_skip, hipMemcpyHostToDevice, stream));
+    // (everything behind the noise rows, one range: staging_layout.h)
+    MZ_HIP(eng, hipMemcpyAsync(b.d_in + b.ctl.rng_skip, c.h_in + b.ctl.rng_skip, b.ctl.bytes - b.ctl.rng_skip, hipMemcpyHostToDevice, stream));
     if (c.general) MZ_HIP(eng, hipMemcpyAsync(b.d_general_t, c.h_general_t, sizeof(double) * static_cast<size_t>(E), hipMemcpyHostToDevice, stream));
     MZ_HIP(eng, hipMemsetAsync(b.d_stall, 0, static_cast<size_t>(E), stream));
     b.enqueued = 0;
@@ -385,10 +361,10 @@ int mzmcts_moves_inputs(mzmcts_engine* eng, int32_t* num_legal, int32_t* legal, 
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_inputs: collect a mzmcts_moves_prepare_device batch first");
     const size_t E = static_cast<size_t>(eng->p.E), A = static_cast<size_t>(eng->p.A);
     for (int m = 0; m < b.enqueued; ++m) {
-        const uint8_t* blk = b.h_inputs + b.in2_stride * static_cast<size_t>(m);
-        if (num_legal) std::memcpy(num_legal + m * E, blk + b.o2_nlegal, sizeof(int32_t) * E);
-        if (to_play) std::memcpy(to_play + m * E, blk + b.o2_to_play, sizeof(int32_t) * E);
-        if (legal) std::memcpy(legal + m * E * A, blk + b.o2_legal, sizeof(int32_t) * E * A);
+        const mz::MoveInputsBlock in = b.inputs.views(b.h_inputs, static_cast<size_t>(m));
+        if (num_legal) std::memcpy(num_legal + m * E, in.num_legal, sizeof(int32_t) * E);
+        if (to_play) std::memcpy(to_play + m * E, in.to_play, sizeof(int32_t) * E);
+        if (legal) std::memcpy(legal + m * E * A, in.legal, sizeof(int32_t) * E * A);
     }
     return MZMCTS_OK;
 }
@@ -446,6 +422,42 @@ int mzmcts_moves_discard_next(mzmcts_engine* eng) {
     return MZMCTS_OK;
 }
 
+// The engine's TreeParams with the root inputs read from the caller's device arrays (device-input batches).
+static mz::TreeParams device_inputs_view(const mzmcts_engine* eng) {
+    mz::TreeParams view = eng->p;
+    view.root_action = const_cast<int32_t*>(eng->batch.dev_legal), view.root_children = const_cast<int32_t*>(eng->batch.dev_nlegal);
+    view.root_to_play = const_cast<int32_t*>(eng->batch.dev_to_play);
+    return view;
+}
+
+// move_inputs_kernel for move m of a device-input batch: records what the move is searched with in block m of the inputs ring,
+// steps over the mirrors' pending words and draws the noise row (of this move's legal count) on the device (see move_extras).
+static int launch_inputs(mzmcts_engine* eng, const mz::TreeParams& view, int m, bool own_inputs, hipStream_t stream) {
+    mzmcts_engine::MoveBatch& b = eng->batch;
+    const mz::MoveControlBlock ctl = b.ctl.views(b.d_in);
+    const mz::MoveInputsBlock in = b.inputs.views(b.d_inputs, static_cast<size_t>(m));
+    const hipError_t err = mz::launch_move_inputs(view, ctl.rng_skip + static_cast<size_t>(m) * view.E, b.d_stall, ctl.move_limit, m,
+                                                  b.set[b.cur].add_noise, in.num_legal, in.to_play, in.noise_words, in.legal,
+                                                  move_extras(eng, own_inputs), stream);
+    b.finished = nullptr;
+    return err == hipSuccess ? MZMCTS_OK : hip_fail(eng, err, "move_inputs_kernel");
+}
+
+// What a whole-move launch and a lock-step finish of move m share: block m of the output ring, temperatures and their threshold.
+static mz::MoveCtl results_ctl(const mzmcts_engine* eng, int m) {
+    const mzmcts_engine::MoveBatch& b = eng->batch;
+    const mz::MoveOutputBlock o = b.out.views(b.d_out, static_cast<size_t>(m));
+    mz::MoveCtl ctl{};
+    ctl.temperature = b.ctl.views(b.d_in).temperature, ctl.move_index = m;
+    ctl.actions = o.actions, ctl.visits = o.visits, ctl.root_value_sum = o.root_value_sum, ctl.root_predicted = o.root_predicted;
+    ctl.max_depth = o.max_depth, ctl.tie_words = o.tie_words, ctl.sample_words = o.sample_words, ctl.depth_sum = o.depth_sum;
+    if (b.device_inputs && b.temperature_threshold > 0) {
+        ctl.game_moves = b.d_game_moves;
+        ctl.temperature_threshold = b.temperature_threshold;
+    }
+    return ctl;
+}
+
 int mzmcts_moves_enqueue(mzmcts_engine* eng, const float* observations, void* stream_) {
     if (!eng || !observations) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_enqueue: null argument");
     mzmcts_engine::MoveBatch& b = eng->batch;
@@ -457,57 +469,24 @@ int mzmcts_moves_enqueue(mzmcts_engine* eng, const float* observations, void* st
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const size_t E = static_cast<size_t>(eng->p.E), A = static_cast<size_t>(eng->p.A);
     const int m = b.enqueued;
-    uint8_t* out = b.d_out + b.out_stride * static_cast<size_t>(m);
-    mz::MoveCtl ctl{};
-    ctl.noise = c.add_noise ? reinterpret_cast<const double*>(b.d_in) + static_cast<size_t>(m) * E * A : nullptr;
-    ctl.rng_skip = reinterpret_cast<const uint32_t*>(b.d_in + b.o_skip) + static_cast<size_t>(m) * E;
-    const int32_t *host_legal = eng->p.root_action, *host_nlegal = eng->p.root_children, *host_to_play = eng->p.root_to_play;
+    const mz::MoveControlBlock in = b.ctl.views(b.d_in);
+    mz::MoveCtl ctl = results_ctl(eng, m);
+    ctl.noise = c.add_noise ? in.noise + static_cast<size_t>(m) * E * A : nullptr;
+    ctl.rng_skip = in.rng_skip + static_cast<size_t>(m) * E;
+    // a device-input batch searches the caller's device arrays, after move_inputs_kernel stepped over the words and drew the noise
+    const mz::TreeParams view = b.device_inputs ? device_inputs_view(eng) : eng->p;
     if (b.device_inputs) {
-        // the search reads the caller's device arrays; first a small kernel records them for the host, steps over the
-        // mirrors' pending words and draws the noise row (of this move's legal count) on the device
-        eng->p.root_action = const_cast<int32_t*>(b.dev_legal);
-        eng->p.root_children = const_cast<int32_t*>(b.dev_nlegal);
-        eng->p.root_to_play = const_cast<int32_t*>(b.dev_to_play);
-        uint8_t* blk = b.d_inputs + b.in2_stride * static_cast<size_t>(m);
-        hipError_t err = mz::launch_move_inputs(eng->p, ctl.rng_skip, b.d_stall, reinterpret_cast<const int32_t*>(b.d_in + b.o_limit), m,
-                                                c.add_noise, reinterpret_cast<int32_t*>(blk + b.o2_nlegal),
-                                                reinterpret_cast<int32_t*>(blk + b.o2_to_play),
-                                                reinterpret_cast<uint32_t*>(blk + b.o2_words),
-                                                reinterpret_cast<int32_t*>(blk + b.o2_legal), move_extras(eng, false), stream);
-        b.finished = nullptr;
-        if (err != hipSuccess) {
-            eng->p.root_action = const_cast<int32_t*>(host_legal), eng->p.root_children = const_cast<int32_t*>(host_nlegal);
-            eng->p.root_to_play = const_cast<int32_t*>(host_to_play);
-            return hip_fail(eng, err, "move_inputs_kernel");
-        }
+        if (int rc = launch_inputs(eng, view, m, false, stream)) return rc;
         ctl.noise = c.add_noise ? eng->p.noise_rows : nullptr;
         ctl.rng_skip = nullptr;
     }
-    ctl.temperature = reinterpret_cast<const double*>(b.d_in + b.o_temp);
-    ctl.move_limit = reinterpret_cast<const int32_t*>(b.d_in + b.o_limit);
-    ctl.stall = b.d_stall;
-    ctl.move_index = m;
-    ctl.expected_ties = (m > 0 && !b.device_inputs) ? reinterpret_cast<const uint32_t*>(b.d_in + b.o_expect) : nullptr;
-    ctl.actions = reinterpret_cast<int32_t*>(out + b.o_actions);
-    ctl.visits = reinterpret_cast<int32_t*>(out + b.o_visits);
-    ctl.root_value_sum = reinterpret_cast<double*>(out + b.o_rvs);
-    ctl.root_predicted = reinterpret_cast<float*>(out + b.o_pred);
-    ctl.max_depth = reinterpret_cast<int32_t*>(out + b.o_depth);
-    ctl.tie_words = reinterpret_cast<uint32_t*>(out + b.o_ties);
-    ctl.sample_words = reinterpret_cast<uint32_t*>(out + b.o_sample);
-    ctl.depth_sum = reinterpret_cast<int32_t*>(out + b.o_dsum);
-    if (b.device_inputs && b.temperature_threshold > 0) {
-        ctl.game_moves = reinterpret_cast<int32_t*>(b.d_game_moves);
-        ctl.temperature_threshold = b.temperature_threshold;
-    }
-    int rc = mzhost_launch_fused_move(eng, observations, ctl, true, stream);
+    ctl.move_limit = in.move_limit, ctl.stall = b.d_stall;
+    ctl.expected_ties = (m > 0 && !b.device_inputs) ? in.expected_ties : nullptr;
+    int rc = mzhost_launch_fused_move(eng, view, observations, ctl, true, stream);
     if (!rc && c.general) {   // the envs whose temperature needs pow: sampled right behind the search (select_action.h)
-        const hipError_t err = mz::launch_select_action_general(eng->p, ctl, b.d_general_t, stream);
+        const hipError_t err = mz::launch_select_action_general(view, ctl, b.d_general_t, stream);
         if (err != hipSuccess) rc = hip_fail(eng, err, "select_action_general_kernel");
     }
-    eng->p.root_action = const_cast<int32_t*>(host_legal);
-    eng->p.root_children = const_cast<int32_t*>(host_nlegal);
-    eng->p.root_to_play = const_cast<int32_t*>(host_to_play);
     if (rc) return rc;
     b.enqueued = m + 1;
     return MZMCTS_OK;
@@ -521,11 +500,11 @@ int mzmcts_moves_temperature_threshold(mzmcts_engine* eng, int32_t threshold, co
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_temperature_threshold: call right after mzmcts_moves_prepare_device");
     b.temperature_threshold = threshold;
     if (threshold == 0) return MZMCTS_OK;
-    const size_t bytes = sizeof(int32_t) * static_cast<size_t>(eng->p.E);
+    const size_t E = static_cast<size_t>(eng->p.E);
     int rc;
-    if (!b.d_game_moves && (rc = dev_alloc(eng, &b.d_game_moves, bytes))) return rc;
+    if (!b.d_game_moves && (rc = dev_alloc(eng, &b.d_game_moves, E))) return rc;
     // (pageable source: the copy is staged before the call returns, the caller's array may go)
-    MZ_HIP(eng, hipMemcpyAsync(b.d_game_moves, game_moves, bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream_)));
+    MZ_HIP(eng, hipMemcpyAsync(b.d_game_moves, game_moves, sizeof(int32_t) * E, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream_)));
     return MZMCTS_OK;
 }
 
@@ -557,7 +536,7 @@ static mz::MoveInputsExtra move_extras(mzmcts_engine* eng, bool own_inputs) {
         x.own_to_play = eng->own_root_to_play;
     }
     if (b.temperature_threshold > 0) {
-        x.game_moves = reinterpret_cast<int32_t*>(b.d_game_moves);
+        x.game_moves = b.d_game_moves;
         x.finished = b.finished;
     }
     x.sit_out = b.sit_out;
@@ -573,26 +552,10 @@ int mzmcts_moves_begin_lockstep(mzmcts_engine* eng, void* stream_) {
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_begin_lockstep: no prepared move left in a device-input batch");
     if (b.lockstep_open) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_begin_lockstep: the move before is still open");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int m = b.enqueued;
-    const size_t E = static_cast<size_t>(eng->p.E);
-    // the kernel reads the caller's device arrays (the env kernels' outputs), records them for the host, copies them
-    // into the engine's own root inputs -- which every later launch of the move reads, a replayed hipGraph included --,
-    // steps over the mirrors' pending words and draws the noise row on the device
-    mz::TreeParams view = eng->p;
-    view.root_action = const_cast<int32_t*>(b.dev_legal);
-    view.root_children = const_cast<int32_t*>(b.dev_nlegal);
-    view.root_to_play = const_cast<int32_t*>(b.dev_to_play);
-    uint8_t* blk = b.d_inputs + b.in2_stride * static_cast<size_t>(m);
-    eng->own_root_action = eng->p.root_action;
-    eng->own_root_children = eng->p.root_children;
-    eng->own_root_to_play = eng->p.root_to_play;
-    hipError_t err = mz::launch_move_inputs(view, reinterpret_cast<const uint32_t*>(b.d_in + b.o_skip) + static_cast<size_t>(m) * E,
-                                            b.d_stall, reinterpret_cast<const int32_t*>(b.d_in + b.o_limit), m, c.add_noise,
-                                            reinterpret_cast<int32_t*>(blk + b.o2_nlegal), reinterpret_cast<int32_t*>(blk + b.o2_to_play),
-                                            reinterpret_cast<uint32_t*>(blk + b.o2_words), reinterpret_cast<int32_t*>(blk + b.o2_legal),
-                                            move_extras(eng, true), stream);
-    b.finished = nullptr;
-    if (err != hipSuccess) return hip_fail(eng, err, "move_inputs_kernel");
+    // the kernel reads the caller's device arrays (the env kernels' outputs) and copies them into the engine's own root
+    // inputs -- which every later launch of the move reads, a replayed hipGraph included
+    eng->own_root_action = eng->p.root_action, eng->own_root_children = eng->p.root_children, eng->own_root_to_play = eng->p.root_to_play;
+    if (int rc = launch_inputs(eng, device_inputs_view(eng), b.enqueued, true, stream)) return rc;
     b.lockstep_open = true;
     eng->noise_this_search = c.add_noise;
     eng->noise_on_device = false;        // (the batch's collect() accounts for the words: readout is not used)
@@ -613,22 +576,7 @@ int mzmcts_moves_end_lockstep(mzmcts_engine* eng, void* stream_) {
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_end_lockstep: expand_roots and all simulations must have run");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int m = b.enqueued;
-    uint8_t* out = b.d_out + b.out_stride * static_cast<size_t>(m);
-    mz::MoveCtl ctl{};
-    ctl.temperature = reinterpret_cast<const double*>(b.d_in + b.o_temp);
-    ctl.move_index = m;
-    ctl.actions = reinterpret_cast<int32_t*>(out + b.o_actions);
-    ctl.visits = reinterpret_cast<int32_t*>(out + b.o_visits);
-    ctl.root_value_sum = reinterpret_cast<double*>(out + b.o_rvs);
-    ctl.root_predicted = reinterpret_cast<float*>(out + b.o_pred);
-    ctl.max_depth = reinterpret_cast<int32_t*>(out + b.o_depth);
-    ctl.tie_words = reinterpret_cast<uint32_t*>(out + b.o_ties);
-    ctl.sample_words = reinterpret_cast<uint32_t*>(out + b.o_sample);
-    ctl.depth_sum = reinterpret_cast<int32_t*>(out + b.o_dsum);
-    if (b.temperature_threshold > 0) {
-        ctl.game_moves = reinterpret_cast<int32_t*>(b.d_game_moves);
-        ctl.temperature_threshold = b.temperature_threshold;
-    }
+    const mz::MoveCtl ctl = results_ctl(eng, m);
     hipError_t err = mz::launch_lockstep_move_finish(eng->p, ctl, stream);
     if (err != hipSuccess) return hip_fail(eng, err, "lockstep_move_finish_kernel");
     if (b.set[b.cur].general) {
@@ -639,9 +587,9 @@ int mzmcts_moves_end_lockstep(mzmcts_engine* eng, void* stream_) {
     if (b.downloaded == m) {
         MZ_HIP(eng, hipEventRecord(b.move_done, stream));
         MZ_HIP(eng, hipStreamWaitEvent(b.copy_stream, b.move_done, 0));
-        MZ_HIP(eng, hipMemcpyAsync(b.h_out + b.out_stride * static_cast<size_t>(m), out, b.out_stride, hipMemcpyDeviceToHost, b.copy_stream));
-        MZ_HIP(eng, hipMemcpyAsync(b.h_inputs + b.in2_stride * static_cast<size_t>(m), b.d_inputs + b.in2_stride * static_cast<size_t>(m),
-                                   b.in2_stride, hipMemcpyDeviceToHost, b.copy_stream));
+        const size_t out_at = b.out.stride * static_cast<size_t>(m), in_at = b.inputs.stride * static_cast<size_t>(m);
+        MZ_HIP(eng, hipMemcpyAsync(b.h_out + out_at, b.d_out + out_at, b.out.stride, hipMemcpyDeviceToHost, b.copy_stream));
+        MZ_HIP(eng, hipMemcpyAsync(b.h_inputs + in_at, b.d_inputs + in_at, b.inputs.stride, hipMemcpyDeviceToHost, b.copy_stream));
         b.downloaded = m + 1;
     }
     b.lockstep_open = false;
@@ -654,8 +602,7 @@ int mzmcts_moves_end_lockstep(mzmcts_engine* eng, void* stream_) {
 
 const int32_t* mzmcts_moves_actions(mzmcts_engine* eng, int32_t move) {
     if (!eng || !eng->batch.in_flight || move < 0 || move >= eng->batch.set[eng->batch.cur].n_moves) return nullptr;
-    return reinterpret_cast<const int32_t*>(eng->batch.d_out + eng->batch.out_stride * static_cast<size_t>(move) +
-                                            eng->batch.o_actions);
+    return eng->batch.out.views(eng->batch.d_out, static_cast<size_t>(move)).actions;
 }
 
 int mzmcts_moves_ring(mzmcts_engine* eng, void** host_base, int64_t* move_stride, int64_t* offsets, int32_t* capacity) {
@@ -663,13 +610,10 @@ int mzmcts_moves_ring(mzmcts_engine* eng, void** host_base, int64_t* move_stride
     mzmcts_engine::MoveBatch& b = eng->batch;
     if (!b.h_out) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_ring: no batch has been prepared yet");
     *host_base = b.h_out;
-    *move_stride = static_cast<int64_t>(b.out_stride);
+    *move_stride = static_cast<int64_t>(b.out.stride);
     *capacity = b.capacity;
-    offsets[0] = static_cast<int64_t>(b.o_actions);
-    offsets[1] = static_cast<int64_t>(b.o_visits);
-    offsets[2] = static_cast<int64_t>(b.o_rvs);
-    offsets[3] = static_cast<int64_t>(b.o_pred);
-    offsets[4] = static_cast<int64_t>(b.o_depth);
+    const size_t fields[5] = {b.out.actions, b.out.visits, b.out.root_value_sum, b.out.root_predicted, b.out.max_depth};
+    for (int i = 0; i < 5; ++i) offsets[i] = static_cast<int64_t>(fields[i]);
     return MZMCTS_OK;
 }
 
@@ -678,10 +622,9 @@ int mzmcts_moves_inputs_ring(mzmcts_engine* eng, void** host_base, int64_t* move
     mzmcts_engine::MoveBatch& b = eng->batch;
     if (!b.h_inputs) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_inputs_ring: no device-input batch has been prepared yet");
     *host_base = b.h_inputs;
-    *move_stride = static_cast<int64_t>(b.in2_stride);
-    offsets[0] = static_cast<int64_t>(b.o2_nlegal);
-    offsets[1] = static_cast<int64_t>(b.o2_to_play);
-    offsets[2] = static_cast<int64_t>(b.o2_legal);
+    *move_stride = static_cast<int64_t>(b.inputs.stride);
+    const size_t fields[3] = {b.inputs.num_legal, b.inputs.to_play, b.inputs.legal};
+    for (int i = 0; i < 3; ++i) offsets[i] = static_cast<int64_t>(fields[i]);
     return MZMCTS_OK;
 }
 
@@ -690,8 +633,7 @@ int mzmcts_moves_device_ring(mzmcts_engine* eng, void** device_base, int64_t* mo
     if (!eng || !device_base || !move_stride || !offsets || !capacity) return MZMCTS_ERR_INVALID;
     mzmcts_engine::MoveBatch& b = eng->batch;
     if (!b.d_out) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_device_ring: no batch has been prepared yet");
-    void* host_base = nullptr;
-    const int rc = mzmcts_moves_ring(eng, &host_base, move_stride, offsets, capacity);   // (the same strides and offsets)
+    const int rc = mzmcts_moves_ring(eng, device_base, move_stride, offsets, capacity);   // (the same strides and offsets)
     *device_base = b.d_out;
     return rc;
 }
@@ -701,8 +643,7 @@ int mzmcts_moves_inputs_device_ring(mzmcts_engine* eng, void** device_base, int6
     mzmcts_engine::MoveBatch& b = eng->batch;
     if (!b.d_inputs)
         return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_moves_inputs_device_ring: no device-input batch has been prepared yet");
-    void* host_base = nullptr;
-    const int rc = mzmcts_moves_inputs_ring(eng, &host_base, move_stride, offsets);
+    const int rc = mzmcts_moves_inputs_ring(eng, device_base, move_stride, offsets);
     *device_base = b.d_inputs;
     return rc;
 }
@@ -722,65 +663,69 @@ int mzmcts_moves_collect(mzmcts_engine* eng, int32_t* moves_done, int32_t* actio
     const double t_kernels = trace ? now() : 0.0;
     const int have = b.device_inputs ? std::min(b.downloaded, M) : 0;      // moves downloaded while the batch ran
     if (M > have) {
-        MZ_HIP(eng, hipMemcpyAsync(b.h_out + b.out_stride * static_cast<size_t>(have), b.d_out + b.out_stride * static_cast<size_t>(have),
-                                   b.out_stride * static_cast<size_t>(M - have), hipMemcpyDeviceToHost, stream));
+        const size_t out_at = b.out.stride * static_cast<size_t>(have), in_at = b.inputs.stride * static_cast<size_t>(have);
+        MZ_HIP(eng, hipMemcpyAsync(b.h_out + out_at, b.d_out + out_at, b.out.stride * static_cast<size_t>(M - have), hipMemcpyDeviceToHost, stream));
         if (b.device_inputs)
-            MZ_HIP(eng, hipMemcpyAsync(b.h_inputs + b.in2_stride * static_cast<size_t>(have), b.d_inputs + b.in2_stride * static_cast<size_t>(have),
-                                       b.in2_stride * static_cast<size_t>(M - have), hipMemcpyDeviceToHost, stream));
+            MZ_HIP(eng, hipMemcpyAsync(b.h_inputs + in_at, b.d_inputs + in_at, b.inputs.stride * static_cast<size_t>(M - have),
+                                       hipMemcpyDeviceToHost, stream));
     }
     if (have > 0) MZ_HIP(eng, hipStreamSynchronize(b.copy_stream));
     b.downloaded = 0;
-    MZ_HIP(eng, hipMemcpyAsync(eng->h_error_flag, eng->p.error_flag, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    MZ_HIP(eng, hipMemcpyAsync(eng->h_down.error_flag, eng->p.error_flag, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     MZ_HIP(eng, hipEventRecord(b.done, stream));
     MZ_HIP(eng, hipEventSynchronize(b.done));
     const double t_copied = trace ? now() : 0.0;
     b.in_flight = false;
     ChainSet& c = b.set[b.cur];
     ChainSet& next = b.set[b.cur ^ 1];
-    if (eng->h_error_flag[0] != 0)
-        return fail(eng, MZMCTS_ERR_INVALID, (eng->h_error_flag[0] & 8) ? "device error flag set: unexpected DPP lane mapping"
-                                             : (eng->h_error_flag[0] & 2)
+    if (eng->h_down.error_flag[0] != 0)
+        return fail(eng, MZMCTS_ERR_INVALID, (eng->h_down.error_flag[0] & 8) ? "device error flag set: unexpected DPP lane mapping"
+                                             : (eng->h_down.error_flag[0] & 2)
                                                  ? "device error flag set: tree links are inconsistent"
                                                  : "device error flag set: a UCB score was NaN (no maximum to select)");
-    auto block = [&](int m, size_t off) { return b.h_out + b.out_stride * static_cast<size_t>(m) + off; };
+    auto block = [&](int m) { return b.out.views(b.h_out, static_cast<size_t>(m)); };   // move m's downloaded results
+    // move m of env e into the caller's [M][E] arrays (null = not wanted); a move that was not searched reads as -1 and zeros
+    auto unpack = [&](const mz::MoveOutputBlock& o, int m, int e, bool live) {
+        const size_t me = static_cast<size_t>(m) * E + e;
+        if (actions) actions[me] = live ? o.actions[e] : -1;
+        if (visits)
+            for (int i = 0; i < A; ++i) visits[me * A + i] = live ? o.visits[static_cast<size_t>(e) * A + i] : 0;
+        if (root_value_sum) root_value_sum[me] = live ? o.root_value_sum[e] : 0.0;
+        if (root_predicted) root_predicted[me] = live ? o.root_predicted[e] : 0.f;
+        if (max_depth) max_depth[me] = live ? o.max_depth[e] : 0;
+    };
     ChainSet* sets[2] = {&c, next.drawn ? &next : nullptr};
     std::atomic<int64_t> played_total{0}, depth_total{0};
     if (b.device_inputs) {
         // nothing was drawn ahead on the mirrors: every word of the batch -- noise, tie-breaks, action sampling -- was
         // consumed on the device copies; the mirrors step over them
-        auto inputs = [&](int m, size_t off) { return b.h_inputs + b.in2_stride * static_cast<size_t>(m) + off; };
+        auto inputs = [&](int m) { return b.inputs.views(b.h_inputs, static_cast<size_t>(m)); };
         eng->for_each_env([&](int lo, int hi) {
             int64_t local = 0, local_depth = 0;
             for (int e = lo; e < hi; ++e) {
                 // (sit-out batches: a move recorded with an empty legal set was played by the caller's environment
                 // kernels -- the env stays live, its output block of that move holds nothing of the search)
-                auto sat_out = [&](int m) { return b.sit_out && reinterpret_cast<const int32_t*>(inputs(m, b.o2_nlegal))[e] == 0; };
+                auto sat_out = [&](int m) { return b.sit_out && inputs(m).num_legal[e] == 0; };
                 int k = 0;
-                while (k < M && (sat_out(k) || reinterpret_cast<const int32_t*>(block(k, b.o_actions))[e] >= 0)) ++k;
+                while (k < M && (sat_out(k) || block(k).actions[e] >= 0)) ++k;
                 if (moves_done) moves_done[e] = k;
                 uint64_t words = 0;
                 int searched = 0;
                 for (int m = 0; m < M; ++m) {
                     const bool live = m < k && !sat_out(m);
                     searched += live ? 1 : 0;
-                    const size_t me = static_cast<size_t>(m) * E + e;
-                    if (actions) actions[me] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_actions))[e] : -1;
-                    if (visits)
-                        for (int i = 0; i < A; ++i)
-                            visits[me * A + i] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_visits))[static_cast<size_t>(e) * A + i] : 0;
-                    if (root_value_sum) root_value_sum[me] = live ? reinterpret_cast<const double*>(block(m, b.o_rvs))[e] : 0.0;
-                    if (root_predicted) root_predicted[me] = live ? reinterpret_cast<const float*>(block(m, b.o_pred))[e] : 0.f;
-                    if (max_depth) max_depth[me] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_depth))[e] : 0;
+                    const mz::MoveOutputBlock o = block(m);
+                    unpack(o, m, e, live);
                     if (live) {
-                        words += reinterpret_cast<const uint32_t*>(inputs(m, b.o2_words))[e];
-                        words += reinterpret_cast<const uint32_t*>(block(m, b.o_ties))[e];
-                        words += reinterpret_cast<const uint32_t*>(block(m, b.o_sample))[e];
-                        if (eng->profiling) local_depth += reinterpret_cast<const int32_t*>(block(m, b.o_dsum))[e];
+                        words += inputs(m).noise_words[e];
+                        words += o.tie_words[e];
+                        words += o.sample_words[e];
+                        if (eng->profiling) local_depth += o.depth_sum[e];
                     }
                 }
                 // (an env that searched nothing kept the pending words of its mirror: they were not stepped over)
                 // (in a sit-out batch move 0 steps over them for every env)
-                if (k == 0 && !(b.sit_out && M > 0)) eng->lag[e] += reinterpret_cast<const uint32_t*>(c.h_in + b.o_skip)[e];
+                if (k == 0 && !(b.sit_out && M > 0)) eng->lag[e] += b.ctl.views(c.h_in).rng_skip[e];
                 eng->behind[e] += words;             // (stepped over when the mirror is next asked for: mirror())
                 local += searched;                   // (the profile counts simulations that ran: not the sat-out plies)
             }
@@ -800,24 +745,16 @@ int mzmcts_moves_collect(mzmcts_engine* eng, int32_t* moves_done, int32_t* actio
             if (active) {
                 // played moves are a prefix of the batch (a stall is sticky, a move limit is a prefix): if the last
                 // one ran, all of them did -- one read instead of M for nearly every env
-                if (M > 0 && reinterpret_cast<const int32_t*>(block(M - 1, b.o_actions))[e] >= 0)
+                if (M > 0 && block(M - 1).actions[e] >= 0)
                     k = M;
                 else
-                    while (k < M && reinterpret_cast<const int32_t*>(block(k, b.o_actions))[e] >= 0) ++k;
+                    while (k < M && block(k).actions[e] >= 0) ++k;
             }
             if (moves_done) moves_done[e] = k;
             const bool per_move = actions || visits || root_value_sum || root_predicted || max_depth || eng->profiling;
             for (int m = 0; per_move && m < M; ++m) {
-                const bool live = m < k;
-                const size_t me = static_cast<size_t>(m) * E + e;
-                if (actions) actions[me] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_actions))[e] : -1;
-                if (visits)
-                    for (int i = 0; i < A; ++i)
-                        visits[me * A + i] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_visits))[static_cast<size_t>(e) * A + i] : 0;
-                if (root_value_sum) root_value_sum[me] = live ? reinterpret_cast<const double*>(block(m, b.o_rvs))[e] : 0.0;
-                if (root_predicted) root_predicted[me] = live ? reinterpret_cast<const float*>(block(m, b.o_pred))[e] : 0.f;
-                if (max_depth) max_depth[me] = live ? reinterpret_cast<const int32_t*>(block(m, b.o_depth))[e] : 0;
-                if (live && eng->profiling) local_depth += reinterpret_cast<const int32_t*>(block(m, b.o_dsum))[e];
+                unpack(block(m), m, e, m < k);
+                if (m < k && eng->profiling) local_depth += block(m).depth_sum[e];
             }
             local += k;
             // The mirror ran ahead over this batch (and over the next one, if it is pre-drawn): put it where the
@@ -833,8 +770,7 @@ int mzmcts_moves_collect(mzmcts_engine* eng, int32_t* moves_done, int32_t* actio
                     eng->lag[e] = (c.tail_ties[e] | c.tail_sample[e]) ? 0u : c.start_lag[e];
                     redraw_next = next.drawn;
                 } else {
-                    const uint32_t ties = reinterpret_cast<const uint32_t*>(block(k - 1, b.o_ties))[e];
-                    const uint32_t sampled = reinterpret_cast<const uint32_t*>(block(k - 1, b.o_sample))[e];
+                    const uint32_t ties = block(k - 1).tie_words[e], sampled = block(k - 1).sample_words[e];
                     const bool as_assumed = next.drawn && !next.deferred[e] && next.nlegal[e] > 0 && k == c.n_moves &&
                                             ties == next.tail_ties[e] && sampled == next.tail_sample[e];
                     if (!as_assumed) {

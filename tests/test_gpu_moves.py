@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import staging_layout_cases as layout_cases
 from parity_helpers import cartpole_model_and_weights
 
 pytestmark = pytest.mark.gpu
@@ -293,5 +294,115 @@ def test_device_input_move_batches_equal_one_move_at_a_time_tictactoe(eng, pkg):
     got_rng = [batch.get_rng_state(e) for e in range(E)]
     for a, b in zip(want_rng, got_rng):
         assert np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+    batch.close()
+    envs.close()
+
+
+# ---- the staging blocks behind a batch: one layout (csrc/staging_layout.h), whichever way the host reads them -------------------
+FIVE = (("actions", torch.int32), ("visits", torch.int32), ("root_value_sum", torch.float64), ("root_predicted", torch.float32),
+        ("max_depth", torch.int32))
+
+
+def read_output_ring_on_device(eng, engine, M):
+    """The five per-move arrays of the batch collected last, read from the device ring at the addresses the library reports;
+    also asserts that both ring entries report the offsets and stride of tests/staging_layout_cases.py."""
+    E, A = engine.E, engine.A
+    want_offsets, want_stride = layout_cases.ring_offsets(E, A)
+    _, stride, offsets = engine._moves_ring()
+    assert offsets[:5] == want_offsets and stride == want_stride
+    ring = engine.moves_device_ring()
+    base = ring["actions"] - want_offsets[0]
+    assert (ring["visits"], ring["root_value_sum"], ring["stride"]) == (base + want_offsets[1], base + want_offsets[2], want_stride)
+    out = {}
+    for (name, dtype), offset in zip(FIVE, want_offsets):
+        n = E * A if name == "visits" else E
+        out[name] = np.stack([eng._device_view(base + offset + m * stride, n, dtype, engine.device).cpu().numpy() for m in range(M)])
+    out["visits"] = out["visits"].reshape(M, E, A)
+    return out
+
+
+def test_host_input_batches_unpacked_viewed_and_on_the_device_are_one(eng, pkg):
+    """A batch of 1 move, then one of 3 (the rings are allocated anew for it), on two engines with equal seeds: what
+    moves_collect() unpacks, the views moves_collect(copy=False) hands out and the device ring at the reported addresses hold
+    the same bits for every move an env played; env 0 is inactive."""
+    config, model = cartpole_setup(pkg, False)
+    E = 5
+    rs = np.random.RandomState(21)
+    legal, to_play, T = [[] if e == 0 else [0, 1] for e in range(E)], [0] * E, np.ones(E)
+    engines = []
+    for _ in range(2):
+        engines.append(eng.BatchedMCTS(config, E, seeds=[500 + e for e in range(E)], group_width=16))
+        engines[-1].configure_fused_fc(model)
+    unpacking, viewing = engines
+    for M in (1, 3):
+        obs = [torch.from_numpy(rs.uniform(-0.05, 0.05, (E, 4)).astype(np.float32)).cuda() for _ in range(M)]
+        copied = unpacking.run_moves(obs, legal, to_play, T, True)
+        viewing.moves_prepare(M, legal, to_play, T, True)
+        for o in obs:
+            viewing.moves_enqueue(o)
+        viewed = viewing.moves_collect(copy=False)
+        on_device = [read_output_ring_on_device(eng, engine, M) for engine in engines]
+        done = copied["moves_done"]
+        assert np.array_equal(done, viewed["moves_done"]) and done[0] == 0 and (done[1:] >= 1).all()
+        for name, _ in FIVE:
+            assert copied[name].shape == viewed[name].shape == on_device[0][name].shape and copied[name].dtype == viewed[name].dtype
+            for e in range(E):
+                want = copied[name][:done[e], e].tobytes()
+                for other in (viewed, on_device[0], on_device[1]):
+                    assert np.ascontiguousarray(other[name][:done[e], e]).tobytes() == want, (M, name, e)
+    for engine in engines:
+        engine.close()
+
+
+def test_device_input_batch_inputs_unpacked_viewed_and_on_the_device_are_one(eng, pkg):
+    """What each move of a device-input batch was searched with (TicTacToe, 5 envs, 3 moves of 8 simulations): moves_inputs(M),
+    its copy=False views of the pinned ring and the device ring at the reported addresses agree; both ring entries report
+    the offsets of tests/staging_layout_cases.py."""
+    import ctypes
+    models_mod = importlib.import_module("muzero-hypermodel_amd.models")
+    device_mod = importlib.import_module("muzero-hypermodel_amd.games.device")
+    config = importlib.import_module("muzero-hypermodel_amd.games.tictactoe").MuZeroConfig()
+    config.network, config.encoding_size = "fullyconnected", 8
+    config.fc_representation_layers, config.fc_dynamics_layers = [], [16]
+    config.fc_reward_layers = config.fc_value_layers = config.fc_policy_layers = [16]
+    config.num_simulations = 8
+    torch.manual_seed(4)
+    model = models_mod.MuZeroNetwork(config).to("cuda").eval()
+    E, M, A = 5, 3, len(config.action_space)
+    seeds = list(range(300, 300 + E))
+    envs = device_mod.DeviceEnvs("tictactoe", E, seeds=seeds, device="cuda")
+    batch = eng.BatchedMCTS(config, E, seeds=seeds, group_width=16)
+    batch.configure_fused_fc(model)
+    obs_in, legal, num_legal, to_play = envs.observe()
+    batch.moves_prepare_device(M, legal, num_legal, to_play, 1.0, True)
+    shape = envs.observation_shape
+    reward = torch.zeros((M, E), dtype=torch.float32, device="cuda")
+    done = torch.zeros((M, E), dtype=torch.uint8, device="cuda")
+    obs_after = torch.zeros((M, E) + shape, dtype=torch.float32, device="cuda")
+    obs_next = torch.zeros((M, E) + shape, dtype=torch.float32, device="cuda")
+    for m in range(M):
+        batch.moves_enqueue(obs_in.reshape(E, -1).contiguous())
+        obs_in = envs.advance(batch.moves_actions(m), reward[m], done[m], obs_after[m], obs_next[m])
+    assert (batch.moves_collect()["moves_done"] == M).all()
+    copied, viewed = batch.moves_inputs(M), batch.moves_inputs(M, copy=False)
+
+    want_offsets, want_stride = layout_cases.inputs_ring_offsets(E, A)
+    assert A == 9 and want_offsets[0] == 0
+    for entry in (batch._lib.mzmcts_moves_inputs_ring, batch._lib.mzmcts_moves_inputs_device_ring):
+        base, stride, offsets = ctypes.c_void_p(), ctypes.c_int64(), (ctypes.c_int64 * 3)()
+        batch._check(entry(batch._h, ctypes.byref(base), ctypes.byref(stride), offsets))
+        assert list(offsets) == want_offsets and stride.value == want_stride
+    ring = batch.moves_inputs_device_ring()
+    assert [ring[k] - ring["num_legal"] for k in ("num_legal", "to_play", "legal")] == want_offsets and ring["stride"] == want_stride
+    on_device = {k: np.stack([eng._device_view(ring[k] + m * want_stride, E * (A if k == "legal" else 1), torch.int32, batch.device).cpu().numpy()
+                              for m in range(M)]) for k in ("num_legal", "to_play", "legal")}
+    on_device["legal"] = on_device["legal"].reshape(M, E, A)
+    assert (copied["num_legal"][0] == A).all() and (copied["num_legal"][M - 1] == A - (M - 1)).all()
+    for other in (viewed, on_device):
+        assert np.array_equal(copied["num_legal"], other["num_legal"]) and np.array_equal(copied["to_play"], other["to_play"])
+        for m in range(M):
+            for e in range(E):
+                n = int(copied["num_legal"][m, e])
+                assert np.array_equal(copied["legal"][m, e, :n], other["legal"][m, e, :n]), (m, e)
     batch.close()
     envs.close()
