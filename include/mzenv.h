@@ -127,6 +127,31 @@ int mzenv_advance_opponent(mzenv *env, const int32_t *actions, float *reward_out
                            float *obs_next_out, int32_t *legal_out, int32_t *num_legal_out, int32_t *to_play_out,
                            int32_t *played_out, uint32_t *words_out, void *stream);
 
+/* ---- paired moves: the opponent replies inside MuZero's move ---------------------------------------------------------
+ * With mzenv_advance_opponent an env on the opponent's turn sits a whole search out.  mzenv_advance_paired plays, in ONE
+ * launch and per env, up to MZENV_PAIRED_SLOTS plies (the rule lives once in csrc/paired_moves.h; kernels and a CPU check
+ * compile it):
+ *   slot 0     MuZero's ply: only if muzero_player is to move and actions[e] >= 0 -- what mzenv_advance_opponent does for
+ *              such an env: step, observation of the position reached, reset if the game is over (rules or move limit)
+ *   slot 1, 2  while the opponent is to move: its choice from the env's stream exactly as in mzenv_advance_opponent, step,
+ *              observation, reset if the game is over.  Slot 1 is the reply, or the opening of the next game when MuZero's
+ *              ply ended the game and MuZero plays second; slot 2 can only be such an opening after a reply that ended
+ *              the game.
+ * Outputs with a leading slot axis: reward_out dev f32[3][E], done_out dev u8[3][E], obs_after_out dev f32[3][E,C,H,W],
+ * played_out dev i32[3][E] (-1 = the slot is empty: reward, done and words read 0, obs_after the position as it stood),
+ * words_out dev u32[3][E] (the host steps its stream mirrors over the sum of an env's slots).  Once per env, for the
+ * position the next search sees: obs_next_out, legal_out, num_legal_out, to_play_out as in mzenv_advance.
+ * Afterwards muzero_player is to move in every env and num_legal > 0 (a full board handed in by mzenv_set_boards on the
+ * opponent's turn excepted: it has no move).  Every ply counts into the env's ply counter and the move limit applies per
+ * ply.  With all actions -1 the launch plays only the opponent's pending plies (the openings after a reset when MuZero
+ * plays second): run it once when the mode is taken up.
+ * Errors: a one-player game; no opponent set; a move limit of 1 with muzero_player = 1 (opening, limit, reset, opening,
+ * ...: MuZero would never move).  mzenv_advance_opponent and mzenv_advance are what they were. */
+#define MZENV_PAIRED_SLOTS 3
+int mzenv_advance_paired(mzenv *env, const int32_t *actions, float *reward_out, uint8_t *done_out, float *obs_after_out,
+                         float *obs_next_out, int32_t *legal_out, int32_t *num_legal_out, int32_t *to_play_out,
+                         int32_t *played_out, uint32_t *words_out, void *stream);
+
 /* Put every env of a board game into a given position: boards host i8[E][cells] (0 empty, +1 first player, -1 second;
  * tic-tac-toe cell = 3 * row + column, connect four cell = 7 * row + column with row 0 at the bottom, gomoku cell =
  * 11 * row + column), players host i8[E] (+1 / -1 to move).  Blocking; cell and player values are checked, reachability is not (see above for what a

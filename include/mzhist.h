@@ -56,6 +56,17 @@ typedef struct mzhist_moves {
                                    * (mzenv_advance_opponent's played_out).  When given, a ply whose legal set is empty
                                    * is an OPPONENT ply (reference self_play.py:497-512, store_search_statistics(None)):
                                    * its action is played[m][e], its root value is NaN and its child_visits row is zero. */
+    int32_t slots;                /* 0 or 1: a move is one ply, as above.  > 1: a PAIRED batch (mzenv_advance_paired): a move is
+                                   * up to `slots` plies, in up to two games of an env, and rewards, done, obs_after,
+                                   * to_play_after and played (required) carry a slot axis: [M][slots][E]...  Per move and env
+                                   * the slots are filed in order; played < 0 = an empty slot, which files nothing.  Slot 0 is
+                                   * the searched ply, filed from the engine's blocks (action, visits, root value sum, legal
+                                   * set); every later slot is an opponent ply as above (action from played, NaN root value,
+                                   * zero child_visits row).  A game that ends in a slot is handed out there and the env's next
+                                   * game starts from reset_obs with player 0 to move (obs_next and to_play_next, which describe
+                                   * the position after ALL slots, are not read). */
+    const float *reset_obs;       /* [obs], slots > 1 only: the observation every game starts from (board games: Game.reset()
+                                   * gives every env the same position) */
 } mzhist_moves;
 
 /* File the batch; *n_finished = games that ended in it. */

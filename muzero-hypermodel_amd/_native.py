@@ -395,6 +395,7 @@ PROTOTYPES = {
     "mzenv_set_opponent": (ctypes.c_int, [c_void, ctypes.c_int32, ctypes.c_int32, c_void, c_void]),
     "mzenv_step_opponent": (ctypes.c_int, [c_void] * 7),
     "mzenv_advance_opponent": (ctypes.c_int, [c_void] * 12),
+    "mzenv_advance_paired": (ctypes.c_int, [c_void] * 12),
     "mzenv_set_boards": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzenv_get_state": (ctypes.c_int, [c_void, c_void, c_void]),
     "mzenv_set_state": (ctypes.c_int, [c_void, c_void, c_void]),
@@ -507,7 +508,8 @@ class MzHistMoves(ctypes.Structure):
                 ("visits_stride", ctypes.c_int64), ("root_value_sum", c_void), ("root_value_sum_stride", ctypes.c_int64),
                 ("legal", c_void), ("num_legal", c_void), ("rewards", c_void), ("done", c_void), ("obs_after", c_void),
                 ("obs_next", c_void), ("to_play_after", c_void), ("to_play_next", c_void),
-                ("legal_stride", ctypes.c_int64), ("num_legal_stride", ctypes.c_int64), ("played", c_void)]
+                ("legal_stride", ctypes.c_int64), ("num_legal_stride", ctypes.c_int64), ("played", c_void),
+                ("slots", ctypes.c_int32), ("reset_obs", c_void)]
 
 
 class MzReplayFileMoves(ctypes.Structure):

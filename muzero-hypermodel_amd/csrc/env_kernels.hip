@@ -7,11 +7,14 @@
 // Rules restate the reference's in-repo envs (games/tictactoe.py:242-305, games/connect4.py:219-304)
 // with the Game wrappers' reward scaling; CartPole restates the classic-control equations (pinned to them bit for bit but for sin / cos: include/mzenv.h).  The board rules
 // and the scripted opponents of evaluation games live in board_rules.h (also compiled for the host by a CPU check).
+// Paired moves (mzenv_advance_paired: MuZero's ply and the opponent's replies in one launch) wrap the same ply functions in
+// the slot loop of paired_moves.h, one wrapper per kernel form.
 #include <hip/hip_runtime.h>
 
 #include "board_rules.h"
 #include "env_layout.h"
 #include "np_legacy_rng.h"
+#include "paired_moves.h"
 #include "solo_rules.h"
 
 namespace mz {
@@ -215,6 +218,54 @@ __global__ __launch_bounds__(256) void env_advance_kernel(EnvParams p, const int
     env_observe_one(p, e, obs_next, legal, num_legal, to_play);
 }
 
+// ---- paired moves (mzenv_advance_paired): MuZero's ply and the opponent's replies in one launch ------------------------
+// The per-slot outputs of a paired launch: arrays with a leading slot axis, [kPairedSlots][E]...
+struct PairedOut {
+    float* reward;      // [3][E]
+    uint8_t* done;      // [3][E]
+    float* obs_after;   // [3][E][obs_floats]  (an empty slot holds the position as it stood)
+    int32_t* played;    // [3][E]              -1 = empty slot
+    uint32_t* words;    // [3][E]
+};
+
+// an empty slot's scalars, as a single-ply launch writes them for an env it leaves untouched
+__device__ __forceinline__ void paired_empty_slot(const PairedOut& out, size_t at) {
+    out.played[at] = -1;
+    out.words[at] = 0;
+    out.reward[at] = 0.f;
+    out.done[at] = 0;
+}
+
+// the plies of paired_move (paired_moves.h) for the one-thread-per-env games: a slot is env_advance_kernel's body
+struct EnvPairedOps {
+    const EnvParams& p;
+    const PairedOut& out;
+    int e;
+    int32_t *legal, *num_legal, *to_play;
+    __device__ bool opponent_to_move() const { return mz::opponent_to_move(p, e); }
+    __device__ void slot(int s, bool play, int a) {
+        const size_t at = static_cast<size_t>(s) * p.E;
+        bool done = false;
+        if (play)
+            done = env_step_one(p, e, a, out.reward + at, out.done + at, out.played + at, out.words + at);
+        else
+            paired_empty_slot(out, at + e);
+        env_observe_one(p, e, out.obs_after + at * p.obs_floats, legal, num_legal, to_play);
+        if (done) env_reset_one(p, e);
+    }
+};
+
+__global__ __launch_bounds__(256) void env_advance_paired_kernel(EnvParams p, const int32_t* __restrict__ actions,
+                                                                 PairedOut out, float* __restrict__ obs_next,
+                                                                 int32_t* __restrict__ legal, int32_t* __restrict__ num_legal,
+                                                                 int32_t* __restrict__ to_play) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.E) return;
+    EnvPairedOps ops{p, out, e, legal, num_legal, to_play};
+    paired_move(ops, actions[e]);
+    env_observe_one(p, e, obs_next, legal, num_legal, to_play);
+}
+
 // ---- Gomoku: a wavefront owns an env, a lane owns cells -------------------------------------------------------------
 // An 11 x 11 board does not fit the one-thread-per-env shape above: 363 strided float stores per observation and lane
 // (every store instruction of a wavefront touching 64 different cache lines) and a serial 121 x 4 x 5 line scan.  Here
@@ -276,45 +327,15 @@ __device__ __forceinline__ void gmk_write_observation(const EnvParams& p, int e,
     }
 }
 
-template <int OP>
-__global__ __launch_bounds__(64 * kGmkEnvsPerBlock) void gomoku_env_kernel(
-    EnvParams p, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
-    uint8_t* __restrict__ done_out, float* __restrict__ obs_after, float* __restrict__ obs_next,
-    int32_t* __restrict__ legal, int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play,
-    int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
-    __shared__ __attribute__((aligned(16))) int8_t padded_all[kGmkEnvsPerBlock][256];  // 225 bytes used per env
-    const int lane = threadIdx.x & 63, group = threadIdx.x >> 6;
-    const int e = blockIdx.x * kGmkEnvsPerBlock + group;
-    const bool live = e < p.E;  // (a wavefront without an env stays for the workgroup barrier and touches no memory)
-    int8_t* padded = padded_all[group];
+// Game.step of one env by its wavefront; returns whether the game ended (by its rules or by the move limit).  Collective
+// over the WORKGROUP: every wavefront of it calls this together (two barriers inside), one without an env or without a
+// ply to play with live == false -- it then touches no memory.  c / player: the lanes' cells and the side to move, kept
+// up to date in registers.  a < 0 on MuZero's turn: the env is left alone.
+__device__ __forceinline__ bool gmk_wave_step(const EnvParams& p, int e, bool live, int lane, int8_t* __restrict__ board,
+                                              int8_t* __restrict__ padded, GmkCells& c, int& player, int a,
+                                              float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                              int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
     const bool second = lane + 64 < kGmkCells;
-    int8_t* board = p.board + static_cast<size_t>(live ? e : 0) * kGmkCells;
-
-    if (OP == kGmkReset) {
-        if (!live || (mask && !mask[e])) return;
-        board[lane] = 0;
-        if (second) board[64 + lane] = 0;
-        if (lane == 0) {
-            p.player[e] = 1;
-            p.steps[e] = 0;
-        }
-        return;
-    }
-
-    GmkCells c{2, 2};
-    int player = 1;
-    if (live) {
-        c.b0 = board[lane];
-        if (second) c.b1 = board[64 + lane];
-        player = p.player[e];
-    }
-    if (OP == kGmkObserve) {
-        if (live) gmk_write_observation(p, e, lane, c, player, obs_after, legal, num_legal, to_play);
-        return;
-    }
-
-    // ---- Game.step ----
-    int a = live ? actions[e] : -1;
     uint32_t words = 0;
     if (live && p.opp_kind != kOpponentSelf && (player == 1 ? 0 : 1) != p.opp_player) {
         // the opponent's turn: the incoming action is ignored, numpy.random.choice(legal) decides (random_legal_action's
@@ -377,21 +398,69 @@ __global__ __launch_bounds__(64 * kGmkEnvsPerBlock) void gomoku_env_kernel(
         reward_out[e] = reward;
         done_out[e] = done ? 1 : 0;
     }
-    if (OP == kGmkStep || !live) return;
+    return done;
+}
 
-    // ---- observation after the move, Game.reset() of a finished env, observation the next search sees ----
-    gmk_write_observation(p, e, lane, c, player, obs_after, legal, num_legal, to_play);
-    if (done) {
-        c.b0 = 0;
-        c.b1 = second ? 0 : 2;
-        player = 1;
+// Game.reset() of one env by its wavefront (cells and side to move in registers follow)
+__device__ __forceinline__ void gmk_wave_reset(const EnvParams& p, int e, int lane, int8_t* __restrict__ board, GmkCells& c,
+                                               int& player) {
+    const bool second = lane + 64 < kGmkCells;
+    c.b0 = 0;
+    c.b1 = second ? 0 : 2;
+    player = 1;
+    board[lane] = 0;
+    if (second) board[64 + lane] = 0;
+    if (lane == 0) {
+        p.player[e] = 1;
+        p.steps[e] = 0;
+    }
+}
+
+template <int OP>
+__global__ __launch_bounds__(64 * kGmkEnvsPerBlock) void gomoku_env_kernel(
+    EnvParams p, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
+    uint8_t* __restrict__ done_out, float* __restrict__ obs_after, float* __restrict__ obs_next,
+    int32_t* __restrict__ legal, int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play,
+    int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
+    __shared__ __attribute__((aligned(16))) int8_t padded_all[kGmkEnvsPerBlock][256];  // 225 bytes used per env
+    const int lane = threadIdx.x & 63, group = threadIdx.x >> 6;
+    const int e = blockIdx.x * kGmkEnvsPerBlock + group;
+    const bool live = e < p.E;  // (a wavefront without an env stays for the workgroup barrier and touches no memory)
+    int8_t* padded = padded_all[group];
+    const bool second = lane + 64 < kGmkCells;
+    int8_t* board = p.board + static_cast<size_t>(live ? e : 0) * kGmkCells;
+
+    if (OP == kGmkReset) {
+        if (!live || (mask && !mask[e])) return;
         board[lane] = 0;
         if (second) board[64 + lane] = 0;
         if (lane == 0) {
             p.player[e] = 1;
             p.steps[e] = 0;
         }
+        return;
     }
+
+    GmkCells c{2, 2};
+    int player = 1;
+    if (live) {
+        c.b0 = board[lane];
+        if (second) c.b1 = board[64 + lane];
+        player = p.player[e];
+    }
+    if (OP == kGmkObserve) {
+        if (live) gmk_write_observation(p, e, lane, c, player, obs_after, legal, num_legal, to_play);
+        return;
+    }
+
+    // ---- Game.step ----
+    const bool done = gmk_wave_step(p, e, live, lane, board, padded, c, player, live ? actions[e] : -1, reward_out, done_out,
+                                    played_out, words_out);
+    if (OP == kGmkStep || !live) return;
+
+    // ---- observation after the move, Game.reset() of a finished env, observation the next search sees ----
+    gmk_write_observation(p, e, lane, c, player, obs_after, legal, num_legal, to_play);
+    if (done) gmk_wave_reset(p, e, lane, board, c, player);
     gmk_write_observation(p, e, lane, c, player, obs_next, legal, num_legal, to_play);
 }
 
@@ -420,24 +489,11 @@ __device__ __forceinline__ void gmk_serial_reset(const EnvParams& p, int e) {
     p.steps[e] = 0;
 }
 
-template <int OP>
-__global__ __launch_bounds__(256) void gomoku_env_serial_kernel(
-    EnvParams p, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
-    uint8_t* __restrict__ done_out, float* __restrict__ obs_after, float* __restrict__ obs_next,
-    int32_t* __restrict__ legal, int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play,
-    int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.E) return;
-    if (OP == kGmkReset) {
-        if (!mask || mask[e]) gmk_serial_reset(p, e);
-        return;
-    }
-    if (OP == kGmkObserve) {
-        gmk_serial_observe(p, e, obs_after, legal, num_legal, to_play);
-        return;
-    }
+// Game.step of env e by one thread; returns whether the game ended (by its rules or by the move limit)
+__device__ __forceinline__ bool gmk_serial_step(const EnvParams& p, int e, int a, float* __restrict__ reward_out,
+                                                uint8_t* __restrict__ done_out, int32_t* __restrict__ played_out,
+                                                uint32_t* __restrict__ words_out) {
     int8_t* b = p.board + static_cast<size_t>(e) * kGmkCells;
-    int a = actions[e];
     uint32_t words = 0;
     if (opponent_to_move(p, e)) {
         int32_t pos = p.opp_pos[e];
@@ -459,9 +515,102 @@ __global__ __launch_bounds__(256) void gomoku_env_serial_kernel(
     }
     reward_out[e] = reward;
     done_out[e] = done ? 1 : 0;
+    return done;
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void gomoku_env_serial_kernel(
+    EnvParams p, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
+    uint8_t* __restrict__ done_out, float* __restrict__ obs_after, float* __restrict__ obs_next,
+    int32_t* __restrict__ legal, int32_t* __restrict__ num_legal, int32_t* __restrict__ to_play,
+    int32_t* __restrict__ played_out, uint32_t* __restrict__ words_out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.E) return;
+    if (OP == kGmkReset) {
+        if (!mask || mask[e]) gmk_serial_reset(p, e);
+        return;
+    }
+    if (OP == kGmkObserve) {
+        gmk_serial_observe(p, e, obs_after, legal, num_legal, to_play);
+        return;
+    }
+    const bool done = gmk_serial_step(p, e, actions[e], reward_out, done_out, played_out, words_out);
     if (OP == kGmkStep) return;
     gmk_serial_observe(p, e, obs_after, legal, num_legal, to_play);
     if (done) gmk_serial_reset(p, e);
+    gmk_serial_observe(p, e, obs_next, legal, num_legal, to_play);
+}
+
+// ---- paired moves of Gomoku (mzenv_advance_paired): the slot rule of paired_moves.h over the ply functions above -----
+// wavefront form: a slot is collective over the workgroup (gmk_wave_step's barriers), so every wavefront visits every
+// slot; the serial part of a move is lane 0's bounded draw, at most once per opponent slot
+struct GmkWavePairedOps {
+    const EnvParams& p;
+    const PairedOut& out;
+    int e, lane;
+    bool live;
+    int8_t *board, *padded;
+    GmkCells c;
+    int player;
+    int32_t *legal, *num_legal, *to_play;
+    __device__ bool opponent_to_move() const { return p.opp_kind != kOpponentSelf && (player == 1 ? 0 : 1) != p.opp_player; }
+    __device__ void slot(int s, bool play, int a) {
+        const size_t at = static_cast<size_t>(s) * p.E;
+        const bool done = gmk_wave_step(p, e, live && play, lane, board, padded, c, player, a, out.reward + at, out.done + at,
+                                        out.played + at, out.words + at);
+        if (!live) return;
+        if (!play && lane == 0) paired_empty_slot(out, at + e);
+        gmk_write_observation(p, e, lane, c, player, out.obs_after + at * (3 * kGmkCells), legal, num_legal, to_play);
+        if (done) gmk_wave_reset(p, e, lane, board, c, player);
+    }
+};
+
+__global__ __launch_bounds__(64 * kGmkEnvsPerBlock) void gomoku_paired_kernel(EnvParams p, const int32_t* __restrict__ actions,
+                                                                              PairedOut out, float* __restrict__ obs_next,
+                                                                              int32_t* __restrict__ legal,
+                                                                              int32_t* __restrict__ num_legal,
+                                                                              int32_t* __restrict__ to_play) {
+    __shared__ __attribute__((aligned(16))) int8_t padded_all[kGmkEnvsPerBlock][256];  // 225 bytes used per env
+    const int lane = threadIdx.x & 63, group = threadIdx.x >> 6;
+    const int e = blockIdx.x * kGmkEnvsPerBlock + group;
+    const bool live = e < p.E;  // (a wavefront without an env stays for the workgroup barriers and touches no memory)
+    int8_t* board = p.board + static_cast<size_t>(live ? e : 0) * kGmkCells;
+    GmkWavePairedOps ops{p, out, e, lane, live, board, padded_all[group], GmkCells{2, 2}, 1, legal, num_legal, to_play};
+    if (live) {
+        ops.c.b0 = board[lane];
+        if (lane + 64 < kGmkCells) ops.c.b1 = board[64 + lane];
+        ops.player = p.player[e];
+    }
+    paired_move(ops, live ? actions[e] : -1);
+    if (live) gmk_write_observation(p, e, lane, ops.c, ops.player, obs_next, legal, num_legal, to_play);
+}
+
+struct GmkSerialPairedOps {
+    const EnvParams& p;
+    const PairedOut& out;
+    int e;
+    int32_t *legal, *num_legal, *to_play;
+    __device__ bool opponent_to_move() const { return mz::opponent_to_move(p, e); }
+    __device__ void slot(int s, bool play, int a) {
+        const size_t at = static_cast<size_t>(s) * p.E;
+        bool done = false;
+        if (play)
+            done = gmk_serial_step(p, e, a, out.reward + at, out.done + at, out.played + at, out.words + at);
+        else
+            paired_empty_slot(out, at + e);
+        gmk_serial_observe(p, e, out.obs_after + at * (3 * kGmkCells), legal, num_legal, to_play);
+        if (done) gmk_serial_reset(p, e);
+    }
+};
+
+__global__ __launch_bounds__(256) void gomoku_paired_serial_kernel(EnvParams p, const int32_t* __restrict__ actions,
+                                                                   PairedOut out, float* __restrict__ obs_next,
+                                                                   int32_t* __restrict__ legal, int32_t* __restrict__ num_legal,
+                                                                   int32_t* __restrict__ to_play) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.E) return;
+    GmkSerialPairedOps ops{p, out, e, legal, num_legal, to_play};
+    paired_move(ops, actions[e]);
     gmk_serial_observe(p, e, obs_next, legal, num_legal, to_play);
 }
 
@@ -505,6 +654,21 @@ hipError_t launch_env_advance(const EnvParams& p, const int32_t* actions, float*
                                           played, words, stream);
     env_advance_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, reward, done, obs_after, obs_next, legal,
                                                                           num_legal, to_play, played, words);
+    return hipGetLastError();
+}
+hipError_t launch_env_advance_paired(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done,
+                                     float* obs_after, float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play,
+                                     int32_t* played, uint32_t* words, hipStream_t stream) {
+    const PairedOut out{reward, done, obs_after, played, words};
+    if (p.game == 3 && !p.gomoku_serial)
+        gomoku_paired_kernel<<<dim3((p.E + kGmkEnvsPerBlock - 1) / kGmkEnvsPerBlock), dim3(64 * kGmkEnvsPerBlock), 0, stream>>>(
+            p, actions, out, obs_next, legal, num_legal, to_play);
+    else if (p.game == 3)
+        gomoku_paired_serial_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, out, obs_next, legal,
+                                                                                       num_legal, to_play);
+    else
+        env_advance_paired_kernel<<<dim3((p.E + 255) / 256), dim3(256), 0, stream>>>(p, actions, out, obs_next, legal, num_legal,
+                                                                                     to_play);
     return hipGetLastError();
 }
 hipError_t launch_env_observe(const EnvParams& p, float* obs, int32_t* legal, int32_t* num_legal, int32_t* to_play,

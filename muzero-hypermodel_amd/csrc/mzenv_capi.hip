@@ -16,6 +16,9 @@ hipError_t launch_env_step(const EnvParams& p, const int32_t* actions, float* re
 hipError_t launch_env_advance(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done, float* obs_after,
                               float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play, int32_t* played,
                               uint32_t* words, hipStream_t stream);
+hipError_t launch_env_advance_paired(const EnvParams& p, const int32_t* actions, float* reward, uint8_t* done,
+                                     float* obs_after, float* obs_next, int32_t* legal, int32_t* num_legal, int32_t* to_play,
+                                     int32_t* played, uint32_t* words, hipStream_t stream);
 hipError_t launch_env_observe(const EnvParams& p, float* obs, int32_t* legal, int32_t* num_legal, int32_t* to_play,
                               hipStream_t stream);
 hipError_t launch_env_construct(const EnvParams& p, const uint32_t* seeds, hipStream_t stream);
@@ -294,6 +297,24 @@ int mzenv_advance_opponent(mzenv* env, const int32_t* actions, float* reward_out
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     MZENV_HIP(env, mz::launch_env_advance(env->p, actions, reward_out, done_out, obs_after_out, obs_next_out, legal_out,
                                           num_legal_out, to_play_out, played_out, words_out, stream));
+    return 0;
+}
+
+int mzenv_advance_paired(mzenv* env, const int32_t* actions, float* reward_out, uint8_t* done_out, float* obs_after_out,
+                         float* obs_next_out, int32_t* legal_out, int32_t* num_legal_out, int32_t* to_play_out,
+                         int32_t* played_out, uint32_t* words_out, void* stream_) {
+    if (!env || !actions || !reward_out || !done_out || !obs_after_out || !obs_next_out || !legal_out || !num_legal_out ||
+        !to_play_out || !played_out || !words_out)
+        return env_fail(env, -1, "mzenv_advance_paired: null argument");
+    if (env->players < 2) return env_fail(env, -1, "mzenv_advance_paired: a one-player game has no opponent");
+    if (env->p.opp_kind == MZENV_OPPONENT_SELF)
+        return env_fail(env, -1, "mzenv_advance_paired: no opponent is set (mzenv_set_opponent); self-play moves are mzenv_advance's");
+    if (env->p.max_moves == 1 && env->p.opp_player != 0)
+        return env_fail(env, -1, "mzenv_advance_paired: with a move limit of 1 and MuZero playing second every game is the "
+                                 "opponent's opening alone: MuZero would never come to move");
+    MZENV_HIP(env, mz::launch_env_advance_paired(env->p, actions, reward_out, done_out, obs_after_out, obs_next_out, legal_out,
+                                                 num_legal_out, to_play_out, played_out, words_out,
+                                                 static_cast<hipStream_t>(stream_)));
     return 0;
 }
 

@@ -75,6 +75,12 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
         if (h) h->error = "mzhist_file: null argument";
         return -1;
     }
+    const int slots = mv->slots > 1 ? mv->slots : 1;  // plies per move (a paired batch: mzhist_moves.slots)
+    const bool paired = slots > 1;
+    if (paired && (!mv->played || !mv->reset_obs)) {
+        h->error = "mzhist_file: a paired batch needs played and reset_obs";
+        return -1;
+    }
     const int E = h->E, A = h->A, M = mv->n_moves, obs = h->obs;
     const size_t L = h->L, L1 = L + 1;
     const double S = static_cast<double>(mv->num_simulations);
@@ -100,19 +106,25 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
                 // the legal sets come back from the device: nothing of them is used as an index before it was checked
                 const int32_t* legal = reinterpret_cast<const int32_t*>(at(mv->legal, mv->legal_stride, m)) + static_cast<size_t>(e) * A;
                 const int n_legal = reinterpret_cast<const int32_t*>(at(mv->num_legal, mv->num_legal_stride, m))[e];
-                if (n_legal < 0 || n_legal > A) {
-                    bad_legal.store(true);
-                } else {
-                    for (int i = 0; i < n_legal; ++i)
-                        if (legal[i] < 0 || legal[i] >= A) bad_legal.store(true);
-                }
-                local_searched += n_legal > 0 ? 1 : 0;
-                ++len;
-                if (len > h->L) overflow.store(true);
-                if (mv->done[static_cast<size_t>(m) * E + e]) {
-                    ++count;
-                    local_longest = std::max(local_longest, len);
-                    len = 0;
+                for (int s = 0; s < slots; ++s) {
+                    const size_t me = (static_cast<size_t>(m) * slots + s) * E + e;
+                    if (paired && mv->played[me] < 0) continue;  // an empty slot
+                    if (s == 0) {
+                        if (n_legal < 0 || n_legal > A) {
+                            bad_legal.store(true);
+                        } else {
+                            for (int i = 0; i < n_legal; ++i)
+                                if (legal[i] < 0 || legal[i] >= A) bad_legal.store(true);
+                        }
+                        local_searched += n_legal > 0 ? 1 : 0;
+                    }
+                    ++len;
+                    if (len > h->L) overflow.store(true);
+                    if (mv->done[me]) {
+                        ++count;
+                        local_longest = std::max(local_longest, len);
+                        len = 0;
+                    }
                 }
             }
             h->fin_count[e] = count;
@@ -158,40 +170,48 @@ int mzhist_file(mzhist* h, const mzhist_moves* mv, int32_t* n_finished) {
             int out_slot = h->fin_offset[e];
             const int k = std::min(mv->moves_done[e], M);
             for (int m = 0; m < k; ++m) {
-                const size_t me = static_cast<size_t>(m) * E + e;
                 const int32_t* visits = reinterpret_cast<const int32_t*>(at(mv->visits, mv->visits_stride, m)) + static_cast<size_t>(e) * A;
                 const int32_t* legal = reinterpret_cast<const int32_t*>(at(mv->legal, mv->legal_stride, m)) + static_cast<size_t>(e) * A;
                 const int n_legal = reinterpret_cast<const int32_t*>(at(mv->num_legal, mv->num_legal_stride, m))[e];
-                double* cv = row_cv + static_cast<size_t>(len) * A;
-                for (int a = 0; a < A; ++a) cv[a] = 0.0;
-                for (int i = 0; i < n_legal; ++i) cv[legal[i]] = static_cast<double>(visits[i]) / S;
-                if (mv->played && n_legal == 0) {   // an opponent's ply: no search statistics (see mzhist_moves.played)
-                    row_rv[len] = std::numeric_limits<double>::quiet_NaN();
-                    row_act[len + 1] = mv->played[me];
-                } else {
-                    row_rv[len] = reinterpret_cast<const double*>(at(mv->root_value_sum, mv->root_value_sum_stride, m))[e] / S;
-                    row_act[len + 1] = reinterpret_cast<const int32_t*>(at(mv->actions, mv->actions_stride, m))[e];
-                }
-                row_rew[len + 1] = mv->rewards[me];
-                std::memcpy(row_obs + static_cast<size_t>(len + 1) * obs, mv->obs_after + me * obs, sizeof(float) * obs);
-                row_tp[len + 1] = mv->to_play_after ? mv->to_play_after[me] : 0;
-                ++len;
-                if (mv->done[me]) {
-                    const size_t o = static_cast<size_t>(out_slot);
-                    h->fin_env[o] = e;
-                    h->fin_length[o] = len;
-                    std::memcpy(h->fin_observations.data() + o * W1 * obs, row_obs, sizeof(float) * (len + 1) * obs);
-                    std::memcpy(h->fin_actions.data() + o * W1, row_act, sizeof(int32_t) * (len + 1));
-                    std::memcpy(h->fin_rewards.data() + o * W1, row_rew, sizeof(float) * (len + 1));
-                    std::memcpy(h->fin_to_play.data() + o * W1, row_tp, sizeof(int32_t) * (len + 1));
-                    std::memcpy(h->fin_child_visits.data() + o * W * A, row_cv, sizeof(double) * len * A);
-                    std::memcpy(h->fin_root_values.data() + o * W, row_rv, sizeof(double) * len);
-                    ++out_slot;
-                    len = 0;
-                    std::memcpy(row_obs, mv->obs_next + me * obs, sizeof(float) * obs);  // the reset observation
-                    row_act[0] = 0;
-                    row_rew[0] = 0.f;
-                    row_tp[0] = mv->to_play_next ? mv->to_play_next[me] : 0;
+                for (int s = 0; s < slots; ++s) {
+                    const size_t me = (static_cast<size_t>(m) * slots + s) * E + e;
+                    if (paired && mv->played[me] < 0) continue;  // an empty slot files nothing
+                    // an opponent's ply has no search statistics (see mzhist_moves.played): a later slot of a paired move,
+                    // or an empty legal set where the batch names the played actions
+                    const bool opponent_ply = s > 0 || (!paired && mv->played && n_legal == 0);
+                    double* cv = row_cv + static_cast<size_t>(len) * A;
+                    for (int a = 0; a < A; ++a) cv[a] = 0.0;
+                    if (s == 0)
+                        for (int i = 0; i < n_legal; ++i) cv[legal[i]] = static_cast<double>(visits[i]) / S;
+                    if (opponent_ply) {
+                        row_rv[len] = std::numeric_limits<double>::quiet_NaN();
+                        row_act[len + 1] = mv->played[me];
+                    } else {
+                        row_rv[len] = reinterpret_cast<const double*>(at(mv->root_value_sum, mv->root_value_sum_stride, m))[e] / S;
+                        row_act[len + 1] = reinterpret_cast<const int32_t*>(at(mv->actions, mv->actions_stride, m))[e];
+                    }
+                    row_rew[len + 1] = mv->rewards[me];
+                    std::memcpy(row_obs + static_cast<size_t>(len + 1) * obs, mv->obs_after + me * obs, sizeof(float) * obs);
+                    row_tp[len + 1] = mv->to_play_after ? mv->to_play_after[me] : 0;
+                    ++len;
+                    if (mv->done[me]) {
+                        const size_t o = static_cast<size_t>(out_slot);
+                        h->fin_env[o] = e;
+                        h->fin_length[o] = len;
+                        std::memcpy(h->fin_observations.data() + o * W1 * obs, row_obs, sizeof(float) * (len + 1) * obs);
+                        std::memcpy(h->fin_actions.data() + o * W1, row_act, sizeof(int32_t) * (len + 1));
+                        std::memcpy(h->fin_rewards.data() + o * W1, row_rew, sizeof(float) * (len + 1));
+                        std::memcpy(h->fin_to_play.data() + o * W1, row_tp, sizeof(int32_t) * (len + 1));
+                        std::memcpy(h->fin_child_visits.data() + o * W * A, row_cv, sizeof(double) * len * A);
+                        std::memcpy(h->fin_root_values.data() + o * W, row_rv, sizeof(double) * len);
+                        ++out_slot;
+                        len = 0;
+                        // the reset observation (a paired move: the env's later slots belong to the new game)
+                        std::memcpy(row_obs, paired ? mv->reset_obs : mv->obs_next + me * obs, sizeof(float) * obs);
+                        row_act[0] = 0;
+                        row_rew[0] = 0.f;
+                        row_tp[0] = (!paired && mv->to_play_next) ? mv->to_play_next[me] : 0;
+                    }
                 }
             }
             h->length[e] = len;

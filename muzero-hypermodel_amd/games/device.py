@@ -21,6 +21,7 @@ MAX_EPISODE_STEPS = {"cartpole": 500, "tictactoe": 9, "connect4": 42, "gomoku": 
                      "simple_grid": 2 ** 31 - 1}
 ONE_PLAYER_GAMES = ("cartpole", "twentyone", "simple_grid")   # every action legal in every state, nobody to play against
 OPPONENT_KINDS = {"self": 0, "expert": 1, "random": 2}      # include/mzenv.h MZENV_OPPONENT_*
+PAIRED_SLOTS = 3                                            # include/mzenv.h MZENV_PAIRED_SLOTS
 
 
 class DeviceEnvs:
@@ -193,6 +194,43 @@ class DeviceEnvs:
         self._check(self._lib.mzenv_advance(self._h, actions.data_ptr(), reward.data_ptr(), done.data_ptr(),
                                             obs_after.data_ptr(), obs_next.data_ptr(), self.legal.data_ptr(),
                                             self.num_legal.data_ptr(), self.to_play.data_ptr(), self._stream()))
+        return obs_next
+
+    def reset_observation(self):
+        """The observation Game.reset() gives in a board game, float32 [C, H, W]: an empty board with the first player
+        (+1) to move -- the same position in every env, which is what lets a paired move, whose outputs show the position
+        after its last ply, start a game's history in the middle of a move."""
+        if self.players < 2:
+            raise NotImplementedError(f"{self.game}: a reset deals from the env's own stream; there is no one reset observation")
+        obs = np.zeros(self.observation_shape, dtype=np.float32)
+        obs[2] = 1.0
+        return obs
+
+    def new_paired_outputs(self, *leading):
+        """Zeroed device tensors for advance_paired, each with the slot axis in front of E (and `leading` in front of
+        that): reward f32, done u8, obs_after f32, played i32, words i32 (u32 bits)."""
+        lead, dev = tuple(leading) + (PAIRED_SLOTS, self.E), self.device
+        return dict(reward=torch.zeros(lead, dtype=torch.float32, device=dev),
+                    done=torch.zeros(lead, dtype=torch.uint8, device=dev),
+                    obs_after=torch.zeros(lead + self.observation_shape, dtype=torch.float32, device=dev),
+                    played=torch.zeros(lead, dtype=torch.int32, device=dev),
+                    words=torch.zeros(lead, dtype=torch.int32, device=dev))
+
+    def advance_paired(self, actions, reward, done, obs_after, obs_next, played, words):
+        """One evaluation move of every env with the opponent's reply inside it, in one launch (include/mzenv.h
+        mzenv_advance_paired): slot 0 is MuZero's ply (actions int32 [E]; < 0 or not MuZero's turn: empty), slots 1 and 2
+        the opponent's plies while it is to move.  reward / done / obs_after / played / words carry the slot axis
+        ([3, E, ...]: new_paired_outputs; played -1 = empty slot); obs_next and this object's legal / num_legal / to_play
+        describe the position the next search sees: MuZero to move in every env.  All actions -1 = the settle launch:
+        only the opponent's pending plies (openings after a reset when MuZero plays second)."""
+        for name, t in (("reward", reward), ("done", done), ("obs_after", obs_after), ("played", played), ("words", words)):
+            if t.shape[:2] != (PAIRED_SLOTS, self.E) or not t.is_contiguous():
+                raise ValueError(f"advance_paired: {name} must be contiguous with shape [{PAIRED_SLOTS}, {self.E}, ...]")
+        self._keep_step = (actions, reward, done, obs_after, obs_next, played, words)
+        self._check(self._lib.mzenv_advance_paired(self._h, actions.data_ptr(), reward.data_ptr(), done.data_ptr(),
+                                                   obs_after.data_ptr(), obs_next.data_ptr(), self.legal.data_ptr(),
+                                                   self.num_legal.data_ptr(), self.to_play.data_ptr(), played.data_ptr(),
+                                                   words.data_ptr(), self._stream()))
         return obs_next
 
     def observe(self, obs=None):

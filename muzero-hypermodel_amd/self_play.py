@@ -483,6 +483,7 @@ class ManyEnvLoop:
     # (opponent, muzero_player) the moves play when a call names none: class-level, because subclasses need not run a
     # base constructor
     _opponent = ("self", 0)
+    _paired = False              # ... and whether the opponent replies inside MuZero's move (set_opponent(paired=True))
 
     def _build_search(self, initial_checkpoint, config, seed, num_envs, device, use_graph):
         """What a single-GPU actor starts from: the checkpoint's network on the device and a search engine of num_envs
@@ -505,21 +506,26 @@ class ManyEnvLoop:
             except (NotImplementedError, RuntimeError):
                 pass
 
-    def set_opponent(self, opponent, muzero_player=None):
+    def set_opponent(self, opponent, muzero_player=None, paired=False):
         """From now on a step() / play_moves() that names no opponent plays `opponent` ("self", "expert" or "random")
         with MuZero as `muzero_player` (None: the config's).  An opponent the actors cannot play is refused by the
-        first move, not here."""
+        first move, not here.
+        paired=True (device actors' move batches only): the opponent replies inside MuZero's move -- one environment
+        launch plays MuZero's ply and the opponent's (games.device.DeviceEnvs.advance_paired), so that every env is
+        searched in every move instead of sitting every other search out.  The games are the same games."""
         self._opponent = (opponent, self.config.muzero_player if muzero_player is None else muzero_player)
+        self._paired = bool(paired)
 
-    def _resolve_opponent(self, opponent, muzero_player):
-        """The (opponent, muzero_player) one call plays: its own arguments, else what set_opponent stored."""
+    def _resolve_opponent(self, opponent, muzero_player, paired=None):
+        """The (opponent, muzero_player, paired) one call plays: its own arguments, else what set_opponent stored."""
         if opponent is None:
             opponent, muzero_player = self._opponent
+            paired = self._paired if paired is None else paired
         elif muzero_player is None:
             muzero_player = self.config.muzero_player
         if opponent not in ("self", "expert", "random"):
             raise NotImplementedError('many-env actors play opponent "self", "expert" or "random" ("human": use SelfPlay)')
-        return (opponent, int(muzero_player)) if opponent != "self" else ("self", 0)
+        return (opponent, int(muzero_player), bool(paired)) if opponent != "self" else ("self", 0, False)
 
     def _loop_state(self):
         st = self.__dict__.get("_loop")
@@ -671,7 +677,10 @@ class BatchedSelfPlay(ManyEnvLoop):
         numpy.random.choice over the legal actions drawn on THAT env's stream -- and no search statistics are stored
         for it (root None: store_search_statistics appends only a None root value, self_play.py:497-512)."""
         cfg = self.config
-        opponent, muzero_player = self._resolve_opponent(opponent, muzero_player)
+        opponent, muzero_player, paired = self._resolve_opponent(opponent, muzero_player)
+        if paired:
+            raise NotImplementedError("paired replies are played by the device environment kernels (DeviceSelfPlay move "
+                                      "batches); host envs play the opponent's ply as a move of its own")
         searching = [opponent == "self" or muzero_player == self.games[e].to_play() for e in range(self.E)]
         stacked = numpy.stack([
             self.histories[e].get_stacked_observations(-1, cfg.stacked_observations)
@@ -826,13 +835,18 @@ class HistoryFiler:
         return numpy.ctypeslib.as_array(self._ct.cast(addr, self._ct.POINTER(self._ct.c_int32)), shape=(self.E,))
 
     def file(self, out, legal, num_legal, num_simulations, rewards, done, obs_after, obs_next, to_play_after=None,
-             to_play_next=None, played=None):
+             to_play_next=None, played=None, slots=1, reset_obs=None):
         """out: engine.moves_collect() result (copies or ring views); legal [E,A] / num_legal [E] for the whole batch or
         [M,E,A] / [M,E] per move (engine.moves_inputs); rewards f32 [M,E], done u8 [M,E],
         obs_after / obs_next f32 [M,E,...] host arrays; to_play_after / to_play_next [M,E] for two-player games.
         played int32 [M,E] (evaluation games: the actions the environment kernels actually played): a ply whose legal
         set is empty is then an opponent's -- its action comes from `played`, its root value is NaN, its child_visits
-        row zero (include/mzhist.h).  Returns PackedGames of the games that ended, or None."""
+        row zero (include/mzhist.h).
+        slots > 1 (a paired batch, games.device.DeviceEnvs.advance_paired): rewards, done, obs_after, to_play_after and
+        played carry the slot axis, [M, slots, E, ...]; a move files up to `slots` plies in up to two games of an env --
+        slot 0 from the search's blocks, the later slots as opponent plies, an empty slot (played < 0) nothing -- and a game
+        that ends inside a move is followed by one that starts from `reset_obs` (f32 observation) with player 0 to move.
+        Returns PackedGames of the games that ended, or None."""
         ct = self._ct
         M = int(out["actions"].shape[0])
         def per_move_rows(a):
@@ -859,12 +873,20 @@ class HistoryFiler:
         mv.rewards, mv.done, mv.obs_after, mv.obs_next = (k.ctypes.data for k in keep[3:7])
         mv.to_play_after = mv.to_play_next = None
         if to_play_after is not None:
-            keep += [numpy.ascontiguousarray(to_play_after, dtype=numpy.int32), numpy.ascontiguousarray(to_play_next, dtype=numpy.int32)]
+            # (a paired batch starts every game with player 0 to move and reads no to_play_next)
+            assert to_play_next is not None or slots > 1
+            keep += [numpy.ascontiguousarray(to_play_after, dtype=numpy.int32),
+                     numpy.ascontiguousarray(to_play_after if to_play_next is None else to_play_next, dtype=numpy.int32)]
             mv.to_play_after, mv.to_play_next = keep[7].ctypes.data, keep[8].ctypes.data
         if played is not None:
             keep.append(numpy.ascontiguousarray(played, dtype=numpy.int32))
-            assert keep[-1].shape == (M, self.E)
+            assert keep[-1].shape == ((M, self.E) if slots <= 1 else (M, slots, self.E))
             mv.played = keep[-1].ctypes.data
+        if slots > 1:
+            keep.append(numpy.ascontiguousarray(reset_obs, dtype=numpy.float32).reshape(self.obs_floats))
+            assert keep[3].shape == keep[4].shape == (M, slots, self.E) and keep[5].shape[:3] == (M, slots, self.E)
+            assert to_play_after is None or keep[7].shape == (M, slots, self.E)
+            mv.slots, mv.reset_obs = int(slots), keep[-1].ctypes.data
         n = ct.c_int32()
         if self._lib.mzhist_file(self._h, ct.byref(mv), ct.byref(n)) != 0:
             raise RuntimeError(self._lib.mzhist_last_error(self._h).decode())
@@ -947,6 +969,7 @@ class UnfiledBatch(typing.NamedTuple):
     to_play_after: typing.Optional[numpy.ndarray] = None    # [M, E]; None: player 0 throughout
     to_play_next: typing.Optional[numpy.ndarray] = None
     played: typing.Optional[numpy.ndarray] = None           # [M, E] evaluation games: what the environment kernels played
+    slots: int = 1                                          # > 1: a paired batch, host / to_play_after / played [M, slots, E, ...]
 
 
 @dataclasses.dataclass(slots=True)
@@ -958,6 +981,8 @@ class DeviceBatch:
     threshold: int               # play_game's temperature threshold (0 / None: none)
     pinned: typing.Optional[dict]    # the host set the outputs are downloaded into, move by move (HostRows.next_set)
     opponent: bool               # evaluation games: the kernels also return the played actions and the words drawn
+    paired: bool = False         # ... and reply inside MuZero's move (advance_paired): the ring's ply outputs carry a slot axis
+    settled: typing.Optional[numpy.ndarray] = None    # plies per env the settle launch in front of the batch played
 
     @property
     def keys(self):
@@ -978,7 +1003,8 @@ class HostRows:
         self.lengths = self.filer.lengths()     # moves played in env e's current game (the filer's own counters)
         self.pending = None                     # UnfiledBatch: collected, not filed yet
         self._copy_stream = torch.cuda.Stream(device=device)    # downloads of a batch's env outputs
-        self._sets, self._flip = None, 0        # their two alternating host sets (next_set)
+        self._sets, self._flip = {}, 0          # their two alternating host sets (next_set), per ring form
+        self._reset_obs = None                  # the observation every game of a board game starts from (paired batches)
 
     def admit(self, step=False, on_game=None, opponent="self", batched_pass=True):
         pass                                    # host rows take every way of playing
@@ -992,14 +1018,37 @@ class HostRows:
     def searched_moves(self, moves_played):
         return self.filer.searched_moves()
 
-    def ring_resized(self, ring):
-        self._sets = [{k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
+    def ring_resized(self, ring, paired=False):
+        self._sets[paired] = [{k: torch.zeros(v.shape, dtype=v.dtype).pin_memory() for k, v in ring.items()} for _ in range(2)]
 
-    def next_set(self):
+    def next_set(self, paired=False):
         """The host set a batch's env outputs are downloaded into (after ring_resized): two alternate, so that the batch
-        waiting to be filed keeps its own."""
+        waiting to be filed keeps its own.  A paired batch's ring has a form of its own (a slot axis), and so have its sets."""
         self._flip ^= 1
-        return self._sets[self._flip]
+        return self._sets[paired][self._flip]
+
+    def _file_kwargs(self, slots):
+        """What a paired batch's filing needs beyond the batch: the slot count and the observation games start from."""
+        if slots <= 1:
+            return {}
+        if self._reset_obs is None:
+            self._reset_obs = self.envs.reset_observation()
+        return dict(slots=slots, reset_obs=self._reset_obs)
+
+    def file_settled(self, host):
+        """The plies of a settle launch (advance_paired with no action: the opponent's pending plies, e.g. its openings)
+        are plies of the games: filed as a paired move whose searched slot is empty.  host: the launch's outputs,
+        [slots, E, ...] host arrays.  Returns the games they finished (PackedGames or None)."""
+        E, A, slots = self.envs.E, self.envs.A, host["played"].shape[0]
+        assert not (host["played"][0] >= 0).any()
+        none = {"actions": numpy.full((1, E), -1, dtype=numpy.int32), "visits": numpy.zeros((1, E, A), dtype=numpy.int32),
+                "root_value_sum": numpy.zeros((1, E), dtype=numpy.float64), "moves_done": numpy.ones(E, dtype=numpy.int32)}
+        self.engine.rng_consumed(host["words"].view(numpy.uint32).sum(axis=0, dtype=numpy.uint64))
+        mzp = int(self.envs.opponent[1])
+        return self.filer.file(none, numpy.zeros((E, A), dtype=numpy.int32), numpy.zeros(E, dtype=numpy.int32),
+                               self.config.num_simulations, host["reward"][None], host["done"][None], host["obs_after"][None],
+                               host["obs_after"][None, 0], to_play_after=numpy.full((1, slots, E), mzp, dtype=numpy.int32),
+                               played=host["played"][None], **self._file_kwargs(slots))
 
     def download_move(self, b, m):
         # the env outputs of a move (reward, done, the observations the history rows need) go to pinned host memory on a
@@ -1029,7 +1078,7 @@ class HostRows:
             return None
         return self.filer.file(u.out, u.legal, u.num_legal, self.config.num_simulations, u.host["reward"], u.host["done"],
                                u.host["obs_after"], u.host["obs_next"], to_play_after=u.to_play_after,
-                               to_play_next=u.to_play_next, played=u.played)
+                               to_play_next=u.to_play_next, played=u.played, **self._file_kwargs(u.slots))
 
     # the batch before's games leave once the current batch has been enqueued, so that host filing runs under the GPU,
     # and before moves_collect overwrites the engine ring the UnfiledBatch views
@@ -1060,15 +1109,23 @@ class HostRows:
         host = {k: b.pinned[k][:b.n_moves].numpy() for k in b.keys}
         played = None
         if b.opponent:
-            # the opponents drew on the device copies of the streams: the host mirrors step over those words
+            # the opponents drew on the device copies of the streams: the host mirrors step over those words (a paired
+            # batch: summed over the moves and their slots)
             played = host["played"]
-            self.engine.rng_consumed(host["words"].view(numpy.uint32).sum(axis=0, dtype=numpy.uint64))
+            words = host["words"].view(numpy.uint32)
+            self.engine.rng_consumed(words.reshape(-1, words.shape[-1]).sum(axis=0, dtype=numpy.uint64))
         two_players = len(self.config.players) > 1
         to_play = inputs["to_play"]
         to_play_after = (1 - to_play) if two_players else numpy.zeros_like(to_play)
         to_play_next = numpy.concatenate([to_play[1:], last_to_play[None]], axis=0)
+        slots = 1
+        if b.paired:
+            # slot 0 is MuZero's ply, after which the opponent is to move; after an opponent's ply (slots 1, 2) MuZero is
+            slots = played.shape[1]
+            to_play_after = numpy.stack([to_play_after] + [to_play] * (slots - 1), axis=1)
         self.pending = UnfiledBatch(out=out, host=host, legal=inputs["legal"], num_legal=inputs["num_legal"],
-                                    to_play_after=to_play_after, to_play_next=to_play_next, played=played)
+                                    to_play_after=to_play_after, to_play_next=to_play_next, played=played, slots=slots)
+        return (played >= 0).sum(axis=(0, 1)) if b.paired else None
 
 
 class StoreRows:
@@ -1208,6 +1265,9 @@ class DeviceSelfPlay(ManyEnvLoop):
         self._batch_ready = None                # (n_moves, temperature) of the batch drawn and uploaded ahead (play_moves)
         self._dev_batch = None                  # DeviceBatch being queued
         self._ring = None                       # env outputs of a batch on the device, sized by the first batch (_move_ring)
+        self._paired_ring = None                # ... of a paired batch: the ply outputs carry a slot axis (_move_ring)
+        self._paired_on = False                 # the envs are in paired mode: MuZero is to move in every env
+        self._settle = None                     # the settle launch's outputs (paired mode taken up: _settle_paired)
         # config.stacked_observations = n > 0: the n previous frames of every env live in a device frame stack
         # (include/mzenv.h mzenv_stack_*).  The plain observations stay what is filed and stored everywhere; only what
         # the searches read changes: `_stacked`, which every move's push rewrites on the actor's stream.  n = 0: no
@@ -1334,11 +1394,38 @@ class DeviceSelfPlay(ManyEnvLoop):
         limit = limit if limit < self.envs.max_episode_steps else 0
         if self.envs.max_moves != limit:
             self.envs.set_max_moves(limit)
-        if self.envs.opponent == mode:
-            return
+        paired_before, self._paired_on = self._paired_on, mode[2]
+        if self.envs.opponent == mode[:2]:
+            return mode[2] and not paired_before
         self.envs.set_opponent(mode[0], mode[1], self.engine)
         obs, _, _, _ = self.envs.observe()
         self._cur = dict(obs_dev=obs, on_device_only=True)
+        return mode[2]      # paired mode taken up: the opponent's pending plies come first (_settle_paired)
+
+    def _paired_check(self, temperature_threshold):
+        """What a paired batch leaves out of scope: say which condition rules it out."""
+        if temperature_threshold:
+            raise NotImplementedError("paired mode with a non-zero temperature_threshold: the engine's per-game ply counter "
+                                      "does not see the opponent's replies; play the sit-out mode (paired=False)")
+        if self._stack is not None:
+            raise NotImplementedError("paired mode with stacked_observations > 0: the frame stack pushes one ply per move; "
+                                      "play the sit-out mode (paired=False)")
+
+    def _settle_paired(self, on_game, on_games):
+        """Paired mode was taken up (or the side MuZero plays changed): one advance_paired launch with no action plays the
+        opponent's pending plies -- its openings after a reset when MuZero plays second -- so that MuZero is to move in
+        every env.  The plies are filed like any other; returns (the observation the first search reads, plies per env)."""
+        envs = self.envs
+        if self._settle is None:
+            self._settle = dict(envs.new_paired_outputs(), obs_next=torch.zeros_like(envs.obs),
+                                actions=torch.full((self.E,), -1, dtype=torch.int32, device=self.device))
+        st = self._settle
+        envs.advance_paired(st["actions"], st["reward"], st["done"], st["obs_after"], st["obs_next"], st["played"], st["words"])
+        host = {k: st[k].cpu().numpy() for k in ("reward", "done", "obs_after", "played", "words")}
+        self._hand_out(self._rows.file_settled(host), on_game, on_games)
+        plies = (host["played"] >= 0).sum(axis=0)
+        self.moves_played += int(plies.sum())
+        return st["obs_next"], plies
 
     def _opponent_step_check(self, temperature):
         """An opponent's plies exist in the device-input form of a move batch only: say what rules it out."""
@@ -1358,6 +1445,9 @@ class DeviceSelfPlay(ManyEnvLoop):
         is queued here (search, action sampling, env step: a one-move batch), so the temperature is needed already."""
         self._rows.admit(step=True)
         mode = self._resolve_opponent(opponent, muzero_player)
+        if mode[2]:
+            raise NotImplementedError("step() in paired mode: a paired move exists as a move batch only; "
+                                      "use play_moves(1, ...)")
         if mode[0] != "self":
             if temperature is None:
                 raise ValueError("step_begin against an opponent samples the action on the device: pass temperature")
@@ -1435,7 +1525,7 @@ class DeviceSelfPlay(ManyEnvLoop):
 
     # ---- whole batches of moves on the device (engine.moves_*, include/mzmcts.h) ---------------------------
     def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, opponent=None,
-                   muzero_player=None):
+                   muzero_player=None, paired=None):
         """`n_moves` moves of every env with no host round trip in between: search (which samples the action),
         env step, terminal observation, reset of finished envs, next observation -- all queued on one stream.
         Fully-connected networks search in the fused whole-move kernel (games with a constant legal set: the exploration
@@ -1446,9 +1536,11 @@ class DeviceSelfPlay(ManyEnvLoop):
         Games end where play_game ends them: by the game's rules or at config.max_moves plies, whichever comes first --
         the environment kernels apply both (DeviceEnvs.set_max_moves), so a limit costs a batch nothing.
         `opponent` / `muzero_player` as in step(): an opponent's plies are played by the environment kernels inside the
-        batch (always its device-input form; every env then plays all n_moves plies)."""
+        batch (always its device-input form; every env then plays all n_moves plies).  `paired` (default: what
+        set_opponent stored): the opponent replies inside MuZero's move, so every env is searched in every move and
+        plays up to three plies per move; the return value then counts plies per env."""
         E, eng, envs, cfg = self.E, self.engine, self.envs, self.config
-        mode = self._resolve_opponent(opponent, muzero_player)
+        mode = self._resolve_opponent(opponent, muzero_player, paired)
         self._rows.admit(on_game=on_game, opponent=mode[0])
         self._rows.queue()                                   # (store rows) the batch before: ahead of anything this one rewrites
         # Everything but a fused search of a game with a constant legal set takes the device-input form of the batch:
@@ -1495,35 +1587,44 @@ class DeviceSelfPlay(ManyEnvLoop):
         return out["moves_done"].copy()
 
     def _play_moves_device_inputs(self, n_moves, temperature, on_game, on_games, temperature_threshold=None,
-                                  opponent=None, muzero_player=None):
+                                  opponent=None, muzero_player=None, paired=None):
         """play_moves with the batch's inputs on the device: the searches read the legal sets and players to move from the
         environment kernels' device outputs and draw their exploration noise on the device (engine.moves_prepare_device),
         so a whole batch -- games ending and restarting inside it -- is queued without the host; afterwards every move
         is filed with the legal set it was searched with.  The search of a move is the fused whole-move kernel
         (fully-connected networks) or the lock-step loop with this actor's network (residual networks)."""
-        self._device_batch_begin(n_moves, temperature, on_game, on_games, temperature_threshold, opponent, muzero_player)
+        self._device_batch_begin(n_moves, temperature, on_game, on_games, temperature_threshold, opponent, muzero_player,
+                                 paired)
         for m in range(n_moves):
             self._device_batch_move(m)
         return self._device_batch_end(on_game, on_games)
 
     # (the three phases are separate so that PipelinedDeviceSelfPlay can interleave the batches of its groups move by move)
     def _device_batch_begin(self, n_moves, temperature, on_game, on_games, temperature_threshold, opponent=None,
-                            muzero_player=None):
+                            muzero_player=None, paired=None):
         eng, envs = self.engine, self.envs
-        mode = self._resolve_opponent(opponent, muzero_player)
+        mode = self._resolve_opponent(opponent, muzero_player, paired)
+        paired = mode[2]
+        if paired:
+            self._paired_check(temperature_threshold)
         if self._batch_ready or temperature_threshold:
             # a batch of the pre-drawn form is waiting to be filed / the threshold rule needs the games' current lengths
             self.flush(on_game, on_games)
         self._drop_batch()
-        self._set_env_mode(mode)
+        settled = None
+        if self._set_env_mode(mode):
+            self.flush(on_game, on_games)                    # (the settle launch's plies are filed behind all played so far)
+            obs, settled = self._settle_paired(on_game, on_games)
+            self._cur = dict(obs_dev=obs, on_device_only=True)
         eng.moves_prepare_device(n_moves, envs.legal, envs.num_legal, envs.to_play, temperature, True)
-        if mode[0] != "self":
+        if mode[0] != "self" and not paired:
             eng.moves_sit_out(True)        # the opponent's plies: played by the environment kernels, filed from `played`
         if temperature_threshold:
             eng.moves_temperature_threshold(temperature_threshold, self._len)
-        ring = self._move_ring(n_moves)
+        ring = self._move_ring(n_moves, paired)
         self._dev_batch = DeviceBatch(n_moves=n_moves, ring=ring, obs_in=self._cur["obs_dev"], threshold=temperature_threshold,
-                                      pinned=self._rows.next_set(), opponent=mode[0] != "self")
+                                      pinned=self._rows.next_set(paired) if paired else self._rows.next_set(),
+                                      opponent=mode[0] != "self", paired=paired, settled=settled)
 
     def _device_batch_move(self, m):
         b, eng, envs = self._dev_batch, self.engine, self.envs
@@ -1536,9 +1637,14 @@ class DeviceSelfPlay(ManyEnvLoop):
         else:
             eng.moves_enqueue_lockstep(self.model, search_input)
         b.obs_in = self._frame_before(b.obs_in, ring["obs_next"][m])
-        obs_next = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
-                                ring["obs_next"][m], played=ring["played"][m] if b.opponent else None,
-                                words=ring["words"][m] if b.opponent else None)
+        if b.paired:
+            # MuZero's ply and the opponent's reply (and what follows a game's end) in one launch: MuZero is to move again
+            obs_next = envs.advance_paired(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
+                                           ring["obs_next"][m], ring["played"][m], ring["words"][m])
+        else:
+            obs_next = envs.advance(eng.moves_actions(m), ring["reward"][m], ring["done"][m], ring["obs_after"][m],
+                                    ring["obs_next"][m], played=ring["played"][m] if b.opponent else None,
+                                    words=ring["words"][m] if b.opponent else None)
         if self._stack is not None:
             # an opponent's ply is a ply of the game: the action the env kernels played, not the search's (-1 there:
             # a full board on the opponent's turn leaves the env alone)
@@ -1554,12 +1660,17 @@ class DeviceSelfPlay(ManyEnvLoop):
         out = self.engine.moves_collect(copy=False)
         # store rows: the batch before's games (filed ahead of this batch)
         self._hand_out(self._rows.games_after_collect(), on_game, on_games)
-        self._rows.keep_device_inputs(out, b)
+        plies = self._rows.keep_device_inputs(out, b)
         # the envs' current positions stay on the device: the next batch starts from the last move's observation (the
         # kernels' output, where it lies); a step() fetches what it needs first (_current)
         self._cur = dict(obs_dev=b.obs_in, on_device_only=True)
-        self.moves_played += int(out["moves_done"].sum())
-        return out["moves_done"].copy()
+        if plies is None:
+            self.moves_played += int(out["moves_done"].sum())
+            return out["moves_done"].copy()
+        # a paired batch: every env was searched in every move and played up to three plies per move (the plies of a
+        # settle launch in front of the batch were counted there and are reported with it)
+        self.moves_played += int(plies.sum())
+        return (plies if b.settled is None else plies + b.settled).astype(out["moves_done"].dtype)
 
     def _batchable(self, temperature, temperature_threshold, moves_per_pass, device_inputs=None):
         """Can a pass of `moves_per_pass` moves run as one move batch on the device (play_moves)?"""
@@ -1602,7 +1713,17 @@ class DeviceSelfPlay(ManyEnvLoop):
             self.engine.moves_collect()
             self._batch_ready = None
 
-    def _move_ring(self, n_moves):
+    def _move_ring(self, n_moves, paired=False):
+        if paired:
+            # the same ring with a slot axis on what a ply produces; the sit-out ring keeps its shape
+            ring = self._paired_ring
+            if ring is None or ring["reward"].shape[0] < n_moves:
+                ring = dict(self.envs.new_paired_outputs(n_moves),
+                            obs_next=torch.zeros((n_moves, self.E) + self.envs.observation_shape, dtype=torch.float32,
+                                                 device=self.device))
+                self._rows.ring_resized(ring, paired=True)
+                self._paired_ring = ring
+            return ring
         ring = self._ring
         if ring is None or ring["reward"].shape[0] < n_moves:
             shape, dev = self.envs.observation_shape, self.device
@@ -1756,6 +1877,9 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         group, queued on the groups' streams in turn; nothing is prefetched."""
         self._no_batch_queued("step")
         mode = self._resolve_opponent(opponent, muzero_player)
+        if mode[2]:
+            raise NotImplementedError("step() in paired mode: a paired move exists as a move batch only; "
+                                      "use play_moves(1, ...)")
         if mode[0] != "self":
             if any(self._started):
                 raise RuntimeError("step against an opponent: a search is queued ahead; call step(..., prefetch=False) first")
@@ -1768,7 +1892,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         for g, actor in enumerate(self.actors):
             if not self._started[g]:
                 with torch.cuda.stream(self.streams[g]):
-                    actor.step_begin(*self._callbacks(g, on_game, on_games), *mode)
+                    actor.step_begin(*self._callbacks(g, on_game, on_games), *mode[:2])
                 self._started[g] = True
         for g, actor in enumerate(self.actors):
             one, many = self._callbacks(g, on_game, on_games)
@@ -1776,11 +1900,11 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
                 actor.step_end(temperature, temperature_threshold, one, many)
                 self._started[g] = False
                 if prefetch:
-                    actor.step_begin(one, many, *mode)   # the next move's search runs while the other groups are served
+                    actor.step_begin(one, many, *mode[:2])   # the next move's search runs while the other groups are served
                     self._started[g] = True
 
     def play_moves(self, n_moves, temperature, on_game=None, on_games=None, temperature_threshold=None, prefetch=False,
-                   opponent=None, muzero_player=None):
+                   opponent=None, muzero_player=None, paired=None):
         """`n_moves` moves of every env of every group with no host round trip (DeviceSelfPlay.play_moves in its
         device-input form): each group's batch is queued on the group's own stream, move by move in turn, so the
         kernels of the groups fill each other's gaps (a tower workgroup's fill / epilogue / export phases leave the matrix
@@ -1792,7 +1916,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
         call returns was queued by the call before (with that call's parameters and the weights of that time), and
         the last call before the weights change passes prefetch=False.
         `opponent` / `muzero_player` as in DeviceSelfPlay.play_moves (a prefetched batch plays what its call asked for)."""
-        mode = self._resolve_opponent(opponent, muzero_player)      # (the groups are told: they keep none of their own)
+        mode = self._resolve_opponent(opponent, muzero_player, paired)      # (the groups are told: they keep none of their own)
         if temperature_threshold is None:
             temperature_threshold = self.config.temperature_threshold
         queued = self._batch_queued
@@ -1865,7 +1989,7 @@ class PipelinedDeviceSelfPlay(ManyEnvLoop):
 
 def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_player=None, num_envs=64, seed=0,
              device=None, moves_per_batch=8, groups=1, use_graph=True, warmup_batches=0, temperature=0,
-             device_temperatures=False):
+             device_temperatures=False, paired=False):
     """`MuZero.test` (reference muzero.py:346-396) on device-resident envs: `num_tests` games at temperature 0 and
     temperature threshold 0 (play_game(0, 0, False, opponent, muzero_player)), `num_envs` of them at a time, env e on
     the game and RNG stream of reference worker `seed + e`.
@@ -1885,6 +2009,13 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
     `temperature` (MuZero.test plays at 0) samples MuZero's moves instead of taking the most visited one;
     `device_temperatures` switches set_device_temperatures on, so that a temperature other than 0, inf and 1 / k runs as
     batches (against an opponent it cannot run at all without it).
+
+    `paired` (against an opponent only): the opponent replies inside MuZero's move (set_opponent(paired=True)), so that
+    every env is searched in every move of a batch instead of sitting every other search out.  Every env plays the games
+    it plays in the sit-out mode, so with warmup_batches = 0 everything below but `seconds`, `env_moves`, `searched_moves`
+    and `simulations` (the envs run on until the counted games are over, which the two modes reach at different points)
+    is the sit-out mode's; warm-up batches cover about twice the plies here, so the games counted after them begin at other
+    points of each env's sequence.  Needs move batches.
 
     Returns a dict: `result` is MuZero.test's number (one player: mean total reward; otherwise the mean of the rewards
     earned on muzero_player's moves), `muzero_reward` / `opponent_reward` the means per side (two players),
@@ -1907,7 +2038,8 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
         probe = actor.actors[0]
     else:
         actor = probe = DeviceSelfPlay(checkpoint, game_name, cfg, seed, E, device=device, use_graph=use_graph)
-    actor.set_opponent(opponent, muzero_player)
+    paired = bool(paired) and opponent != "self"
+    actor.set_opponent(opponent, muzero_player, paired=paired)
     if device_temperatures:
         actor.set_device_temperatures(True)
     clock = numpy.zeros(E, dtype=numpy.int64)          # plies of env e's finished games
@@ -1935,6 +2067,9 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
 
     # the pipelined actor's batches always take the device-input form
     batched = probe._batchable(temperature, 0, moves_per_batch, device_inputs=True if groups > 1 else None)
+    if paired and not batched:
+        raise NotImplementedError("evaluate(paired=True) plays move batches: give moves_per_batch, a temperature the batches "
+                                  "sample on the device and 0 < root_dirichlet_alpha <= 1")
 
     def play():
         if batched:
@@ -1976,7 +2111,7 @@ def evaluate(checkpoint, game_name, config, num_tests, opponent=None, muzero_pla
     col = {k: numpy.concatenate(v)[pick] for k, v in found.items()}
     out = dict(games=int(len(pick)), mean_episode_length=float(col["length"].mean()), env_moves=int(env_moves),
                searched_moves=int(searched), simulations=int(searched) * int(cfg.num_simulations), seconds=seconds,
-               opponent=opponent, muzero_player=int(muzero_player), num_envs=E)
+               opponent=opponent, muzero_player=int(muzero_player), num_envs=E, paired=paired)
     if two_players:
         out.update(result=float(col["mine"].mean()), muzero_reward=float(col["mine"].mean()),
                    opponent_reward=float(col["theirs"].mean()), wins=int((col["mine"] > col["theirs"]).sum()),

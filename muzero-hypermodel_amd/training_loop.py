@@ -49,19 +49,21 @@ def game_config(game_name, overrides=None):
 class TrainingLoop:
     def __init__(self, game_name, config, envs, moves_per_iteration, train_steps_per_iteration, seed, reanalyse_games=0,
                  eval_every=0, eval_games=0, eval_opponent=None, groups=1, trainer_flags=None, device_filing=True,
-                 log=None):
+                 log=None, eval_paired=False):
         """`config`: a games.*.MuZeroConfig (game_config()).  `envs` device envs play `moves_per_iteration` plies each per
         iteration, then `train_steps_per_iteration` steps are trained.  `groups` > 1: a PipelinedDeviceSelfPlay.
         `trainer_flags`: Trainer's keyword flags verbatim (default: graph=True, and fc_step / fc_optimizer for a
         fully-connected network); what the trainer refuses it says itself.  device_filing=False plays the same games
         through on_games -> save_games and asks the store for their outcomes (ReplayBuffer.game_outcomes): the twin the
-        tests compare against.  `log`: called with a line of text for the few things the loop decides on its own."""
+        tests compare against.  eval_paired=True: evaluation games against an opponent let it reply inside MuZero's move
+        (self_play.evaluate(paired=True)): the same games and `eval` numbers in less GPU time; off by default.  `log`: called with a line of text for the few things the loop decides on its own."""
         if game_name not in DEVICE_GAMES:
             raise ValueError(f"no device game {game_name!r}: one of {', '.join(DEVICE_GAMES)}")
         self.game_name, self.config, self.seed = game_name, config, int(seed)
         self.moves, self.steps = int(moves_per_iteration), int(train_steps_per_iteration)
         self.reanalyse_games, self.device_filing = int(reanalyse_games), bool(device_filing)
         self.eval_every, self.eval_games = int(eval_every), int(eval_games)
+        self.eval_paired = bool(eval_paired)
         self._say = log or (lambda line: None)
         config.seed = self.seed
         fully_connected = config.network == "fullyconnected"
@@ -181,7 +183,8 @@ class TrainingLoop:
         """self_play.evaluate with the trainer's weights: the reference's five test metrics."""
         weights = {k: v.detach().cpu().clone() for k, v in self.trainer.model.state_dict().items()}
         out = self_play.evaluate({"weights": weights}, self.game_name, self.config, self.eval_games,
-                                 opponent=self.eval_opponent, num_envs=min(64, self.eval_games), seed=self.seed)
+                                 opponent=self.eval_opponent, num_envs=min(64, self.eval_games), seed=self.seed,
+                                 paired=self.eval_paired and self.eval_opponent not in (None, "self"))
         return dict(total_reward=out["result"], episode_length=out["mean_episode_length"],
                     muzero_reward=out["muzero_reward"], opponent_reward=out["opponent_reward"], games=out["games"],
                     opponent=out["opponent"])

@@ -2,14 +2,15 @@
 
     python tools/evaluate.py --game tictactoe --envs 65536 --tests 200000 [--opponent expert] [--muzero-player 0]
                              [--fc 0] [--batch 8] [--groups 1] [--warmup-batches 3] [--compare-self] [--max-moves N]
-                             [--temperature 0.35 --device-temperatures]
+                             [--temperature 0.35 --device-temperatures] [--paired]
 
 Prints one JSON line: self_play.evaluate's result (MuZero.test's number, rewards per side, win / draw / loss counts, mean
-episode length) with games per second, env-moves per second, simulations per second and the share of env-moves that
-sat a search out (searched plies are counted by the history filer, not estimated).  The warm-up batches run on the actor
+episode length) with games per second, env-moves per second, simulations per second, the share of plies the opponent
+played and the share of env-moves that sat a search out (searched plies are counted by the history filer, not estimated).  The warm-up batches run on the actor
 that is timed afterwards (buffers, hipGraph capture and filer are set up in them); a rate is worth quoting when
 `seconds` is at least one -- raise --tests otherwise.  --compare-self adds the same command line played as "self"
-(every ply searched) for the ratio.
+(every ply searched) for the ratio.  --paired: the opponent replies inside MuZero's move, so no env sits a search out
+(the same games); with --compare-self the sit-out mode of the same command line is added as "sit_out" beside "self".
 Weights are the seed-0 initialisation unless --weights points to a checkpoint (torch.save of {"weights": ...})."""
 import argparse
 import importlib
@@ -24,14 +25,16 @@ sp = importlib.import_module("muzero-hypermodel_amd.self_play")
 models = importlib.import_module("muzero-hypermodel_amd.models")
 
 
-def run(args, config, checkpoint, opponent, num_tests):
+def run(args, config, checkpoint, opponent, num_tests, paired=False):
     out = sp.evaluate(checkpoint, args.game, config, num_tests, opponent=opponent, muzero_player=args.muzero_player,
                       num_envs=args.envs, seed=args.seed, moves_per_batch=args.batch, groups=args.groups,
                       warmup_batches=args.warmup_batches, temperature=args.temperature,
-                      device_temperatures=args.device_temperatures)
+                      device_temperatures=args.device_temperatures, paired=paired)
     s = out["seconds"]
     out.update(games_per_s=out["games"] / s, env_moves_per_s=out["env_moves"] / s, simulations_per_s=out["simulations"] / s,
-               sat_out_share=1.0 - out["searched_moves"] / max(1, out["env_moves"]))
+               opponent_ply_share=1.0 - out["searched_moves"] / max(1, out["env_moves"]))
+    # (sit-out mode: an opponent's ply is an env that sat a search out; paired mode: no env sits a search out)
+    out["sat_out_share"] = 0.0 if out.get("paired") else out["opponent_ply_share"]
     return out
 
 
@@ -53,6 +56,8 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0, help="softmax temperature of MuZero's moves (MuZero.test: 0)")
     ap.add_argument("--device-temperatures", action="store_true", help="a temperature other than 0, inf and 1 / k, k = 1..4, "
                     "sampled on the GPU: batches (and plies against an opponent at all) instead of one move per round trip")
+    ap.add_argument("--paired", action="store_true", help="the opponent replies inside MuZero's move: every env is searched "
+                    "in every move (evaluate(paired=True))")
     ap.add_argument("--max-moves", type=int, default=None, help="end games after N plies (config.max_moves; default: the "
                     "config's)")
     args = ap.parse_args()
@@ -70,11 +75,14 @@ def main():
         torch.manual_seed(0)
         checkpoint = {"weights": models.MuZeroNetwork(config).get_weights()}
     opponent = args.opponent if args.opponent is not None else config.opponent
-    line = run(args, config, checkpoint, opponent, args.tests)
+    line = run(args, config, checkpoint, opponent, args.tests, paired=args.paired)
     line.update(game=args.game, network=config.network, max_moves=config.max_moves)
     if args.compare_self and opponent != "self":
         line["self"] = run(args, config, checkpoint, "self", args.tests)
         line["simulations_vs_self"] = line["simulations_per_s"] / line["self"]["simulations_per_s"]
+        if args.paired:
+            line["sit_out"] = run(args, config, checkpoint, opponent, args.tests)
+            line["games_vs_sit_out"] = line["games_per_s"] / line["sit_out"]["games_per_s"]
     print(json.dumps(line))
 
 

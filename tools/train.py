@@ -5,7 +5,7 @@ drawn on the device -> Trainer.train_steps -> optional batched Reanalyse -> weig
 
     python tools/train.py --game cartpole|tictactoe|connect4|gomoku|twentyone|simple_grid [--envs 64] [--iterations 30]
                           [--moves 8] [--train-steps 100] [--seed 0] [--reanalyse N] [--eval-every K --eval-games G]
-                          [--eval-opponent expert|random|self] [--groups N] [--host-filing] [--seconds S]
+                          [--eval-opponent expert|random|self] [--eval-paired] [--groups N] [--host-filing] [--seconds S]
                           [--set key=value ...] [--log PATH]
 
 --set key=value overrides an attribute of the game's MuZeroConfig (the value is a Python literal: --set num_simulations=10
@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--eval-every", type=int, default=0, help="evaluate every K iterations (0: never)")
     ap.add_argument("--eval-games", type=int, default=0)
     ap.add_argument("--eval-opponent", default=None, choices=["self", "expert", "random"], help="default: the config's")
+    ap.add_argument("--eval-paired", action="store_true", help="evaluation games: the opponent replies inside MuZero's move "
+                    "(the same games; no env sits a search out)")
     ap.add_argument("--groups", type=int, default=1, help="> 1: env groups on HIP streams of their own")
     ap.add_argument("--host-filing", action="store_true", help="games through on_games -> save_games (the twin of the default)")
     ap.add_argument("--seconds", type=float, default=None, help="stop after the iteration that ends past this wall time")
@@ -68,7 +70,7 @@ def main():
     loop = loop_mod.TrainingLoop(args.game, config, args.envs, args.moves, args.train_steps, args.seed,
                                  reanalyse_games=args.reanalyse, eval_every=args.eval_every, eval_games=args.eval_games,
                                  eval_opponent=args.eval_opponent, groups=args.groups, device_filing=not args.host_filing,
-                                 log=lambda text: say({"note": text}))
+                                 log=lambda text: say({"note": text}), eval_paired=args.eval_paired)
     for _ in range(args.iterations):
         row = loop.iterate()
         say(row)
