@@ -125,6 +125,9 @@ int mzmcts_rng_get_state(mzmcts_engine *engine, int32_t env, uint32_t *key, int3
  * the last report; the host mirrors step over them before they are next used. */
 int mzmcts_rng_streams(mzmcts_engine *engine, uint32_t **mt_key_dev, int32_t **mt_pos_dev);
 int mzmcts_rng_consumed(mzmcts_engine *engine, const uint32_t *words);
+/* Read-only: *noise_dev = dev f64[E][A], the exploration-noise rows of the search in flight or run last when the device
+ * drew them (mzmcts_set_device_noise, every move of a mzmcts_moves_prepare_device batch); a move overwrites them. */
+int mzmcts_noise_rows(mzmcts_engine *engine, const double **noise_dev);
 
 /* ---- one search = MCTS.run (self_play.py:261-362) -------------------------------------------
  * begin_search: host side of the root set-up (self_play.py:297-315).

@@ -241,6 +241,7 @@ PROTOTYPES = {
     "mzmcts_moves_sit_out": (ctypes.c_int, [c_void, ctypes.c_int32]),
     "mzmcts_rng_streams": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), ctypes.POINTER(c_void)]),
     "mzmcts_rng_consumed": (ctypes.c_int, [c_void, c_u32_p]),
+    "mzmcts_noise_rows": (ctypes.c_int, [c_void, ctypes.POINTER(c_void)]),
     "mzmcts_moves_actions": (c_void, [c_void, ctypes.c_int32]),
     "mzmcts_moves_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p, c_i32_p]),
     "mzmcts_moves_inputs_ring": (ctypes.c_int, [c_void, ctypes.POINTER(c_void), c_i64_p, c_i64_p]),

@@ -241,6 +241,12 @@ int mzmcts_rng_streams(mzmcts_engine* eng, uint32_t** mt_key_dev, int32_t** mt_p
     return MZMCTS_OK;
 }
 
+int mzmcts_noise_rows(mzmcts_engine* eng, const double** noise_dev) {
+    if (!eng || !noise_dev) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_noise_rows: null argument");
+    *noise_dev = eng->p.noise_rows;
+    return MZMCTS_OK;
+}
+
 int mzmcts_rng_consumed(mzmcts_engine* eng, const uint32_t* words) {
     if (!eng || !words) return fail(eng, MZMCTS_ERR_INVALID, "mzmcts_rng_consumed: null argument");
     for (int e = 0; e < eng->p.E; ++e) {

@@ -646,6 +646,13 @@ class BatchedMCTS:
         assert w.shape == (self.E,)
         self._check(self._lib.mzmcts_rng_consumed(self._h, ptr(w, c_u32_p)))
 
+    def noise_rows(self):
+        """Device tensor (float64 [E, A], read-only use) over the exploration-noise rows the GPU drew for the search run
+        last -- the last move of a device-input batch included; the next move overwrites them."""
+        rows = ctypes.c_void_p()
+        self._check(self._lib.mzmcts_noise_rows(self._h, ctypes.byref(rows)))
+        return _device_view(rows.value, self.E * self.A, torch.float64, self.device).view(self.E, self.A)
+
     def moves_actions(self, move):
         """Device tensor (int32 [E]) holding move `move`'s sampled actions once its search has run."""
         addr = self._lib.mzmcts_moves_actions(self._h, int(move))
